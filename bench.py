@@ -6,7 +6,7 @@ stratified sampler -> [bbox hits/labels] -> coarse MLP + compositing -> [sample_
 fine MLP + compositing].  Inputs (rays, boxes, packed weights) are resident in HBM before the
 timed region.  MLP sample evaluations per ray = N_samples + (N_samples + N_importance).
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 1..5] [--scaling weak|strong]
+  python bench.py [--gpus N --steps K --warmup W] [--config 1..5] [--scaling weak|strong] [--dump-outputs DIR]
 
 --gpus N > 1 started as a PLAIN process (no WORLD_SIZE in the environment) launches its own N ranks, one per GPU, under
 torch.distributed.run (nccl = RCCL); started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it
@@ -14,6 +14,8 @@ joins the ranks it was given.  Rank 0 prints the ONE JSON line either way.
 
 --config n   BASELINE.json configs[n-1] (panopticnerf_amd/synthetic.py::BASELINE_CONFIGS); default 5 = the
              configuration the metric is quoted on (full panoptic, 64+128 samples, 8x256 MLPs, 45+32 heads, bbox prior).
+--dump-outputs DIR  after the timed steps, rank 0 writes what the headline form's LAST timed step returned, one DIR/<key>.npy
+             per output (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare array for array.
 --scaling    which form the headline `value` is: strong = ONE frame, rays sharded over the ranks (shard.render_sharded), fine-level
              label maps + rgb + depth all-gathered inside the timed region (BASELINE configs[4]: "rays sharded over 8 GPUs";
              the DEFAULT with --gpus > 1: north_star's ">= 6x ray-throughput at 8 GPUs" is a statement about this form);
@@ -101,6 +103,47 @@ def rocprof_recorded(kernel, bytes_per_launch):
                 "rocprof_source": t.get("rocprof_source")}
     except (OSError, KeyError, ValueError):
         return {}
+
+
+DUMP_BYTES = 60 << 20      # --dump-outputs stays under 64 MiB in all
+
+
+def dump_outputs(out, n_rays, d, seed=0):
+    """--dump-outputs: the dict the timed step returned to its caller -> one DIR/<key>.npy per entry, float32 (float64 stays
+    float64; integer maps become float64, exactly).  Per-ray maps (leading dims multiplying to n_rays) are flattened to
+    [n_rays, ...] rows; when all of them do not fit in DUMP_BYTES, every map keeps the SAME rows: a sorted sample drawn with
+    numpy RandomState(seed), identical from run to run.  Returns the dump's summary for the result line."""
+    import numpy as np
+
+    def host_dtype(v):
+        return torch.float64 if (v.dtype == torch.float64 or not v.is_floating_point()) else torch.float32
+
+    rows, whole = {}, {}
+    for k, v in out.items():
+        v = v.detach()
+        lead = next((j for j in range(1, v.dim() + 1) if int(np.prod(v.shape[:j])) == n_rays), None)
+        if lead is None:
+            whole[k] = v
+        else:
+            rows[k] = v.reshape(n_rays, *v.shape[lead:])
+    item = lambda v: torch.empty((), dtype=host_dtype(v)).element_size()
+    fixed = sum(v.numel() * item(v) for v in whole.values())
+    per_ray = sum(v[0].numel() * item(v) for v in rows.values())
+    n = min(n_rays, max(1, (DUMP_BYTES - fixed) // max(per_ray, 1)))
+    idx = None
+    if n < n_rays:
+        idx = np.sort(np.random.RandomState(seed).choice(n_rays, n, replace=False))
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for k, v in list(rows.items()) + list(whole.items()):
+        if idx is not None and k in rows:
+            v = v.index_select(0, torch.from_numpy(idx).to(v.device))
+        a = v.to(host_dtype(v)).cpu().numpy()
+        np.save(os.path.join(d, k + ".npy"), a)
+        total += a.nbytes
+    return {"dir": d, "arrays": sorted(out), "rays": n_rays if idx is None else n, "of_rays": n_rays,
+            "sample": None if idx is None else "numpy RandomState(%d).choice(%d, %d, replace=False), sorted" % (seed, n_rays, n),
+            "bytes": total}
 
 
 class LaunchProbe:
@@ -438,10 +481,14 @@ def main():
     ap.add_argument("--train-steps", type=int, default=None, help="secondary training-step measurement (0 = skip; "
                     "default 3 with --config 5, else 0)")
     ap.add_argument("--train-rays", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0, headline form)")
     ap.add_argument("--graph-step-child", action="store_true", help=argparse.SUPPRESS)
     # launch / collective plumbing test (tests/test_host.py): no GPU, gloo, a stub in place of the renderer -- never a measurement
     ap.add_argument("--fake-render", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
     if args.train_steps is None:
@@ -550,15 +597,20 @@ def main():
         if not fake:
             torch.cuda.synchronize()
 
-    def timed(frame):
-        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides; max over ranks."""
+    def timed(frame, keep=False):
+        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.  With keep,
+        the LAST timed step's result is returned too (the earlier ones are dropped as they come, like every step without it)."""
+        last = None
         with torch.no_grad():
             for _ in range(args.warmup):
                 frame()
             sync()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                frame()
+            for i in range(args.steps):
+                if keep and i == args.steps - 1:
+                    last = frame()
+                else:
+                    frame()
             sync()
             dt = time.perf_counter() - t0
         # every rank's own wall time between the two barriers' END points (its GPU work finished somewhere inside): the max is
@@ -568,7 +620,7 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, mine_ms
+        return dt, mine_ms, last
 
     def rank_busy_ms(frame):
         """Per-rank GPU-busy time of ONE step WITHOUT the closing barrier: hipEvents around the step on this rank's stream, all
@@ -588,10 +640,15 @@ def main():
         return round(ms, 3), round(ms, 3)
 
     modes = {}
+    dumped = None
     order = ["weak", "strong"] if args.scaling == "weak" else ["strong", "weak"]
     for mode in order:          # the headline form first
         fr = frame_weak if mode == "weak" else frame_strong
-        dt, _ = timed(fr)
+        dt, _, last = timed(fr, keep=args.dump_outputs is not None and mode == args.scaling)
+        if last is not None:
+            if rank == 0:
+                dumped = dump_outputs(last, n_rays, args.dump_outputs)
+            del last
         frames = world if mode == "weak" else 1
         modes[mode] = {"value": round(n_rays * per_ray * frames * args.steps / dt / 1e6, 2), "unit": "Msamples/s",
                        "ms_per_step": round(dt / args.steps * 1e3, 3), "frames_per_step": frames}
@@ -930,6 +987,8 @@ def main():
                 "scaling_modes": modes, "rccl": rccl,
                 "roofline": roofline, "cpu_baseline": cpu_baseline}
         line.update(extra)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if train_info is not None:
             line["train_step"] = train_info
         print(json.dumps(line), flush=True)

@@ -469,6 +469,9 @@ def test_bench_eight_ranks_strong_scaling_headline_on_gloo():
 
 
 def _reducer8_worker(rank, world, port, q):
+    # a CPU rank: GradReducer asks torch.cuda whether a graph capture is running, which would bring up the GPU runtime in each
+    # of the eight ranks on a machine that has a GPU.  Nothing here is on the GPU, so none is visible to this process
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from panopticnerf_amd import train
@@ -512,6 +515,28 @@ def test_grad_reducer_world8_gloo_uneven_shards():
         p.join(timeout=60)
         assert p.exitcode == 0
     assert len(res) == 8 and all(ok for _, ok in res)
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what the timed path returned in its last step, one DIR/<key>.npy per output in float32 /
+    float64 and under 64 MiB in all, and two runs with the same arguments write the same arrays (stub renderer on CPU: this
+    checks the plumbing, not the HIP path).  `--steps` sets the timed step count and `ms_per_step` is in the line."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        line = _bench_line([os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--fake-render", "--cpu-seconds", "0",
+                            "--train-steps", "0", "--dump-outputs", str(d)])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        info = line["dump_outputs"]
+        files = sorted(p.name for p in d.glob("*.npy"))
+        assert files == sorted(k + ".npy" for k in info["arrays"]) and "rgb_1.npy" in files
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) == info["bytes"] <= 64 << 20
+        assert arrays["rgb_1.npy"].shape == (info["rays"], 3)
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
 
 
 def test_bench_refuses_a_rank_count_that_is_not_the_launchers():
