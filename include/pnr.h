@@ -21,6 +21,7 @@
  *   pnr_sample_labels   per-sample fixed semantic / instance labels        (8a row a8)
  *   pnr_ray_setup       a8 + a3 + a8 of the coarse level in one launch    (8a rows a3, a8)
  *   pnr_sample_pdf_labels   a7 + a8 of the fine level in one launch       (8a rows a7, a8)
+ *   pnr_*_rng, pnr_rng_begin / _fill   the above with torch.rand / torch.randn drawn in the kernel (8a rows a3, a6, a7, a9)
  *
  * Conventions:
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
@@ -381,6 +382,64 @@ int pnr_ray_setup(const float* rays, int64_t n_rays, const float* box, int n_box
 int pnr_sample_pdf_labels(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
                           float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
                           int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream);
+
+/* ---- in-kernel RNG ("an in-kernel RNG is a separate fast path").  The _rng twins below draw the uniforms /
+ * the sigma noise that their plain entry points take as tensors INSIDE the kernel, from one counter-based stream contract:
+ *
+ *   generator  Philox4x32-10 (Random123; panopticnerf_amd/csrc/pnr_philox.h): no per-thread state, any draw recomputable anywhere.
+ *   call       {seed, offset}: two int64 in DEVICE memory, read by the kernels when they RUN (not at launch), so a captured
+ *              graph draws fresh numbers on every replay.  pnr_rng_begin writes it from a caller-owned state.
+ *   key        (lo32(seed), hi32(seed)).
+ *   counter    sample j of global ray g = ray_base + r (r: the ray's row in the launch), stream tag t:
+ *              (j >> 2 | t << 24, (uint32) g, lo32(offset), hi32(offset));  the draw is word j & 3 of the output block.
+ *   tags       1 = stratified jitter (t_rand), 2 = sample_pdf uniforms (u), 3 + level = sigma noise of that level (the
+ *              renderer's convention; any tag in 1..255 is accepted).
+ *   uniform    (w >> 8) * 2^-24, in [0, 1) like torch.rand.
+ *   normal     Box-Muller on the word pairs (2k, 2k + 1) of a block: u1 = ((w_2k >> 8) + 1) 2^-24, u2 = (w_2k+1 >> 8) 2^-24,
+ *              r = sqrt(-2 log u1), n_2k = r cos(2 pi u2), n_2k+1 = r sin(2 pi u2);  noise = scale * n.  One Philox call gives
+ *              the four consecutive samples a compositing lane holds.
+ *
+ * The draws of a ray depend on (seed, offset, tag, g, j) only: not on the launch, its grid or how a batch is cut into chunks.
+ * Every _rng entry point refuses (PNR_EINVAL, before any device work) a NULL descriptor or call, a tag outside 1..255, a
+ * scale < 0 (or NaN), ray_base < 0 and ray_base + n_rays > 2^32. */
+typedef struct pnr_rng {
+    const int64_t* call;   /* DEVICE {seed, offset} (pnr_rng_begin) */
+    int64_t ray_base;      /* global index of the launch's ray 0 */
+    int32_t tag;           /* stream tag, 1..255 */
+    float scale;           /* normal draws: noise = scale * n (uniform draws ignore it) */
+} pnr_rng;
+
+/* One thread: call[0..1] = state[0..1], then state[1] += 1.  state and call are caller-owned DEVICE int64[2]; the library keeps
+ * no state.  One begin per render() call: every chunk and level of the call shares its `call`. */
+int pnr_rng_begin(int64_t* state, int64_t* call, void* stream);
+/* out (n_rays, n_samples) = the stream's draws: uniforms (normal == 0) or scale * normals (normal != 0).  The link between the
+ * explicit-tensor entry points and the _rng twins, and the op for callers that want the tensors. */
+int pnr_rng_fill(const pnr_rng* rng_host, int64_t n_rays, int n_samples, int normal, float* out, void* stream);
+/* pnr_stratified with t_rand (R,N) = the stream's uniforms. */
+int pnr_stratified_rng(const float* rays, int64_t n_rays, int n_samples, int lindisp, const pnr_rng* rng_host, float* z_out,
+                       void* stream);
+/* pnr_ray_setup with t_rand (R,N) = the stream's uniforms. */
+int pnr_ray_setup_rng(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits, const int32_t* box_ids,
+                      int n_samples, int lindisp, const pnr_rng* rng_host, int hull, float* hit_t, int32_t* hit_box,
+                      int32_t* hit_count, float* z_out, int32_t* label_sem, int32_t* label_inst, void* stream);
+/* pnr_sample_pdf / pnr_sample_pdf_labels with u (R, n_fine) = the stream's uniforms. */
+int pnr_sample_pdf_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse, int n_fine,
+                       float* z_samples, int32_t* inds, float* z_fine, void* stream);
+int pnr_sample_pdf_labels_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse,
+                              int n_fine, float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
+                              int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream);
+/* pnr_composite with noise (R,N) = rng->scale * the stream's normals. */
+int pnr_composite_rng(const float* raw, int64_t raw_stride_s, int64_t raw_stride_c, const float* z, const float* rays,
+                      const pnr_rng* noise_host, const int32_t* label_sem, const int32_t* label_inst, int64_t n_rays, int n_samples,
+                      int n_sem, int n_inst, int sem_mode, int white_bkgd, float* rgb, float* depth, float* acc, float* weights,
+                      float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream);
+/* pnr_composite_backward3 with the same noise REGENERATED from the descriptor (no noise tensor is saved). */
+int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                               const pnr_rng* noise_host, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
+                               const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                               const float* g_inst, const float* g_weights, const int32_t* label_sem,
+                               const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
+                               const float* ce_sem, const float* ce_inst, float* d_raw, void* stream);
 
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable

@@ -31,6 +31,11 @@ class MlpDesc(ctypes.Structure):
                 ("head_depth", ctypes.c_int32), ("schedule", ctypes.c_int32), ("clk_probe", ctypes.c_int32 * 2), ("flags", ctypes.c_int32)]
 
 
+class RngDesc(ctypes.Structure):
+    """pnr_rng (include/pnr.h): one in-kernel stream of a launch."""
+    _fields_ = [("call", ctypes.c_void_p), ("ray_base", ctypes.c_int64), ("tag", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
 _fp = ctypes.POINTER(ctypes.c_float)
 _fpp = ctypes.POINTER(_fp)
 
@@ -98,6 +103,18 @@ SIGNATURES = {
     "pnr_ray_setup": (c_int, [c_f, c_i64, c_f, c_int, c_int, c_f, c_int, c_int, c_f, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_sample_pdf_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_f]),
     "pnr_mlp_forward_tiles": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_f, c_i64, c_int, c_f, c_f]),
+    "pnr_rng_begin": (c_int, [c_f, c_f, c_f]),
+    "pnr_rng_fill": (c_int, [ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_f, c_f]),
+    "pnr_stratified_rng": (c_int, [c_f, c_i64, c_int, c_int, ctypes.POINTER(RngDesc), c_f, c_f]),
+    "pnr_ray_setup_rng": (c_int, [c_f, c_i64, c_f, c_int, c_int, c_f, c_int, c_int, ctypes.POINTER(RngDesc), c_int, c_f, c_f, c_f, c_f,
+                                  c_f, c_f, c_f]),
+    "pnr_sample_pdf_rng": (c_int, [c_f, c_f, ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
+    "pnr_sample_pdf_labels_rng": (c_int, [c_f, c_f, ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_f,
+                                          c_f]),
+    "pnr_composite_rng": (c_int, [c_f, c_i64, c_i64, c_f, c_f, ctypes.POINTER(RngDesc), c_f, c_f, c_i64, c_int, c_int, c_int, c_int,
+                                  c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_composite_backward_rng": (c_int, [c_f, c_i64, c_f, c_f, ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_int, c_int,
+                                           c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_composite_combine": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_i64, c_int, c_f, c_f, c_int,
                                       c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
 }

@@ -22,6 +22,7 @@
 #include "pnr_common.h"
 #include "pnr_fuse_record.h"
 #include "pnr_lane_ops.h"
+#include "pnr_philox.h"
 
 struct CompositeArgs {
     const float* raw; int64_t stride_s, stride_c;
@@ -67,9 +68,12 @@ __device__ __forceinline__ float dot4(const f4& w, const f4& v)
     return fmaf(w.v[3], v.v[3], fmaf(w.v[2], v.v[2], fmaf(w.v[1], v.v[1], w.v[0] * v.v[0])));
 }
 
-template <bool CH_MAJOR, int SUB, bool SOFTMAX>
-__global__ __launch_bounds__(256) void k_composite(CompositeArgs a)
+// Rng = PnrRngDev (pnr_composite_rng): the sigma noise is the in-kernel stream's -- lane q of a ray holds samples 4 q .. 4 q + 3 =
+// one Philox block; the plain instances (empty pack) are the kernel as it was
+template <bool CH_MAJOR, int SUB, bool SOFTMAX, class... Rng>
+__global__ __launch_bounds__(256) void k_composite(CompositeArgs a, const Rng... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t s_hist[];   // [4 waves][RPW][C+K] when use_hist
     constexpr int RPW = 64 / SUB;          // rays per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -82,6 +86,8 @@ __global__ __launch_bounds__(256) void k_composite(CompositeArgs a)
     const int CK = a.C + a.K;
     const int nq = 3 + CK;                 // composited raw channels: rgb, semantic, instance (sigma excluded)
     uint32_t* hist = s_hist + ((size_t)wave * RPW + g) * CK;
+    PnrRngKey key;
+    if constexpr (RNG) key = pnr_rng_key(rng...);
 
     // z and sigma of a ray group: the head of the dependent chain (load -> exp -> scan -> weights).  With CMP_PREFETCH
     // they are requested one group ahead, while the previous group's channel rows are being reduced, so a wave's next
@@ -118,7 +124,13 @@ __global__ __launch_bounds__(256) void k_composite(CompositeArgs a)
 #pragma unroll
         for (int j = 0; j < CMP_UB; ++j) nxt[j] = load4<CH_MAJOR>(a.raw, a.stride_s, a.stride_c, s0, j < 3 ? j : j + 1, active && j < nq);
         if (CMP_PREFETCH) load_zs(grp + n_waves, pz, ps);         // next group's chain head
-        if (a.noise && active) {
+        if constexpr (RNG) {
+            if (active) {
+                float n[4];
+                pnr_rng_normal4(key, (uint32_t)ray, (uint32_t)q, n);
+                sg.v[0] += n[0]; sg.v[1] += n[1]; sg.v[2] += n[2]; sg.v[3] += n[3];
+            }
+        } else if (a.noise && active) {
             const float4 t = *reinterpret_cast<const float4*>(a.noise + s0);
             sg.v[0] += t.x; sg.v[1] += t.y; sg.v[2] += t.z; sg.v[3] += t.w;
         }
@@ -265,9 +277,11 @@ __global__ __launch_bounds__(256) void k_composite(CompositeArgs a)
 #define CMP2_UB 8
 #endif
 
-template <int L, int M4, bool SOFTMAX>
-__global__ __launch_bounds__(256) void k_composite2(CompositeArgs a)
+// Rng = PnrRngDev: lane q's samples i0 + 4 j + k (i0 = q M, a multiple of 4) take word k of Philox block i0 / 4 + j
+template <int L, int M4, bool SOFTMAX, class... Rng>
+__global__ __launch_bounds__(256) void k_composite2(CompositeArgs a, const Rng... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t s_hist[];   // [4 waves][RPW][C+K] when use_hist
     constexpr int M = 4 * M4, RPW = 64 / L;
     static_assert(L == 8 || L == 16, "a ray must sit inside one 16-lane DPP row");
@@ -282,6 +296,8 @@ __global__ __launch_bounds__(256) void k_composite2(CompositeArgs a)
     const int nq = 3 + CK;
     uint32_t* hist = s_hist + ((size_t)wave * RPW + g) * CK;
     const int64_t sc = a.stride_c;
+    PnrRngKey key;
+    if constexpr (RNG) key = pnr_rng_key(rng...);
 
     for (int64_t grp = wave_global; grp < n_groups; grp += n_waves) {
         const int64_t ray = grp * RPW + g;
@@ -310,7 +326,16 @@ __global__ __launch_bounds__(256) void k_composite2(CompositeArgs a)
         for (int j = 0; j < CMP2_UB; ++j) {
             if (j < nq) row(a.raw + (int64_t)(j < 3 ? j : j + 1) * sc, nxt[j]);
         }
-        if (a.noise) {
+        if constexpr (RNG) {
+#pragma unroll
+            for (int j = 0; j < M4; ++j) {
+                if (!act[j]) continue;
+                float n[4];
+                pnr_rng_normal4(key, (uint32_t)ray, (uint32_t)((i0 >> 2) + j), n);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[4 * j + k] += n[k];
+            }
+        } else if (a.noise) {
             float nz[M];
             row(a.noise, nz);
 #pragma unroll
@@ -445,12 +470,30 @@ __global__ __launch_bounds__(256) void k_composite2(CompositeArgs a)
 }
 
 template <bool SOFTMAX>
-static void launch_composite2(int L, int m4, int grid, size_t lds, hipStream_t st, const CompositeArgs& a)
+static void launch_composite2(int L, int m4, int grid, size_t lds, hipStream_t st, const CompositeArgs& a, const PnrRngDev* rng)
 {
-#define PNR_C2(LL, MM) hipLaunchKernelGGL((k_composite2<LL, MM, SOFTMAX>), dim3(grid), dim3(256), lds, st, a)
+#define PNR_C2(LL, MM)                                                                                                 \
+    do {                                                                                                               \
+        if (rng) hipLaunchKernelGGL((k_composite2<LL, MM, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, *rng);     \
+        else hipLaunchKernelGGL((k_composite2<LL, MM, SOFTMAX>), dim3(grid), dim3(256), lds, st, a);                   \
+    } while (0)
     if (L == 16) { if (m4 == 1) PNR_C2(16, 1); else if (m4 == 2) PNR_C2(16, 2); else if (m4 == 3) PNR_C2(16, 3); else PNR_C2(16, 4); }
     else { if (m4 == 1) PNR_C2(8, 1); else PNR_C2(8, 2); }
 #undef PNR_C2
+}
+
+template <bool SOFTMAX>
+static void launch_composite_rng(int sub, int grid, size_t lds, hipStream_t st, const CompositeArgs& a, const PnrRngDev& rng)
+{
+    switch (sub) {
+    case 1: hipLaunchKernelGGL((k_composite<true, 1, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    case 2: hipLaunchKernelGGL((k_composite<true, 2, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    case 4: hipLaunchKernelGGL((k_composite<true, 4, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    case 8: hipLaunchKernelGGL((k_composite<true, 8, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    case 16: hipLaunchKernelGGL((k_composite<true, 16, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    case 32: hipLaunchKernelGGL((k_composite<true, 32, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    default: hipLaunchKernelGGL((k_composite<true, 64, SOFTMAX, PnrRngDev>), dim3(grid), dim3(256), lds, st, a, rng); break;
+    }
 }
 
 template <bool CH_MAJOR, bool SOFTMAX>
@@ -481,11 +524,40 @@ static int composite_variant()
     return v;
 }
 
+static int composite_impl(const float* raw, int64_t raw_stride_s, int64_t raw_stride_c, const float* z, const float* rays,
+                          const float* noise, const PnrRngDev* rng, const int32_t* label_sem, const int32_t* label_inst, int64_t n_rays,
+                          int n_samples, int n_sem, int n_inst, int sem_mode, int white_bkgd, float* rgb, float* depth, float* acc,
+                          float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream);
+
 PNR_EXPORT int pnr_composite(const float* raw, int64_t raw_stride_s, int64_t raw_stride_c, const float* z,
                              const float* rays, const float* noise, const int32_t* label_sem,
                              const int32_t* label_inst, int64_t n_rays, int n_samples, int n_sem, int n_inst,
                              int sem_mode, int white_bkgd, float* rgb, float* depth, float* acc, float* weights,
                              float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream)
+{
+    return composite_impl(raw, raw_stride_s, raw_stride_c, z, rays, noise, nullptr, label_sem, label_inst, n_rays, n_samples, n_sem, n_inst,
+                          sem_mode, white_bkgd, rgb, depth, acc, weights, sem, inst, fix_sem, fix_inst, stream);
+}
+
+// sigma noise drawn in the kernel: channel-major images only (what the renderer composites)
+PNR_EXPORT int pnr_composite_rng(const float* raw, int64_t raw_stride_s, int64_t raw_stride_c, const float* z, const float* rays,
+                                 const pnr_rng* noise_host, const int32_t* label_sem, const int32_t* label_inst, int64_t n_rays,
+                                 int n_samples, int n_sem, int n_inst, int sem_mode, int white_bkgd, float* rgb, float* depth, float* acc,
+                                 float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(noise_host, n_rays < 0 ? 0 : n_rays, "pnr_composite_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(n_rays <= 0 || (raw_stride_s == 1 && (raw_stride_c % 4) == 0 && (((uintptr_t)raw) & 15) == 0),
+                "pnr_composite_rng: channel-major, 16-byte aligned raw images only");
+    return composite_impl(raw, raw_stride_s, raw_stride_c, z, rays, nullptr, &rng, label_sem, label_inst, n_rays, n_samples, n_sem, n_inst,
+                          sem_mode, white_bkgd, rgb, depth, acc, weights, sem, inst, fix_sem, fix_inst, stream);
+}
+
+static int composite_impl(const float* raw, int64_t raw_stride_s, int64_t raw_stride_c, const float* z, const float* rays,
+                          const float* noise, const PnrRngDev* rng, const int32_t* label_sem, const int32_t* label_inst, int64_t n_rays,
+                          int n_samples, int n_sem, int n_inst, int sem_mode, int white_bkgd, float* rgb, float* depth, float* acc,
+                          float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream)
 {
     PNR_REQUIRE(n_rays <= 0 || (raw && z && rays), "pnr_composite: null pointer");
     PNR_REQUIRE(n_samples >= 4 && n_samples <= 256 && (n_samples % 4) == 0,
@@ -522,14 +594,15 @@ PNR_EXPORT int pnr_composite(const float* raw, int64_t raw_stride_s, int64_t raw
             const int64_t ng = (n_rays + rpw2 - 1) / rpw2;
             const int grid2 = pnr_grid_cap((ng + 3) / 4, CMP_GRID_PER_CU);
             a.use_hist = want_fix ? 1 : 0;
-            if (sem_mode) launch_composite2<true>(L, m4, grid2, want_fix ? hb : 0, st, a); else launch_composite2<false>(L, m4, grid2, want_fix ? hb : 0, st, a);
+            if (sem_mode) launch_composite2<true>(L, m4, grid2, want_fix ? hb : 0, st, a, rng); else launch_composite2<false>(L, m4, grid2, want_fix ? hb : 0, st, a, rng);
             PNR_CHECK_LAUNCH("pnr_composite");
             return PNR_OK;
         }
     }
     const int64_t n_groups = (n_rays + rpw - 1) / rpw;
     const int grid = pnr_grid_cap((n_groups + 3) / 4, CMP_GRID_PER_CU);
-    if (ch_major) { if (sem_mode) launch_composite<true, true>(sub, grid, lds, st, a); else launch_composite<true, false>(sub, grid, lds, st, a); }
+    if (rng) { if (sem_mode) launch_composite_rng<true>(sub, grid, lds, st, a, *rng); else launch_composite_rng<false>(sub, grid, lds, st, a, *rng); }
+    else if (ch_major) { if (sem_mode) launch_composite<true, true>(sub, grid, lds, st, a); else launch_composite<true, false>(sub, grid, lds, st, a); }
     else { if (sem_mode) launch_composite<false, true>(sub, grid, lds, st, a); else launch_composite<false, false>(sub, grid, lds, st, a); }
     PNR_CHECK_LAUNCH("pnr_composite");
     return PNR_OK;

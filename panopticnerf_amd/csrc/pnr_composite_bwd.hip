@@ -12,6 +12,7 @@
 // Fixed (bbox-prior) fields have no learnable input.  Softmax-composited fields (sem_mode 1) are
 // not differentiated here (forward-only option); the caller is told so.
 #include "pnr_common.h"
+#include "pnr_philox.h"
 
 struct CompositeBwdArgs {
     const float* raw; int64_t sc;          // channel-major: element (s, c) at raw[c*sc + s]
@@ -83,9 +84,12 @@ __device__ __forceinline__ void st4(float* p, const f4& v, bool active)
 
 // SM: softmax compositing (sem_mode 1) -- a template parameter so that the default (logit compositing) instance carries neither
 // the dot products nor their branches in its register budget
-template <int SUB, bool SM>
-__global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(CompositeBwdArgs a)
+// Rng = PnrRngDev (pnr_composite_backward_rng): the forward's sigma noise regenerated from the in-kernel stream (k_composite's lane
+// mapping, so lane q's four samples are one Philox block); the plain instances (empty pack) are the kernel as it was
+template <int SUB, bool SM, class... Rng>
+__global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(CompositeBwdArgs a, const Rng... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
     constexpr int RPW = 64 / SUB;
     constexpr int CB = BWD_CB_OF(SUB);      // channel rows in flight per lane (log-sum-exp / dot passes)
     constexpr int BWD_PB = BWD_PB_OF(SUB);  // logit rows per pipelined batch of the main pass
@@ -95,6 +99,8 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
     const int64_t wave_global = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int64_t n_groups = (a.R + RPW - 1) / RPW;
+    PnrRngKey key;
+    if constexpr (RNG) key = pnr_rng_key(rng...);
 
     for (int64_t grp = wave_global; grp < n_groups; grp += n_waves) {
         const int64_t ray = grp * RPW + g;
@@ -106,7 +112,13 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
         const uint32_t ob = (uint32_t)s0 * 4u;          // byte offset of the lane's first sample in a row (R * N < 2^30: the launcher checks)
         const f4 zz = ld4o(a.z, ob, active);
         f4 sg = ld4o(a.raw + 3 * a.sc, ob, active);
-        if (a.noise) { const f4 nz = ld4o(a.noise, ob, active); for (int k = 0; k < 4; ++k) sg.v[k] += nz.v[k]; }
+        if constexpr (RNG) {
+            if (active) {
+                float n[4];
+                pnr_rng_normal4(key, (uint32_t)ray, (uint32_t)q, n);
+                for (int k = 0; k < 4; ++k) sg.v[k] += n[k];
+            }
+        } else if (a.noise) { const f4 nz = ld4o(a.noise, ob, active); for (int k = 0; k < 4; ++k) sg.v[k] += nz.v[k]; }
         const float dx = a.rays[rayc * 8 + 3], dy = a.rays[rayc * 8 + 4], dz = a.rays[rayc * 8 + 5];
         const float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
         const float znext = __shfl_down(zz.v[0], 1, 64);
@@ -338,7 +350,7 @@ static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const
                                    const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
                                    const float* g_inst, const float* g_weights, const int32_t* label_sem,
                                    const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream);
+                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream, const PnrRngDev* rng = nullptr);
 
 PNR_EXPORT int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
                                        const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
@@ -349,6 +361,22 @@ PNR_EXPORT int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, c
 {
     return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, 0, g_rgb, g_depth, g_acc, g_sem,
                                    g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream);
+}
+
+PNR_EXPORT int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                                          const pnr_rng* noise_host, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
+                                          const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                                          const float* g_inst, const float* g_weights, const int32_t* label_sem,
+                                          const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
+                                          const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(noise_host, n_rays < 0 ? 0 : n_rays, "pnr_composite_backward_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(sem_mode == 0 || sem_mode == 1, "pnr_composite_backward_rng: sem_mode must be 0 (logits) or 1 (softmax)");
+    return composite_backward_impl(raw, raw_stride_c, z, rays, nullptr, n_rays, n_samples, n_sem, n_inst, sem_mode, g_rgb, g_depth, g_acc,
+                                   g_sem, g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream,
+                                   &rng);
 }
 
 PNR_EXPORT int pnr_composite_backward3(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
@@ -368,7 +396,7 @@ static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const
                                    const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
                                    const float* g_inst, const float* g_weights, const int32_t* label_sem,
                                    const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
+                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream, const PnrRngDev* rng)
 {
     PNR_REQUIRE(n_samples >= 4 && n_samples <= 256 && (n_samples % 4) == 0,
                 "pnr_composite_backward: n_samples=%d must be a multiple of 4 in [4,256]", n_samples);
@@ -393,15 +421,26 @@ static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const
     const int64_t n_groups = (n_rays + rpw - 1) / rpw;
     const int grid = pnr_grid_cap((n_groups + 3) / 4, 8);
     hipStream_t st = (hipStream_t)stream;
+#define PNR_CB(S)                                                                                                            \
+    do {                                                                                                                     \
+        if (rng) {                                                                                                           \
+            if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<S, true, PnrRngDev>), dim3(grid), dim3(256), 0, st, a, *rng);       \
+            else hipLaunchKernelGGL((k_composite_bwd<S, false, PnrRngDev>), dim3(grid), dim3(256), 0, st, a, *rng);                 \
+        } else {                                                                                                             \
+            if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<S, true>), dim3(grid), dim3(256), 0, st, a);                 \
+            else hipLaunchKernelGGL((k_composite_bwd<S, false>), dim3(grid), dim3(256), 0, st, a);                           \
+        }                                                                                                                    \
+    } while (0)
     switch (sub) {
-    case 1: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<1, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<1, false>), dim3(grid), dim3(256), 0, st, a); break;
-    case 2: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<2, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<2, false>), dim3(grid), dim3(256), 0, st, a); break;
-    case 4: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<4, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<4, false>), dim3(grid), dim3(256), 0, st, a); break;
-    case 8: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<8, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<8, false>), dim3(grid), dim3(256), 0, st, a); break;
-    case 16: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<16, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<16, false>), dim3(grid), dim3(256), 0, st, a); break;
-    case 32: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<32, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<32, false>), dim3(grid), dim3(256), 0, st, a); break;
-    default: if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<64, true>), dim3(grid), dim3(256), 0, st, a); else hipLaunchKernelGGL((k_composite_bwd<64, false>), dim3(grid), dim3(256), 0, st, a); break;
+    case 1: PNR_CB(1); break;
+    case 2: PNR_CB(2); break;
+    case 4: PNR_CB(4); break;
+    case 8: PNR_CB(8); break;
+    case 16: PNR_CB(16); break;
+    case 32: PNR_CB(32); break;
+    default: PNR_CB(64); break;
     }
+#undef PNR_CB
     PNR_CHECK_LAUNCH("pnr_composite_backward");
     return PNR_OK;
 }

@@ -7,6 +7,7 @@
 // Reference functions these replace (the reference source
 // is not in the mount, include/pnr.h explains the citation form).
 #include "pnr_common.h"
+#include "pnr_philox.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -71,16 +72,27 @@ __global__ __launch_bounds__(256) void k_gen_rays(const GenRaysArgs a)
 }
 
 // One thread per sample; HBM-bound: reads 8 B/ray amortised (+4 B t_rand), writes 4 B.
+// Rng = PnrRngDev (pnr_stratified_rng): the jitter is the in-kernel stream's uniform of the sample instead of t_rand[s]; the plain
+// instance k_stratified<> (empty pack) is the kernel as it was.
+template <class... Rng>
 __global__ __launch_bounds__(256) void k_stratified(const float* __restrict__ rays, int64_t R, int N,
                                                      int lindisp, const float* __restrict__ t_rand,
-                                                     float* __restrict__ z_out)
+                                                     float* __restrict__ z_out, const Rng... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
+    PnrRngKey key;
+    if constexpr (RNG) key = pnr_rng_key(rng...);
     const int64_t total = R * N;
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < total;
          s += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = s / N;
         const int i = (int)(s - r * N);
-        z_out[s] = strat_sample(rays[r * 8 + 6], rays[r * 8 + 7], i, N, lindisp, t_rand ? t_rand + s : nullptr);
+        if constexpr (RNG) {
+            const float t = pnr_rng_uniform_at(key, (uint32_t)r, i);
+            z_out[s] = strat_sample(rays[r * 8 + 6], rays[r * 8 + 7], i, N, lindisp, &t);
+        } else {
+            z_out[s] = strat_sample(rays[r * 8 + 6], rays[r * 8 + 7], i, N, lindisp, t_rand ? t_rand + s : nullptr);
+        }
     }
 }
 
@@ -154,12 +166,15 @@ struct PdfLabelArgs {
 };
 #define PDF_MAXC 256
 #define PDF_MAXT 512
-template <int MAXC, int MAXT>
+template <int MAXC, int MAXT, bool RNG = false>
 __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, const float* __restrict__ weights,
                                                     const float* __restrict__ u, int64_t R, int Nc, int Nf,
                                                     float* __restrict__ zs_out, int32_t* __restrict__ inds_out,
-                                                    float* __restrict__ zfine_out, const PdfLabelArgs lab)
+                                                    float* __restrict__ zfine_out, const PdfLabelArgs lab,
+                                                    const PnrRngDev& rng = PnrRngDev{})
 {
+    PnrRngKey key;         // RNG: u of (ray r, sample i) is the in-kernel stream's uniform (pnr_sample_pdf_rng)
+    if constexpr (RNG) key = pnr_rng_key(rng);
     // MAXC / MAXT: the LDS footprint sets how many rays a CU has in flight, and this kernel is all latency (dependent LDS searches,
     // a dozen barriers per ray): 9.4 KiB per ray held 17 waves per CU, the <64, 256> instance (64 + 128 samples: every BASELINE
     // config) 3.4 KiB holds the CU's 32
@@ -253,7 +268,9 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
         }
         __syncthreads();
         for (int i = lane; i < Nf; i += 64) {
-            const float uu = u ? u[r * Nf + i] : pnr_linspace01(i, Nf);
+            float uu;
+            if constexpr (RNG) uu = pnr_rng_uniform_at(key, (uint32_t)r, i);
+            else uu = u ? u[r * Nf + i] : pnr_linspace01(i, Nf);
             int lo = 0, hi = nb;
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
@@ -556,6 +573,20 @@ void k_sample_pdf_big(const float* __restrict__ z, const float* __restrict__ wei
 {
     sample_pdf_body<PDF_MAXC, PDF_MAXT>(z, weights, u, R, Nc, Nf, zs_out, inds_out, zfine_out, lab);
 }
+// the two instances with u drawn in the kernel (pnr_sample_pdf_rng / pnr_sample_pdf_labels_rng)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void k_sample_pdf_rng(const float* __restrict__ z, const float* __restrict__ weights, int64_t R, int Nc, int Nf, float* __restrict__ zs_out,
+                      int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab, const PnrRngDev rng)
+{
+    sample_pdf_body<64, 256, true>(z, weights, nullptr, R, Nc, Nf, zs_out, inds_out, zfine_out, lab, rng);
+}
+__global__ __launch_bounds__(64)
+void k_sample_pdf_big_rng(const float* __restrict__ z, const float* __restrict__ weights, int64_t R, int Nc, int Nf,
+                          float* __restrict__ zs_out, int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab,
+                          const PnrRngDev rng)
+{
+    sample_pdf_body<PDF_MAXC, PDF_MAXT, true>(z, weights, nullptr, R, Nc, Nf, zs_out, inds_out, zfine_out, lab, rng);
+}
 
 // ------------------------------------------------------------------------------- a8
 // One thread per ray; the box table is wave-uniform (scalar loads, L2/K$ resident: M*60 B).
@@ -627,13 +658,19 @@ struct RaySetupArgs {
     int N, lindisp, hull; const float* t_rand;
     float* hit_t; int32_t* hit_box; int32_t* hit_count; float* z; int32_t* label_sem; int32_t* label_inst;
 };
-__global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a)
+// Rng = PnrRngDev (pnr_ray_setup_rng): the jitter of sample i of ray r is the in-kernel stream's uniform (r, i) instead of
+// t_rand; k_ray_setup<> (empty pack) is the plain kernel
+template <class... Rng>
+__global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a, const Rng... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
     __shared__ float2 s_t[SETUP_MAXH][64];      // (t_in, t_out)
     __shared__ float s_nr[64], s_fr[64];
     __shared__ int s_hb[SETUP_MAXH][64], s_cnt[64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int mh = a.max_hits, N = a.N;
+    PnrRngKey key;
+    if constexpr (RNG) key = pnr_rng_key(rng...);
     for (int64_t base = (int64_t)blockIdx.x * 64; base < a.R; base += (int64_t)gridDim.x * 64) {
         const int64_t r = base + tid;
         if (tid < 64 && r < a.R) {              // phase 1: the block's first wave (the others are in another block's phase 2)
@@ -718,7 +755,13 @@ __global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a)
                 if (ray >= a.R) break;                              // wave-uniform
                 for (int i = lane; i < N; i += 64) {
                     const int64_t s = ray * N + i;
-                    const float zz = strat_sample(nr[u], fr[u], i, N, a.lindisp, a.t_rand ? a.t_rand + s : nullptr);
+                    float zz;
+                    if constexpr (RNG) {
+                        const float t = pnr_rng_uniform_at(key, (uint32_t)ray, i);
+                        zz = strat_sample(nr[u], fr[u], i, N, a.lindisp, &t);
+                    } else {
+                        zz = strat_sample(nr[u], fr[u], i, N, a.lindisp, a.t_rand ? a.t_rand + s : nullptr);
+                    }
                     a.z[s] = zz;
                     if (a.label_sem) {
                         int best = -1, m = -1;
@@ -781,9 +824,26 @@ PNR_EXPORT int pnr_stratified(const float* rays, int64_t n_rays, int n_samples, 
     if (n_rays == 0) return PNR_OK;     // empty input is a no-op
     PNR_REQUIRE(rays && z_out, "pnr_stratified: null pointer");
     const int64_t total = n_rays * n_samples;
-    hipLaunchKernelGGL(k_stratified, dim3(pnr_grid_cap((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_stratified<>, dim3(pnr_grid_cap((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        rays, n_rays, n_samples, lindisp, t_rand, z_out);
     PNR_CHECK_LAUNCH("pnr_stratified");
+    return PNR_OK;
+}
+
+PNR_EXPORT int pnr_stratified_rng(const float* rays, int64_t n_rays, int n_samples, int lindisp, const pnr_rng* rng_host,
+                                  float* z_out, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(rng_host, n_rays, "pnr_stratified_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(n_rays >= 0 && n_samples >= 1 && n_samples <= (1 << 26), "pnr_stratified_rng: bad size R=%lld N=%d", (long long)n_rays,
+                n_samples);
+    if (n_rays == 0) return PNR_OK;
+    PNR_REQUIRE(rays && z_out, "pnr_stratified_rng: null pointer");
+    const int64_t total = n_rays * n_samples;
+    hipLaunchKernelGGL(k_stratified<PnrRngDev>, dim3(pnr_grid_cap((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       rays, n_rays, n_samples, lindisp, (const float*)nullptr, z_out, rng);
+    PNR_CHECK_LAUNCH("pnr_stratified_rng");
     return PNR_OK;
 }
 
@@ -830,6 +890,20 @@ PNR_EXPORT int pnr_embed(const float* x, int64_t n, int L, float* out, void* str
     return PNR_OK;
 }
 
+// u drawn in the kernel: the instances that take u (never k_sample_pdf_det: its u is deterministic)
+static void launch_sample_pdf_rng(const float* z, const float* weights, const PnrRngDev& rng, int64_t n_rays, int n_coarse, int n_fine,
+                                  float* z_samples, int32_t* inds, float* z_fine, const PdfLabelArgs& lab, hipStream_t st)
+{
+    int P = 1;
+    while (P < n_coarse + n_fine) P <<= 1;
+    if (n_coarse <= 64 && P <= 256)
+        hipLaunchKernelGGL(k_sample_pdf_rng, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, n_rays, n_coarse, n_fine,
+                           z_samples, inds, z_fine, lab, rng);
+    else
+        hipLaunchKernelGGL(k_sample_pdf_big_rng, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, n_rays, n_coarse, n_fine,
+                           z_samples, inds, z_fine, lab, rng);
+}
+
 static void launch_sample_pdf(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
                               float* z_samples, int32_t* inds, float* z_fine, const PdfLabelArgs& lab, hipStream_t st)
 {
@@ -861,6 +935,45 @@ PNR_EXPORT int pnr_sample_pdf(const float* z, const float* weights, const float*
     return PNR_OK;
 }
 
+PNR_EXPORT int pnr_sample_pdf_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse,
+                                  int n_fine, float* z_samples, int32_t* inds, float* z_fine, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, "pnr_sample_pdf_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(n_rays <= 0 || (z && weights), "pnr_sample_pdf_rng: null pointer");
+    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf_rng: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
+    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf_rng: n_coarse+n_fine=%d > %d", n_coarse + n_fine, PDF_MAXT);
+    if (n_rays <= 0) return PNR_OK;
+    PdfLabelArgs lab;
+    memset(&lab, 0, sizeof(lab));
+    launch_sample_pdf_rng(z, weights, rng, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, lab, (hipStream_t)stream);
+    PNR_CHECK_LAUNCH("pnr_sample_pdf_rng");
+    return PNR_OK;
+}
+
+PNR_EXPORT int pnr_sample_pdf_labels_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse,
+                                         int n_fine, float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
+                                         int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, "pnr_sample_pdf_labels_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(n_rays <= 0 || (z && weights && z_fine), "pnr_sample_pdf_labels_rng: null pointer");
+    PNR_REQUIRE(n_rays <= 0 || (hit_t && hit_box && hit_count && box_ids && label_sem && label_inst), "pnr_sample_pdf_labels_rng: null pointer");
+    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf_labels_rng: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
+    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf_labels_rng: n_coarse+n_fine=%d > %d", n_coarse + n_fine,
+                PDF_MAXT);
+    PNR_REQUIRE(max_hits >= 1, "pnr_sample_pdf_labels_rng: bad max_hits");
+    if (n_rays <= 0) return PNR_OK;
+    PdfLabelArgs lab;
+    lab.hit_t = hit_t; lab.hit_box = hit_box; lab.hit_count = hit_count; lab.max_hits = max_hits; lab.box_ids = box_ids;
+    lab.label_sem = label_sem; lab.label_inst = label_inst;
+    launch_sample_pdf_rng(z, weights, rng, n_rays, n_coarse, n_fine, nullptr, nullptr, z_fine, lab, (hipStream_t)stream);
+    PNR_CHECK_LAUNCH("pnr_sample_pdf_labels_rng");
+    return PNR_OK;
+}
+
 // a7 + a8: z_fine as pnr_sample_pdf, and the labels pnr_sample_labels would give for it, in the same launch
 PNR_EXPORT int pnr_sample_pdf_labels(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
                                      float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
@@ -882,9 +995,33 @@ PNR_EXPORT int pnr_sample_pdf_labels(const float* z, const float* weights, const
 
 // a8 + a3 (+ a8): hit lists as pnr_bbox_hits, z as pnr_stratified (over the hull of the kept intervals with hull != 0:
 // pnr_restrict_rays), labels as pnr_sample_labels (label_sem / label_inst may both be null), in one launch.  max_hits <= 8.
+static int ray_setup_impl(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits, const int32_t* box_ids,
+                          int n_samples, int lindisp, const float* t_rand, const PnrRngDev* rng, int hull, float* hit_t, int32_t* hit_box,
+                          int32_t* hit_count, float* z_out, int32_t* label_sem, int32_t* label_inst, void* stream);
+
 PNR_EXPORT int pnr_ray_setup(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits, const int32_t* box_ids,
                              int n_samples, int lindisp, const float* t_rand, int hull, float* hit_t, int32_t* hit_box,
                              int32_t* hit_count, float* z_out, int32_t* label_sem, int32_t* label_inst, void* stream)
+{
+    return ray_setup_impl(rays, n_rays, box, n_box, max_hits, box_ids, n_samples, lindisp, t_rand, nullptr, hull, hit_t, hit_box, hit_count,
+                          z_out, label_sem, label_inst, stream);
+}
+
+PNR_EXPORT int pnr_ray_setup_rng(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits, const int32_t* box_ids,
+                                 int n_samples, int lindisp, const pnr_rng* rng_host, int hull, float* hit_t, int32_t* hit_box,
+                                 int32_t* hit_count, float* z_out, int32_t* label_sem, int32_t* label_inst, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, "pnr_ray_setup_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(n_samples <= (1 << 26), "pnr_ray_setup_rng: n_samples=%d > 2^26", n_samples);
+    return ray_setup_impl(rays, n_rays, box, n_box, max_hits, box_ids, n_samples, lindisp, nullptr, &rng, hull, hit_t, hit_box, hit_count,
+                          z_out, label_sem, label_inst, stream);
+}
+
+static int ray_setup_impl(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits, const int32_t* box_ids,
+                          int n_samples, int lindisp, const float* t_rand, const PnrRngDev* rng, int hull, float* hit_t, int32_t* hit_box,
+                          int32_t* hit_count, float* z_out, int32_t* label_sem, int32_t* label_inst, void* stream)
 {
     PNR_REQUIRE(n_rays >= 0 && n_samples >= 1, "pnr_ray_setup: bad size R=%lld N=%d", (long long)n_rays, n_samples);
     PNR_REQUIRE(max_hits >= 1 && max_hits <= SETUP_MAXH, "pnr_ray_setup: max_hits=%d outside [1,%d] (use the separate entry points)",
@@ -899,7 +1036,10 @@ PNR_EXPORT int pnr_ray_setup(const float* rays, int64_t n_rays, const float* box
     a.rays = rays; a.R = n_rays; a.box = box; a.M = n_box; a.max_hits = max_hits; a.box_ids = box_ids;
     a.N = n_samples; a.lindisp = lindisp; a.hull = hull; a.t_rand = t_rand;
     a.hit_t = hit_t; a.hit_box = hit_box; a.hit_count = hit_count; a.z = z_out; a.label_sem = label_sem; a.label_inst = label_inst;
-    hipLaunchKernelGGL(k_ray_setup, dim3(pnr_grid_cap((n_rays + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
+    if (rng)
+        hipLaunchKernelGGL(k_ray_setup<PnrRngDev>, dim3(pnr_grid_cap((n_rays + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a, *rng);
+    else
+        hipLaunchKernelGGL(k_ray_setup<>, dim3(pnr_grid_cap((n_rays + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_ray_setup");
     return PNR_OK;
 }

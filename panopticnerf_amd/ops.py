@@ -71,6 +71,57 @@ def gen_rays(intr, c2w, width, height, near, far, pix=None, device=None):
     return rays
 
 
+class Draw:
+    """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
+    {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global
+    index of the launch's ray 0, `scale` the standard deviation of normal draws.  The ops that take explicit uniforms / noise
+    (stratified, ray_setup, sample_pdf, sample_pdf_labels, composite, composite_backward) accept a Draw in their place and then
+    call the _rng twin of their entry point: the draws are made inside the kernel, and equal what rng_fill materialises."""
+    __slots__ = ("call", "tag", "ray_base", "scale")
+
+    def __init__(self, call, tag, ray_base=0, scale=1.0):
+        self.call, self.tag, self.ray_base, self.scale = call, int(tag), int(ray_base), float(scale)
+
+    def at(self, ray_base):
+        """the same stream for a launch whose ray 0 is global ray `ray_base`"""
+        return Draw(self.call, self.tag, ray_base, self.scale)
+
+    def desc(self):
+        _chk(self.call, "call", torch.int64)
+        if self.call.numel() != 2:
+            raise ValueError("Draw.call must hold 2 int64 values (seed, offset)")
+        return _lib.RngDesc(self.call.data_ptr(), self.ray_base, self.tag, self.scale)
+
+
+def _draw(x):
+    return isinstance(x, Draw)
+
+
+@_on_device
+def rng_begin(state, call=None):
+    """pnr_rng_begin: call = state (seed, offset), then state[1] += 1, on the current stream.  state: (2,) int64 GPU tensor owned
+    by the caller (Renderer.rng_state).  Returns call (a fresh (2,) int64 tensor unless one is given)."""
+    _chk(state, "state", torch.int64)
+    if call is None:
+        call = torch.empty(2, device=state.device, dtype=torch.int64)
+    _chk(call, "call", torch.int64)
+    if state.numel() != 2 or call.numel() != 2:
+        raise ValueError("rng_begin: state and call hold 2 int64 values each")
+    _lib.check(_lib.load().pnr_rng_begin(_p(state), _p(call), _stream()), "pnr_rng_begin")
+    return call
+
+
+@_on_device
+def rng_fill(call, tag, ray_base, n_rays, n, normal=False, std=1.0):
+    """The stream `tag` of `call` for global rays ray_base .. ray_base + n_rays - 1 as an (n_rays, n) fp32 tensor: uniforms in
+    [0, 1), or std * standard normals (pnr_rng_fill) -- exactly the values the _rng kernels draw in line."""
+    d = Draw(call, tag, ray_base, std)
+    out = torch.empty((int(n_rays), int(n)), device=call.device, dtype=torch.float32)
+    _lib.check(_lib.load().pnr_rng_fill(ctypes.byref(d.desc()), int(n_rays), int(n), int(bool(normal)), _p(out), _stream()),
+               "pnr_rng_fill")
+    return out
+
+
 def _own(out, shape, dtype, dev, what):
     """`out` (a caller-owned tensor: checked) or a fresh tensor."""
     if out is None:
@@ -82,15 +133,19 @@ def _own(out, shape, dtype, dev, what):
 
 @_on_device
 def stratified(rays, n_samples, lindisp=False, t_rand=None, out=None):
-    """rays (R,8) -> z (R,N).  SURVEY 8a row a3."""
+    """rays (R,8) -> z (R,N).  SURVEY 8a row a3.  t_rand: (R,N) uniforms, a Draw (pnr_stratified_rng) or None."""
     rays = _chk(rays, "rays")
-    t_rand = _chk(t_rand, "t_rand")
     R = rays.shape[0]
     assert rays.shape[-1] == 8
-    if t_rand is not None:
-        assert tuple(t_rand.shape) == (R, n_samples)
     z = _own(out, (R, n_samples), torch.float32, rays.device, "stratified")
     lib = _lib.load()
+    if _draw(t_rand):
+        _lib.check(lib.pnr_stratified_rng(_p(rays), R, n_samples, int(bool(lindisp)), ctypes.byref(t_rand.desc()), _p(z), _stream()),
+                   "pnr_stratified_rng")
+        return z
+    t_rand = _chk(t_rand, "t_rand")
+    if t_rand is not None:
+        assert tuple(t_rand.shape) == (R, n_samples)
     _lib.check(lib.pnr_stratified(_p(rays), R, n_samples, int(bool(lindisp)), _p(t_rand), _p(z), _stream()),
                "pnr_stratified")
     return z
@@ -390,9 +445,11 @@ def mlp_forward(desc, packed, rays, z, channel_major=True, out=None):
 @_on_device
 def composite(raw, z, rays, n_sem=0, n_inst=0, channel_major=True, noise=None, label_sem=None, label_inst=None,
               sem_mode=0, white_bkgd=False, want_weights=True, out=None):
-    """raw2outputs.  SURVEY 8a row a6.  Returns dict of maps (out: optional caller-owned tensors, see _maps)."""
+    """raw2outputs.  SURVEY 8a row a6.  Returns dict of maps (out: optional caller-owned tensors, see _maps).  noise: (R,N) sigma
+    noise, a Draw (pnr_composite_rng: noise = draw.scale * the stream's normals, channel-major raw only) or None."""
     z, rays = _chk(z, "z"), _chk(rays, "rays")
-    noise = _chk(noise, "noise")
+    draw = noise if _draw(noise) else None
+    noise = None if draw is not None else _chk(noise, "noise")
     label_sem = _chk(label_sem, "label_sem", torch.int32)
     label_inst = _chk(label_inst, "label_inst", torch.int32)
     R, N = z.shape
@@ -406,6 +463,13 @@ def composite(raw, z, rays, n_sem=0, n_inst=0, channel_major=True, noise=None, l
     dev = z.device
     out = _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev)
     g = out.get
+    if draw is not None:
+        _lib.check(_lib.load().pnr_composite_rng(_p(raw), ss, sc, _p(z), _p(rays), ctypes.byref(draw.desc()), _p(label_sem),
+                                                 _p(label_inst), R, N, n_sem, n_inst, int(sem_mode), int(bool(white_bkgd)),
+                                                 _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]), _p(g("weights")),
+                                                 _p(g("semantic")), _p(g("instance")), _p(g("fix_semantic")),
+                                                 _p(g("fix_instance")), _stream()), "pnr_composite_rng")
+        return out
     _lib.check(_lib.load().pnr_composite(_p(raw), ss, sc, _p(z), _p(rays), _p(noise), _p(label_sem), _p(label_inst),
                                          R, N, n_sem, n_inst, int(sem_mode), int(bool(white_bkgd)),
                                          _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]), _p(g("weights")),
@@ -510,9 +574,11 @@ def composite_backward(raw, z, rays, n_sem, n_inst, grads, noise=None, label_sem
     """Backward of composite() for channel-major raw.  grads: dict with any of rgb, depth, acc, semantic,
     instance, weights, fix_semantic, fix_instance (upstream gradients, contiguous fp32); the fixed-field
     gradients need the per-sample labels.  ce_sem / ce_inst: 1-element device tensors, the scale of the per-sample
-    3D cross-entropy gradient (see ce3d).  sem_mode as in composite().  Returns d_raw (ch, R*N).  SURVEY 8a row a9, 8f-1."""
+    3D cross-entropy gradient (see ce3d).  sem_mode as in composite().  noise: the forward's tensor, or its Draw (the noise is then
+    regenerated in the kernel: pnr_composite_backward_rng).  Returns d_raw (ch, R*N).  SURVEY 8a row a9, 8f-1."""
     raw, z, rays = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays")
-    noise = _chk(noise, "noise")
+    draw = noise if _draw(noise) else None
+    noise = None if draw is not None else _chk(noise, "noise")
     label_sem = _chk(label_sem, "label_sem", torch.int32)
     label_inst = _chk(label_inst, "label_inst", torch.int32)
     R, N = z.shape
@@ -520,6 +586,14 @@ def composite_backward(raw, z, rays, n_sem, n_inst, grads, noise=None, label_sem
     ce_sem = None if ce_sem is None else _chk(ce_sem.reshape(1).float().contiguous(), "ce_sem")
     ce_inst = None if ce_inst is None else _chk(ce_inst.reshape(1).float().contiguous(), "ce_inst")
     d_raw = torch.empty_like(raw)
+    if draw is not None:
+        _lib.check(_lib.load().pnr_composite_backward_rng(_p(raw), R * N, _p(z), _p(rays), ctypes.byref(draw.desc()), R, N, n_sem, n_inst,
+                                                          int(sem_mode), _p(g.get("rgb")), _p(g.get("depth")), _p(g.get("acc")),
+                                                          _p(g.get("semantic")), _p(g.get("instance")), _p(g.get("weights")),
+                                                          _p(label_sem), _p(label_inst), _p(g.get("fix_semantic")),
+                                                          _p(g.get("fix_instance")), _p(ce_sem), _p(ce_inst),
+                                                          _p(d_raw), _stream()), "pnr_composite_backward_rng")
+        return d_raw
     _lib.check(_lib.load().pnr_composite_backward3(_p(raw), R * N, _p(z), _p(rays), _p(noise), R, N, n_sem, n_inst, int(sem_mode),
                                                    _p(g.get("rgb")), _p(g.get("depth")), _p(g.get("acc")),
                                                    _p(g.get("semantic")), _p(g.get("instance")), _p(g.get("weights")),
@@ -578,8 +652,10 @@ def ce3d(raw, first_channel, n_classes, label):
 @_on_device
 def sample_pdf(z, weights, n_importance, u=None, want_samples=True, out=None):
     """Coarse z, weights (R,Nc) -> z_fine (R,Nc+Nf) sorted [, z_samples (R,Nf), inds (R,Nf)].
-    SURVEY 8a row a7."""
-    z, weights, u = _chk(z, "z"), _chk(weights, "weights"), _chk(u, "u")
+    SURVEY 8a row a7.  u: (R,Nf) uniforms, a Draw (pnr_sample_pdf_rng) or None (deterministic u)."""
+    z, weights = _chk(z, "z"), _chk(weights, "weights")
+    draw = u if _draw(u) else None
+    u = None if draw is not None else _chk(u, "u")
     R, Nc = z.shape
     dev = z.device
     z_fine = _own(out, (R, Nc + n_importance), torch.float32, dev, "sample_pdf")
@@ -587,6 +663,10 @@ def sample_pdf(z, weights, n_importance, u=None, want_samples=True, out=None):
     if want_samples:
         zs = torch.empty((R, n_importance), device=dev, dtype=torch.float32)
         inds = torch.empty((R, n_importance), device=dev, dtype=torch.int32)
+    if draw is not None:
+        _lib.check(_lib.load().pnr_sample_pdf_rng(_p(z), _p(weights), ctypes.byref(draw.desc()), R, Nc, n_importance, _p(zs), _p(inds),
+                                                  _p(z_fine), _stream()), "pnr_sample_pdf_rng")
+        return z_fine, zs, inds
     _lib.check(_lib.load().pnr_sample_pdf(_p(z), _p(weights), _p(u), R, Nc, n_importance, _p(zs), _p(inds),
                                           _p(z_fine), _stream()), "pnr_sample_pdf")
     return z_fine, zs, inds
@@ -613,8 +693,11 @@ RAY_SETUP_MAX_HITS = 8      # pnr_ray_setup keeps the hit lists of 256 rays in L
 def ray_setup(rays, box, box_ids=None, n_samples=64, max_hits=8, lindisp=False, t_rand=None, hull=False, out=None):
     """The coarse level's per-ray preamble in ONE launch (pnr_ray_setup): (hit_t, hit_box, hit_count) as bbox_hits, z (R,N) as
     stratified -- over the hull of the kept intervals with hull=True, as restrict_rays + stratified --, and (label_sem,
-    label_inst) as sample_labels when box_ids is given (else None, None).  Bit for bit the separate ops; max_hits <= 8."""
-    rays, box, t_rand = _chk(rays, "rays"), _chk(box, "box"), _chk(t_rand, "t_rand")
+    label_inst) as sample_labels when box_ids is given (else None, None).  Bit for bit the separate ops; max_hits <= 8.  t_rand: (R,N)
+    uniforms, a Draw (pnr_ray_setup_rng) or None."""
+    rays, box = _chk(rays, "rays"), _chk(box, "box")
+    draw = t_rand if _draw(t_rand) else None
+    t_rand = None if draw is not None else _chk(t_rand, "t_rand")
     box_ids = _chk(box_ids, "box_ids", torch.int32)
     R, M, N = rays.shape[0], box.shape[0], int(n_samples)
     dev = rays.device
@@ -628,17 +711,24 @@ def ray_setup(rays, box, box_ids=None, n_samples=64, max_hits=8, lindisp=False, 
     if box_ids is not None:
         ls = torch.empty((R, N), device=dev, dtype=torch.int32)
         li = torch.empty((R, N), device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().pnr_ray_setup(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)), _p(t_rand),
-                                         int(bool(hull)), _p(hit_t), _p(hit_box), _p(hit_count), _p(z), _p(ls), _p(li), _stream()),
-               "pnr_ray_setup")
+    if draw is not None:
+        _lib.check(_lib.load().pnr_ray_setup_rng(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)),
+                                                 ctypes.byref(draw.desc()), int(bool(hull)), _p(hit_t), _p(hit_box), _p(hit_count), _p(z),
+                                                 _p(ls), _p(li), _stream()), "pnr_ray_setup_rng")
+    else:
+        _lib.check(_lib.load().pnr_ray_setup(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)), _p(t_rand),
+                                             int(bool(hull)), _p(hit_t), _p(hit_box), _p(hit_count), _p(z), _p(ls), _p(li), _stream()),
+                   "pnr_ray_setup")
     return (hit_t, hit_box, hit_count), z, ls, li
 
 
 @_on_device
 def sample_pdf_labels(z, weights, n_importance, hits, box_ids, u=None, out=None):
     """sample_pdf + sample_labels of its result in ONE launch (pnr_sample_pdf_labels): (z_fine (R,Nc+Nf), label_sem, label_inst).
-    hits = (hit_t, hit_box, hit_count) of bbox_hits / ray_setup.  Bit for bit the separate ops."""
-    z, weights, u = _chk(z, "z"), _chk(weights, "weights"), _chk(u, "u")
+    hits = (hit_t, hit_box, hit_count) of bbox_hits / ray_setup.  Bit for bit the separate ops.  u: as in sample_pdf."""
+    z, weights = _chk(z, "z"), _chk(weights, "weights")
+    draw = u if _draw(u) else None
+    u = None if draw is not None else _chk(u, "u")
     hit_t, hit_box, hit_count = _chk(hits[0], "hit_t"), _chk(hits[1], "hit_box", torch.int32), _chk(hits[2], "hit_count", torch.int32)
     box_ids = _chk(box_ids, "box_ids", torch.int32)
     R, Nc = z.shape
@@ -647,9 +737,14 @@ def sample_pdf_labels(z, weights, n_importance, hits, box_ids, u=None, out=None)
     z_fine = _own(out, (R, Nt), torch.float32, dev, "sample_pdf_labels")
     ls = torch.empty((R, Nt), device=dev, dtype=torch.int32)
     li = torch.empty((R, Nt), device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().pnr_sample_pdf_labels(_p(z), _p(weights), _p(u), R, Nc, int(n_importance), _p(z_fine), _p(hit_t), _p(hit_box),
-                                                 _p(hit_count), hit_box.shape[1], _p(box_ids), _p(ls), _p(li), _stream()),
-               "pnr_sample_pdf_labels")
+    if draw is not None:
+        _lib.check(_lib.load().pnr_sample_pdf_labels_rng(_p(z), _p(weights), ctypes.byref(draw.desc()), R, Nc, int(n_importance), _p(z_fine),
+                                                         _p(hit_t), _p(hit_box), _p(hit_count), hit_box.shape[1], _p(box_ids), _p(ls),
+                                                         _p(li), _stream()), "pnr_sample_pdf_labels_rng")
+    else:
+        _lib.check(_lib.load().pnr_sample_pdf_labels(_p(z), _p(weights), _p(u), R, Nc, int(n_importance), _p(z_fine), _p(hit_t),
+                                                     _p(hit_box), _p(hit_count), hit_box.shape[1], _p(box_ids), _p(ls), _p(li), _stream()),
+                   "pnr_sample_pdf_labels")
     return z_fine, ls, li
 
 

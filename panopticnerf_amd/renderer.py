@@ -11,7 +11,7 @@ the compositing kernel streams.  No torch math is on the path.
 batch keys:  "rays" (B,N_rays,8) = o,d,near,far  (required)
              "bbox" (M,15), "bbox_ids" (M,2) int32  (optional: 3D bbox prior)
              "t_rand" (B,N_rays,N_samples), "u" (B,N_rays,N_importance)  (optional explicit uniforms;
-             otherwise drawn with torch.rand on the device when cfg.perturb > 0)
+             otherwise drawn when cfg.perturb > 0: with torch.rand, or inside the kernels with cfg.rng = "device")
 output keys, level l in {0 (coarse), 1 (fine)}:
              rgb_l (B,N_rays,3) depth_l acc_l (B,N_rays) weights_l z_vals_l (B,N_rays,N_l)
              semantic_l / fix_semantic_l (B,N_rays,C), instance_l / fix_instance_l (B,N_rays,K)
@@ -84,6 +84,20 @@ class Renderer:
         if self.bbox_sampling not in ("none", "hull"):
             raise ValueError("cfg.bbox_sampling must be 'none' or 'hull', not %r" % (self.bbox_sampling,))
         self._overflow = None
+        # training perturbation (t_rand, u) and sigma noise: "torch" draws them with torch.rand / torch.randn chunk by chunk; "device"
+        # draws them inside the kernels from a counter-based stream (include/pnr.h "in-kernel RNG"): seeded by cfg.rng_seed, independent of
+        # the chunk plan, replayable under a HIP graph, no uniform / noise tensors.  rng_state = (seed, offset) on the render device, one
+        # offset per render() call that draws -- public so that checkpoints can save and restore it (None with "torch")
+        self.rng = _get(cfg, "rng", "torch")
+        if self.rng not in ("torch", "device"):
+            raise ValueError("cfg.rng must be 'torch' or 'device', not %r" % (self.rng,))
+        self.rng_state = None
+        if self.rng == "device":
+            seed = _get(cfg, "rng_seed", None)
+            seed = torch.initial_seed() if seed is None else int(seed)        # (reads torch's seed; draws nothing from its generator)
+            seed = (seed + 2 ** 63) % 2 ** 64 - 2 ** 63                        # as int64 bits
+            p0 = next(iter(net.parameters()), None)
+            self.rng_state = torch.tensor([seed, 0], dtype=torch.int64, device=p0.device if p0 is not None else "cpu")
         # inference frames of several chunks are written into frame-sized maps chunk by chunk (no concatenation at the end);
         # cfg.frame_outputs = False (or PNR_FRAME_OUT=0) restores per-chunk maps + torch.cat
         self.frame_outputs = bool(_get(cfg, "frame_outputs", os.environ.get("PNR_FRAME_OUT", "1") != "0"))
@@ -114,8 +128,9 @@ class Renderer:
         return hits, z, lab0
 
     # --- one chunk of rays: the reference's render_rays (row a2)
-    def render_rays(self, rays, box=None, box_ids=None, t_rand=None, u=None, train=False, grad=False, out=None, sched=None):
-        """out: optional {output key: caller-owned tensor of this chunk's shape} (inference only) -- render() passes row slices
+    def render_rays(self, rays, box=None, box_ids=None, t_rand=None, u=None, train=False, grad=False, out=None, sched=None, rng=None):
+        """rng: (call, ray_base) of the device RNG (cfg.rng = "device": render() issued the call, ray_base = this chunk's first row
+        of the flattened batch) -- t_rand, u and the sigma noise are then drawn inside the kernels.  out: optional {output key: caller-owned tensor of this chunk's shape} (inference only) -- render() passes row slices
         of the frame-sized maps, so the chunks of a frame are never concatenated.  sched: _render_overlapped's hooks for this
         chunk -- {"wait": event the coarse MLP launch waits for, "caps": (coarse, fine) workgroup caps, "pdf_done": filled with the
         event recorded behind sample_pdf}."""
@@ -126,7 +141,7 @@ class Renderer:
         ret = {}
         hits = lab0 = None
         if t_rand is None and self.perturb > 0 and train:
-            t_rand = torch.rand((rays.shape[0], Nc), device=dev)
+            t_rand = ops.Draw(rng[0], 1, rng[1]) if rng is not None else torch.rand((rays.shape[0], Nc), device=dev)
         own = (lambda key: out.get(key)) if (out and not grad) else (lambda key: None)
         if sched is not None and sched.get("pre") is not None:
             hits, z, lab0 = sched["pre"]                    # this chunk's preamble was issued earlier on this stream (_render_overlapped)
@@ -145,7 +160,10 @@ class Renderer:
                 ls, li = ops.sample_labels(zz, hits[0], hits[1], hits[2], box_ids)
             noise = None
             if self.raw_noise_std > 0 and train:
-                noise = torch.randn(zz.shape, device=dev) * self.raw_noise_std
+                if rng is not None:
+                    noise = ops.Draw(rng[0], 3 + lv, rng[1], self.raw_noise_std)
+                else:
+                    noise = torch.randn(zz.shape, device=dev) * self.raw_noise_std
             if grad:
                 from . import train as _train       # autograd path
                 res = _train.level_train(self, lv, rays, zz, ls, li, noise)
@@ -172,7 +190,7 @@ class Renderer:
         o0 = level(0, z, lab0)
         if Nf > 0:
             if u is None and self.perturb > 0 and train:
-                u = torch.rand((rays.shape[0], Nf), device=dev)
+                u = ops.Draw(rng[0], 2, rng[1]) if rng is not None else torch.rand((rays.shape[0], Nf), device=dev)
             w0 = o0["weights"].detach().contiguous()
             if hits is not None:        # rows a7 + a8 in one launch: the wave that merged a ray's samples labels them
                 z_fine, ls1, li1 = ops.sample_pdf_labels(z, w0, Nf, hits, box_ids, u, out=own("z_vals_1"))
@@ -307,13 +325,19 @@ class Renderer:
         caps = self._overlap_caps(rays.device, plan, grad, train, box is not None, t_rand, u)
         if caps is not None:
             return self._render_overlapped(rays, box, box_ids, plan, caps, lead)
+        call = None
+        if self.rng == "device" and train and (self.perturb > 0 or self.raw_noise_std > 0):
+            if self.rng_state.device != rays.device:
+                self.rng_state = self.rng_state.to(rays.device)
+            call = ops.rng_begin(self.rng_state)        # one offset per call; every chunk and level draws from it
         outs = []
         frame = None        # inference frames of several chunks: frame-sized maps, every later chunk writes its own rows
         for s, e in plan:
             o = self.render_rays(rays[s:e], box, box_ids,
                                  None if t_rand is None else t_rand[s:e],
                                  None if u is None else u[s:e], train, grad,
-                                 out=None if frame is None else {k: v[s:e] for k, v in frame.items()})
+                                 out=None if frame is None else {k: v[s:e] for k, v in frame.items()},
+                                 rng=None if call is None else (call, s))
             if s == 0 and e < R and not grad and self.frame_outputs and all(v.dim() >= 1 and v.shape[0] == e for v in o.values()):
                 frame = {k: torch.empty((R,) + tuple(v.shape[1:]), device=v.device, dtype=v.dtype) for k, v in o.items()}
                 for k, v in o.items():

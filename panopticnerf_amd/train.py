@@ -42,6 +42,10 @@ class LevelFn(torch.autograd.Function):
         ce_i = ops.ce3d(raw, 4 + C, K, li) if (K and li is not None) else None
         ctx.rend, ctx.lv, ctx.names = rend, lv, names
         ctx.set_materialize_grads(False)            # unused outputs arrive as None, not as zero tensors
+        # device RNG (ops.Draw): the 16-byte call is saved and the backward regenerates the noise -- no (R, N) tensor is kept
+        ctx.draw = (noise.tag, noise.ray_base, noise.scale) if isinstance(noise, ops.Draw) else None
+        if ctx.draw is not None:
+            noise = noise.call
         ctx.save_for_backward(raw, acts, z, rays, noise if noise is not None else empty,
                               ls if ls is not None else empty, li if li is not None else empty,
                               ce_s if ce_s is not None else empty, ce_i if ce_i is not None else empty)
@@ -73,6 +77,8 @@ class LevelFn(torch.autograd.Function):
         # d(mean CE)/d logits = (softmax - onehot) / count, times the upstream gradient of the scalar
         sc_s = (g_ces / ce_s[1].clamp(min=1.0)) if (g_ces is not None and ce_s.numel()) else None
         sc_i = (g_cei / ce_i[1].clamp(min=1.0)) if (g_cei is not None and ce_i.numel()) else None
+        if ctx.draw is not None:
+            noise = ops.Draw(noise, *ctx.draw)
         d_raw = ops.composite_backward(raw, z, rays, C, K, grads, noise if ctx.has_noise else None,
                                        ls if ctx.has_ls else None, li if ctx.has_li else None, sc_s, sc_i, rend.sem_mode)
         if ctx.fp32:
@@ -87,7 +93,7 @@ class LevelFn(torch.autograd.Function):
 
 
 def level_train(rend, lv, rays, z, ls, li, noise):
-    """Differentiable level: returns the same dict as ops.composite()."""
+    """Differentiable level: returns the same dict as ops.composite().  noise: (R, N) tensor, ops.Draw (device RNG) or None."""
     nerf = rend.net.nerf(lv)
     named = list(nerf.named_parameters())
     names = tuple((n, p.dtype) for n, p in named)
@@ -264,6 +270,10 @@ class GraphedStep:
         keep_p = [p.detach().clone() for p in params]
         # optimiser state that exists already (a resumed run) is restored; state the warm-up creates is reset to its initial zeros
         keep_s = {id(v): v.detach().clone() for st in optimizer.state.values() for v in st.values() if torch.is_tensor(v)}
+        # the device RNG's (seed, offset) (Renderer.rng_state, cfg.rng = "device"): the warm-up steps' draws are undone too, so the
+        # first replay draws what the first eager step from this state would
+        rend = getattr(wrapper, "renderer", None)
+        keep_rng = rend.rng_state.detach().cpu().clone() if getattr(rend, "rng_state", None) is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -283,6 +293,8 @@ class GraphedStep:
                             v.copy_(keep_s[id(v)])
                         else:
                             v.zero_()
+            if keep_rng is not None:
+                rend.rng_state.copy_(keep_rng)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         self.graph_opt = None
