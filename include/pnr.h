@@ -270,8 +270,9 @@ int pnr_composite_backward(const float* raw, int64_t raw_stride_c, const float* 
  *   g_fix_sem (R,n_sem) / g_fix_inst (R,n_inst): gradients of the FIXED (bbox-prior) maps; since
  *     fix_x[c] = sum_i w_i [label_i == c], they reach the densities through the weights: dL/dw_i += g_fix_x[label_i];
  *   ce_sem / ce_inst: DEVICE scalars s; adds s * (softmax_c(raw logits of sample) - [c == label]) to d_raw for every
- *     sample with a label >= 0 -- the gradient of the per-sample 3D cross-entropy whose value pnr_ce3d computes
- *     (s = upstream gradient * loss weight / number of labelled samples).
+ *     sample with 0 <= label < n_sem (n_inst; other labels are ignored, as in the fixed fields) -- the gradient of the
+ *     per-sample 3D cross-entropy whose value pnr_ce3d computes (s = upstream gradient * loss weight / number of labelled
+ *     samples).
  * label_sem / label_inst (R,N) int32 are the labels pnr_sample_labels produced for this level. */
 int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
                             const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,

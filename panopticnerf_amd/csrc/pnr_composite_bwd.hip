@@ -24,7 +24,7 @@ struct CompositeBwdArgs {
     const int32_t *label_sem, *label_inst; // (R,N), -1 = none; needed by g_fix_* and ce_*
     const float *g_fix_sem, *g_fix_inst;   // (R,C), (R,K) or null
     // per-sample 3D cross-entropy of the learned logits against the bbox labels (pnr_ce3d is its forward):
-    // d_raw[c][s] += *ce_x * (softmax_c(raw_x[:, s]) - [c == label_s])  for label_s >= 0
+    // d_raw[c][s] += *ce_x * (softmax_c(raw_x[:, s]) - [c == label_s])  for 0 <= label_s < C (K): other labels are ignored
     const float *ce_sem, *ce_inst;         // device scalars (upstream gradient * weight / count) or null
     int sem_mode;                          // 0: logits are composited; 1: softmax(logits) per sample is composited
 };

@@ -127,7 +127,7 @@ def _composite_inputs(dev, R, N, C, K, seed):
     return rays, z, raw, ls, li
 
 
-@pytest.mark.parametrize("N", [64, 192, 256])
+@pytest.mark.parametrize("N", [4, 8, 16, 36, 60, 64, 68, 132, 192, 256])
 @pytest.mark.parametrize("sem_mode", [0, 1])
 def test_composite_rng_equals_explicit(dev, N, sem_mode):
     R, C, K, base, std = 301, 45, 32, 9999, 1.0
@@ -141,7 +141,7 @@ def test_composite_rng_equals_explicit(dev, N, sem_mode):
         _same(a[k], b[k], k)
 
 
-@pytest.mark.parametrize("N", [64, 192])
+@pytest.mark.parametrize("N", [4, 8, 16, 36, 60, 64, 68, 132, 192])
 @pytest.mark.parametrize("sem_mode", [0, 1])
 def test_composite_backward_rng_equals_explicit(dev, N, sem_mode):
     R, C, K, base, std = 257, 45, 32, 2**31, 0.7
