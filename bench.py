@@ -6,7 +6,12 @@ stratified sampler -> [bbox hits/labels] -> coarse MLP + compositing -> [sample_
 fine MLP + compositing].  Inputs (rays, boxes, packed weights) are resident in HBM before the
 timed region.  MLP sample evaluations per ray = N_samples + (N_samples + N_importance).
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 1..5] [--scaling weak|strong] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--config 1..5] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps of the headline form, writes the
+--dump-outputs arrays and prints the result line.  Everything else it can measure or check (the other scaling form, per-rank
+busy time, the gather check, the process-group proof, the rooflines, frame_accounting, the training step, the CPU baselines)
+runs only with --full.
 
 --gpus N > 1 started as a PLAIN process (no WORLD_SIZE in the environment) launches its own N ranks, one per GPU, under
 torch.distributed.run (nccl = RCCL); started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it
@@ -20,9 +25,11 @@ joins the ranks it was given.  Rank 0 prints the ONE JSON line either way.
              label maps + rgb + depth all-gathered inside the timed region (BASELINE configs[4]: "rays sharded over 8 GPUs";
              the DEFAULT with --gpus > 1: north_star's ">= 6x ray-throughput at 8 GPUs" is a statement about this form);
              weak = every rank renders its own full frame, no collective on the data path (the default on one GPU, where the
-             two forms are the same frame).  BOTH forms are timed in every run and reported in `scaling_modes`.
+             two forms are the same frame).  A plain run times the headline form alone; with --full BOTH forms are timed, and
+             both are reported in `scaling_modes`.
+--full       the whole measurement: everything below, on top of the headline.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries extra objects:
   roofline                  -- the dominant kernel (fused top-level MLP, MFMA-bound): algorithmic FLOP per launch /
                                mean launch duration from hipEvents on the launch stream (libpnr_bench.so);
   roofline_composite[_coarse] -- the standalone compositing scan (HBM-bound; training / two-kernel path) at the top / coarse level;
@@ -474,11 +481,13 @@ def main():
     ap.add_argument("--semantic-activation", default="logits", choices=["logits", "softmax"],
                     help="what the learned semantic / instance fields composite (the reference's cfg.semantic_activation)")
     ap.add_argument("--chunk", type=int, default=65536)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also time the other scaling form and run every secondary measurement "
+                    "and check (rooflines, frame accounting, training step, CPU baselines, process-group proof)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (0 = skip; --full only)")
     ap.add_argument("--cpu1-seconds", type=float, default=None,
-                    help="time budget of the config-1 CPU leg (default: 10 s with --config 5 or 1, else 0)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--train-steps", type=int, default=None, help="secondary training-step measurement (0 = skip; "
+                    help="time budget of the config-1 CPU leg (default: 10 s with --config 5 or 1, else 0; --full only)")
+    ap.add_argument("--no-roofline", action="store_true", help="skip the rooflines and frame accounting of --full")
+    ap.add_argument("--train-steps", type=int, default=None, help="secondary training-step measurement of --full (0 = skip; "
                     "default 3 with --config 5, else 0)")
     ap.add_argument("--train-rays", type=int, default=4096)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -642,6 +651,8 @@ def main():
     modes = {}
     dumped = None
     order = ["weak", "strong"] if args.scaling == "weak" else ["strong", "weak"]
+    if not args.full:
+        order = order[:1]       # a plain run: the headline form alone, nothing after its timed steps but the dump
     for mode in order:          # the headline form first
         fr = frame_weak if mode == "weak" else frame_strong
         dt, _, last = timed(fr, keep=args.dump_outputs is not None and mode == args.scaling)
@@ -652,6 +663,8 @@ def main():
         frames = world if mode == "weak" else 1
         modes[mode] = {"value": round(n_rays * per_ray * frames * args.steps / dt / 1e6, 2), "unit": "Msamples/s",
                        "ms_per_step": round(dt / args.steps * 1e3, 3), "frames_per_step": frames}
+        if not args.full:
+            continue
         if not fake:
             # where a shortfall against ideal scaling would come from: the spread of the ranks' own busy time
             # for one step, and -- strong form -- the gather's own time
@@ -686,7 +699,9 @@ def main():
     # ---- the process group, machine-checkable: backend, size, one device per rank, the gradient bucket's all-reduce
     n_bucket = 1_300_000 if fake or net is None else sum(p.numel() for p in net.parameters())
     mine = "cpu:rank%d (fake)" % rank if fake else "cuda:%d %s" % (local_rank, torch.cuda.get_device_name(local_rank))
-    if world > 1:
+    if not args.full:
+        rccl = None
+    elif world > 1:
         devices = [None] * world
         dist.all_gather_object(devices, mine)
         bucket = torch.ones(n_bucket, device=dev, dtype=torch.float32)
@@ -708,7 +723,7 @@ def main():
     roofline = None
     extra = {}
     rays = rays_weak
-    if rank == 0 and not args.no_roofline and not fake:
+    if rank == 0 and args.full and not args.no_roofline and not fake:
         with torch.no_grad():
             # dominant kernel: the fused top-level MLP on one renderer chunk
             rc = rays[: args.chunk].contiguous()
@@ -819,7 +834,7 @@ def main():
             if N_F:
                 extra["roofline_composite_coarse"] = comp_roofline(N_C, True, "coarse level, weights written")
 
-    if rank == 0 and not fake and not args.no_roofline:
+    if rank == 0 and args.full and not fake and not args.no_roofline:
         # on the SERIAL frame (every launch on one stream, cfg.overlap_levels = False): per-launch event differences only add up there;
         # the timed frames run the fine level of a chunk beside the coarse level of the next (Renderer._render_overlapped)
         overlapped = bool(getattr(rend, "overlap_levels", False))
@@ -838,7 +853,7 @@ def main():
     # backward through the HIP kernels (compositing, dgrad, wgrad), flat-bucket
     # gradient all-reduce over RCCL, Adam.  Guarded: a failure here must not lose the headline line.
     train_info = None
-    if args.train_steps > 0 and not fake:
+    if args.full and args.train_steps > 0 and not fake:
         try:
             from panopticnerf_amd import NetworkWrapper, train as pnr_train
             tnet = make_network(cfg).to(dev).train()
@@ -936,7 +951,7 @@ def main():
 
     cpu_baseline = None
     # the CPU legs run at N = 1 only (rank 0 would otherwise keep N - 1 idle ranks waiting, on host cores the other ranks share)
-    if rank == 0 and world == 1 and not fake and (args.cpu_seconds > 0 or args.cpu1_seconds > 0):
+    if rank == 0 and world == 1 and args.full and not fake and (args.cpu_seconds > 0 or args.cpu1_seconds > 0):
         rays_c = rays.cpu()
         box_c, ids_c = (None, None) if box is None else (box.cpu(), ids.cpu())
         if args.cpu_seconds > 0:
@@ -984,8 +999,9 @@ def main():
                                           "alternate between two streams so that the fine level of chunk c (3/4 of the compute units) runs beside the coarse "
                                           "level of chunk c + 1 (1/4) -- same kernels, same bits (cfg.overlap_levels, PNR_OVERLAP=0 switches it off)",
                            "semantic_activation": args.semantic_activation, "parallelism": par},
-                "scaling_modes": modes, "rccl": rccl,
-                "roofline": roofline, "cpu_baseline": cpu_baseline}
+                "scaling_modes": modes, "full": args.full}
+        if args.full:
+            line.update(rccl=rccl, roofline=roofline, cpu_baseline=cpu_baseline)
         line.update(extra)
         if dumped is not None:
             line["dump_outputs"] = dumped

@@ -418,11 +418,11 @@ def test_bench_starts_its_own_ranks_and_reports_the_process_group(how):
     """`python bench.py --gpus 2` started as a PLAIN process (no WORLD_SIZE: how the driver starts the N = 1 run) must bring up
     its own 2 ranks instead of dying on an assertion, and rank 0 must print exactly ONE JSON line; under
     `python -m torch.distributed.run` it must join the ranks it was given.  Run with --fake-render (gloo on CPU, a stub in
-    place of the renderer): this checks the launch / sharding / collective / JSON plumbing, not a measurement.  The line
-    carries machine-checkable proof of the group (`rccl`: backend, world size, one device per rank, a summed all-reduce) and
-    BOTH scaling forms."""
+    place of the renderer): this checks the launch / sharding / collective / JSON plumbing, not a measurement.  With --full the
+    line carries machine-checkable proof of the group (`rccl`: backend, world size, one device per rank, a summed all-reduce)
+    and BOTH scaling forms."""
     import socket
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--fake-render", "--cpu-seconds", "0", "--train-steps", "0"]
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--fake-render", "--full", "--cpu-seconds", "0", "--train-steps", "0"]
     if how == "plain":
         line = _bench_line([os.path.join(ROOT, "bench.py")] + args)
         head = "strong"                     # the default headline with --gpus > 1 (round 5): ONE frame sharded over the ranks
@@ -453,10 +453,10 @@ def test_bench_starts_its_own_ranks_and_reports_the_process_group(how):
 def test_bench_eight_ranks_strong_scaling_headline_on_gloo():
     """The 8-rank form the driver's scaling bench launches -- `bench.py --gpus 8` -- before an 8-GPU node has ever been seen
     (VERDICT r4 item 7): eight ranks on gloo with the stub renderer.  The headline is the STRONG form (one frame, rays interleaved
-    over 8 ranks, per-ray maps all-gathered inside the timed region), the weak value stays in `scaling_modes`; the process group
-    is proven (world size 8, eight distinct devices, a summed all-reduce) and the gathered frame equals the frame one rank
-    renders alone, bit for bit."""
-    line = _bench_line([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--fake-render",
+    over 8 ranks, per-ray maps all-gathered inside the timed region); with --full the weak value is in `scaling_modes` too, the
+    process group is proven (world size 8, eight distinct devices, a summed all-reduce) and the gathered frame equals the frame
+    one rank renders alone, bit for bit."""
+    line = _bench_line([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--fake-render", "--full",
                         "--cpu-seconds", "0", "--train-steps", "0"], timeout=600)
     assert line["n_gpus"] == 8 and line["scaling"] == "strong" and line["data"].startswith("fake")
     r = line["rccl"]
@@ -466,6 +466,21 @@ def test_bench_eight_ranks_strong_scaling_headline_on_gloo():
     assert m["strong"]["gather_equals_single_rank"] is True
     assert line["value"] == m["strong"]["value"] and line["config"]["frames_per_step"] == 1
     assert "interleaved over 8 rank" in line["config"]["parallelism"]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_times_the_headline_form_alone(gpus):
+    """A plain run (no --full) times the headline form and reports nothing else: one entry in `scaling_modes`, the line's
+    value and ms_per_step are that entry's, and none of the secondary objects of --full is there."""
+    line = _bench_line([os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--fake-render"])
+    head = "strong" if gpus > 1 else "weak"
+    assert line["full"] is False and line["n_gpus"] == gpus and line["scaling"] == head
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["higher_is_better"] is True and line["unit"] == "Msamples/s"
+    m = line["scaling_modes"]
+    assert list(m) == [head] and line["value"] == m[head]["value"] and line["ms_per_step"] == m[head]["ms_per_step"]
+    assert not {"rccl", "roofline", "roofline_composite", "frame_accounting", "cpu_baseline", "cpu_baseline_config1",
+                "train_step", "dump_outputs"} & set(line)
+    assert not {"rank_busy_ms_min", "gather_ms", "gather_equals_single_rank"} & set(m[head])
 
 
 def _reducer8_worker(rank, world, port, q):

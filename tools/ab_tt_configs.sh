@@ -3,7 +3,7 @@
 T=${1:-r05x}; mkdir -p gpurun_out/$T; O=gpurun_out/$T
 for n in 2 3 4 5; do for l in tt pp tt pp; do
   unset PNR_FUSED_PLAN; [ $l = pp ] && export PNR_FUSED_PLAN=1
-  timeout 200 python bench.py --config $n --steps 5 --warmup 2 --cpu-seconds 0 --train-steps 0 > $O/b.json 2> $O/b.err
+  timeout 200 python bench.py --full --config $n --steps 5 --warmup 2 --cpu-seconds 0 --train-steps 0 > $O/b.json 2> $O/b.err
   python -c "
 import json
 d=json.load(open('$O/b.json')); r=d['roofline']

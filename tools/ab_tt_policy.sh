@@ -6,7 +6,7 @@ T=${1:-r05q}; mkdir -p gpurun_out/$T; O=gpurun_out/$T
 for rep in 1 2; do for l in default ttnt pp ppdef; do
   unset PNR_LIB_PATH PNR_FUSED_PLAN
   case $l in ttnt) export PNR_LIB_PATH=$PWD/build/ab/libpnr_ttnt.so ;; pp) export PNR_FUSED_PLAN=1 ;; ppdef) export PNR_FUSED_PLAN=1 PNR_LIB_PATH=$PWD/build/ab/libpnr_ppdef.so ;; esac
-  timeout 200 python bench.py --steps 6 --warmup 2 --cpu-seconds 0 --train-steps 0 > $O/bench_${l}_$rep.json 2> $O/err_${l}_$rep.log
+  timeout 200 python bench.py --full --steps 6 --warmup 2 --cpu-seconds 0 --train-steps 0 > $O/bench_${l}_$rep.json 2> $O/err_${l}_$rep.log
   python -c "
 import json
 d=json.load(open('$O/bench_${l}_$rep.json')); r=d['roofline']

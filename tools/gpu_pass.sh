@@ -3,7 +3,7 @@
 # Every step runs under its own `timeout`; rocpd databases are summarised on the box and deleted (gpurun_out/ is capped at 64 MiB).
 #   usage: tools/gpu_pass.sh <mode> <tag> [args]
 #   tests   GPU tests (+ smoke): -m gpu, optional pytest -k expression as $3
-#   bench   bench.py (config 5) [+ configs 1-4 with $3 = all]
+#   bench   bench.py --full (config 5) [+ configs 1-4 with $3 = all]
 #   full    tests + smoke + bench for every BASELINE config + rocprofv3 kernel trace and FETCH / WRITE / SQ / L2 PMC passes of the
 #           bench + kernel trace and HBM traffic of the training step  (the round's final pass; ~20 GPU-minutes)
 #   ab      same-box A/B of builds under build/ab: $3 = composite|fused|wgrad, $4... = lib names
@@ -21,9 +21,9 @@ run_tests() {
 }
 run_smoke() { timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log; }
 run_bench() {
-  timeout 600 python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json; tail -3 $O/bench.err
+  timeout 600 python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json; tail -3 $O/bench.err
   if [ "$1" = "all" ]; then
-    for n in 1 2 3 4; do timeout 200 python bench.py --config $n --steps 5 --warmup 2 --cpu-seconds 0 > $O/bench_config$n.json 2>> $O/bench.err; done
+    for n in 1 2 3 4; do timeout 200 python bench.py --full --config $n --steps 5 --warmup 2 --cpu-seconds 0 > $O/bench_config$n.json 2>> $O/bench.err; done
   fi
 }
 db() { find $O/$1 -name "*.db" | head -1; }
@@ -33,11 +33,11 @@ run_prof() {
   # bench.py's roofline launch (hipEvents around standalone launches) is compared with; the timed frames of bench.py itself run the
   # fine level of a chunk beside the coarse level of the next on 192 + 64 workgroups (profiles/r06/r06r)
   export PNR_OVERLAP=0
-  timeout 240 rocprofv3 --kernel-trace --stats -d $O/prof_trace -o bench -- python $R/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --train-steps 0 > $O/prof_trace.log 2>&1
-  timeout 240 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch -o bench -- python $R/bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_fetch.log 2>&1
-  timeout 240 rocprofv3 --pmc WRITE_SIZE -d $O/prof_write -o bench -- python $R/bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_write.log 2>&1
-  timeout 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT -d $O/prof_sq -o bench -- python $R/bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_sq.log 2>&1
-  timeout 240 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum -d $O/prof_l2 -o bench -- python $R/bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_l2.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --stats -d $O/prof_trace -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --train-steps 0 > $O/prof_trace.log 2>&1
+  timeout 240 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch -o bench -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_fetch.log 2>&1
+  timeout 240 rocprofv3 --pmc WRITE_SIZE -d $O/prof_write -o bench -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_write.log 2>&1
+  timeout 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT -d $O/prof_sq -o bench -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_sq.log 2>&1
+  timeout 240 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum -d $O/prof_l2 -o bench -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline --train-steps 0 > $O/prof_l2.log 2>&1
   timeout 200 rocprofv3 --kernel-trace --stats -d $O/train_trace -o t -- python $R/tools/train_trace.py 4 > $O/train_trace.log 2>&1
   timeout 200 rocprofv3 --pmc FETCH_SIZE -d $O/train_fetch -o t -- python $R/tools/train_trace.py 3 > $O/train_fetch.log 2>&1
   timeout 200 rocprofv3 --pmc WRITE_SIZE -d $O/train_write -o t -- python $R/tools/train_trace.py 3 > $O/train_write.log 2>&1
