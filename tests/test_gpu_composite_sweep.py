@@ -2,8 +2,10 @@
 the float64 reference of tests/_composite_ref.py, at every admissible sample count, at head widths that hit every batching tail,
 at edge inputs, and across several passes of the grid-stride loop.  SURVEY.md 8a rows a6, a9.
 
-Error = max |kernel - ref64| per output map, or per channel row of d_raw; scale = max(1, max |ref64|), far for depth.  Each
-(kernel, quantity) has one bound on error / scale: 4x the worst value measured on an MI355X over this whole file (`worst`),
+Error = max |kernel - ref64| / scale over the rays, per output map or per channel row of d_raw; scale = max(1, max |ref64|) over
+that ray's values of the map (of the row), far for depth.  Two exceptions keep the older global scale, each pinned by a strict
+xfail test that shows the per-ray gap: the semantic / instance maps of the edge rays whose logits are all +-80
+(test_edge_logit_rays_per_ray_gap), and the d_sigma row at N <= 12 (test_small_N_d_sigma_per_ray_gap).  Each (kernel, quantity) has one bound on error / scale: 4x the worst value measured on an MI355X over this whole file (`worst`),
 floored at 1e-6, and never looser than the suite's older bars (1e-4 for forward maps, 2e-4 for d_raw).  Inputs are seeded and
 the kernels are deterministic, so the errors repeat exactly; the margin is for compiler changes.  `fp32 torch` is the same
 oracle graph run in float32 against ref64, for context only (not asserted).  PNR_SWEEP_REPORT=<file.json> makes a run write
@@ -153,16 +155,29 @@ def _note(table, key, v):
     table[key] = max(table.get(key, 0.0), v)
 
 
-def check_fwd(kernel, out, ref, what, ref32=None):
+def _ray_scale(k, v, logit_rays=None):
+    """per-ray scale of a map (R, ...): max(1, max |ref64[ray]|), FAR for depth.  logit_rays (edge inputs: rays whose logits are all
+    +-80): their semantic / instance maps keep the map's global scale -- see test_edge_logit_rays_per_ray_gap"""
+    if k == "depth":
+        return torch.full((v.shape[0],), FAR, dtype=torch.float64)
+    s = v.reshape(v.shape[0], -1).abs().amax(1).clamp(min=1.0)
+    if logit_rays is not None and k in ("semantic", "instance"):
+        s[logit_rays] = max(1.0, v.abs().max().item())
+    return s
+
+
+def check_fwd(kernel, out, ref, what, ref32=None, logit_rays=None):
     assert set(out) == set(ref), (what, sorted(out), sorted(ref))
     for k, v in ref.items():
         if v.numel() == 0:
             continue
-        scale = FAR if k == "depth" else max(1.0, v.abs().max().item())
-        e = (out[k].detach().cpu().double() - v).abs().max().item() / scale
+        R = v.shape[0]
+        scale = _ray_scale(k, v, logit_rays)
+        v = v.reshape(R, -1)
+        e = ((out[k].detach().cpu().double().reshape(R, -1) - v).abs().amax(1) / scale).max().item()
         _note(_WORST, (kernel, k), e)
         if ref32 is not None:
-            _note(_WORST32, (kernel, k), (ref32[k].double() - v).abs().max().item() / scale)
+            _note(_WORST32, (kernel, k), ((ref32[k].double().reshape(R, -1) - v).abs().amax(1) / scale).max().item())
         assert e <= BOUND[(kernel, k)], (what, kernel, k, e, BOUND[(kernel, k)])
 
 
@@ -170,12 +185,19 @@ def _row_kind(c, C):
     return BWD_ROWS[0] if c < 3 else BWD_ROWS[1] if c == 3 else BWD_ROWS[2] if c < 4 + C else BWD_ROWS[3]
 
 
-def check_bwd(d_raw, ref, C, what, ref32=None):
+SIGMA_GAP_N = 12          # see test_small_N_d_sigma_per_ray_gap
+
+
+def check_bwd(d_raw, ref, C, N, what, ref32=None):
     got = d_raw.detach().cpu().double()
     assert got.shape == ref.shape, what
-    scale = ref.abs().amax(1).clamp(min=1.0)
-    err = (got - ref).abs().amax(1) / scale
-    e32 = (ref32.double() - ref).abs().amax(1) / scale if ref32 is not None else None
+    ch = ref.shape[0]
+    per_ray = lambda x: x.reshape(ch, -1, N)                        # noqa: E731  (channel row, ray, sample)
+    scale = per_ray(ref).abs().amax(2).clamp(min=1.0)               # per channel row and ray
+    if N <= SIGMA_GAP_N:                                            # the d_sigma row keeps its global scale: test_small_N_d_sigma_per_ray_gap
+        scale[3] = max(1.0, ref[3].abs().max().item())
+    err = ((per_ray(got) - per_ray(ref)).abs().amax(2) / scale).amax(1)
+    e32 = ((per_ray(ref32.double()) - per_ray(ref)).abs().amax(2) / scale).amax(1) if ref32 is not None else None
     for c in range(ref.shape[0]):
         key = ("k_composite_bwd", _row_kind(c, C))
         _note(_WORST, key, err[c].item())
@@ -185,7 +207,7 @@ def check_bwd(d_raw, ref, C, what, ref32=None):
     assert not bad, (what, bad[:8])
 
 
-def run_fwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, white, what, layouts=(True, False)):
+def run_fwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, white, what, layouts=(True, False), logit_rays=None):
     """pnr_composite on a channel-major (True) and / or a sample-major (False) copy of raw, each against forward64; returns
     the kernel's maps per layout"""
     R, N = z.shape
@@ -196,7 +218,7 @@ def run_fwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, white, what, layou
         rg = _cm(raw, dev) if cm else torch.tensor(raw).to(dev)
         outs[cm] = ops.composite(rg, _g(z, dev), _g(rays, dev), C, K, cm, _g(noise, dev), _g(ls, dev), _g(li, dev), sem_mode, white)
         kernel, _ = fwd_kernel(N, C, K, ls is not None or li is not None, cm)
-        check_fwd(kernel, outs[cm], ref, f"{what} channel_major={cm}", ref32)
+        check_fwd(kernel, outs[cm], ref, f"{what} channel_major={cm}", ref32, logit_rays)
     return outs
 
 
@@ -208,7 +230,7 @@ def run_bwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, grads, ce_sem, ce_
     ref = cref.backward64(raw, z, rays, C, K, grads, noise, ls, li, ce_sem or 0.0, ce_inst or 0.0, sem_mode)
     ref32 = (cref.backward64(raw, z, rays, C, K, grads, noise, ls, li, ce_sem or 0.0, ce_inst or 0.0, sem_mode, torch.float32)
              if _REPORT else None)
-    check_bwd(d, ref, C, what, ref32)
+    check_bwd(d, ref, C, z.shape[1], what, ref32)
     return d
 
 
@@ -282,6 +304,7 @@ def test_head_widths(dev, N):
 
 # ------------------------------------------------------------------------------------------------------------------ d. edge inputs
 EDGE_N = [4, 8, 28, 36, 44, 64, 100, 192, 256]
+LOGIT_RAYS = slice(4, None, 5)      # the edge rays whose logits are all +-80 (_inputs)
 
 
 @pytest.mark.parametrize("N", EDGE_N)
@@ -294,7 +317,8 @@ def test_edge_inputs(dev, N):
     ign_i = np.where((li >= 0) & (li < K), li, -1).astype(np.int32)
     for sem_mode in (0, 1):
         for white in (False, True):
-            outs = run_fwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, white, f"edge N={N} sm={sem_mode} wb={white}")
+            outs = run_fwd(dev, raw, z, rays, noise, ls, li, C, K, sem_mode, white, f"edge N={N} sm={sem_mode} wb={white}",
+                           logit_rays=LOGIT_RAYS)
             for cm, out in outs.items():
                 what = f"edge N={N} sm={sem_mode} wb={white} cm={cm}"
                 assert out["acc"][1].item() == 0.0 and (out["weights"][1] == 0).all(), what           # the empty ray
@@ -309,6 +333,44 @@ def test_edge_inputs(dev, N):
                                          _g(noise, dev), _g(ign_s, dev), _g(ign_i, dev), torch.tensor([CE_SEM], device=dev),
                                          torch.tensor([CE_INST], device=dev), sem_mode)
         assert torch.equal(d, d_clean), f"edge N={N} sm={sem_mode}: ignored labels changed d_raw"
+
+
+@pytest.mark.xfail(strict=True, reason="known gap, kept for a follow-up: on rays whose logits are all +-80, k_composite's semantic "
+                   "map misses its bound under the per-ray scale (7.8e-6 against 4.8e-6 at N = 256; the float32 torch graph: 2.0e-5)")
+def test_edge_logit_rays_per_ray_gap(dev):
+    """What the LOGIT_RAYS exception of test_edge_inputs leaves out.  On these rays a map of sum_i w_i v_i with v = +-80 cancels to
+    a few units, so an fp32 rounding of the weights (relative ~1e-7 after 256 transmittance factors) costs 80 x that against a
+    scale of a few: the per-ray error is bounded by max |v| sum_i w_i, not by the map's size.  Strict: the day the kernel meets the
+    per-ray bound here, this test fails and the exception goes."""
+    N, C, K = 256, 7, 5
+    raw, z, rays, noise, ls, li = _inputs(5 * N + 3, R_SWEEP, N, C, K, edge=True)
+    ref = cref.forward64(raw, z, rays, C, K, noise, ls, li, 0, False)["semantic"][LOGIT_RAYS]
+    out = ops.composite(_cm(raw, dev), _g(z, dev), _g(rays, dev), C, K, True, _g(noise, dev), _g(ls, dev), _g(li, dev), 0, False)
+    got = out["semantic"].cpu().double()[LOGIT_RAYS]
+    e = float(((got - ref).abs().amax(1) / ref.abs().amax(1).clamp(min=1.0)).max())
+    assert e <= BOUND[("k_composite", "semantic")], e
+
+
+@pytest.mark.xfail(strict=True, reason="known gap, kept for a follow-up: at N <= 12, k_composite_bwd's d_sigma misses its bound under the "
+                   "per-ray scale (up to 2.8e-5 against 3.4e-6; the float32 torch graph: 3.9e-6)")
+def test_small_N_d_sigma_per_ray_gap(dev):
+    """What the SIGMA_GAP_N exception of check_bwd leaves out.  d_sigma = delta (1 - alpha) (G T - S / (1 - alpha + 1e-10)): at
+    N <= 12 the intervals delta are tens of units, and k_composite_bwd forms 1 - alpha, T and the suffix sums S in fp32, so one
+    rounding of 1 - alpha (an ulp of 1) and of the cancelling difference are multiplied by delta.  Against a ray's own d_sigma
+    scale that is up to 2.8e-5 (the float32 torch graph, whose autograd takes d alpha / d sigma from exp directly: 3.9e-6).
+    Taking the factor from exp and the sums in double meets the bound, but changes the rounding of every training step, and the
+    chaotic fp32-mode student of test_gpu_convergence.py then lands outside its gate: that change needs its own pull request.
+    Strict: the day the kernel meets the per-ray bound here, this test fails and the exception goes."""
+    N, C, K = 4, 7, 5
+    raw, z, rays, noise, ls, li = _inputs(N + 1, R_SWEEP, N, C, K)
+    grads = _grads(N, R_SWEEP, N, C, K)
+    dt = lambda v: torch.tensor([v], dtype=torch.float32, device=dev)   # noqa: E731
+    d = ops.composite_backward(_cm(raw, dev), _g(z, dev), _g(rays, dev), C, K, {k: v.to(dev) for k, v in grads.items()},
+                               _g(noise, dev), _g(ls, dev), _g(li, dev), dt(CE_SEM), dt(CE_INST), 0)
+    ref = cref.backward64(raw, z, rays, C, K, grads, noise, ls, li, CE_SEM, CE_INST, 0)[3].reshape(-1, N)
+    got = d[3].detach().cpu().double().reshape(-1, N)
+    e = float(((got - ref).abs().amax(1) / ref.abs().amax(1).clamp(min=1.0)).max())
+    assert e <= BOUND[("k_composite_bwd", "d_sigma")], e
 
 
 # ------------------------------------------------------------------------------------------------------------------ e. grid-stride loop
@@ -385,4 +447,4 @@ def test_backward_grid_stride(dev, N):
     s_raw = raw.reshape(-1, R, N)[:, idx].permute(1, 2, 0).cpu().numpy()
     ref = cref.backward64(s_raw, z[idx], rays[idx], C, K, {k: v[idx] for k, v in grads.items()}, noise[idx], ls[idx], li[idx],
                           CE_SEM, CE_INST)
-    check_bwd(full.reshape(-1, R, N)[:, idx].reshape(4 + C + K, -1), ref, C, f"grid-stride bwd N={N} R={R}")
+    check_bwd(full.reshape(-1, R, N)[:, idx].reshape(4 + C + K, -1), ref, C, N, f"grid-stride bwd N={N} R={R}")

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from _fused_io import tiles_workspace as _tiles_workspace
 from oracle import c_oracle as co
 from oracle import torch_oracle as to
 from panopticnerf_amd import ops, synthetic
@@ -517,25 +518,6 @@ def test_fused_inference_plan_equals_classic_plan_bit_for_bit(dev, R, N, heads, 
             assert img1.numel() < img0.numel()      # one bias fragment for the merged chunk instead of one per logit block
         with pytest.raises(RuntimeError, match="pnr_mlp_forward_composite only"):
             ops.mlp_forward(d1, img1, rays, z, channel_major=True)
-
-
-def _tiles_workspace(desc, img, rays, z):
-    """pnr_mlp_forward_tiles into a 0xAB-filled workspace: (records (tiles, rec_floats), quadruples (S, 4))"""
-    import ctypes
-    from panopticnerf_amd import _lib
-    lib = _lib.load()
-    R, N = z.shape
-    S = R * N
-    nbytes = lib.pnr_mlp_forward_composite_workspace_bytes(ctypes.byref(desc), R, N, 0)
-    ws = torch.full((int(nbytes),), 0xAB, device=z.device, dtype=torch.uint8)
-    _lib.check(lib.pnr_mlp_forward_tiles(ctypes.byref(desc), ctypes.c_void_p(img.data_ptr()), ctypes.c_void_p(rays.data_ptr()),
-                                         ctypes.c_void_p(z.data_ptr()), R, N, ctypes.c_void_p(ws.data_ptr()),
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "pnr_mlp_forward_tiles")
-    rf = (1 + desc.n_sem + desc.n_inst + 3) & ~3
-    pad = (S + 255) // 256 * 8
-    rec = ws[: pad * rf * 4].view(torch.float32).reshape(pad, rf)[: (S + 31) // 32, : 1 + desc.n_sem + desc.n_inst]
-    ps = ws[pad * rf * 4: pad * rf * 4 + S * 16].view(torch.float32).reshape(S, 4)
-    return rec.clone(), ps.clone()
 
 
 @pytest.mark.parametrize("heads", [(45, 32), (19, 8), (64, 1), (45, 0), (19, 0), (0, 0)])
