@@ -75,7 +75,8 @@ typedef struct pnr_mlp_desc {
     int32_t n_sem, n_inst, head_W;
     int32_t precision; /* PNR_PREC_* */
     int32_t plan;      /* chunk order of the packed image: 0 = classic (every kernel); 1 = fused-inference order, 2 = two-tile order,
-                          see pnr_mlp_fused_plan (only pnr_mlp_forward_composite accepts them) */
+                          see pnr_mlp_fused_plan; 3 = sigma only (opt-in, below) -- only pnr_mlp_forward_composite / _tiles /
+                          pnr_composite_combine accept 1..3 */
     int32_t head_tap;  /* what the semantic / instance heads read: 0 = the trunk output h (default), 1 = the feature_linear
                           output (the reference's tap point cannot be checked here, so it is a switch) */
     int32_t head_depth;/* 0 or 2 = W -> head_W -> n (ReLU between; default), 1 = one Linear W -> n */
@@ -161,7 +162,7 @@ int pnr_mlp_forward(const pnr_mlp_desc* desc, const void* packed, const float* r
  * associated per tile).  Outputs as pnr_composite's (any may be null; fix_* need their labels); weights (R,N) optional.
  * workspace: pnr_mlp_forward_composite_workspace_bytes(desc, n_rays, n_samples, weights != null) device bytes (tile records,
  * per-sample quadruples and 128 B per ray: |d| and gamma(d / |d|) once per ray, written by a pre-kernel for the plan-2 kernel --
- * which takes at most 2^24 rays per call). */
+ * which takes at most 2^24 rays per call; plan 3: records of the transmittance factor alone and the quadruples, no per-ray table). */
 /* Chunk order for images that only pnr_mlp_forward_composite will consume: the BEST plan `desc`'s geometry has.
  *   1: the fused-inference plan (bf16, W = 256, 1..2 semantic and 0..1 instance logit blocks of 32): the appearance branch, then
  *      BOTH head hidden layers, then the two logit layers as ONE chunk (k_mlp_pp: 8 waves, one 32-sample tile per wave);
@@ -172,7 +173,15 @@ int pnr_mlp_forward(const pnr_mlp_desc* desc, const void* packed, const float* r
  *   0: the classic order, which every entry point accepts.
  * Set desc.plan to the returned value (or to a smaller supported one: plan 1 needs a semantic head) before pnr_mlp_packed_bytes / pnr_mlp_pack* and keep it
  * for the forward call.  Same arithmetic per layer under every plan: records and maps are bit-identical (head_depth 1: plan 2 against
- * plan 0 to fp32 rounding).  With PNR_MLP_SOFTMAX in desc.flags the answer is the best plan that has a SOFTMAX kernel (2, 1, or 0 = none). */
+ * plan 0 to fp32 rounding).  With PNR_MLP_SOFTMAX in desc.flags the answer is the best plan that has a SOFTMAX kernel (2, 1, or 0 = none).
+ *
+ * Plan 3, the sigma-only image (never returned here: set desc.plan = 3 yourself).  For a level that is read only for its compositing
+ * weights -- the coarse level of a frame with a fine level.  bf16, W = 128 or 256, any trunk: the trunk chunked as in plan 1 (layer 0
+ * as one chunk), then ONE 32-row block whose row 3 is alpha_linear over h (bias alpha_b) and every other row zero; no feature, views,
+ * rgb or head layers (pnr_mlp_pack* read only pts_* and alpha_*).  Through pnr_mlp_forward_composite / pnr_mlp_forward_tiles /
+ * pnr_composite_combine with rgb, sem and inst NULL (PNR_EINVAL otherwise): depth, acc, weights and fix_* are the bits every other
+ * plan of the same network gives; the records hold no logit sums, so n_sem / n_inst only size fix_*; PNR_MLP_SOFTMAX is accepted and
+ * has no effect; N a multiple of 32 in [32, 256] as for every plan.  pnr_mlp_forward and the backward refuse it (plan 0 only). */
 int pnr_mlp_fused_plan(const pnr_mlp_desc* desc);
 int64_t pnr_mlp_forward_composite_workspace_bytes(const pnr_mlp_desc* desc, int64_t n_rays, int n_samples, int want_weights);
 int pnr_mlp_forward_composite(const pnr_mlp_desc* desc, const void* packed, const float* rays, const float* z,

@@ -617,12 +617,15 @@ static int composite_impl(const float* raw, int64_t raw_stride_s, int64_t raw_st
 // One wave per ray, lane = sample (i = lane + 64 j) for the per-sample part and lane = column for the logits; 26 B per sample of
 // traffic at 45 / 32 heads (+ z, + 4 B per labelled field) instead of the raw image's 324 B.  The fixed fields are a
 // fixed-point histogram in LDS (integer adds: order-independent, deterministic).
+// LOGITS: the records hold the C + K logit sums behind Q (every plan but 3).  Plan 3 (k_mlp_pp_sigma) writes records of Q alone:
+// no logit map can be produced, and C / K only size the fix_* histograms.
 struct CombineArgs {
     const float* rec; int rec_floats; const float4* ps; const float* z; const int32_t* lab_s; const int32_t* lab_i;
     int64_t R; int N, C, K, white_bkgd;
     float *rgb, *depth, *acc, *weights, *sem, *inst, *fix_sem, *fix_inst;
 };
 
+template <bool LOGITS>
 __global__ __launch_bounds__(256) void k_composite_combine(CombineArgs a)
 {
     __shared__ uint32_t hist_all[4][128];       // C + K <= 128 (pnr_mlp_forward_composite)
@@ -657,7 +660,7 @@ __global__ __launch_bounds__(256) void k_composite_combine(CombineArgs a)
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int k = 0; k < 8; ++k) lg[h][k] = (k < T && lane + 64 * h < CK) ? rec[k * RF + PNR_FUSE_REC_LOGITS + lane + 64 * h] : 0.0f;
+        for (int k = 0; k < 8; ++k) lg[h][k] = (LOGITS && k < T && lane + 64 * h < CK) ? rec[k * RF + PNR_FUSE_REC_LOGITS + lane + 64 * h] : 0.0f;
     float Tk[8];
     float t = 1.0f;
 #pragma unroll
@@ -704,27 +707,31 @@ __global__ __launch_bounds__(256) void k_composite_combine(CombineArgs a)
     for (int h = 0; h < 2; ++h) {
         const int c = lane + 64 * h;
         if (c >= CK) continue;
-        float v = 0.0f;
+        if constexpr (LOGITS) {
+            float v = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) if (k < T) v = fmaf(Tk[k], lg[h][k], v);
-        if (c < C) { if (a.sem) a.sem[ray * C + c] = v; }
-        else if (a.inst) a.inst[ray * K + (c - C)] = v;
+            for (int k = 0; k < 8; ++k) if (k < T) v = fmaf(Tk[k], lg[h][k], v);
+            if (c < C) { if (a.sem) a.sem[ray * C + c] = v; }
+            else if (a.inst) a.inst[ray * K + (c - C)] = v;
+        }
         // LDS operations of one wave execute in order and only this wave touches its histogram: no barrier
         if (c < C) { if (want_s) a.fix_sem[ray * C + c] = (float)hist[c] * (1.0f / PNR_FUSE_FIX_SCALE); }
         else if (want_i) a.fix_inst[ray * K + (c - C)] = (float)hist[c] * (1.0f / PNR_FUSE_FIX_SCALE);
     }
 }
 
-int pnr_composite_combine_launch(const float* rec, int rec_floats, const float4* ps, const float* z, const int32_t* label_sem,
-                                 const int32_t* label_inst, int64_t R, int N, int C, int K, int white_bkgd, float* rgb, float* depth,
-                                 float* acc, float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, hipStream_t st)
+int pnr_composite_combine_launch(const float* rec, int rec_floats, bool logit_sums, const float4* ps, const float* z,
+                                 const int32_t* label_sem, const int32_t* label_inst, int64_t R, int N, int C, int K, int white_bkgd,
+                                 float* rgb, float* depth, float* acc, float* weights, float* sem, float* inst, float* fix_sem,
+                                 float* fix_inst, hipStream_t st)
 {
     CombineArgs a;
     a.rec = rec; a.rec_floats = rec_floats; a.ps = ps; a.z = z; a.lab_s = label_sem; a.lab_i = label_inst;
     a.R = R; a.N = N; a.C = C; a.K = K; a.white_bkgd = white_bkgd;
     a.rgb = rgb; a.depth = depth; a.acc = acc; a.weights = weights; a.sem = sem; a.inst = inst; a.fix_sem = fix_sem; a.fix_inst = fix_inst;
     const int64_t blocks = (R + 3) / 4;
-    hipLaunchKernelGGL(k_composite_combine, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    if (logit_sums) hipLaunchKernelGGL(k_composite_combine<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_composite_combine<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     PNR_CHECK_LAUNCH("pnr_mlp_forward_composite (combine)");
     return PNR_OK;
 }

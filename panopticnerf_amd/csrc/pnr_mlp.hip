@@ -828,7 +828,142 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
 #endif
 }
 
-template <int W, bool TRAIN, bool FUSE = false, int TAIL = 0>
+// ------------------------------------------------------------------------------- sigma-only form (plan 3)
+// An inference level that is read only for its compositing weights -- the coarse level of a frame with a fine level: sample_pdf's
+// input -- needs sigma and nothing else.  This kernel is k_mlp_pp<W, false, true> cut down to the trunk and ONE output block, the
+// plan-3 image's sigma chunk: row 3 = alpha_linear over h, the same fragments in the same order as the h segment of the rgb / sigma
+// chunk (whose g-segment fragments are zero in row 3: their MFMAs add exact zeros).  The fused epilogue (fuse_rgbs) therefore
+// writes the same Q and lw bits as every other plan, with r = g = b = 0 and records of pnr_fuse_record_floats(0, 0) floats.  No
+// gamma(d), no feature / views / rgb layers, no heads.  The next sample group's input fetch and its gamma(x) staging, which k_mlp_pp
+// places in the L phases of the feature layer, run in those of the LAST TRUNK LAYER here -- into a second register set, because
+// that layer may be the one behind the skip connection and still read this group's gamma(x).
+template <int W>
+__global__ __launch_bounds__(512, 2) void k_mlp_pp_sigma(const MlpArgs a)
+{
+    constexpr int WAVES = 8;
+    using CTX = CtxPP<WAVES>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NFB = W / 32;
+    constexpr int HR = NFB * 8, GXR = 16;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    CTX c{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
+#if PNR_PP_ABL & 16
+    c.abl_sink = u32x4{0, 0, 0, 0};
+#endif
+#if PNR_TRACE
+    c.tr = reinterpret_cast<unsigned long long*>(smem + 3 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
+    c.titer = 0;
+#endif
+    const int n = c.lane & 31;
+    c.start();
+    unsigned long long clk_c0 = 0, clk_r0 = 0;
+    if (a.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
+
+    uint32_t dummy[1] = {0};
+    u32x4 A[CTX::P];
+    struct SampleIn { float4 o4, d4; float zz, zn; bool last; };
+    auto fetch = [&](int grp) {             // k_mlp_pp's fetch<FUSE>
+        const int s = (grp * WAVES + c.wave) * 32 + n;
+        const int sl = s < a.S ? s : a.S - 1;
+        const int ray = pnr_div_magic(sl, a.n_magic, a.n_shift);
+        SampleIn in;
+        in.o4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8);
+        in.d4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8 + 4);
+        in.zz = a.z[sl];
+        in.zn = a.z[sl + 1 < a.S ? sl + 1 : sl];
+        in.last = sl - ray * a.N + 1 == a.N;
+        return in;
+    };
+    SampleIn nextin = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0);
+    FuseState fst;
+    uint32_t ex[GXR], exn[GXR];            // gamma(x) of this sample group / of the next one (staged in the last trunk layer)
+    float dn_next;
+    auto points = [&](const SampleIn& in, float& px, float& py, float& pz, float& nrm) {
+        const float dx = in.o4.w, dy = in.d4.x, dz = in.d4.y;
+        px = __fadd_rn(in.o4.x, __fmul_rn(dx, in.zz));
+        py = __fadd_rn(in.o4.y, __fmul_rn(dy, in.zz));
+        pz = __fadd_rn(in.o4.z, __fmul_rn(dz, in.zz));
+        nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    };
+    {
+        float px, py, pz;
+        points(nextin, px, py, pz, dn_next);
+        embed_lane<PNR_PREC_BF16, 5, 32, GXR>(px, py, pz, c.hi, ex);
+    }
+
+    for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
+        const int s0 = (grp * WAVES + c.wave) * 32 + n;
+        const int samp = s0 < a.S ? s0 : -1;
+        fst.zz = nextin.zz; fst.zn = nextin.zn; fst.dn = dn_next; fst.samp = samp; fst.last = nextin.last;
+        fst.rec = a.rec + (int64_t)(grp * WAVES + c.wave) * a.rec_floats;
+        uint32_t cur[HR], nxt[HR];
+        pp_layer_regs<CTX, PNR_L_TRUNK0, GXR, 0, NFB, MODE_RELU, HR, (PNR_PLAN1_TRUNK0_MERGE ? NFB : 0)>(c, A, ex, dummy, cur, nullptr, s0);
+        auto trunk = [&](int l, const uint32_t (&in)[HR], uint32_t (&out)[HR], auto&& side) {
+            if (l - 1 == a.skip)
+                pp_layer_regs<CTX, PNR_L_TRUNK, GXR, HR, NFB, MODE_RELU, HR>(c, A, ex, in, out, nullptr, s0, side);
+            else
+                pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, nullptr, s0, side);
+        };
+#pragma unroll 1
+        for (int l = 1; l < a.D - 1; ++l) {
+            trunk(l, cur, nxt, NoSide{});
+#pragma unroll
+            for (int i = 0; i < HR; ++i) cur[i] = nxt[i];
+        }
+        // side work of the last trunk layer: k_mlp_pp's stages 4..7 (gamma(x) of the next sample group) in the slots k_mlp_pp gives
+        // them in the feature layer, whose width this layer has; stages 0..3 (gamma(d)) have no reader here
+        const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
+        EmbedSC esc;
+        float q0, q1, q2;
+        auto stage = [&](int k) {
+            switch (k) {
+            case 4: points(nextin, q0, q1, q2, dn_next); exn[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
+            case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &exn[1]); break;
+            case 6: embed_next_band(esc); embed_pack_band(esc, &exn[4]); embed_next_band(esc); embed_pack_band(esc, &exn[7]); break;
+            case 7: embed_next_band(esc); embed_pack_band(esc, &exn[10]); embed_next_band(esc); embed_pack_band(esc, &exn[13]); break;
+            default: break;
+            }
+        };
+        auto side = [&](int slot) {
+            if (slot == -1) {
+                // the four loads of fetch(), the youngest vector-memory operations of the phase: the next m_done() waits for all but
+                // them (k_mlp_pp's side(-1); tests/test_asm_lint.py checks the count on the compiled assembly)
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
+                nextin = fetch(g2);
+                asm volatile("; PNR_FETCH_END 4" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                c.pending_stores = 4;
+            }
+            if (slot < 0) return;
+            constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
+#pragma unroll
+            for (int j = 0; j < PER; ++j) stage(slot * PER + j);
+        };
+        trunk(a.D - 1, cur, nxt, side);
+#pragma unroll
+        for (int i = 0; i < GXR; ++i) ex[i] = exn[i];
+        pp_layer_out<false, true, CTX, HR, 0>(c, A, nxt, dummy, 4, 0, samp, &fst);
+#if PNR_TRACE
+        ++c.titer;
+#endif
+    }
+    c.end();
+    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
+        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
+        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
+    }
+#if PNR_TRACE
+    __syncthreads();
+    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 3 * a.slot_bytes);
+        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
+    }
+#endif
+}
+
+// SIGMA: k_mlp_pp_sigma<W> (plan 3) instead of k_mlp_pp -- the same weight stream, LDS slots and launch shape
+template <int W, bool TRAIN, bool FUSE = false, int TAIL = 0, bool SIGMA = false>
 static int launch_mlp_pp(const MlpArgs& a0, hipStream_t stream)
 {
     MlpArgs a = a0;
@@ -837,6 +972,7 @@ static int launch_mlp_pp(const MlpArgs& a0, hipStream_t stream)
     PNR_REQUIRE(a.n_chunks >= 4, "pnr_mlp_forward: network too small for the weight stream");
     a.n_groups = (a.S + 255) / 256;
     auto kern = k_mlp_pp<W, TRAIN, FUSE, TAIL>;
+    if constexpr (SIGMA) kern = k_mlp_pp_sigma<W>;
     static thread_local bool attr_set = false;
     if (!attr_set) {
         PNR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
@@ -958,17 +1094,26 @@ PNR_EXPORT int pnr_mlp_forward(const pnr_mlp_desc* desc, const void* packed, con
 // two-tile kernel stores every packed activation block to a scratch region behind the per-ray table (profiles/r06/r06p)
 #define PNR_TT_SAVE_REGION (352 * 1024)
 static bool pnr_tt_save_proto() { static const bool on = getenv("PNR_TT_SAVE_PROTO") != nullptr; return on; }
-int pnr_composite_combine_launch(const float* rec, int rec_floats, const float4* ps, const float* z, const int32_t* label_sem,
-                                 const int32_t* label_inst, int64_t R, int N, int C, int K, int white_bkgd, float* rgb, float* depth,
-                                 float* acc, float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, hipStream_t st);
+int pnr_composite_combine_launch(const float* rec, int rec_floats, bool logit_sums, const float4* ps, const float* z,
+                                 const int32_t* label_sem, const int32_t* label_inst, int64_t R, int N, int C, int K, int white_bkgd,
+                                 float* rgb, float* depth, float* acc, float* weights, float* sem, float* inst, float* fix_sem,
+                                 float* fix_inst, hipStream_t st);
+
+// plan 3 (k_mlp_pp_sigma): records of Q alone -- no logit sums, whatever n_sem / n_inst the descriptor has (they size the fix_* maps)
+static int record_floats(const pnr_mlp_desc& d)
+{
+    return d.plan == 3 ? pnr_fuse_record_floats(0, 0) : pnr_fuse_record_floats(d.n_sem, d.n_inst);
+}
 
 // workspace of pnr_mlp_forward_composite: one record per 32-sample tile (padded to whole 256-sample groups) and one
-// (lw, r, g, b) quadruple per sample (want_weights is accepted for ABI stability and no longer changes the size)
+// (lw, r, g, b) quadruple per sample (want_weights is accepted for ABI stability and no longer changes the size); plan 3 needs
+// no per-ray table (that is the two-tile kernel's)
 PNR_EXPORT int64_t pnr_mlp_forward_composite_workspace_bytes(const pnr_mlp_desc* desc, int64_t n_rays, int n_samples, int want_weights)
 {
     (void)want_weights;
     if (pnr_mlp_validate(desc) != PNR_OK || n_rays < 0 || n_samples < 32 || (n_samples & 31)) return -1;
     const int64_t S = n_rays * n_samples, tiles = (S + 255) / 256 * 8;
+    if (desc->plan == 3) return tiles * record_floats(*desc) * 4 + S * 16 + 256;
     return tiles * pnr_fuse_record_floats(desc->n_sem, desc->n_inst) * 4 + S * 16 + 256 + PNR_RAY_AUX_BYTES + n_rays * PNR_RAY_AUX_BYTES +
            (pnr_tt_save_proto() ? tiles / 8 * 4 * PNR_TT_SAVE_REGION + 4096 : 0);
 }
@@ -1019,7 +1164,7 @@ static int fused_mlp_launch(const pnr_mlp_desc* desc, const void* packed, const 
     pnr_set_div_magic(n_samples, a.n_magic, a.n_shift);
     a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
     a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
-    a.rec_floats = pnr_fuse_record_floats(desc->n_sem, desc->n_inst);
+    a.rec_floats = record_floats(*desc);
     a.rec = (float*)workspace;
     const int64_t tiles = ((int64_t)a.S + 255) / 256 * 8;
     a.ps = (float4*)(a.rec + tiles * a.rec_floats);           // rec_floats % 4 == 0: 16-byte aligned
@@ -1029,6 +1174,8 @@ static int fused_mlp_launch(const pnr_mlp_desc* desc, const void* packed, const 
 #endif
     hipStream_t st = (hipStream_t)stream;
     const bool softmax = (desc->flags & PNR_MLP_SOFTMAX) && desc->n_sem + desc->n_inst > 0;
+    if (desc->plan == 3)        // sigma only: no learned field, so PNR_MLP_SOFTMAX has nothing to act on
+        return desc->W == 256 ? launch_mlp_pp<256, false, true, 0, true>(a, st) : launch_mlp_pp<128, false, true, 0, true>(a, st);
     if (desc->plan == 2) {      // the two-tile assembly kernel (csrc/asm/gen_mlp_tt.py): same records, bit for bit
         PnrTTArgs t;
         memset(&t, 0, sizeof(t));
@@ -1085,10 +1232,12 @@ PNR_EXPORT int pnr_composite_combine(const pnr_mlp_desc* desc, const void* works
     if (n_rays == 0) return PNR_OK;
     PNR_REQUIRE(workspace && z, "pnr_composite_combine: null pointer");
     PNR_REQUIRE((!fix_sem || label_sem) && (!fix_inst || label_inst), "pnr_composite_combine: fix_* outputs need their labels");
-    const int rf = pnr_fuse_record_floats(desc->n_sem, desc->n_inst);
+    PNR_REQUIRE(desc->plan != 3 || (!rgb && !sem && !inst), "pnr_composite_combine: a plan-3 (sigma-only) workspace has no rgb, semantic "
+                "or instance maps: pass null for them");
+    const int rf = record_floats(*desc);
     const int64_t tiles = (n_rays * n_samples + 255) / 256 * 8;
     const float* rec = (const float*)workspace;
-    return pnr_composite_combine_launch(rec, rf, (const float4*)(rec + tiles * rf), z, fix_sem ? label_sem : nullptr,
+    return pnr_composite_combine_launch(rec, rf, desc->plan != 3, (const float4*)(rec + tiles * rf), z, fix_sem ? label_sem : nullptr,
                                         fix_inst ? label_inst : nullptr, n_rays, n_samples, desc->n_sem, desc->n_inst, white_bkgd,
                                         rgb, depth, acc, weights, sem, inst, fix_sem, fix_inst, (hipStream_t)stream);
 }
@@ -1103,10 +1252,12 @@ PNR_EXPORT int pnr_mlp_forward_composite(const pnr_mlp_desc* desc, const void* p
     PNR_REQUIRE(n_rays >= 0, "pnr_mlp_forward_composite: bad size");
     if (n_rays == 0) return PNR_OK;
     PNR_REQUIRE((!fix_sem || label_sem) && (!fix_inst || label_inst), "pnr_mlp_forward_composite: fix_* outputs need their labels");
+    PNR_REQUIRE(!desc || desc->plan != 3 || (!rgb && !sem && !inst), "pnr_mlp_forward_composite: a plan-3 (sigma-only) image has no "
+                "rgb, semantic or instance maps: pass null for them");
     MlpArgs a;
     int rc = fused_mlp_launch(desc, packed, rays, z, n_rays, n_samples, workspace, stream, a);
     if (rc != PNR_OK) return rc;
-    return pnr_composite_combine_launch(a.rec, a.rec_floats, a.ps, z, fix_sem ? label_sem : nullptr, fix_inst ? label_inst : nullptr,
+    return pnr_composite_combine_launch(a.rec, a.rec_floats, desc->plan != 3, a.ps, z, fix_sem ? label_sem : nullptr, fix_inst ? label_inst : nullptr,
                                         n_rays, n_samples, desc->n_sem, desc->n_inst, white_bkgd, rgb, depth, acc, weights, sem, inst,
                                         fix_sem, fix_inst, (hipStream_t)stream);
 }

@@ -33,8 +33,9 @@ int pnr_mlp_validate(const pnr_mlp_desc* d)
 #define PNR_TRAIN_TILES_EXPERIMENT 0
 #endif
     PNR_REQUIRE(d->schedule >= 0 && d->schedule <= (PNR_TRAIN_TILES_EXPERIMENT ? 6 : 2), "pnr_mlp: schedule=%d must be 0 (default), 1 (lock-step) or 2 (ping-pong)", d->schedule);
-    PNR_REQUIRE(d->plan == 0 || (d->plan == 1 && pnr_plan1_supported(*d)) || (d->plan == 2 && pnr_plan2_supported(*d)),
-                "pnr_mlp: plan=%d is not available for this geometry (ask pnr_mlp_fused_plan)", d->plan);
+    PNR_REQUIRE(d->plan == 0 || (d->plan == 1 && pnr_plan1_supported(*d)) || (d->plan == 2 && pnr_plan2_supported(*d)) ||
+                (d->plan == 3 && pnr_plan3_supported(*d)),
+                "pnr_mlp: plan=%d is not available for this geometry (ask pnr_mlp_fused_plan; plan 3: bf16 only)", d->plan);
     // the descriptor must be zero-initialised (include/pnr.h): the diagnostic words are READ -- clk_probe is a device address the
     // forward kernels store 16 bytes to, flags select kernels -- so garbage there is rejected where it can be recognised
     const uint32_t trace = (uint32_t)d->flags & 0xFF00u;
@@ -72,6 +73,10 @@ static int bwd_validate(const pnr_mlp_desc* d)
 static int check_params(const pnr_mlp_desc* desc, const pnr_mlp_params_host* p, bool bias)
 {
     PNR_REQUIRE(p, "pnr_mlp_pack: null params");
+    if (desc->plan == 3) {      // the sigma-only image reads the trunk and alpha_linear alone
+        PNR_REQUIRE(p->pts_w && p->alpha_w && (!bias || (p->pts_b && p->alpha_b)), "pnr_mlp_pack: missing trunk or alpha_linear parameter");
+        return PNR_OK;
+    }
     PNR_REQUIRE(p->pts_w && p->alpha_w && p->feature_w && p->views_w && p->rgb_w, "pnr_mlp_pack: missing trunk parameter");
     if (bias) PNR_REQUIRE(p->pts_b && p->alpha_b && p->feature_b && p->views_b && p->rgb_b, "pnr_mlp_pack: missing trunk bias");
     const bool deep = pnr_head_depth(*desc) == 2;
@@ -154,6 +159,7 @@ static void describe_forward(const pnr_mlp_desc& d, const pnr_mlp_params_host& p
                         if (seg == 0) { f.src = p.rgb_w; f.ld = H; f.lo = 0; f.hi = 3; f.off = 0; }             // rows 0..2 <- g
                         else { f.src = p.alpha_w; f.ld = W; f.lo = 3; f.hi = 4; f.off = 3; }                    // row 3 <- h
                         break;
+                    case PNR_L_SIGMA: f.src = p.alpha_w; f.ld = W; f.lo = 3; f.hi = 4; f.off = 3; break;        // the h fragments above
                     }
                     im.frags.push_back(f);
                 }
@@ -172,6 +178,7 @@ static void describe_forward(const pnr_mlp_desc& d, const pnr_mlp_params_host& p
         case PNR_L_FEATURE: b.src = p.feature_b; break;
         case PNR_L_VIEWS: b.src = p.views_b; break;
         case PNR_L_RGBSIGMA: b.src = p.rgb_b; b.lo = 0; b.hi = 3; b.src2 = p.alpha_b; b.lo2 = 3; b.hi2 = 4; b.off2 = 3; break;
+        case PNR_L_SIGMA: b.src = p.alpha_b; b.lo = 3; b.hi = 4; b.off = 3; break;
         case PNR_L_LOGITS:      // rows [0, 32 nbs): sem1's bias; rows 32 nbs + [0, n_inst): inst1's
             b.src = p.sem1_b; b.lo = 0; b.hi = d.n_sem; b.off = 0;
             b.src2 = p.inst1_b; b.lo2 = L.index * 32; b.hi2 = L.index * 32 + d.n_inst; b.off2 = L.index * 32;

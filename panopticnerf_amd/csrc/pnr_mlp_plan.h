@@ -8,6 +8,9 @@
 //                              as ONE chunk EACH (all blocks of the layer), and no chunk above 33 fragments -- a layer whose 2-block chunk would be larger (the layer behind
 //                              the skip: 2 x 20 + 1, views: 2 x 18 + 1) is cut into 1-block chunks -- so that FOUR weight slots fit
 //                              the LDS; the number of chunks is then a multiple of 4 (slot = chunk % 4 is static)
+//   plan 3 (sigma only, k_mlp_pp_sigma): trunk 0..D-1 chunked as in plan 1 (layer 0 as one chunk) | sigma: ONE 32-row block whose
+//                              row 3 is alpha_linear over h (the h segment of the rgb+sigma block, same fragments) and every
+//                              other row zero -- what an inference level that is read only for its weights needs
 #pragma once
 #include <stddef.h>
 
@@ -39,6 +42,7 @@ static inline int pnr_plan2_supported(const pnr_mlp_desc& d)
 #ifndef PNR_PLAN1_TRUNK0_MERGE
 #define PNR_PLAN1_TRUNK0_MERGE 1
 #endif
+
 struct PnrLayer {
     int kind, index;       // index: trunk layer number; PNR_L_LOGITS: number of semantic blocks
     int out_dim, n_fb;     // output rows, 32-row blocks
@@ -66,7 +70,7 @@ static inline void pnr_build_plan(const pnr_mlp_desc& d, PnrPlan& plan)
         L.nks = pnr_seg_vl(k0, n0) / kpl + (k1 >= 0 ? pnr_seg_vl(k1, n1) / kpl : 0);
         L.fbc = pnr_layer_fbc(kind, d.precision);
         if (L.n_fb % L.fbc) L.fbc = 1;
-        if (PNR_PLAN1_TRUNK0_MERGE && d.plan >= 1 && kind == PNR_L_TRUNK0) L.fbc = L.n_fb;      // plan 1, 2: layer 0 is ONE chunk of W/32 blocks x 4 k-steps
+        if (PNR_PLAN1_TRUNK0_MERGE && d.plan >= 1 && kind == PNR_L_TRUNK0) L.fbc = L.n_fb;      // plan 1, 2, 3: layer 0 is ONE chunk of W/32 blocks x 4 k-steps
         if (d.plan == 2 && (kind == PNR_L_SEM1 || kind == PNR_L_INST1)) L.fbc = L.n_fb;         // plan 2: a logit layer is one chunk
         if (d.plan == 2 && L.fbc * L.nks + 1 > PNR_PLAN2_MAX_CHUNK_FRAGS) L.fbc = 1;            // plan 2: four slots must fit the LDS
         plan.layers.push_back(L);
@@ -78,33 +82,38 @@ static inline void pnr_build_plan(const pnr_mlp_desc& d, PnrPlan& plan)
         else if (i - 1 == d.skip) add(PNR_L_TRUNK, i, d.W, PNR_SEG_GX, 0, PNR_SEG_FEAT, d.W);
         else add(PNR_L_TRUNK, i, d.W, PNR_SEG_FEAT, d.W);
     }
-    // appearance first, panoptic heads last: sigma (hence every sample's compositing weight) is known before the logit
-    // blocks are produced, which is what lets the fused inference epilogue reduce them over the ray on the fly
-    add(PNR_L_FEATURE, 0, d.W, PNR_SEG_FEAT, d.W);
-    add(PNR_L_VIEWS, 0, d.W / 2, PNR_SEG_FEAT, d.W, PNR_SEG_GD, 0);
-    add(PNR_L_RGBSIGMA, 0, 4, PNR_SEG_FEAT, d.W / 2, PNR_SEG_FEAT, d.W);
-    if (d.plan == 1) {
-        const int nbs = (d.n_sem + 31) / 32, nbi = (d.n_inst + 31) / 32;
-        if (d.n_sem) add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-        if (d.n_inst) add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-        add(PNR_L_LOGITS, nbs, (nbs + nbi) * 32, PNR_SEG_FEAT, d.head_W);
-        plan.layers.back().fbc = nbs + nbi;         // every logit block in one chunk
-    } else if (d.plan == 2 && pnr_head_depth(d) == 2) {
-        if (d.n_sem) add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-        if (d.n_inst) add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-        if (d.n_sem) add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.head_W);
-        if (d.n_inst) add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.head_W);
-    } else if (pnr_head_depth(d) == 1) {      // one Linear per head, straight from the tap (W inputs)
-        if (d.n_sem) add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.W);
-        if (d.n_inst) add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.W);
+    if (d.plan == 3) {
+        // plan 3: the sigma row alone, over h -- rows 0..2 (rgb) are zero, so the quadruples the fused epilogue writes are (lw, 0, 0, 0)
+        add(PNR_L_SIGMA, 0, 4, PNR_SEG_FEAT, d.W);
     } else {
-        if (d.n_sem) {
-            add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-            add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.head_W);
-        }
-        if (d.n_inst) {
-            add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
-            add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.head_W);
+        // appearance first, panoptic heads last: sigma (hence every sample's compositing weight) is known before the logit
+        // blocks are produced, which is what lets the fused inference epilogue reduce them over the ray on the fly
+        add(PNR_L_FEATURE, 0, d.W, PNR_SEG_FEAT, d.W);
+        add(PNR_L_VIEWS, 0, d.W / 2, PNR_SEG_FEAT, d.W, PNR_SEG_GD, 0);
+        add(PNR_L_RGBSIGMA, 0, 4, PNR_SEG_FEAT, d.W / 2, PNR_SEG_FEAT, d.W);
+        if (d.plan == 1) {
+            const int nbs = (d.n_sem + 31) / 32, nbi = (d.n_inst + 31) / 32;
+            if (d.n_sem) add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+            if (d.n_inst) add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+            add(PNR_L_LOGITS, nbs, (nbs + nbi) * 32, PNR_SEG_FEAT, d.head_W);
+            plan.layers.back().fbc = nbs + nbi;         // every logit block in one chunk
+        } else if (d.plan == 2 && pnr_head_depth(d) == 2) {
+            if (d.n_sem) add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+            if (d.n_inst) add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+            if (d.n_sem) add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.head_W);
+            if (d.n_inst) add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.head_W);
+        } else if (pnr_head_depth(d) == 1) {      // one Linear per head, straight from the tap (W inputs)
+            if (d.n_sem) add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.W);
+            if (d.n_inst) add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.W);
+        } else {
+            if (d.n_sem) {
+                add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+                add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, d.head_W);
+            }
+            if (d.n_inst) {
+                add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+                add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, d.head_W);
+            }
         }
     }
     int off = 0, mx = 0;
@@ -123,6 +132,18 @@ static inline void pnr_build_plan(const pnr_mlp_desc& d, PnrPlan& plan)
     size_t t = plan.table_off + plan.chunks.size() * sizeof(pnr_chunk_entry);
     plan.data_off = (t + 1023) & ~(size_t)1023;
     plan.total_bytes = plan.data_off + (size_t)off * PNR_FRAG_BYTES;
+}
+
+// plan 3 (the sigma-only image) exists for: bf16, W = 128 or 256 (the ping-pong kernel's widths), and at least the 4 chunks
+// its three-slot weight stream needs (launch_mlp_pp).  Opt-in: pnr_mlp_fused_plan never answers 3.
+static inline int pnr_plan3_supported(const pnr_mlp_desc& d)
+{
+    if (d.precision != PNR_PREC_BF16 || (d.W != 128 && d.W != 256)) return 0;
+    pnr_mlp_desc d3 = d;
+    d3.plan = 3;
+    PnrPlan plan;
+    pnr_build_plan(d3, plan);
+    return plan.chunks.size() >= 4;
 }
 
 // ---- backward (dgrad) plan, bf16 only.  Every backward layer computes  dX^T = W^T * dY^T  for one tensor X:

@@ -478,10 +478,11 @@ def composite(raw, z, rays, n_sem=0, n_inst=0, channel_major=True, noise=None, l
     return out
 
 
-def _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev):
+def _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev, drop=()):
     """The per-ray output tensors of a compositing call.  `out`: optional dict of caller-owned tensors (e.g. row slices of
     frame-sized maps: Renderer.render hands every chunk its slice, so a frame is never concatenated); anything it lacks is
-    allocated.  Caller-owned tensors must be contiguous fp32 of the exact shape on the right device."""
+    allocated.  Caller-owned tensors must be contiguous fp32 of the exact shape on the right device.  drop: keys the call does
+    not produce (mlp_forward_weights: rgb, semantic, instance)."""
     f32 = dict(device=dev, dtype=torch.float32)
     shapes = {"rgb": (R, 3), "depth": (R,), "acc": (R,)}
     if want_weights:
@@ -494,6 +495,8 @@ def _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev):
         shapes["instance"] = (R, n_inst)
         if label_inst is not None:
             shapes["fix_instance"] = (R, n_inst)
+    for k in drop:
+        shapes.pop(k, None)
     res = {}
     for k, shp in shapes.items():
         t = out.get(k) if out else None
@@ -565,6 +568,47 @@ def mlp_forward_composite(desc, packed, rays, z, label_sem=None, label_inst=None
                                              int(bool(white_bkgd)), _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]),
                                              _p(g("weights")), _p(g("semantic")), _p(g("instance")), _p(g("fix_semantic")),
                                              _p(g("fix_instance")), _p(ws), _stream()), "pnr_mlp_forward_composite")
+    return out
+
+
+WEIGHTS_ONLY_DROPS = ("rgb", "semantic", "instance")      # the maps a level rendered for its weights alone does not have
+
+
+def sigma_pass_supported(desc, n_samples, noise=None):
+    """Can mlp_forward_weights take this level?  bf16, no sigma noise, N a multiple of 32 in [32, 256], n_sem + n_inst <= 128 (the
+    fix_* histograms), and a geometry with a plan-3 image (net.packed(level, device, fused="sigma"))."""
+    if not (desc.precision == _lib.PREC_BF16 and noise is None and n_samples % 32 == 0 and 32 <= n_samples <= 256
+            and desc.n_sem + desc.n_inst <= 128):
+        return False
+    d3 = _lib.MlpDesc()
+    ctypes.memmove(ctypes.byref(d3), ctypes.byref(desc), ctypes.sizeof(d3))
+    d3.plan = 3
+    return int(_lib.load().pnr_mlp_packed_bytes(ctypes.byref(d3))) > 0
+
+
+@_on_device
+def mlp_forward_weights(desc, packed, rays, z, label_sem=None, label_inst=None, out=None):
+    """The compositing weights of a level and nothing else (inference): pnr_mlp_forward_composite on a plan-3 image
+    (net.packed(level, device, fused="sigma")), whose kernel runs the trunk and the sigma row alone -- no feature, views, rgb or
+    head layers.  Returns {depth, acc, weights[, fix_semantic][, fix_instance]}: bit for bit what mlp_forward_composite returns
+    for these keys on any other plan of the same network."""
+    if desc.plan != 3:
+        raise ValueError("mlp_forward_weights: needs the plan-3 image (net.packed(level, device, fused='sigma')), not plan %d" % desc.plan)
+    rays, z, packed = _chk(rays, "rays"), _chk(z, "z"), _chk(packed, "packed", torch.uint8)
+    label_sem = _chk(label_sem, "label_sem", torch.int32)
+    label_inst = _chk(label_inst, "label_inst", torch.int32)
+    R, N = z.shape
+    dev = z.device
+    lib = _lib.load()
+    nbytes = lib.pnr_mlp_forward_composite_workspace_bytes(ctypes.byref(desc), R, N, 1)
+    if nbytes < 0:
+        raise RuntimeError("pnr_mlp_forward_composite: unsupported geometry (n_samples=%d must be a multiple of 32)" % N)
+    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+    out = _maps(out, R, N, desc.n_sem, desc.n_inst, label_sem, label_inst, True, dev, drop=WEIGHTS_ONLY_DROPS)
+    g = out.get
+    _lib.check(lib.pnr_mlp_forward_composite(ctypes.byref(desc), _p(packed), _p(rays), _p(z), R, N, _p(label_sem), _p(label_inst),
+                                             0, None, _p(out["depth"]), _p(out["acc"]), _p(out["weights"]), None, None,
+                                             _p(g("fix_semantic")), _p(g("fix_instance")), _p(ws), _stream()), "pnr_mlp_forward_composite")
     return out
 
 

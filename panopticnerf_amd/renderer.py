@@ -15,6 +15,7 @@ batch keys:  "rays" (B,N_rays,8) = o,d,near,far  (required)
 output keys, level l in {0 (coarse), 1 (fine)}:
              rgb_l (B,N_rays,3) depth_l acc_l (B,N_rays) weights_l z_vals_l (B,N_rays,N_l)
              semantic_l / fix_semantic_l (B,N_rays,C), instance_l / fix_instance_l (B,N_rays,K)
+             cfg.coarse_outputs = "weights" (inference with a fine level): no rgb_0, semantic_0, instance_0
 """
 import os
 
@@ -78,6 +79,16 @@ class Renderer:
         # cfg.fuse_composite = False (or PNR_FUSE=0) keeps the two-kernel path with the raw image in HBM
         self.fuse = bool(_get(cfg, "fuse_composite", os.environ.get("PNR_FUSE", "1") != "0"))
         self.strict_hits = bool(_get(cfg, "strict_hits", False))
+        # "all": every map of both levels.  "weights": an inference render (no autograd) returns the coarse level only for what the
+        # fine level and the bbox prior read of it -- z_vals_0, weights_0, depth_0, acc_0 and fix_*_0 -- and evaluates it with the
+        # sigma-only kernel (trunk + alpha_linear: ops.mlp_forward_weights) where that applies, bit for bit the same values; rgb_0,
+        # semantic_0 and instance_0 are absent.  Under autograd (training) the switch has no effect: the losses read the coarse maps.
+        self.coarse_outputs = _get(cfg, "coarse_outputs", "all")
+        if self.coarse_outputs not in ("all", "weights"):
+            raise ValueError("cfg.coarse_outputs must be 'all' or 'weights', not %r" % (self.coarse_outputs,))
+        if self.coarse_outputs == "weights" and self.N_importance <= 0:
+            raise ValueError("cfg.coarse_outputs = 'weights' needs a fine level (N_importance > 0): without one the coarse maps are "
+                             "the render's output")
         # "none": stratified over [near, far] (canonical NeRF); "hull": rays that hit boxes are sampled over the hull of their
         # hit intervals (SURVEY.md 9 item 2 -- which of the two the reference does is unverifiable here: a switch)
         self.bbox_sampling = _get(cfg, "bbox_sampling", "none")
@@ -167,6 +178,17 @@ class Renderer:
             if grad:
                 from . import train as _train       # autograd path
                 res = _train.level_train(self, lv, rays, zz, ls, li, noise)
+            elif lv == 0 and self.coarse_outputs == "weights":
+                mine = {k: own(f"{k}_0") for k in ("depth", "acc", "weights", "fix_semantic", "fix_instance")}
+                mine = {k: v for k, v in mine.items() if v is not None}
+                if self.fuse and ops.sigma_pass_supported(n0.desc(net.precision), zz.shape[1], noise):
+                    desc, img = net.packed(0, dev, fused="sigma")          # trunk + sigma only (pnr_mlp_forward_composite, plan 3)
+                    res = ops.mlp_forward_weights(desc, img, rays, zz, ls, li, out=mine)
+                else:       # fp32, sigma noise, an N the fused pass does not take: the full level, its maps dropped
+                    desc, img = net.packed(0, dev)
+                    raw = ops.mlp_forward(desc, img, rays, zz, channel_major=True)
+                    res = ops.composite(raw, zz, rays, C, K, True, noise, ls, li, self.sem_mode, self.white_bkgd, True, out=mine)
+                    res = {k: v for k, v in res.items() if k not in ops.WEIGHTS_ONLY_DROPS}
             else:
                 need_w = self.keep_weights or (lv == 0 and Nf > 0)
                 mine = {k: own(f"{k}_{lv}") for k in ("rgb", "depth", "acc", "weights", "semantic", "instance", "fix_semantic", "fix_instance")}
@@ -206,7 +228,7 @@ class Renderer:
             level(1, z_fine, lab1)
         return ret
 
-    def _empty_outputs(self, lead, has_box, dev):
+    def _empty_outputs(self, lead, has_box, dev, grad=False):
         """render() of zero rays: every output key of a non-empty call, with zero rows and no launch (the edge case a caller
         hits with an empty shard: n_rays < world, or a mask that selects nothing)."""
         n0 = self.net.nerf(0)
@@ -214,7 +236,8 @@ class Renderer:
         ret = {}
         for lv, N in ((0, self.N_samples),) + (((1, self.N_samples + self.N_importance),) if self.N_importance > 0 else ()):
             need_w = self.keep_weights or (lv == 0 and self.N_importance > 0)
-            m = ops._maps(None, 0, N, C, K, True if has_box else None, True if has_box else None, need_w, dev)
+            drop = ops.WEIGHTS_ONLY_DROPS if (lv == 0 and not grad and self.coarse_outputs == "weights") else ()
+            m = ops._maps(None, 0, N, C, K, True if has_box else None, True if has_box else None, need_w, dev, drop=drop)
             m["z_vals"] = torch.empty((0, N), device=dev, dtype=torch.float32)
             for k, v in m.items():
                 ret[f"{k}_{lv}"] = v.reshape(*lead, *v.shape[1:])
@@ -226,10 +249,11 @@ class Renderer:
         on the two-tile kernel (the only launch that takes PNR_MLP_WG_CAP), frame-sized outputs, and a device whose compute units
         split into two multiples of 8 (one per XCD: the dispatcher deals workgroups round-robin over the 8 XCDs, and a ninth
         workgroup on a 32-CU XCD waits for a whole launch -- 196 + 60 took 25 ms where 192 + 64 takes 14.2, tools/overlap_probe.py) in
-        the ratio of the levels' samples within 5 %."""
+        the ratio of the levels' samples within 5 %.  Not with cfg.coarse_outputs = "weights": the sigma-only coarse kernel takes no
+        workgroup cap, and the split above assumes the same cost per sample at both levels -- such frames run serially."""
         if (not self.overlap_levels or grad or train or len(plan) < 2 or not self.fuse or not self.frame_outputs or self.N_importance <= 0
                 or self.strict_hits or t_rand is not None or u is not None or self.raw_noise_std > 0 and train
-                or torch.cuda.is_current_stream_capturing()):
+                or self.coarse_outputs == "weights" or torch.cuda.is_current_stream_capturing()):
             return None
         net, Nc, Nt = self.net, self.N_samples, self.N_samples + self.N_importance
         for lv, N in ((0, Nc), (1, Nt)):
@@ -320,7 +344,7 @@ class Renderer:
         train = self.net.training
         self._overflow = None
         if R == 0:
-            return self._empty_outputs(lead, box is not None, rays.device)
+            return self._empty_outputs(lead, box is not None, rays.device, grad)
         plan = chunk_plan(R, self.chunk_size)
         caps = self._overlap_caps(rays.device, plan, grad, train, box is not None, t_rand, u)
         if caps is not None:
