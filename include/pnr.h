@@ -76,7 +76,7 @@ typedef struct pnr_mlp_desc {
     int32_t precision; /* PNR_PREC_* */
     int32_t plan;      /* chunk order of the packed image: 0 = classic (every kernel); 1 = fused-inference order, 2 = two-tile order,
                           see pnr_mlp_fused_plan; 3 = sigma only (opt-in, below) -- only pnr_mlp_forward_composite / _tiles /
-                          pnr_composite_combine accept 1..3 */
+                          pnr_composite_combine accept 1..3; 4 = field query (opt-in) -- only pnr_mlp_query accepts it */
     int32_t head_tap;  /* what the semantic / instance heads read: 0 = the trunk output h (default), 1 = the feature_linear
                           output (the reference's tap point cannot be checked here, so it is a switch) */
     int32_t head_depth;/* 0 or 2 = W -> head_W -> n (ReLU between; default), 1 = one Linear W -> n */
@@ -198,6 +198,33 @@ int pnr_mlp_forward_tiles(const pnr_mlp_desc* desc, const void* packed, const fl
 int pnr_composite_combine(const pnr_mlp_desc* desc, const void* workspace, const float* z, int64_t n_rays, int n_samples,
                           const int32_t* label_sem, const int32_t* label_inst, int white_bkgd, float* rgb, float* depth,
                           float* acc, float* weights, float* sem, float* inst, float* fix_sem, float* fix_inst, void* stream);
+
+/* Field query: what the network holds AT A 3D POINT -- density and the two panoptic distributions, none of which reads a view
+ * direction (no ray, no z, no rgb).  Needs the plan-4 image (never returned by pnr_mlp_fused_plan: set desc.plan = 4 yourself
+ * before pnr_mlp_packed_bytes / pnr_mlp_pack*; bf16, W = 128 or 256, every trunk plan 3 takes, heads of any width up to 256):
+ * plan 3's chunks (trunk, layer 0 as one chunk; the sigma block), then feature_linear where head_tap = 1 and a head exists, then
+ * the head layers chunked as in plan 0.  Every fragment is plan 0's fragment of the same layer, block and k-step, and the kernel
+ * (k_mlp_pp_field) multiplies them in plan 0's order: sigma and the logits are BIT FOR BIT rows 3, 4.., 4 + n_sem.. of
+ * pnr_mlp_forward's raw image at the same fp32 position (a ray with o = point, z = 0).  pnr_mlp_pack* read pts_*, alpha_*, the
+ * heads, and feature_* only where it is in the image.
+ *   points      (n_points, 3) fp32, contiguous.  0 <= n_points < 2^31 - 4096 per call; n_points = 0 returns PNR_OK at once.
+ *   sigma       (n_points) fp32: the raw pre-activation density (no relu, no noise), or NULL.
+ *   sem_label, inst_label, panoptic   (n_points) int32 or NULL: argmax of the head's logits taken in registers -- the largest value,
+ *               the lowest index among equals, a NaN read as -inf (the rule of pnr_panoptic_labels).  With is_thing (int32[n_sem])
+ *               inst_label = -1 where the point's semantic class is not a thing; panoptic = class * 1000 + instance, or the class
+ *               where there is no instance (pnr_panoptic_labels' contract; with no instance head panoptic = class).
+ *   sem_logits  (n_sem, logit_stride), inst_logits (n_inst, logit_stride) fp32 channel-major, logit_stride >= n_points, or NULL.
+ * Any subset of the outputs (at least one); a NULL output is never written, and layers no requested output needs are not
+ * evaluated or streamed (sigma alone: trunk + alpha_linear; semantic outputs alone: no instance head; instance outputs of a
+ * two-head network evaluate the semantic head as well -- the weight stream is sequential).  A point's outputs depend on that
+ * point alone.  PNR_EINVAL before any device work for a bad argument (null desc / packed / points, every output null, an output or
+ * is_thing for a head the descriptor lacks, logit_stride < n_points, plan != 4, not bf16, unsupported geometry).  Never
+ * synchronises; capture-safe after one eager call per geometry.
+ * pnr_mlp_query_supported: host only, 1 where the kernel exists for desc's geometry (desc.plan is ignored). */
+int pnr_mlp_query(const pnr_mlp_desc* desc, const void* packed, const float* points, int64_t n_points,
+                  float* sigma, int32_t* sem_label, int32_t* inst_label, int32_t* panoptic, const int32_t* is_thing,
+                  float* sem_logits, float* inst_logits, int64_t logit_stride, void* stream);
+int pnr_mlp_query_supported(const pnr_mlp_desc* desc);
 
 /* ---- a9 (training): forward that also saves what the backward needs, the data-gradient pass, and the
  * buffer layouts.  bf16 only; n_sem, n_inst <= 64.

@@ -115,6 +115,8 @@ SIGNATURES = {
                                   c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_composite_backward_rng": (c_int, [c_f, c_i64, c_f, c_f, ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_int, c_int,
                                            c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_mlp_query": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_f]),
+    "pnr_mlp_query_supported": (c_int, [ctypes.POINTER(MlpDesc)]),
     "pnr_composite_combine": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_i64, c_int, c_f, c_f, c_int,
                                       c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
 }

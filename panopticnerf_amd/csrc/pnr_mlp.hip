@@ -41,6 +41,11 @@ int pnr_mlp_validate(const pnr_mlp_desc* d);
 #endif
 #include "pnr_mlp_fuse.h"
 #include "pnr_mlp_tt.h"
+// vector-memory instructions hipcc emits for k_mlp_pp_field's fetch() (one point = three floats; tools/asm_lint.py counts them on
+// the compiled assembly): what the m_done() behind it leaves outstanding
+#define PNR_FIELD_FETCH_LOADS 1
+#define PNR_FIELD_FETCH_LOADS_S "1"
+#define PNR_QUERY_MAX_POINTS (((int64_t)1 << 31) - 4096)
 #ifndef PNR_OPT_EAGER_EPI
 #define PNR_OPT_EAGER_EPI 1
 #endif
@@ -1036,6 +1041,7 @@ static int mlp_forward_impl(const pnr_mlp_desc* desc, const void* packed, const 
     PNR_REQUIRE((((uintptr_t)rays) & 15) == 0 && (((uintptr_t)packed) & 15) == 0 && (((uintptr_t)acts) & 15) == 0,
                 "pnr_mlp_forward: rays / packed / acts must be 16-byte aligned");
     PNR_REQUIRE(!acts || desc->precision == PNR_PREC_BF16, "pnr_mlp_forward_train: the training path is bf16 only");
+    PNR_REQUIRE(desc->plan != 4, "pnr_mlp_forward: a plan-4 (field) image is for pnr_mlp_query only");
     PNR_REQUIRE(desc->plan == 0, "pnr_mlp_forward: plan=%d images are for pnr_mlp_forward_composite only", desc->plan);
     PnrPlan plan;
     pnr_build_plan(*desc, plan);
@@ -1146,6 +1152,7 @@ static int fused_mlp_launch(const pnr_mlp_desc* desc, const void* packed, const 
     int rc = pnr_mlp_validate(desc);
     if (rc != PNR_OK) return rc;
     PNR_REQUIRE(desc->precision == PNR_PREC_BF16, "pnr_mlp_forward_composite: bf16 only");
+    PNR_REQUIRE(desc->plan != 4, "pnr_mlp_forward_composite: a plan-4 (field) image is for pnr_mlp_query only");
     PNR_REQUIRE(n_rays >= 1 && n_samples >= 32 && n_samples <= 256 && (n_samples & 31) == 0,
                 "pnr_mlp_forward_composite: n_samples=%d must be a multiple of 32 in [32,256]", n_samples);
     PNR_REQUIRE(desc->n_sem + desc->n_inst <= 128, "pnr_mlp_forward_composite: n_sem + n_inst <= 128");
@@ -1231,6 +1238,7 @@ PNR_EXPORT int pnr_composite_combine(const pnr_mlp_desc* desc, const void* works
     PNR_REQUIRE(n_rays >= 0 && n_samples >= 32 && n_samples <= 256 && (n_samples & 31) == 0, "pnr_composite_combine: bad size");
     if (n_rays == 0) return PNR_OK;
     PNR_REQUIRE(workspace && z, "pnr_composite_combine: null pointer");
+    PNR_REQUIRE(desc->plan != 4, "pnr_composite_combine: a plan-4 (field) image has no compositing workspace");
     PNR_REQUIRE((!fix_sem || label_sem) && (!fix_inst || label_inst), "pnr_composite_combine: fix_* outputs need their labels");
     PNR_REQUIRE(desc->plan != 3 || (!rgb && !sem && !inst), "pnr_composite_combine: a plan-3 (sigma-only) workspace has no rgb, semantic "
                 "or instance maps: pass null for them");
@@ -1281,4 +1289,291 @@ PNR_EXPORT int pnr_mlp_train_layout(const pnr_mlp_desc* desc, int64_t n_samples,
     memcpy(acts_off_host, a, sizeof(int64_t) * (size_t)(desc->D + 7));
     memcpy(dys_off_host, d, sizeof(int64_t) * (size_t)(desc->D + 8));
     return PNR_OK;
+}
+
+// ------------------------------------------------------------------------------- field query (plan 4)
+// What the network holds at a 3D point: sigma and the two panoptic heads, which read no view direction.  k_mlp_pp_sigma<W> with
+// POINTS at the input (no ray record, no z, no |d|, no gamma(d)), the heads behind the sigma block and an argmax at the output:
+//   trunk | sigma block (row 3 = alpha_linear over h) | [feature_linear, head_tap 1] | [sem0] sem1 | [inst0] inst1
+// over the plan-4 image, whose fragments are plan 0's for every layer it has -- so sigma and the logits are the bits of
+// pnr_mlp_forward's raw rows 3, 4.. at the same position.  A query streams the PREFIX of the image its outputs need
+// (MlpArgs::n_chunks = pnr_field_chunks): nothing behind sigma for a sigma-only query, nothing of the instance head for a
+// semantic-only one.  (An instance-only query of a two-head network evaluates the semantic head too and drops it: the stream is
+// sequential.)
+// The output blocks are computed UNTRANSPOSED, as the classic pass computes them (lane = sample, register r = channel
+// fb * 32 + row(r, hi)) and not in the fused epilogue's transposed form: that is the layout whose sums are the classic pass's by
+// construction, a channel-major logit store from it is coalesced (32 consecutive samples per row), and the argmax over a head
+// is 16 in-lane compares per block in ascending channel order plus ONE exchange between the half-waves per head
+// (v_permlane32_swap), where the transposed form would need a 32-lane butterfly per sample row.
+// Rule of the argmax = pnr_argmax16 (pnr_post.hip): the largest value, the lowest channel among equals, a NaN read as -inf,
+// channel 0 for a row without a non-NaN value.
+// No address depends on a point's VALUE: positions enter arithmetic only (embed_*), the stores are indexed by the sample number,
+// and the is_thing lookup by a label that is in [0, n_sem) by construction.
+struct FieldArgs {
+    MlpArgs m;                       // weight stream and geometry; S = points; rays / z / raw / rec unused
+    const float* pts;                // (S, 3)
+    float* sigma;                    // (S) or null
+    int32_t* sem_label; int32_t* inst_label; int32_t* panoptic;      // (S) each or null
+    const int32_t* is_thing;         // [n_sem] or null
+    float* sem_logits; float* inst_logits; int64_t lstride;          // (n, lstride) channel-major or null
+    int run_sem, run_inst;           // the heads this launch evaluates (their chunks are in the stream)
+};
+
+// one output layer of 32-row blocks, untransposed (pp_layer_out's two-kernel form); epi(fb, acc) runs in the L phase behind the
+// first refill piece, where pp_layer_out stores the block
+template <class CTX, int NA, class EPI>
+__device__ __forceinline__ void pp_field_out(CTX& c, u32x4 (&A)[CTX::P], const uint32_t (&in)[NA], int n_out, EPI&& epi)
+{
+    using CH = PPChunk<1, NA, 0>;
+    const uint32_t dummy[1] = {0};
+    const int nfb = (n_out + 31) >> 5;
+#pragma unroll 1
+    for (int fb = 0; fb < nfb; ++fb) {
+        f32x16 acc[1];
+        CH::prologue(c.frag_addr(), c.bias_addr(), A, acc);
+        CH::mma(c.frag_addr(), A, in, dummy, acc, [&](auto... k) { if constexpr (sizeof...(k) == 0) { c.stamp(6); c.barrier(); c.stamp(2); } else c.stamp(k...); });
+        c.m_done();
+        c.refill_begin();
+        c.refill_one();
+        epi(fb, acc[0]);
+        c.refill_rest();
+        c.advance();
+    }
+}
+
+// running argmax of one lane over the channels it holds (ascending), and the merge of the two half-waves of a sample
+struct FieldBest { float v; int i; };
+__device__ __forceinline__ void field_best_merge(FieldBest& b, int hi)
+{
+    const auto pv = __builtin_amdgcn_permlane32_swap(__float_as_uint(b.v), __float_as_uint(b.v), false, false);
+    const auto pi = __builtin_amdgcn_permlane32_swap((uint32_t)b.i, (uint32_t)b.i, false, false);
+    const float ov = __uint_as_float(hi ? pv[0] : pv[1]);       // the partner lane's (lane ^ 32)
+    const int oi = (int)(hi ? pi[0] : pi[1]);
+    if (ov > b.v || (ov == b.v && oi < b.i)) { b.v = ov; b.i = oi; }
+    if (b.i == 0x7fffffff) b.i = 0;                              // no non-NaN value above -inf anywhere: channel 0
+}
+
+// HEADS = false: the sigma-only instance (no head code, fewer registers)
+template <int W, bool HEADS>
+__global__ __launch_bounds__(512, 2) void k_mlp_pp_field(const FieldArgs fa)
+{
+    constexpr int WAVES = 8;
+    using CTX = CtxPP<WAVES>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NFB = W / 32, HFB = W / 64;
+    constexpr int HR = NFB * 8, GR = HFB * 8, GXR = 16;
+    const MlpArgs& a = fa.m;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    CTX c{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
+#if PNR_PP_ABL & 16
+    c.abl_sink = u32x4{0, 0, 0, 0};
+#endif
+#if PNR_TRACE
+    c.tr = reinterpret_cast<unsigned long long*>(smem + 3 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
+    c.titer = 0;
+#endif
+    const int n = c.lane & 31;
+    c.start();
+    unsigned long long clk_c0 = 0, clk_r0 = 0;
+    if (a.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
+
+    uint32_t dummy[1] = {0};
+    u32x4 A[CTX::P];
+    struct PointIn { float x, y, z; };
+    auto fetch = [&](int grp) {             // rows past the end read the last point (computed, never stored)
+        const int s = (grp * WAVES + c.wave) * 32 + n;
+        const int sl = s < a.S ? s : a.S - 1;
+        const float* p = fa.pts + (int64_t)sl * 3;
+        PointIn in;
+        in.x = p[0]; in.y = p[1]; in.z = p[2];
+        return in;
+    };
+    PointIn nextin = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0);
+    uint32_t ex[GXR], exn[GXR];            // gamma(x) of this sample group / of the next one (staged in the last trunk layer)
+    // x + 0: a -0.0 coordinate becomes +0.0, as it does in the classic pass's o + d * z at z = 0 -- the same position, bit for bit
+    embed_lane<PNR_PREC_BF16, 5, 32, GXR>(__fadd_rn(nextin.x, 0.0f), __fadd_rn(nextin.y, 0.0f), __fadd_rn(nextin.z, 0.0f), c.hi, ex);
+
+    for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
+        const int s0 = (grp * WAVES + c.wave) * 32 + n;
+        const int samp = s0 < a.S ? s0 : -1;
+        uint32_t cur[HR], nxt[HR];
+        pp_layer_regs<CTX, PNR_L_TRUNK0, GXR, 0, NFB, MODE_RELU, HR, (PNR_PLAN1_TRUNK0_MERGE ? NFB : 0)>(c, A, ex, dummy, cur, nullptr, s0);
+        auto trunk = [&](int l, const uint32_t (&in)[HR], uint32_t (&out)[HR], auto&& side) {
+            if (l - 1 == a.skip)
+                pp_layer_regs<CTX, PNR_L_TRUNK, GXR, HR, NFB, MODE_RELU, HR>(c, A, ex, in, out, nullptr, s0, side);
+            else
+                pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, nullptr, s0, side);
+        };
+#pragma unroll 1
+        for (int l = 1; l < a.D - 1; ++l) {
+            trunk(l, cur, nxt, NoSide{});
+#pragma unroll
+            for (int i = 0; i < HR; ++i) cur[i] = nxt[i];
+        }
+        // side work of the last trunk layer, as in k_mlp_pp_sigma: the next group's points are requested behind chunk 0's refill
+        // pieces and its gamma(x) is staged in the slots k_mlp_pp gives stages 4..7 in the feature layer
+        const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
+        EmbedSC esc;
+        float q0, q1, q2;
+        auto stage = [&](int k) {
+            switch (k) {
+            case 4: q0 = __fadd_rn(nextin.x, 0.0f); q1 = __fadd_rn(nextin.y, 0.0f); q2 = __fadd_rn(nextin.z, 0.0f);
+                    exn[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
+            case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &exn[1]); break;
+            case 6: embed_next_band(esc); embed_pack_band(esc, &exn[4]); embed_next_band(esc); embed_pack_band(esc, &exn[7]); break;
+            case 7: embed_next_band(esc); embed_pack_band(esc, &exn[10]); embed_next_band(esc); embed_pack_band(esc, &exn[13]); break;
+            default: break;
+            }
+        };
+        auto side = [&](int slot) {
+            if (slot == -1) {
+                // the loads of fetch(), the youngest vector-memory operations of the phase: the next m_done() waits for all but
+                // them (k_mlp_pp's side(-1); tests/test_asm_lint.py checks the count on the compiled assembly)
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
+                nextin = fetch(g2);
+                asm volatile("; PNR_FETCH_END " PNR_FIELD_FETCH_LOADS_S ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                c.pending_stores = PNR_FIELD_FETCH_LOADS;
+            }
+            if (slot < 0) return;
+            constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
+#pragma unroll
+            for (int j = 0; j < PER; ++j) stage(slot * PER + j);
+        };
+        trunk(a.D - 1, cur, nxt, side);
+#pragma unroll
+        for (int i = 0; i < GXR; ++i) ex[i] = exn[i];
+        // sigma: row 3 of the block = register 3 of the hi = 0 half-wave (pnr_row_of)
+        pp_field_out<CTX, HR>(c, A, nxt, 4, [&](int, const f32x16& acc) {
+            if (fa.sigma && samp >= 0 && c.hi == 0) fa.sigma[samp] = acc[3];
+        });
+        if constexpr (HEADS) {
+            if (a.head_tap) {               // the heads read feature_linear's output: it takes h's registers (h is dead)
+                pp_layer_regs<CTX, PNR_L_FEATURE, HR, 0, NFB, MODE_LINEAR, HR>(c, A, nxt, dummy, cur, nullptr, s0);
+#pragma unroll
+                for (int i = 0; i < HR; ++i) nxt[i] = cur[i];
+            }
+            int lab_sem = 0, lab_inst = -1;
+            // the two heads are the same code over consecutive chunks of the stream (PNR_L_SEM0 / PNR_L_INST0 chunk alike)
+#pragma unroll 1
+            for (int hd = 0; hd < 2; ++hd) {
+                if (!(hd ? fa.run_inst : fa.run_sem)) continue;
+                const int n_out = hd ? a.n_inst : a.n_sem;
+                float* const lg = hd ? fa.inst_logits : fa.sem_logits;
+                FieldBest best{-INFINITY, 0x7fffffff};
+                auto epi = [&](int fb, const f32x16& acc) {
+                    const int lim = n_out - 4 * c.hi;               // channel u (of the hi = 0 half) exists iff u < lim
+                    float* const dst0 = lg + ((int64_t)(4 * c.hi) * fa.lstride + (samp >= 0 ? samp : 0));
+                    const bool st = lg != nullptr && samp >= 0;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int u = fb * 32 + (r & 3) + 8 * (r >> 2);
+                        if (u < lim) {
+                            if (st) dst0[(int64_t)u * fa.lstride] = acc[r];
+                            const float v = acc[r] == acc[r] ? acc[r] : -INFINITY;
+                            if (v > best.v) { best.v = v; best.i = u + 4 * c.hi; }
+                        }
+                    }
+                };
+                if (a.head_depth == 1) pp_field_out<CTX, HR>(c, A, nxt, n_out, epi);
+                else {
+                    uint32_t sh[GR];
+                    pp_layer_regs<CTX, PNR_L_SEM0, HR, 0, HFB, MODE_RELU, GR>(c, A, nxt, dummy, sh, nullptr, s0);
+                    pp_field_out<CTX, GR>(c, A, sh, n_out, epi);
+                }
+                field_best_merge(best, c.hi);
+                if (hd) lab_inst = best.i; else lab_sem = best.i;
+            }
+            if (samp >= 0 && c.hi == 0) {
+                // pnr_panoptic_labels' contract: an instance only where the semantic class is a thing (or no table is given)
+                if (fa.is_thing && fa.is_thing[lab_sem] == 0) lab_inst = -1;
+                if (fa.sem_label) fa.sem_label[samp] = lab_sem;
+                if (fa.inst_label) fa.inst_label[samp] = lab_inst;
+                if (fa.panoptic) fa.panoptic[samp] = lab_inst >= 0 ? lab_sem * 1000 + lab_inst : lab_sem;
+            }
+        }
+#if PNR_TRACE
+        ++c.titer;
+#endif
+    }
+    c.end();
+    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
+        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
+        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
+    }
+#if PNR_TRACE
+    __syncthreads();
+    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 3 * a.slot_bytes);
+        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
+    }
+#endif
+}
+
+template <int W, bool HEADS>
+static int launch_field(const FieldArgs& fa0, hipStream_t stream)
+{
+    FieldArgs fa = fa0;
+    const int lds_bytes = 3 * fa.m.slot_bytes + (PNR_TRACE ? 8 * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS * 8 : 0);
+    fa.m.n_groups = (fa.m.S + 255) / 256;
+    auto kern = k_mlp_pp_field<W, HEADS>;
+    static thread_local bool attr_set = false;
+    if (!attr_set) {
+        PNR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
+        attr_set = true;
+    }
+    const int cap = pnr_cu_count();           // one 8-wave workgroup per CU, as k_mlp_pp
+    const int grid = fa.m.n_groups < cap ? fa.m.n_groups : cap;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, fa);
+    PNR_CHECK_LAUNCH("pnr_mlp_query");
+    return PNR_OK;
+}
+
+PNR_EXPORT int pnr_mlp_query(const pnr_mlp_desc* desc, const void* packed, const float* points, int64_t n_points,
+                             float* sigma, int32_t* sem_label, int32_t* inst_label, int32_t* panoptic, const int32_t* is_thing,
+                             float* sem_logits, float* inst_logits, int64_t logit_stride, void* stream)
+{
+    PNR_REQUIRE(desc, "pnr_mlp_query: null descriptor");
+    PNR_REQUIRE(desc->plan == 4, "pnr_mlp_query: needs the plan-4 (field) image, not plan %d", desc->plan);
+    PNR_REQUIRE(desc->precision == PNR_PREC_BF16, "pnr_mlp_query: bf16 only");
+    PNR_REQUIRE(pnr_mlp_query_supported(desc), "pnr_mlp_query: no field-query kernel for this geometry (pnr_mlp_query_supported)");
+    int rc = pnr_mlp_validate(desc);
+    if (rc != PNR_OK) return rc;
+    PNR_REQUIRE(n_points >= 0 && n_points < PNR_QUERY_MAX_POINTS, "pnr_mlp_query: n_points=%lld outside [0, 2^31 - 4096)", (long long)n_points);
+    PNR_REQUIRE(sigma || sem_label || inst_label || panoptic || sem_logits || inst_logits, "pnr_mlp_query: every output is null");
+    PNR_REQUIRE(desc->n_sem > 0 || (!sem_label && !sem_logits && !panoptic),
+                "pnr_mlp_query: sem_label / sem_logits / panoptic need a semantic head (n_sem = 0)");
+    PNR_REQUIRE(desc->n_inst > 0 || (!inst_label && !inst_logits), "pnr_mlp_query: inst_label / inst_logits need an instance head (n_inst = 0)");
+    PNR_REQUIRE(!is_thing || desc->n_sem > 0, "pnr_mlp_query: is_thing needs a semantic head (n_sem = 0)");
+    PNR_REQUIRE((!sem_logits && !inst_logits) || logit_stride >= n_points, "pnr_mlp_query: logit_stride=%lld < n_points=%lld",
+                (long long)logit_stride, (long long)n_points);
+    if (n_points == 0) return PNR_OK;
+    PNR_REQUIRE(packed && points, "pnr_mlp_query: null pointer");
+    PNR_REQUIRE((((uintptr_t)packed) & 15) == 0 && (((uintptr_t)points) & 3) == 0, "pnr_mlp_query: packed must be 16-byte, points 4-byte aligned");
+    PnrPlan plan;
+    pnr_build_plan(*desc, plan);
+    FieldArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    MlpArgs& a = fa.m;
+    // the heads whose chunks the launch streams: what the outputs need, and the semantic head in front of a wanted instance head
+    fa.run_inst = desc->n_inst > 0 && (inst_label || inst_logits || panoptic);
+    fa.run_sem = desc->n_sem > 0 && (sem_label || sem_logits || panoptic || fa.run_inst);
+    a.data = (const uint8_t*)packed + plan.data_off;
+    a.table = (const pnr_chunk_entry*)((const uint8_t*)packed + plan.table_off);
+    a.n_chunks = pnr_field_chunks(plan, fa.run_sem, fa.run_inst);
+    a.slot_bytes = plan.max_chunk_frags * PNR_FRAG_BYTES;
+    PNR_REQUIRE(a.n_chunks >= 4 && 3 * a.slot_bytes <= 163840, "pnr_mlp_query: weight stream does not fit (chunks=%d, slot=%d bytes)", a.n_chunks, a.slot_bytes);
+    a.S = (int)n_points; a.N = 1;
+    a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
+    a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
+    a.clk = clk_probe_of(desc);
+#if PNR_TRACE
+    if (const char* e = getenv("PNR_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
+#endif
+    fa.pts = points; fa.sigma = sigma; fa.sem_label = sem_label; fa.inst_label = inst_label; fa.panoptic = panoptic;
+    fa.is_thing = is_thing; fa.sem_logits = sem_logits; fa.inst_logits = inst_logits; fa.lstride = logit_stride;
+    hipStream_t st = (hipStream_t)stream;
+    if (fa.run_sem || fa.run_inst) return desc->W == 256 ? launch_field<256, true>(fa, st) : launch_field<128, true>(fa, st);
+    return desc->W == 256 ? launch_field<256, false>(fa, st) : launch_field<128, false>(fa, st);
 }

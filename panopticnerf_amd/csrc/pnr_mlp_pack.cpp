@@ -34,8 +34,8 @@ int pnr_mlp_validate(const pnr_mlp_desc* d)
 #endif
     PNR_REQUIRE(d->schedule >= 0 && d->schedule <= (PNR_TRAIN_TILES_EXPERIMENT ? 6 : 2), "pnr_mlp: schedule=%d must be 0 (default), 1 (lock-step) or 2 (ping-pong)", d->schedule);
     PNR_REQUIRE(d->plan == 0 || (d->plan == 1 && pnr_plan1_supported(*d)) || (d->plan == 2 && pnr_plan2_supported(*d)) ||
-                (d->plan == 3 && pnr_plan3_supported(*d)),
-                "pnr_mlp: plan=%d is not available for this geometry (ask pnr_mlp_fused_plan; plan 3: bf16 only)", d->plan);
+                (d->plan == 3 && pnr_plan3_supported(*d)) || (d->plan == 4 && pnr_plan4_supported(*d)),
+                "pnr_mlp: plan=%d is not available for this geometry (ask pnr_mlp_fused_plan; plans 3 and 4: bf16 only)", d->plan);
     // the descriptor must be zero-initialised (include/pnr.h): the diagnostic words are READ -- clk_probe is a device address the
     // forward kernels store 16 bytes to, flags select kernels -- so garbage there is rejected where it can be recognised
     const uint32_t trace = (uint32_t)d->flags & 0xFF00u;
@@ -59,6 +59,16 @@ PNR_EXPORT int pnr_mlp_fused_plan(const pnr_mlp_desc* desc)
     return pnr_plan2_supported(d) ? 2 : pnr_plan1_supported(d) ? 1 : 0;
 }
 
+// host only: does k_mlp_pp_field (pnr_mlp_query) exist for this geometry?  The descriptor's own `plan` is ignored.
+PNR_EXPORT int pnr_mlp_query_supported(const pnr_mlp_desc* desc)
+{
+    if (!desc) return 0;
+    pnr_mlp_desc d = *desc;
+    d.plan = 0;
+    if (pnr_mlp_validate(&d) != PNR_OK) return 0;
+    return pnr_plan4_supported(d);
+}
+
 static int bwd_validate(const pnr_mlp_desc* d)
 {
     int rc = pnr_mlp_validate(d);
@@ -77,8 +87,14 @@ static int check_params(const pnr_mlp_desc* desc, const pnr_mlp_params_host* p, 
         PNR_REQUIRE(p->pts_w && p->alpha_w && (!bias || (p->pts_b && p->alpha_b)), "pnr_mlp_pack: missing trunk or alpha_linear parameter");
         return PNR_OK;
     }
+    if (desc->plan == 4) {      // the field-query image: no views / rgb layers; feature_linear only where the heads read it
+        const bool feat = desc->head_tap == 1 && (desc->n_sem || desc->n_inst);
+        PNR_REQUIRE(p->pts_w && p->alpha_w && (!bias || (p->pts_b && p->alpha_b)), "pnr_mlp_pack: missing trunk or alpha_linear parameter");
+        PNR_REQUIRE(!feat || (p->feature_w && (!bias || p->feature_b)), "pnr_mlp_pack: missing feature_linear parameter");
+    } else {
     PNR_REQUIRE(p->pts_w && p->alpha_w && p->feature_w && p->views_w && p->rgb_w, "pnr_mlp_pack: missing trunk parameter");
     if (bias) PNR_REQUIRE(p->pts_b && p->alpha_b && p->feature_b && p->views_b && p->rgb_b, "pnr_mlp_pack: missing trunk bias");
+    }
     const bool deep = pnr_head_depth(*desc) == 2;
     if (desc->n_sem) PNR_REQUIRE((!deep || p->sem0_w) && p->sem1_w && (!bias || ((!deep || p->sem0_b) && p->sem1_b)), "pnr_mlp_pack: missing semantic head");
     if (desc->n_inst) PNR_REQUIRE((!deep || p->inst0_w) && p->inst1_w && (!bias || ((!deep || p->inst0_b) && p->inst1_b)), "pnr_mlp_pack: missing instance head");

@@ -11,6 +11,11 @@
 //   plan 3 (sigma only, k_mlp_pp_sigma): trunk 0..D-1 chunked as in plan 1 (layer 0 as one chunk) | sigma: ONE 32-row block whose
 //                              row 3 is alpha_linear over h (the h segment of the rgb+sigma block, same fragments) and every
 //                              other row zero -- what an inference level that is read only for its weights needs
+//   plan 4 (field query, k_mlp_pp_field): plan 3's chunks | [feature, when head_tap = feature and there is a head] |
+//                              [sem0, sem1] | [inst0, inst1] chunked as in plan 0 -- sigma and the panoptic heads at a 3D point,
+//                              nothing that reads a view direction.  Every PREFIX that ends behind sigma, behind the semantic
+//                              head or behind the instance head is a weight stream of its own: a query streams only the layers
+//                              its outputs need (pnr_field_chunks)
 #pragma once
 #include <stddef.h>
 
@@ -82,9 +87,22 @@ static inline void pnr_build_plan(const pnr_mlp_desc& d, PnrPlan& plan)
         else if (i - 1 == d.skip) add(PNR_L_TRUNK, i, d.W, PNR_SEG_GX, 0, PNR_SEG_FEAT, d.W);
         else add(PNR_L_TRUNK, i, d.W, PNR_SEG_FEAT, d.W);
     }
-    if (d.plan == 3) {
+    if (d.plan == 3 || d.plan == 4) {
         // plan 3: the sigma row alone, over h -- rows 0..2 (rgb) are zero, so the quadruples the fused epilogue writes are (lw, 0, 0, 0)
         add(PNR_L_SIGMA, 0, 4, PNR_SEG_FEAT, d.W);
+        if (d.plan == 4 && (d.n_sem || d.n_inst)) {
+            // plan 4: the heads behind it, the layers and chunks of plan 0 (feature_linear only where the heads read it)
+            const bool deep = pnr_head_depth(d) == 2;
+            if (d.head_tap == 1) add(PNR_L_FEATURE, 0, d.W, PNR_SEG_FEAT, d.W);
+            if (d.n_sem) {
+                if (deep) add(PNR_L_SEM0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+                add(PNR_L_SEM1, 0, d.n_sem, PNR_SEG_FEAT, deep ? d.head_W : d.W);
+            }
+            if (d.n_inst) {
+                if (deep) add(PNR_L_INST0, 0, d.head_W, PNR_SEG_FEAT, d.W);
+                add(PNR_L_INST1, 0, d.n_inst, PNR_SEG_FEAT, deep ? d.head_W : d.W);
+            }
+        }
     } else {
         // appearance first, panoptic heads last: sigma (hence every sample's compositing weight) is known before the logit
         // blocks are produced, which is what lets the fused inference epilogue reduce them over the ray on the fly
@@ -144,6 +162,31 @@ static inline int pnr_plan3_supported(const pnr_mlp_desc& d)
     PnrPlan plan;
     pnr_build_plan(d3, plan);
     return plan.chunks.size() >= 4;
+}
+
+// plan 4 (the field-query image, k_mlp_pp_field) exists where plan 3 does and three of its largest chunks fit the LDS.  Opt-in:
+// pnr_mlp_fused_plan never answers 4.
+static inline int pnr_plan4_supported(const pnr_mlp_desc& d)
+{
+    if (!pnr_plan3_supported(d)) return 0;
+    pnr_mlp_desc d4 = d;
+    d4.plan = 4;
+    PnrPlan plan;
+    pnr_build_plan(d4, plan);
+    return 3 * plan.max_chunk_frags * PNR_FRAG_BYTES <= 163840;
+}
+// chunks of a plan-4 image that a query needs: through sigma (no head), through the semantic head, or all of them
+static inline int pnr_field_chunks(const PnrPlan& plan, bool sem, bool inst)
+{
+    int n = 0;
+    for (const PnrChunk& c : plan.chunks) {
+        const int k = plan.layers[c.layer].kind;
+        const bool is_inst = k == PNR_L_INST0 || k == PNR_L_INST1;
+        const bool is_head = is_inst || k == PNR_L_SEM0 || k == PNR_L_SEM1 || k == PNR_L_FEATURE;
+        if ((is_inst && !inst) || (is_head && !sem && !inst)) break;
+        ++n;
+    }
+    return n;
 }
 
 // ---- backward (dgrad) plan, bf16 only.  Every backward layer computes  dX^T = W^T * dY^T  for one tensor X:

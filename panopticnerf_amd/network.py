@@ -116,6 +116,8 @@ class Network(nn.Module):
                 desc.plan = ops.fused_plan(ops.desc_for_mode(desc, 1), None)
             elif fused == "sigma":      # the sigma-only image of ops.mlp_forward_weights (trunk + alpha_linear; opt-in, never the default)
                 desc.plan = 3
+            elif fused == "field":      # the field-query image of ops.mlp_query (sigma + the panoptic heads at a 3D point; opt-in)
+                desc.plan = 4
             else:
                 desc.plan = ops.fused_plan(desc, None if fused is True else int(fused))
         key = ("bwd" if backward else "fwd", level if self.nerf_1 is not None else 0, str(device), precision, int(desc.plan))
@@ -143,12 +145,141 @@ class Network(nn.Module):
     def packed(self, level, device, precision=None, fused=False):
         """(desc, packed image).  fused=True: the image only ops.mlp_forward_composite consumes (desc.plan as
         pnr_mlp_fused_plan says; fused = 1 | 2 caps the plan, "softmax" asks for the best plan with a softmax kernel); fused="sigma":
-        the plan-3 image of ops.mlp_forward_weights (the trunk and the sigma row alone); every other op takes the classic image
-        (fused=False)."""
+        the plan-3 image of ops.mlp_forward_weights (the trunk and the sigma row alone); fused="field": the plan-4 image of
+        ops.mlp_query (where ops.field_query_supported); every other op takes the classic image (fused=False)."""
         return self._pack(level, device, precision or self.precision, False, fused)
 
     def packed_bwd(self, level, device):
         return self._pack(level, device, "bf16", True)
+
+    # --- the field itself: density and panoptic labels at 3D points (no camera)
+    QUERY_CHUNK = 1 << 20
+
+    def _query_run(self, n, get_points, dev, level, want, is_thing, chunk, fast):
+        """query / query_grid: `n` points, produced chunk by chunk by get_points(a, b) -> (b - a, 3), into preallocated outputs."""
+        if level is None:
+            level = 1 if self.nerf_1 is not None else 0
+        desc0 = self.nerf(level).desc(self.precision)
+        keys = ops.query_keys(desc0, want)
+        if fast is None:
+            fast = ops.field_query_supported(desc0)
+        elif fast and not ops.field_query_supported(desc0):
+            raise RuntimeError("Network.query(fast=True): no field-query kernel for this network (precision %r, W=%d)"
+                               % (self.precision, desc0.W))
+        chunk = int(chunk or self.QUERY_CHUNK)
+        if chunk < 1:
+            raise ValueError("query: chunk must be >= 1")
+        if is_thing is not None:
+            is_thing = torch.as_tensor(is_thing).to(device=dev, dtype=torch.int32).contiguous()
+            if not desc0.n_sem or is_thing.numel() != desc0.n_sem:
+                raise ValueError("query: is_thing must hold num_classes=%d entries of a network with a semantic head" % desc0.n_sem)
+        C, K = desc0.n_sem, desc0.n_inst
+        res = {}
+        for k in keys:
+            if k.endswith("_logits"):
+                res[k] = torch.empty((C if k == "sem_logits" else K, n), device=dev, dtype=torch.float32)
+            else:
+                res[k] = torch.empty(n, device=dev, dtype=torch.float32 if k == "sigma" else torch.int32)
+        with torch.no_grad():
+            desc, img = self.packed(level, dev, fused="field" if fast else False)
+            for a in range(0, n, chunk):
+                b = min(n, a + chunk)
+                pts = get_points(a, b)
+                view = {k: (v[:, a:b] if k.endswith("_logits") else v[a:b]) for k, v in res.items()}
+                if fast:
+                    ops.mlp_query(desc, img, pts, want, is_thing, out=view)
+                else:
+                    self._query_classic(desc, img, pts, is_thing, view)
+        return res
+
+    @staticmethod
+    def _query_classic(desc, img, pts, is_thing, view):
+        """The fallback of query(): the classic pass on degenerate rays (o = point, d = (0, 0, 1), z = 0, one sample per ray) and
+        the outputs derived from its raw rows.  Same contract as the field-query kernel; evaluates the view branch for nothing."""
+        P, dev = pts.shape[0], pts.device
+        rays = torch.zeros((P, 8), device=dev, dtype=torch.float32)
+        rays[:, :3] = pts
+        rays[:, 5] = 1.0
+        rays[:, 7] = 1.0
+        raw = ops.mlp_forward(desc, img, rays, torch.zeros((P, 1), device=dev, dtype=torch.float32))
+        C, K = desc.n_sem, desc.n_inst
+        sem, inst = raw[4:4 + C], raw[4 + C:4 + C + K]
+        for k, src in (("sigma", raw[3]), ("sem_logits", sem), ("inst_logits", inst)):
+            if k in view:
+                view[k].copy_(src)
+        if not any(k in view for k in ("sem_label", "inst_label", "panoptic")):
+            return
+        if C:
+            lab = ops.panoptic_labels(sem.t().contiguous(), inst.t().contiguous() if K else None, is_thing)
+        else:       # an instance head alone: the lowest index that attains the maximum (NaN read as -inf, pnr_panoptic_labels' rule)
+            l = torch.where(torch.isnan(inst), torch.full_like(inst, float("-inf")), inst)
+            idx = torch.arange(K, device=dev, dtype=torch.int32)[:, None].expand(K, P)
+            lab = (None, torch.where(l == l.max(0).values, idx, torch.full_like(idx, K)).min(0).values.to(torch.int32), None)
+        for k, src in zip(("sem_label", "inst_label", "panoptic"), lab):
+            if k in view:
+                view[k].copy_(src)
+
+    def query(self, points, level=None, want=("sigma", "labels"), is_thing=None, chunk=None, fast=None):
+        """What the network holds at 3D points: density, semantic / instance labels and (on request) the logits -- no camera,
+        no view direction (sigma and both heads do not depend on one).  INFERENCE ONLY: the returned tensors carry no autograd
+        history, whatever requires_grad says of the points or the parameters.
+
+        points: GPU float32 tensor (..., 3) in the scene's coordinates; every output has the leading shape (...).
+        level: 0 = coarse NeRF, 1 = fine; None = the fine NeRF when the network has one, else the coarse one.
+        want: any of "sigma" -> sigma, the RAW pre-activation density (relu it yourself; no noise); "labels" -> sem_label /
+        inst_label (int32; argmax of the head's logits, lowest index among equals); "panoptic" -> panoptic (int32, class * 1000
+        + instance, or the class where the point has no instance); "logits" -> sem_logits (num_classes, ...) / inst_logits
+        (num_instances, ...), channel first.  Keys of heads the network lacks are left out.
+        is_thing: optional int32[num_classes] table; inst_label is -1 (and panoptic the bare class) where the class is not a thing.
+        chunk: points per launch (default 2^20); the outputs are allocated once and filled chunk by chunk.
+        fast: None = the field-query kernel where ops.field_query_supported says it exists (bf16, W = 128 / 256), else the
+        classic pass on degenerate rays (o = point, d = (0, 0, 1), z = 0) with the same outputs derived from its raw image --
+        slower, same contract (for a bf16 network the same bits); False forces that fallback, True refuses it."""
+        ops.query_keys(self.nerf_0.desc(self.precision), want)          # an unknown name is a ValueError before anything else
+        if not isinstance(points, torch.Tensor) or not points.is_cuda:
+            raise RuntimeError("Network.query: points must be a GPU tensor (the network is evaluated by HIP kernels; there is no CPU path)")
+        if points.dtype != torch.float32 or points.dim() < 1 or points.shape[-1] != 3:
+            raise ValueError("Network.query: points must be float32 of shape (..., 3), got %s %s" % (points.dtype, tuple(points.shape)))
+        lead = tuple(points.shape[:-1])
+        flat = points.detach().reshape(-1, 3).contiguous()
+        res = self._query_run(flat.shape[0], lambda a, b: flat[a:b], flat.device, level, want, is_thing, chunk, fast)
+        return {k: (v.reshape((v.shape[0],) + lead) if k.endswith("_logits") else v.reshape(lead)) for k, v in res.items()}
+
+    def query_grid(self, lo, hi, res, device=None, **kw):
+        """query() on the cell centres of a regular grid over the box [lo, hi] (3-vectors, x y z), res cells per axis (an int or
+        (res_x, res_y, res_z)).  Every output comes back as a (res_z, res_y, res_x) array (logits: (n, res_z, res_y, res_x)):
+        element [iz, iy, ix] is the point
+
+            x = lo_x + (ix + 0.5) * step_x,   step_x = (hi_x - lo_x) / res_x     (y, z alike)
+
+        evaluated in float32 in exactly that order: lo, hi and res are rounded to float32, the step is one float32 subtraction
+        and division, and a coordinate is one float32 multiply and one float32 add.  The points are generated chunk by chunk on
+        the device (flat index (iz * res_y + iy) * res_x + ix), so a large grid never exists as a (res^3, 3) tensor.  device:
+        where to run (default: where the parameters are).  Other keywords as query()."""
+        ops.query_keys(self.nerf_0.desc(self.precision), kw.get("want", ("sigma", "labels")))
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("Network.query_grid: needs a GPU device (the network is evaluated by HIP kernels; there is no CPU path)")
+        r = (int(res),) * 3 if isinstance(res, int) else tuple(int(v) for v in res)
+        if len(r) != 3 or min(r) < 1:
+            raise ValueError("query_grid: res must be a positive int or (res_x, res_y, res_z)")
+        lo32 = torch.tensor([float(v) for v in lo], dtype=torch.float32, device=dev)
+        hi32 = torch.tensor([float(v) for v in hi], dtype=torch.float32, device=dev)
+        if lo32.numel() != 3 or hi32.numel() != 3:
+            raise ValueError("query_grid: lo and hi must be 3-vectors")
+        step = (hi32 - lo32) / torch.tensor(r, dtype=torch.float32, device=dev)
+        rx, ry, rz = r
+
+        def cells(a, b):
+            f = torch.arange(a, b, device=dev, dtype=torch.int64)
+            i = torch.stack((f % rx, (f // rx) % ry, f // (rx * ry)), 1).to(torch.float32)
+            return ((i + 0.5) * step + lo32).contiguous()          # a multiply, then an add: two roundings, never an FMA
+
+        out = self._query_run(rx * ry * rz, cells, dev, kw.pop("level", None), kw.pop("want", ("sigma", "labels")),
+                              kw.pop("is_thing", None), kw.pop("chunk", None), kw.pop("fast", None))
+        if kw:
+            raise TypeError("query_grid: unexpected keyword %r" % sorted(kw)[0])
+        return {k: (v.reshape(v.shape[0], rz, ry, rx) if k.endswith("_logits") else v.reshape(rz, ry, rx)) for k, v in out.items()}
 
     # --- checkpoint interop (SURVEY.md 8f rank 3): reference-trained weights -> this module
     DEFAULT_KEY_MAP = (

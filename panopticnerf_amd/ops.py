@@ -612,6 +612,79 @@ def mlp_forward_weights(desc, packed, rays, z, label_sem=None, label_inst=None, 
     return out
 
 
+QUERY_WANTS = ("sigma", "labels", "panoptic", "logits")
+
+
+def field_query_supported(desc):
+    """Does the field-query kernel (pnr_mlp_query, the plan-4 image) exist for this geometry?  bf16, W = 128 or 256."""
+    return bool(_lib.load().pnr_mlp_query_supported(ctypes.byref(desc)))
+
+
+def query_keys(desc, want):
+    """The keys mlp_query / Network.query return for `want` on a network of this geometry (ValueError for an unknown name)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in QUERY_WANTS]
+    if bad:
+        raise ValueError("query: unknown output %r in want (known: %s)" % (bad[0], ", ".join(QUERY_WANTS)))
+    keys = []
+    if "sigma" in want:
+        keys.append("sigma")
+    if "labels" in want:
+        keys += (["sem_label"] if desc.n_sem else []) + (["inst_label"] if desc.n_inst else [])
+    if "panoptic" in want and desc.n_sem:
+        keys.append("panoptic")
+    if "logits" in want:
+        keys += (["sem_logits"] if desc.n_sem else []) + (["inst_logits"] if desc.n_inst else [])
+    if not keys:
+        raise ValueError("query: want=%r asks for nothing this network has (n_sem=%d, n_inst=%d)" % (want, desc.n_sem, desc.n_inst))
+    return keys
+
+
+@_on_device
+def mlp_query(desc, packed, points, want=("sigma", "labels"), is_thing=None, out=None):
+    """Density and panoptic labels at 3D points (pnr_mlp_query; inference, no autograd).  desc / packed: the plan-4 image
+    (net.packed(level, device, fused="field")).  points (P, 3) fp32.  want: any of "sigma" (raw pre-activation density, (P) fp32),
+    "labels" (sem_label / inst_label, (P) int32: argmax of the head, lowest index among equals; inst_label = -1 off the things of
+    is_thing, an int32[n_sem] table), "panoptic" ((P) int32: class * 1000 + instance, or the class), "logits" (sem_logits
+    (n_sem, P) / inst_logits (n_inst, P) fp32, channel-major, channel stride >= P).  Returns a dict of the keys asked for that the
+    network has; only the layers they need are evaluated.  out: dict of caller tensors to write into (any missing key is
+    allocated).  sigma and the logits are bit for bit rows 3, 4.. of mlp_forward's raw image at the same positions."""
+    if desc.plan != 4:
+        raise ValueError("mlp_query: needs the plan-4 image (net.packed(level, device, fused='field')), not plan %d" % desc.plan)
+    keys = query_keys(desc, want)
+    points, packed = _chk(points, "points"), _chk(packed, "packed", torch.uint8)
+    is_thing = _chk(is_thing, "is_thing", torch.int32)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("mlp_query: points must be (P, 3), got %s" % (tuple(points.shape),))
+    if is_thing is not None and (not desc.n_sem or is_thing.numel() != desc.n_sem):
+        raise ValueError("mlp_query: is_thing must hold n_sem=%d entries of a network with a semantic head" % desc.n_sem)
+    P, dev = points.shape[0], points.device
+    out = dict(out) if out else {}
+    res, stride = {}, P
+    for k in keys:
+        if k.endswith("_logits"):
+            n = desc.n_sem if k == "sem_logits" else desc.n_inst
+            t = out.get(k)
+            if t is None:
+                t = alloc_raw(n, P, dev)
+            elif (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, P) or (P > 0 and t.stride(1) != 1)
+                  or (n > 1 and t.stride(0) < P)):
+                raise ValueError("mlp_query: out[%r] must be a float32 GPU tensor of shape %s with unit point stride" % (k, (n, P)))
+            res[k] = t
+        else:
+            res[k] = _own(out.get(k), (P,), torch.float32 if k == "sigma" else torch.int32, dev, "mlp_query: out[%r]" % k)
+    lg = [res[k] for k in ("sem_logits", "inst_logits") if k in res]
+    if lg:
+        stride = lg[0].stride(0) if lg[0].shape[0] > 1 else max(P, lg[0].stride(0))
+        if any((t.stride(0) if t.shape[0] > 1 else stride) != stride for t in lg):
+            raise ValueError("mlp_query: sem_logits and inst_logits must share one channel stride")
+    g = res.get
+    _lib.check(_lib.load().pnr_mlp_query(ctypes.byref(desc), _p(packed), _p(points), P, _p(g("sigma")), _p(g("sem_label")),
+                                         _p(g("inst_label")), _p(g("panoptic")), _p(is_thing), _p(g("sem_logits")),
+                                         _p(g("inst_logits")), stride, _stream()), "pnr_mlp_query")
+    return res
+
+
 @_on_device
 def composite_backward(raw, z, rays, n_sem, n_inst, grads, noise=None, label_sem=None, label_inst=None,
                        ce_sem=None, ce_inst=None, sem_mode=0):
