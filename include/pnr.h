@@ -366,6 +366,39 @@ int pnr_ce3d(const float* raw, int64_t raw_stride_c, int first_channel, int n_cl
 int pnr_gen_rays(const float* intr4_host, const float* c2w12_host, int width, int height, float near_, float far_,
                  const int32_t* pix, int64_t n_rays, float* rays, void* stream);
 
+/* ---- cameras: fisheye ray generation and 3D -> 2D projection for both camera models (csrc/pnr_camera.hip; DESIGN.md
+ * "Fisheye cameras").  The fisheye model is the unified omnidirectional (MEI) model with two radial terms, as the public
+ * KITTI-360 calibration files parametrise it; cam7_host = {xi, k1, k2, gamma1, gamma2, u0, v0}.  Camera axes as pnr_gen_rays.
+ *
+ * Projection of a camera-space point p (the defining direction):
+ *   (x, y, z) = p / |p|;  x /= z + xi;  y /= z + xi;  r2 = x^2 + y^2;  s = 1 + k1 r2 + k2 r2^2
+ *   u = gamma1 x s + u0;  v = gamma2 y s + v0
+ *   in the domain iff z + xi > 0 and xi z + 1 > 0 (the second: for xi > 1 no pixel sees a direction behind the rim
+ *   z = -1/xi; without it such a point would fold back into the image) and |p| is finite in float32.
+ * Un-projection of pixel (i, j), its inverse:
+ *   x = (i - u0)/gamma1;  y = (j - v0)/gamma2;  rd = sqrt(x^2 + y^2)
+ *   r (1 + k1 r^2 + k2 r^4) = rd solved for r by PNR_FISHEYE_NEWTON_STEPS Newton steps from r = rd (no data-dependent exit)
+ *   (x, y) *= r / rd (rd == 0: unchanged);  r2 = x^2 + y^2;  disc = 1 + (1 - xi^2) r2
+ *   valid iff disc >= 0 (and r2 finite);  lam = (xi + sqrt(disc)) / (r2 + 1);  d_cam = (lam x, lam y, lam - xi)
+ *   d = R d_cam, o = t.  d is UNIT LENGTH (pnr_gen_rays' d has z_cam = 1): depth along such a ray is range, not z-depth.
+ * Every operation is a single + - * / sqrt in one fixed order (tests/_camera_ref.py restates it in float32, bit for bit). */
+#define PNR_FISHEYE_NEWTON_STEPS 8      /* float32 is as close to float64 as it gets from 4 steps on (tests/test_camera_ref.py) */
+#define PNR_CAMERA_PINHOLE 0            /* pnr_project_points: cam_host = {fx, fy, cx, cy} */
+#define PNR_CAMERA_FISHEYE 1            /* pnr_project_points: cam_host = cam7 */
+
+/* rays (n_rays, 8) = o d near far as pnr_gen_rays (16-byte aligned); pix / n_rays as pnr_gen_rays.  valid (n_rays) bytes or
+ * NULL: 1 where the pixel sees anything.  A pixel that does not gets o, d = 0, near = far = 0 and valid = 0, never NaN. */
+int pnr_gen_rays_fisheye(const float* cam7_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                         const int32_t* pix, int64_t n_rays, float* rays, uint8_t* valid, void* stream);
+
+/* World points (n, 3) -> uv (n, 2) pixel coordinates (u = column, v = row, pixel centres at integers), range (n) = the
+ * distance |p_cam| from the camera centre, valid (n) bytes = inside the projection's domain (pinhole: z_cam > 0) AND inside
+ * the image (-0.5 <= u < width - 0.5, -0.5 <= v < height - 0.5).  w2c12_host: 3x4 row-major world-to-camera (host).  The
+ * pinhole branch is the inverse of pnr_gen_rays: u = fx x/z + cx.  Outside the domain uv = 0; never NaN.  Any output NULL =
+ * not written. */
+int pnr_project_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
+                       int64_t n, float* uv, float* range, uint8_t* valid, void* stream);
+
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).
  * pnr_panoptic_labels: sem_label = argmax_c sem (lowest index on ties); inst_label = argmax_k inst where is_thing[sem_label]

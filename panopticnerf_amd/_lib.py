@@ -13,6 +13,7 @@ c_int = ctypes.c_int
 
 PREC_BF16, PREC_FP32 = 0, 1
 MLP_SOFTMAX, MLP_TRACE = 1, 0x7A00        # pnr_mlp_desc.flags (include/pnr.h PNR_MLP_*)
+CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1     # pnr_project_points' model word (include/pnr.h PNR_CAMERA_*)
 
 
 class LossCfg(ctypes.Structure):
@@ -94,6 +95,10 @@ SIGNATURES = {
     "pnr_ce3d": (c_int, [c_f, c_i64, c_int, c_int, c_f, c_i64, c_f, c_f, c_f]),
     "pnr_gen_rays": (c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
                              ctypes.c_float, c_f, c_i64, c_f, c_f]),
+    "pnr_gen_rays_fisheye": (c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
+                                     ctypes.c_float, c_f, c_i64, c_f, c_f, c_f]),
+    "pnr_project_points": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_i64,
+                                   c_f, c_f, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

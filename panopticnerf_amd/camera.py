@@ -1,0 +1,144 @@
+"""Camera models behind one interface: Pinhole (the rectified perspective pair) and Fisheye (the side-facing cameras of a
+360 rig).  Both make rays on the GPU (`rays`), say which pixels see anything (`valid_pix`) and carry 3D points into the
+image (`project`); `Renderer.render_view` renders a frame of either.
+
+The fisheye model is the unified omnidirectional (MEI) model with two radial terms as the public KITTI-360 calibration files
+parametrise it, written out in include/pnr.h ("cameras") and DESIGN.md ("Fisheye cameras"); like every convention of this
+build it is unpinned against the reference's own 360 code.  Fisheye rays are UNIT LENGTH (depth along them is range);
+pinhole rays keep `ops.gen_rays`' convention (z_cam = 1, depth is z-depth).
+"""
+import math
+
+import torch
+
+from . import ops
+
+
+def _pose12(m, what):
+    t = torch.as_tensor(m, dtype=torch.float32).reshape(-1)
+    if t.numel() == 16:
+        t = t[:12]
+    if t.numel() != 12:
+        raise ValueError(f"{what}: expected a 3x4 (or 4x4) matrix")
+    return t
+
+
+class _Camera:
+    """Shared half of the two models: the per-device cache of valid pixels and the GPU-device check."""
+
+    def __init__(self, width, height):
+        self.width, self.height = int(width), int(height)
+        if self.width < 1 or self.height < 1:
+            raise ValueError("camera: width and height must be >= 1")
+        self._valid_pix = {}
+
+    @staticmethod
+    def _device(device, pix=None):
+        dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise RuntimeError("camera: expected a GPU device (the HIP path has no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return dev
+
+    def valid_pix(self, device=None):
+        """Sorted int32 linear indices (j * width + i) of the pixels that see anything, on `device`.  Depends on the intrinsics
+        (and the user mask) only, never on the pose: computed once per camera and device, then the SAME tensor is returned, so
+        after the first frame a frame costs no host synchronisation."""
+        dev = self._device(device)
+        if dev not in self._valid_pix:
+            self._valid_pix[dev] = self._find_valid(dev)
+        return self._valid_pix[dev]
+
+
+class Pinhole(_Camera):
+    """fx, fy, cx, cy as `ops.gen_rays`: d = R ((i - cx)/fx, (j - cy)/fy, 1), every pixel valid."""
+    model = "pinhole"
+
+    def __init__(self, fx, fy, cx, cy, width, height):
+        super().__init__(width, height)
+        self.intr = (float(fx), float(fy), float(cx), float(cy))
+        if self.intr[0] == 0.0 or self.intr[1] == 0.0:
+            raise ValueError("Pinhole: zero focal length")
+
+    def _find_valid(self, dev):
+        return torch.arange(self.width * self.height, dtype=torch.int32, device=dev)
+
+    def rays(self, c2w, near, far, pix=None, device=None):
+        """(R, 8) rays of the whole frame or of the int32 GPU pixel indices `pix` (ops.gen_rays)."""
+        return ops.gen_rays(self.intr, _pose12(c2w, "Pinhole.rays: c2w"), self.width, self.height, near, far, pix=pix,
+                            device=None if pix is not None else self._device(device))
+
+    def project(self, points, w2c):
+        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (z-depth is range times the
+        z of the unit direction, or uv back through the intrinsics), valid (P) bool: z_cam > 0 and inside the image."""
+        uv, rng, valid = ops.project_points("pinhole", self.intr, _pose12(w2c, "Pinhole.project: w2c"), self.width, self.height, points)
+        return uv, rng, valid.bool()
+
+
+class Fisheye(_Camera):
+    """xi, k1, k2, gamma1, gamma2, u0, v0 of the MEI model (include/pnr.h "cameras").  mask: optional (height, width) bool /
+    0-1 array, True where the pixel is to be used (e.g. the dataset's mask of the car body); it only narrows `valid_pix`."""
+    model = "fisheye"
+
+    def __init__(self, xi, k1, k2, gamma1, gamma2, u0, v0, width, height, mask=None):
+        super().__init__(width, height)
+        self.cam = tuple(float(v) for v in (xi, k1, k2, gamma1, gamma2, u0, v0))
+        if not all(math.isfinite(v) for v in self.cam):
+            raise ValueError("Fisheye: non-finite parameter")
+        if self.cam[0] < 0.0:
+            raise ValueError("Fisheye: xi must be >= 0")
+        if self.cam[3] == 0.0 or self.cam[4] == 0.0:
+            raise ValueError("Fisheye: zero gamma")
+        self._check_monotone()
+        self.mask = None
+        if mask is not None:
+            m = torch.as_tensor(mask).detach().cpu() != 0
+            if tuple(m.shape) != (self.height, self.width):
+                raise ValueError("Fisheye: mask must be (height, width) = (%d, %d), not %s" % (self.height, self.width, tuple(m.shape)))
+            self.mask = m.reshape(-1)
+
+    def _check_monotone(self):
+        """The un-projection inverts r (1 + k1 r^2 + k2 r^4) by Newton's method, which needs the polynomial strictly increasing
+        (derivative g = 1 + 3 k1 r^2 + 5 k2 r^4 > 0) from the centre up to the rim: r^2 = 1/(xi^2 - 1) for xi > 1, else the
+        radius of the farthest image corner."""
+        xi, k1, k2, g1, g2, u0, v0 = self.cam
+        g = lambda t: 1.0 + 3.0 * k1 * t + 5.0 * k2 * t * t         # t = r^2
+        poly = lambda r: r * (1.0 + k1 * r * r + k2 * r ** 4)
+        if xi > 1.0:
+            r_hi = 1.0 / math.sqrt(xi * xi - 1.0)
+        else:
+            rd_max = max(math.hypot((i - u0) / g1, (j - v0) / g2) for i in (0, self.width - 1) for j in (0, self.height - 1))
+            r_hi, n = max(rd_max, 1e-6), 0
+            while poly(r_hi) < rd_max and g(r_hi * r_hi) > 0.0 and n < 64:
+                r_hi, n = r_hi * 1.5, n + 1
+            if poly(r_hi) < rd_max and g(r_hi * r_hi) > 0.0:
+                raise ValueError("Fisheye: the radial polynomial never reaches the image corners")
+        T = r_hi * r_hi
+        cand = [T * k / 1024.0 for k in range(1025)]
+        if k2 != 0.0:
+            cand.append(min(max(-3.0 * k1 / (10.0 * k2), 0.0), T))   # the vertex of g, where it lies inside
+        worst = min(g(t) for t in cand)
+        if not worst > 0.0:
+            raise ValueError("Fisheye: the radial polynomial 1 + k1 r^2 + k2 r^4 times r is not strictly increasing up to the rim "
+                             "(r = %.4g): its derivative falls to %.3g -- k1 = %g, k2 = %g cannot be un-projected" % (r_hi, worst, k1, k2))
+
+    def _find_valid(self, dev):
+        eye = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+        _, valid = ops.gen_rays_fisheye(self.cam, eye, self.width, self.height, 0.0, 1.0, device=dev)
+        valid = valid != 0
+        if self.mask is not None:
+            valid &= self.mask.to(dev)
+        return torch.nonzero(valid).reshape(-1).to(torch.int32)      # (the camera's one host synchronisation per device)
+
+    def rays(self, c2w, near, far, pix=None, device=None):
+        """(R, 8) rays of the whole frame or of the int32 GPU pixel indices `pix` (ops.gen_rays_fisheye): unit-length d; a
+        pixel outside the lens gets d = 0, near = far = 0 -- pass pix = valid_pix() to leave those out."""
+        return ops.gen_rays_fisheye(self.cam, _pose12(c2w, "Fisheye.rays: c2w"), self.width, self.height, near, far, pix=pix,
+                                    device=None if pix is not None else self._device(device), want_valid=False)[0]
+
+    def project(self, points, w2c):
+        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (what depth_* of a fisheye
+        render holds), valid (P) bool: a direction the lens sees and inside the image (the user mask is not consulted)."""
+        uv, rng, valid = ops.project_points("fisheye", self.cam, _pose12(w2c, "Fisheye.project: w2c"), self.width, self.height, points)
+        return uv, rng, valid.bool()

@@ -1,0 +1,132 @@
+// Cameras: fisheye ray generation and 3D -> 2D projection for both camera models (include/pnr.h "cameras").
+// Small write-bound kernels in the style of k_gen_rays (pnr_sampling.hip): one thread per ray / point, grid-stride, camera
+// and pose in the kernel arguments.  Every operation is a single + - * / sqrt in one fixed order (the build has
+// -ffp-contract=off and correctly rounded divide / sqrt): tests/_camera_ref.py restates both kernels in float32, bit for bit.
+#include <float.h>
+
+#include "pnr_common.h"
+
+struct FisheyeCam { float xi, k1, k2, g1, g2, u0, v0; };
+
+// Un-projection: one thread per ray, two float4 stores (32 B/ray) + one byte into `valid`.
+struct GenRaysFisheyeArgs { FisheyeCam c; float c2w[12]; int width; float near_, far_; const int32_t* pix; int64_t R; float* rays; uint8_t* valid; };
+__global__ __launch_bounds__(256) void k_gen_rays_fisheye(const GenRaysFisheyeArgs a)
+{
+    const FisheyeCam c = a.c;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = a.pix ? (int64_t)a.pix[r] : r;
+        const int j = (int)(p / a.width), i = (int)(p - (int64_t)j * a.width);
+        float x = ((float)i - c.u0) / c.g1;
+        float y = ((float)j - c.v0) / c.g2;
+        const float rd = sqrtf(x * x + y * y);
+        // r (1 + k1 r^2 + k2 r^4) = rd: a fixed number of Newton steps from r = rd (a converged r is a fixed point of the step)
+        float rr = rd;
+#pragma unroll
+        for (int s = 0; s < PNR_FISHEYE_NEWTON_STEPS; ++s) {
+            const float r2 = rr * rr;
+            const float r4 = r2 * r2;
+            const float ka = c.k1 * r2, kb = c.k2 * r4;
+            const float f = rr * ((1.0f + ka) + kb) - rd;
+            const float fp = (1.0f + 3.0f * ka) + 5.0f * kb;
+            rr = rr - f / fp;
+        }
+        const float sc = rd > 0.0f ? rr / rd : 1.0f;
+        x = x * sc;
+        y = y * sc;
+        const float r2 = x * x + y * y;
+        const float disc = 1.0f + (1.0f - c.xi * c.xi) * r2;
+        const bool ok = disc >= 0.0f && r2 <= FLT_MAX;           // (both false for NaN)
+        const float lam = (c.xi + sqrtf(disc)) / (r2 + 1.0f);
+        const float dx = lam * x, dy = lam * y, dz = lam - c.xi;
+        float d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float u = a.c2w[k * 4 + 0] * dx, v = a.c2w[k * 4 + 1] * dy, w = a.c2w[k * 4 + 2] * dz;
+            d[k] = ok ? (u + v) + w : 0.0f;
+        }
+        float4* o = reinterpret_cast<float4*>(a.rays + r * 8);
+        o[0] = make_float4(a.c2w[3], a.c2w[7], a.c2w[11], d[0]);
+        o[1] = make_float4(d[1], d[2], ok ? a.near_ : 0.0f, ok ? a.far_ : 0.0f);
+        if (a.valid) a.valid[r] = ok ? 1 : 0;
+    }
+}
+
+// Projection: one thread per point; reads 12 B, writes 8 + 4 + 1 B.  cam: pinhole {fx, fy, cx, cy} or fisheye cam7.
+struct ProjectArgs { int model; float cam[7]; float w2c[12]; float umax, vmax; const float* pts; int64_t P; float2* uv; float* range; uint8_t* valid; };
+__global__ __launch_bounds__(256) void k_project_points(const ProjectArgs a)
+{
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.P; n += (int64_t)gridDim.x * blockDim.x) {
+        const float X = a.pts[n * 3 + 0], Y = a.pts[n * 3 + 1], Z = a.pts[n * 3 + 2];
+        float p[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float t0 = a.w2c[k * 4 + 0] * X, t1 = a.w2c[k * 4 + 1] * Y, t2 = a.w2c[k * 4 + 2] * Z;
+            p[k] = ((t0 + t1) + t2) + a.w2c[k * 4 + 3];
+        }
+        const float rng = sqrtf((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+        float u, v;
+        bool dom;
+        if (a.model == PNR_CAMERA_PINHOLE) {
+            dom = p[2] > 0.0f;
+            const float x = p[0] / p[2], y = p[1] / p[2];
+            u = a.cam[0] * x + a.cam[2];
+            v = a.cam[1] * y + a.cam[3];
+        } else {
+            const float xi = a.cam[0], k1 = a.cam[1], k2 = a.cam[2];
+            const float xs = p[0] / rng, ys = p[1] / rng, zs = p[2] / rng;
+            const float den = zs + xi;
+            dom = den > 0.0f && xi * zs + 1.0f > 0.0f && rng <= FLT_MAX;       // (a range that overflowed has lost its direction)
+            const float x = xs / den, y = ys / den;
+            const float r2 = x * x + y * y;
+            const float s = (1.0f + k1 * r2) + k2 * (r2 * r2);
+            u = (a.cam[3] * x) * s + a.cam[5];
+            v = (a.cam[4] * y) * s + a.cam[6];
+        }
+        dom = dom && fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX;     // (false for NaN and Inf)
+        u = dom ? u : 0.0f;
+        v = dom ? v : 0.0f;
+        const bool inside = u >= -0.5f && u < a.umax && v >= -0.5f && v < a.vmax;
+        if (a.uv) a.uv[n] = make_float2(u, v);
+        if (a.range) a.range[n] = rng;
+        if (a.valid) a.valid[n] = (dom && inside) ? 1 : 0;
+    }
+}
+
+PNR_EXPORT int pnr_gen_rays_fisheye(const float* cam7_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                                    const int32_t* pix, int64_t n_rays, float* rays, uint8_t* valid, void* stream)
+{
+    PNR_REQUIRE(cam7_host && c2w12_host, "pnr_gen_rays_fisheye: null camera");
+    PNR_REQUIRE(width >= 1 && height >= 1 && n_rays >= 0, "pnr_gen_rays_fisheye: bad size");
+    if (n_rays == 0) return PNR_OK;             // before the pointer checks: an empty pixel list has a null pointer
+    PNR_REQUIRE(pix || n_rays == (int64_t)width * height, "pnr_gen_rays_fisheye: without pixel indices n_rays must be width*height");
+    PNR_REQUIRE(cam7_host[3] != 0.0f && cam7_host[4] != 0.0f, "pnr_gen_rays_fisheye: zero gamma");
+    PNR_REQUIRE(rays && (((uintptr_t)rays) & 15) == 0, "pnr_gen_rays_fisheye: rays must be a 16-byte aligned device buffer");
+    GenRaysFisheyeArgs a;
+    a.c = FisheyeCam{cam7_host[0], cam7_host[1], cam7_host[2], cam7_host[3], cam7_host[4], cam7_host[5], cam7_host[6]};
+    for (int k = 0; k < 12; ++k) a.c2w[k] = c2w12_host[k];
+    a.width = width; a.near_ = near_; a.far_ = far_; a.pix = pix; a.R = n_rays; a.rays = rays; a.valid = valid;
+    hipLaunchKernelGGL(k_gen_rays_fisheye, dim3(pnr_grid_cap((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    PNR_CHECK_LAUNCH("pnr_gen_rays_fisheye");
+    return PNR_OK;
+}
+
+PNR_EXPORT int pnr_project_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
+                                  int64_t n, float* uv, float* range, uint8_t* valid, void* stream)
+{
+    PNR_REQUIRE(model == PNR_CAMERA_PINHOLE || model == PNR_CAMERA_FISHEYE, "pnr_project_points: unknown camera model %d", model);
+    PNR_REQUIRE(cam_host && w2c12_host, "pnr_project_points: null camera");
+    PNR_REQUIRE(width >= 1 && height >= 1 && n >= 0, "pnr_project_points: bad size");
+    if (n == 0) return PNR_OK;
+    PNR_REQUIRE(points, "pnr_project_points: null points");
+    PNR_REQUIRE((((uintptr_t)uv) & 7) == 0, "pnr_project_points: uv must be an 8-byte aligned device buffer");
+    ProjectArgs a;
+    a.model = model;
+    const int nc = model == PNR_CAMERA_PINHOLE ? 4 : 7;
+    for (int k = 0; k < 7; ++k) a.cam[k] = k < nc ? cam_host[k] : 0.0f;
+    for (int k = 0; k < 12; ++k) a.w2c[k] = w2c12_host[k];
+    a.umax = (float)width - 0.5f; a.vmax = (float)height - 0.5f;
+    a.pts = points; a.P = n; a.uv = reinterpret_cast<float2*>(uv); a.range = range; a.valid = valid;
+    hipLaunchKernelGGL(k_project_points, dim3(pnr_grid_cap((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    PNR_CHECK_LAUNCH("pnr_project_points");
+    return PNR_OK;
+}

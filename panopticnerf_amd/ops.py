@@ -56,7 +56,8 @@ def _on_device(fn):
 
 def gen_rays(intr, c2w, width, height, near, far, pix=None, device=None):
     """Pinhole ray generation on the GPU (pnr_gen_rays).  intr: fx, fy, cx, cy; c2w: 3x4 camera-to-world
-    (host values); pix: int32 GPU tensor of linear pixel indices or None (whole frame).  Returns rays (R,8)."""
+    (host values); pix: int32 GPU tensor of linear pixel indices or None (whole frame).  Returns rays (R,8).  d is NOT normalised
+    (z_cam = 1), so depth_* of a render on these rays is z-depth; gen_rays_fisheye's rays are unit length and its depth is range."""
     intr_h = (ctypes.c_float * 4)(*[float(v) for v in torch.as_tensor(intr, dtype=torch.float32).reshape(4).tolist()])
     c2w_h = (ctypes.c_float * 12)(*[float(v) for v in torch.as_tensor(c2w, dtype=torch.float32).reshape(12).tolist()])
     pix = _chk(pix, "pix", torch.int32)
@@ -69,6 +70,54 @@ def gen_rays(intr, c2w, width, height, near, far, pix=None, device=None):
         _lib.check(_lib.load().pnr_gen_rays(intr_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
                                             _p(rays), _stream()), "pnr_gen_rays")
     return rays
+
+
+def _host_floats(v, n, what):
+    vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float32).reshape(-1).tolist()]
+    if len(vals) != n:
+        raise ValueError(f"{what}: expected {n} values, got {len(vals)}")
+    return (ctypes.c_float * n)(*vals)
+
+
+def gen_rays_fisheye(cam, c2w, width, height, near, far, pix=None, device=None, want_valid=True):
+    """Fisheye ray generation on the GPU (pnr_gen_rays_fisheye; the model is in include/pnr.h "cameras").  cam: xi, k1, k2,
+    gamma1, gamma2, u0, v0; c2w, pix, device as gen_rays.  Returns rays (R,8) and valid (R) uint8 (None with
+    want_valid=False).  Unlike gen_rays' directions (z_cam = 1: depth along them is z-depth) these are UNIT LENGTH, so
+    depth_* of a render on them is range along the ray.  A pixel outside the lens gets o, d = 0, near = far = 0, valid = 0."""
+    cam_h, c2w_h = _host_floats(cam, 7, "gen_rays_fisheye: cam"), _host_floats(c2w, 12, "gen_rays_fisheye: c2w")
+    pix = _chk(pix, "pix", torch.int32)
+    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError("gen_rays_fisheye: expected a GPU device (the HIP path has no CPU fallback)")
+    R = pix.numel() if pix is not None else int(width) * int(height)
+    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
+    valid = torch.empty((R,), device=dev, dtype=torch.uint8) if want_valid else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pnr_gen_rays_fisheye(cam_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
+                                                    _p(rays), _p(valid), _stream()), "pnr_gen_rays_fisheye")
+    return rays, valid
+
+
+@_on_device
+def project_points(model, cam, w2c, width, height, points):
+    """World points (P,3) -> uv (P,2) pixel coordinates, range (P) = distance from the camera centre, valid (P) uint8 = inside
+    the projection's domain and inside the image (pnr_project_points).  model: "pinhole" (cam: fx, fy, cx, cy) or "fisheye"
+    (cam: xi, k1, k2, gamma1, gamma2, u0, v0); w2c: 3x4 world-to-camera (host values)."""
+    if model not in ("pinhole", "fisheye"):
+        raise ValueError("project_points: model must be 'pinhole' or 'fisheye', not %r" % (model,))
+    word = _lib.CAMERA_PINHOLE if model == "pinhole" else _lib.CAMERA_FISHEYE
+    cam_h = _host_floats(cam, 4 if model == "pinhole" else 7, "project_points: cam")
+    w2c_h = _host_floats(w2c, 12, "project_points: w2c")
+    points = _chk(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("project_points: points must be (P, 3)")
+    P, dev = points.shape[0], points.device
+    uv = torch.empty((P, 2), device=dev, dtype=torch.float32)
+    rng = torch.empty((P,), device=dev, dtype=torch.float32)
+    valid = torch.empty((P,), device=dev, dtype=torch.uint8)
+    _lib.check(_lib.load().pnr_project_points(word, cam_h, w2c_h, int(width), int(height), _p(points), P, _p(uv), _p(rng), _p(valid),
+                                              _stream()), "pnr_project_points")
+    return uv, rng, valid
 
 
 class Draw:

@@ -397,6 +397,41 @@ class Renderer:
             ret[k] = v.reshape(*lead, *v.shape[1:])
         return ret
 
+    # --- a whole frame of a camera (panopticnerf_amd/camera.py): rays for the pixels that see anything, maps as images
+    def render_view(self, camera, c2w, near, far, bbox=None, bbox_ids=None):
+        """Render one frame of `camera` (camera.Pinhole / camera.Fisheye) at pose c2w (3x4, host values): rays are made for
+        camera.valid_pix() only -- a fisheye frame skips the pixels outside the lens (and the user mask) --, rendered by
+        render() (chunking, overlap and fused-plan decisions are render()'s), and every per-ray output is placed into a
+        (height, width, ...) image that is 0 where a pixel sees nothing; "valid" (height, width) bool says where that is.
+        Labels derived from such maps (ops.panoptic_labels, shard.label_maps) must be set to -1, the evaluator's "ignore",
+        where valid is False: the argmax of an all-zero pixel is class 0, not "nothing".  depth_* of a Fisheye frame is range
+        along the unit-length ray, of a Pinhole frame z-depth (camera.py).  Inference only."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters()):
+            raise RuntimeError("Renderer.render_view is inference only: call it under torch.no_grad() (training batches are made "
+                               "with camera.rays(pix=...) and rendered with render())")
+        p0 = next(iter(self.net.parameters()), None)
+        if p0 is None or not p0.is_cuda:
+            raise RuntimeError("Renderer.render_view: the network must be on the GPU (no CPU fallback)")
+        dev, H, W = p0.device, camera.height, camera.width
+        pix = camera.valid_pix(dev)
+        whole = pix.numel() == H * W
+        batch = {"rays": camera.rays(c2w, near, far, pix=None if whole else pix, device=dev)}
+        if bbox is not None:
+            batch.update(bbox=bbox, bbox_ids=bbox_ids)
+        out = self.render(batch)
+        valid = torch.ones((H, W), dtype=torch.bool, device=dev)
+        if whole:
+            ret = {k: v.reshape(H, W, *v.shape[1:]) for k, v in out.items()}
+        else:
+            idx = pix.long()
+            valid = torch.zeros(H * W, dtype=torch.bool, device=dev).index_fill_(0, idx, True).reshape(H, W)
+            ret = {}
+            for k, v in out.items():
+                img = torch.zeros((H * W,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
+                ret[k] = img.index_copy_(0, idx, v).reshape(H, W, *v.shape[1:])
+        ret["valid"] = valid
+        return ret
+
 
 def make_renderer(cfg, network):
     """Reference plugin surface: make_renderer(cfg, network) -> obj with .render(batch)."""

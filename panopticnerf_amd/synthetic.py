@@ -8,6 +8,11 @@ import torch
 KITTI_W, KITTI_H = 1408, 376
 KITTI_F, KITTI_CX, KITTI_CY = 552.554261, 682.049453, 238.769549
 
+# KITTI-360-shaped fisheye (the side-facing 1400 x 1400 cameras; MEI model, include/pnr.h "cameras"): shaped, not a calibration file
+FISHEYE_W, FISHEYE_H = 1400, 1400
+FISHEYE_XI, FISHEYE_K1, FISHEYE_K2 = 2.2134, 0.016798, 1.6548
+FISHEYE_GAMMA1, FISHEYE_GAMMA2, FISHEYE_U0, FISHEYE_V0 = 1336.3, 1335.8, 716.94, 705.76
+
 
 # BASELINE.json `configs` as renderer / network config keys (SURVEY.md 8d "config mapping").  `bbox`: whether the 3D
 # bbox prior is part of the workload.  C = 45 / K = 32 are this build's choices (the reference's are unverifiable,
@@ -45,6 +50,19 @@ def camera_rays(width=KITTI_W, height=KITTI_H, yaw=0.0, origin=(0.0, 1.55, 0.0),
     o = torch.tensor(origin, dtype=torch.float32).expand_as(d)
     nf = torch.tensor([near, far], dtype=torch.float32).expand(d.shape[0], 2)
     return torch.cat([o, d, nf], -1).contiguous()
+
+
+def fisheye_camera(scale=1.0, yaw=math.pi / 2, origin=(0.0, 1.55, 0.0), mask=None):
+    """(camera.Fisheye, c2w (3,4)) for tests and examples: the KITTI-360-shaped parameter set above and a sideways pose (the
+    optical axis turned by `yaw` about y from camera_rays' forward axis).  scale < 1 shrinks the image with its intrinsics
+    (pixel centres kept: u0 -> (u0 + 0.5) scale - 0.5), e.g. scale = 96 / 1400 for a 96 x 96 test frame."""
+    from .camera import Fisheye
+    w, h = int(round(FISHEYE_W * scale)), int(round(FISHEYE_H * scale))
+    cam = Fisheye(FISHEYE_XI, FISHEYE_K1, FISHEYE_K2, FISHEYE_GAMMA1 * scale, FISHEYE_GAMMA2 * scale,
+                  (FISHEYE_U0 + 0.5) * scale - 0.5, (FISHEYE_V0 + 0.5) * scale - 0.5, w, h, mask=mask)
+    c, s = math.cos(yaw), math.sin(yaw)
+    c2w = torch.tensor([[c, 0.0, s, origin[0]], [0.0, 1.0, 0.0, origin[1]], [-s, 0.0, c, origin[2]]], dtype=torch.float32)
+    return cam, c2w
 
 
 def random_boxes(n_box=64, n_sem=45, n_inst=32, seed=1):
