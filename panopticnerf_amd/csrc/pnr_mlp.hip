@@ -41,28 +41,9 @@ int pnr_mlp_validate(const pnr_mlp_desc* d);
 #endif
 #include "pnr_mlp_fuse.h"
 #include "pnr_mlp_tt.h"
-// vector-memory instructions hipcc emits for k_mlp_pp_field's fetch() (one point = three floats; tools/asm_lint.py counts them on
-// the compiled assembly): what the m_done() behind it leaves outstanding
-#define PNR_FIELD_FETCH_LOADS 1
-#define PNR_FIELD_FETCH_LOADS_S "1"
 #define PNR_QUERY_MAX_POINTS (((int64_t)1 << 31) - 4096)
-#ifndef PNR_OPT_EAGER_EPI
-#define PNR_OPT_EAGER_EPI 1
-#endif
-#ifndef PNR_PP_STORES_LAST
-#define PNR_PP_STORES_LAST 0      /* pieces first + counted vmcnt (1): no gain measured; the plain order stays */
-#endif
-#ifndef PNR_RAW_STORE
-#define PNR_RAW_STORE 0           /* cache policy of the raw-output stores: 0 plain, 1 nt, 2 sc1 */
-#endif
-#ifndef PNR_PP_EPI_IN_M
-#define PNR_PP_EPI_IN_M 0
-#endif
 #ifndef PNR_TRAIN_TILES_EXPERIMENT
 #define PNR_TRAIN_TILES_EXPERIMENT 0
-#endif
-#ifndef PNR_PP_UNROLL2
-#define PNR_PP_UNROLL2 0     /* two trunk layers per loop trip (no hand-over copies): -2 % measured (code size) */
 #endif
 // Hidden layer: inputs = up to two register segments, output -> registers (next B operand).
 // save != nullptr (training, bf16): the output block is also stored slot-ordered for the backward.
@@ -104,9 +85,7 @@ __device__ __forceinline__ void layer_regs(CTX& c, const uint32_t (&inA)[TILES][
                         // ReLU after rounding (they commute, bit for bit): a negative bf16 is a negative int16,
                         // so one v_pk_max_i16 against 0 gates both halves -- 8 ops per block instead of 16 v_max_f32.
                         if (MODE == MODE_RELU) v = relu_bf16x2(v);
-#if PNR_OPT_EAGER_EPI
                         asm volatile("" : "+v"(v));      // materialise here: hipcc otherwise parks all of a layer's pack/ReLU at its end
-#endif
                         out[t][fb * RPB + p] = v;
                     }
                     if (save) store_slots(save, NFB_OUT * 32, srow[t], fb, c.hi, &out[t][fb * RPB]);
@@ -138,13 +117,7 @@ __device__ __forceinline__ void store_raw_block(const MlpArgs& a, int samp, int 
         const int u = fb * 32 + (r & 3) + 8 * (r >> 2);
         if (u < lim) {
             float* const p = dst0 + (int64_t)(ch_base + u) * a.sc;
-#if PNR_RAW_STORE == 1
-            __builtin_nontemporal_store(acc[r], p);                                   // nt
-#elif PNR_RAW_STORE == 2
-            __hip_atomic_store(p, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // sc1: write-through, line dropped from L2
-#else
             *p = acc[r];
-#endif
         }
     }
 }
@@ -182,12 +155,8 @@ __device__ __forceinline__ void layer_out(CTX& c, const uint32_t (&inA)[TILES][N
 // phases whose partner group has nothing to multiply (group start, first views chunk: ~4 % of the fine-level launch).
 // Absolute error <= 2e-7, doubled per octave by the recurrences that follow: far below the bf16 rounding (2^-9).
 // The fp32 parity mode keeps libm's sincosf at every band.
-#ifndef PNR_EMBED_FAST_SINCOS
-#define PNR_EMBED_FAST_SINCOS 1
-#endif
 __device__ __forceinline__ void sincos_cw(float x, float& s, float& c)
 {
-#if PNR_EMBED_FAST_SINCOS
     const float kf = __builtin_rintf(x * 0.636619772367581343f);
     float r = fmaf(-kf, 1.57079637050628662109375f, x);            // fl(pi/2)
     r = fmaf(-kf, -4.371139000186241e-08f, r);                      // pi/2 - fl(pi/2)
@@ -203,9 +172,6 @@ __device__ __forceinline__ void sincos_cw(float x, float& s, float& c)
     const float so = (k & 1) ? cs : sn, co = (k & 1) ? sn : cs;
     s = __uint_as_float(__float_as_uint(so) ^ ((uint32_t)(k & 2) << 30));
     c = __uint_as_float(__float_as_uint(co) ^ ((uint32_t)((k + 1) & 2) << 30));
-#else
-    sincosf(x, &s, &c);
-#endif
 }
 
 // The bf16 encoding in stages (k_mlp_pp computes the NEXT sample group's gamma(x) and this group's gamma(d) piece by piece in
@@ -291,10 +257,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mlp_fused(const MlpArgs a)
 
     CTX c{a, smem, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)),
           (int)((threadIdx.x & 63) >> 5), 0, 0, {0, 0}, {0, 0}};
-#if PNR_TRACE
-    c.tr = reinterpret_cast<unsigned long long*>(smem + 2 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
-    c.titer = 0;
-#endif
+    trace_begin<2>(c);
     const int n = c.lane & 31;
     c.start();
     unsigned long long clk_c0 = 0, clk_r0 = 0;
@@ -304,21 +267,22 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mlp_fused(const MlpArgs a)
 #pragma unroll
     for (int t = 0; t < TILES; ++t) dummy[t][0] = 0;
 
-    // per-sample inputs of one tile: o(3) dx | dy dz (near far unused) | z
-    struct SampleIn { float4 o4, d4; float zz; };
-    auto fetch = [&](int grp, int t) {
+    // per-sample inputs of one tile: o(3) dx | dy dz (near far unused) | z.  This kernel's own form of fetch_sample() and
+    // sample_point() (pnr_mlp_pp.h), kept in its body because its machine code is pinned: see the note there
+    struct TileIn { float4 o4, d4; float zz; };
+    auto fetch_tile = [&](int grp, int t) {
         const int s = ((grp * WAVES + c.wave) * TILES + t) * 32 + n;
         const int sl = s < a.S ? s : a.S - 1;
         const int ray = pnr_div_magic(sl, a.n_magic, a.n_shift);
-        SampleIn in;
+        TileIn in;
         in.o4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8);
         in.d4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8 + 4);
         in.zz = a.z[sl];
         return in;
     };
-    SampleIn nextin[TILES];
+    TileIn nextin[TILES];
 #pragma unroll
-    for (int t = 0; t < TILES; ++t) nextin[t] = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0, t);
+    for (int t = 0; t < TILES; ++t) nextin[t] = fetch_tile(blockIdx.x < a.n_groups ? blockIdx.x : 0, t);
 
     // persistent loop: one group = WAVES * TILES tiles of 32 samples
     for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
@@ -373,7 +337,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mlp_fused(const MlpArgs a)
         {
             const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
 #pragma unroll
-            for (int t = 0; t < TILES; ++t) nextin[t] = fetch(g2, t);
+            for (int t = 0; t < TILES; ++t) nextin[t] = fetch_tile(g2, t);
         }
         layer_regs<PREC, TILES, CTX, PNR_L_FEATURE, HR, 0, NFB, MODE_LINEAR, HR>(c, cur, dummy, nxt, sv(2 + a.D), srow);
         uint32_t ed[TILES][GDR];
@@ -415,18 +379,12 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mlp_fused(const MlpArgs a)
         ++c.titer;
 #endif
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the refill issued past the last chunk
     if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
         a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
         a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-    }   // the refill issued past the last chunk
-#if PNR_TRACE
-    __syncthreads();
-    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 2 * a.slot_bytes);
-        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
     }
-#endif
+    trace_dump<2, WAVES>(a, smem);
 }
 
 // ------------------------------------------------------------------------------- ping-pong form (pnr_mlp_pp.h)
@@ -446,13 +404,13 @@ __device__ __forceinline__ void pp_layer_regs(CTX& c, u32x4 (&A)[CTX::P], const 
     constexpr int FBC = FBC_PLAN > 0 ? FBC_PLAN : (NFB_OUT % FBC0 == 0) ? FBC0 : 1;      // mirrors pnr_build_plan
     using CH = PPChunk<FBC, NA, NB>;
     static_assert(NOUT >= NFB_OUT * 8, "output register array too small");
-    f32x4 q[FBC][4];                                            // bias quads in flight across the chunk boundary
+    f32x4 q[FBC][4];
 #pragma unroll
     for (int cb = 0; cb < NFB_OUT / FBC; ++cb) {
-        // L of chunk cb, last part.  For the layer's 2nd, 3rd, ... chunk the first fragments and the bias were already
-        // requested (below) in the shadow of the previous chunk's refill / epilogue; only the drain is left.
+        // L of chunk cb, last part.  For the layer's 2nd, 3rd, ... chunk the first fragments were already requested (below)
+        // in the shadow of the previous chunk's refill / epilogue; the bias reads and the drain are left.
         if (cb == 0 || !PNR_PP_EARLY) CH::first_frags(c.frag_addr(), A);
-        if (cb == 0 || !PNR_PP_EARLY_BIAS) CH::bias_issue(c.bias_addr(), q);
+        CH::bias_issue(c.bias_addr(), q);
         f32x16 acc[FBC];
         CH::bias_finish(q, acc);                                // waits for every LDS read of the phase
         CH::mma(c.frag_addr(), A, inA, inB, acc, [&](auto... k) { if constexpr (sizeof...(k) == 0) { c.stamp(6); c.barrier(); c.stamp(2); } else c.stamp(k...); });      // L -> M (barrier inside, see mma)
@@ -466,10 +424,6 @@ __device__ __forceinline__ void pp_layer_regs(CTX& c, u32x4 (&A)[CTX::P], const 
                 out[fb * 8 + p] = v;
             }
         };
-        // The M wave reaches the barrier ~200 cycles before its partner finishes L: the pack / ReLU of the chunk's first
-        // PNR_PP_EPI_IN_M blocks (complete one MFMA before the chunk's last) is done here, in that slack, instead of in L.
-#pragma unroll
-        for (int b = 0; b < (PNR_PP_EPI_IN_M < FBC ? PNR_PP_EPI_IN_M : FBC); ++b) epilogue(b);
         c.m_done();                                             // M -> L of the next chunk; own refill pieces landed
         const bool nxt_same = cb + 1 < NFB_OUT / FBC;           // the next chunk has this chunk's shape
         if (PNR_PP_EARLY && nxt_same) CH::first_frags(c.next_frag_addr(), A);
@@ -477,11 +431,10 @@ __device__ __forceinline__ void pp_layer_regs(CTX& c, u32x4 (&A)[CTX::P], const 
 #pragma unroll
         for (int b = 0; b < FBC; ++b) {
             c.refill_one();                                     // one LDS-DMA piece, then a block's pack / ReLU in its shadow
-            if (b >= PNR_PP_EPI_IN_M) epilogue(b);
+            epilogue(b);
             if (save) store_slots(save, NFB_OUT * 32, srow, cb * FBC + b, c.hi, &out[(cb * FBC + b) * 8]);
             side(cb * FBC + b);                                 // a constant once the loops are unrolled
         }
-        if (PNR_PP_EARLY_BIAS && nxt_same) CH::bias_issue(c.next_bias_addr(), q);   // accumulators free: next chunk's bias, asynchronous
         c.refill_rest();
         side(-1 - cb);                                          // end of chunk cb's refill: behind every piece of this L phase
         c.advance();
@@ -510,29 +463,12 @@ __device__ __forceinline__ void pp_layer_out(CTX& c, u32x4 (&A)[CTX::P], const u
         c.m_done();          // its vmcnt(0) precedes the stores below: it never waits for an HBM write issued in this phase
         c.refill_begin();
         c.refill_one();
-#if PNR_PP_STORES_LAST
-        static_assert(!FUSE, "PNR_PP_STORES_LAST: two-kernel path only (the fused kernel has no raw stores)");
-        // Every piece first, then the stores, and the NUMBER of store instructions this wave issues is handed to the next
-        // m_done(): VMEM operations of a wave complete in order, so `s_waitcnt vmcnt(#stores)` there covers the pieces
-        // without waiting for the stores' HBM write acknowledgements (which take longer than two phases).
-        c.refill_rest();
-        if (!(PNR_PP_ABL & 4)) {
-            store_raw_block(c.a, samp, c.hi, fb, n_out, ch_base, acc[0]);
-            int cnt = 0;
-            if (!TRAIN && __builtin_amdgcn_ballot_w64(samp >= 0) != 0) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) cnt += (fb * 32 + (r & 3) + 8 * (r >> 2) < n_out) ? 1 : 0;   // row of the hi = 0 half
-            }
-            c.pending_stores = cnt;
-        }
-#else
         if constexpr (FUSE) {
             if (ch_base == 0) fuse_rgbs(c.a, *st, c.hi, c.lane & 31, acc[0]);
             else if (PNR_FUSE_TRANSPOSED) fuse_logits_t(*st, c.hi, c.lane, fb, n_out, PNR_FUSE_REC_LOGITS + (ch_base - 4), acc[0]);
             else fuse_logits(*st, c.hi, c.lane & 31, fb, n_out, PNR_FUSE_REC_LOGITS + (ch_base - 4), acc[0]);
         } else if (!(PNR_PP_ABL & 4)) store_raw_block(c.a, samp, c.hi, fb, n_out, ch_base, acc[0]);
         c.refill_rest();
-#endif
         c.advance();
     }
 }
@@ -640,35 +576,14 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NFB = W / 32, HFB = W / 64;
     constexpr int HR = NFB * 8, GR = HFB * 8, GXR = 16, GDR = 8;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CTX c{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
-#if PNR_PP_ABL & 16
-    c.abl_sink = u32x4{0, 0, 0, 0};
-#endif
-#if PNR_TRACE
-    c.tr = reinterpret_cast<unsigned long long*>(smem + 3 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
-    c.titer = 0;
-#endif
+    CTX c = pp_ctx<WAVES>(a, smem);
+    unsigned long long clk_c0, clk_r0;
+    pp_begin(c, clk_c0, clk_r0);
     const int n = c.lane & 31;
-    c.start();
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (a.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 
     uint32_t dummy[1] = {0};
     u32x4 A[CTX::P];
-    struct SampleIn { float4 o4, d4; float zz, zn; bool last; };
-    auto fetch = [&](int grp) {
-        const int s = (grp * WAVES + c.wave) * 32 + n;
-        const int sl = s < a.S ? s : a.S - 1;
-        const int ray = pnr_div_magic(sl, a.n_magic, a.n_shift);     // sl / N without the ~40-instruction integer division
-        SampleIn in;
-        in.o4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8);
-        in.d4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8 + 4);
-        in.zz = a.z[sl];
-        in.zn = FUSE ? a.z[sl + 1 < a.S ? sl + 1 : sl] : 0.0f;     // z of the next sample (used inside a ray only)
-        in.last = FUSE ? (sl - ray * a.N + 1 == a.N) : false;      // the ray's last sample: its interval is 1e10
-        return in;
-    };
+    auto fetch = [&](int grp) { return fetch_sample<FUSE>(a, grp * WAVES + c.wave, n); };
     SampleIn nextin = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0);
     FuseState fst;
     // Staged encodings (see embed_sincos): gamma(d) of THIS sample group and gamma(x) of the NEXT one are computed piece by
@@ -679,18 +594,9 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
     // group's values from the end of the trunk on (layer 0 and the skip layer are its only readers).
     uint32_t ex[GXR], ed[GDR];
     float dn_next;                         // |d| of the next group's sample
-    auto points = [&](const SampleIn& in, float& px, float& py, float& pz, float& nrm) {
-        const float dx = in.o4.w, dy = in.d4.x, dz = in.d4.y;
-        // pts = o + d*z: separate multiply and add, as the sampler's pnr_points does
-        px = __fadd_rn(in.o4.x, __fmul_rn(dx, in.zz));
-        py = __fadd_rn(in.o4.y, __fmul_rn(dy, in.zz));
-        pz = __fadd_rn(in.o4.z, __fmul_rn(dz, in.zz));
-        // k_composite's |d|: sqrtf((dx*dx + dy*dy) + dz*dz), contraction off
-        nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    };
     {
         float px, py, pz;
-        points(nextin, px, py, pz, dn_next);
+        sample_point(nextin, px, py, pz, dn_next);
         embed_lane<PNR_PREC_BF16, 5, 32, GXR>(px, py, pz, c.hi, ex);
     }
 
@@ -718,26 +624,12 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
                 pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, sv(2 + l), srow);
             gv(2 + l, out);
         };
-#if PNR_PP_UNROLL2
-        // two layers per trip, cur -> nxt -> cur: no 64-register hand-over copy per layer (it sat in the L phase of every
-        // layer's first chunk); one copy per sample group remains when D-1 is odd
-#pragma unroll 1
-        for (int l = 1; l < a.D; l += 2) {
-            trunk(l, cur, nxt);
-            if (l + 1 < a.D) trunk(l + 1, nxt, cur);
-            else {
-#pragma unroll
-                for (int i = 0; i < HR; ++i) cur[i] = nxt[i];
-            }
-        }
-#else
 #pragma unroll 1
         for (int l = 1; l < a.D; ++l) {
             trunk(l, cur, nxt);
 #pragma unroll
             for (int i = 0; i < HR; ++i) cur[i] = nxt[i];       // (32 v_pk_mov_b32 instead of these 64 v_mov_b32: +-0 measured)
         }
-#endif
         // side work of the feature layer: eight stages over its NFB slots -- gamma(d) of this group (D0..D3), then gamma(x) of
         // the next one (X0..X3), whose inputs are requested behind chunk 0's refill pieces (two chunks ahead of X0 at W = 256)
         const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
@@ -749,26 +641,14 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
             case 1: embed_sincos<2>(q0, 0, c.hi, esc); embed_sincos<2>(q1, 1, c.hi, esc); break;
             case 2: embed_sincos<2>(q2, 2, c.hi, esc); ed[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_pack_band(esc, &ed[1]); break;
             case 3: embed_next_band(esc); embed_pack_band(esc, &ed[4]); ed[7] = 0u; break;
-            case 4: points(nextin, q0, q1, q2, dn_next); ex[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
+            case 4: sample_point(nextin, q0, q1, q2, dn_next); ex[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
             case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &ex[1]); break;
             case 6: embed_next_band(esc); embed_pack_band(esc, &ex[4]); embed_next_band(esc); embed_pack_band(esc, &ex[7]); break;
             default: embed_next_band(esc); embed_pack_band(esc, &ex[10]); embed_next_band(esc); embed_pack_band(esc, &ex[13]); break;
             }
         };
         auto side = [&](int slot) {
-            if (slot == -1) {
-                // the four loads of fetch(): vector-memory operations of a wave complete in order, so the next m_done() may
-                // wait for "all but the youngest four" -- the refill pieces -- instead of an HBM round trip
-                // (the count is the number of vector-memory instructions hipcc emits for fetch(); the markers let
-                // tests/test_asm_lint.py verify it, and that no LDS-DMA piece sits between them, on the compiled assembly)
-                __builtin_amdgcn_sched_barrier(0);     // the loads must stay the YOUNGEST operations: nothing may move across
-                asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
-                nextin = fetch(g2);
-                if constexpr (FUSE) asm volatile("; PNR_FETCH_END 4" ::: "memory");
-                else asm volatile("; PNR_FETCH_END 3" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                c.pending_stores = FUSE ? 4 : 3;
-            }
+            if (slot == -1) pp_fetch_youngest<(FUSE ? 4 : 3)>(c, [&] { nextin = fetch(g2); });     // ray record (2), z [, next z]
             if (slot < 0) return;
             constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
 #pragma unroll
@@ -819,18 +699,58 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
         ++c.titer;
 #endif
     }
-    c.end();
-    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
-        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
+    pp_end(c, clk_c0, clk_r0);
+}
+
+// The trunk of the kernels that end behind it (k_mlp_pp_sigma, k_mlp_pp_field): layer 0, layers 1..D-2, and the last trunk layer
+// with the NEXT sample group's inputs and gamma(x) in its L phases -- k_mlp_pp's stages 4..7 in the slots k_mlp_pp gives them in the
+// feature layer, whose width this layer has (stages 0..3, gamma(d), have no reader here) -- into a second register set, because
+// that layer may be the one behind the skip connection and still read this group's gamma(x).  The trunk output comes out in h, and ex holds
+// the next group's gamma(x).  request(g2): load the inputs of sample group g2 (LOADS vector-memory instructions, behind chunk 0's
+// refill pieces: pp_fetch_youngest); point(x, y, z): the position those inputs give.
+template <int W, int LOADS, class CTX, class REQ, class PT>
+__device__ __forceinline__ void pp_trunk_staged(CTX& c, u32x4 (&A)[CTX::P], int grp, int srow, uint32_t (&ex)[16], uint32_t (&h)[W / 4],
+                                                REQ&& request, PT&& point)
+{
+    constexpr int NFB = W / 32, HR = NFB * 8, GXR = 16;
+    const MlpArgs& a = c.a;
+    uint32_t dummy[1] = {0};
+    uint32_t cur[HR], exn[GXR];
+    pp_layer_regs<CTX, PNR_L_TRUNK0, GXR, 0, NFB, MODE_RELU, HR, (PNR_PLAN1_TRUNK0_MERGE ? NFB : 0)>(c, A, ex, dummy, cur, nullptr, srow);
+    auto trunk = [&](int l, const uint32_t (&in)[HR], uint32_t (&out)[HR], auto&& side) {
+        if (l - 1 == a.skip)
+            pp_layer_regs<CTX, PNR_L_TRUNK, GXR, HR, NFB, MODE_RELU, HR>(c, A, ex, in, out, nullptr, srow, side);
+        else
+            pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, nullptr, srow, side);
+    };
+#pragma unroll 1
+    for (int l = 1; l < a.D - 1; ++l) {
+        trunk(l, cur, h, NoSide{});
+#pragma unroll
+        for (int i = 0; i < HR; ++i) cur[i] = h[i];
     }
-#if PNR_TRACE
-    __syncthreads();
-    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 3 * a.slot_bytes);
-        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
-    }
-#endif
+    const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
+    EmbedSC esc;
+    float q0, q1, q2;
+    auto stage = [&](int k) {
+        switch (k) {
+        case 4: point(q0, q1, q2); exn[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
+        case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &exn[1]); break;
+        case 6: embed_next_band(esc); embed_pack_band(esc, &exn[4]); embed_next_band(esc); embed_pack_band(esc, &exn[7]); break;
+        case 7: embed_next_band(esc); embed_pack_band(esc, &exn[10]); embed_next_band(esc); embed_pack_band(esc, &exn[13]); break;
+        default: break;
+        }
+    };
+    auto side = [&](int slot) {
+        if (slot == -1) pp_fetch_youngest<LOADS>(c, [&] { request(g2); });
+        if (slot < 0) return;
+        constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
+#pragma unroll
+        for (int j = 0; j < PER; ++j) stage(slot * PER + j);
+    };
+    trunk(a.D - 1, cur, h, side);
+#pragma unroll
+    for (int i = 0; i < GXR; ++i) ex[i] = exn[i];
 }
 
 // ------------------------------------------------------------------------------- sigma-only form (plan 3)
@@ -840,8 +760,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp(const MlpArgs a)
 // chunk (whose g-segment fragments are zero in row 3: their MFMAs add exact zeros).  The fused epilogue (fuse_rgbs) therefore
 // writes the same Q and lw bits as every other plan, with r = g = b = 0 and records of pnr_fuse_record_floats(0, 0) floats.  No
 // gamma(d), no feature / views / rgb layers, no heads.  The next sample group's input fetch and its gamma(x) staging, which k_mlp_pp
-// places in the L phases of the feature layer, run in those of the LAST TRUNK LAYER here -- into a second register set, because
-// that layer may be the one behind the skip connection and still read this group's gamma(x).
+// places in the L phases of the feature layer, run in those of the LAST TRUNK LAYER here (pp_trunk_staged).
 template <int W>
 __global__ __launch_bounds__(512, 2) void k_mlp_pp_sigma(const MlpArgs a)
 {
@@ -850,49 +769,21 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp_sigma(const MlpArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NFB = W / 32;
     constexpr int HR = NFB * 8, GXR = 16;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CTX c{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
-#if PNR_PP_ABL & 16
-    c.abl_sink = u32x4{0, 0, 0, 0};
-#endif
-#if PNR_TRACE
-    c.tr = reinterpret_cast<unsigned long long*>(smem + 3 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
-    c.titer = 0;
-#endif
+    CTX c = pp_ctx<WAVES>(a, smem);
+    unsigned long long clk_c0, clk_r0;
+    pp_begin(c, clk_c0, clk_r0);
     const int n = c.lane & 31;
-    c.start();
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (a.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 
     uint32_t dummy[1] = {0};
     u32x4 A[CTX::P];
-    struct SampleIn { float4 o4, d4; float zz, zn; bool last; };
-    auto fetch = [&](int grp) {             // k_mlp_pp's fetch<FUSE>
-        const int s = (grp * WAVES + c.wave) * 32 + n;
-        const int sl = s < a.S ? s : a.S - 1;
-        const int ray = pnr_div_magic(sl, a.n_magic, a.n_shift);
-        SampleIn in;
-        in.o4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8);
-        in.d4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8 + 4);
-        in.zz = a.z[sl];
-        in.zn = a.z[sl + 1 < a.S ? sl + 1 : sl];
-        in.last = sl - ray * a.N + 1 == a.N;
-        return in;
-    };
+    auto fetch = [&](int grp) { return fetch_sample<true>(a, grp * WAVES + c.wave, n); };
     SampleIn nextin = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0);
     FuseState fst;
-    uint32_t ex[GXR], exn[GXR];            // gamma(x) of this sample group / of the next one (staged in the last trunk layer)
+    uint32_t ex[GXR];
     float dn_next;
-    auto points = [&](const SampleIn& in, float& px, float& py, float& pz, float& nrm) {
-        const float dx = in.o4.w, dy = in.d4.x, dz = in.d4.y;
-        px = __fadd_rn(in.o4.x, __fmul_rn(dx, in.zz));
-        py = __fadd_rn(in.o4.y, __fmul_rn(dy, in.zz));
-        pz = __fadd_rn(in.o4.z, __fmul_rn(dz, in.zz));
-        nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    };
     {
         float px, py, pz;
-        points(nextin, px, py, pz, dn_next);
+        sample_point(nextin, px, py, pz, dn_next);
         embed_lane<PNR_PREC_BF16, 5, 32, GXR>(px, py, pz, c.hi, ex);
     }
 
@@ -901,70 +792,35 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp_sigma(const MlpArgs a)
         const int samp = s0 < a.S ? s0 : -1;
         fst.zz = nextin.zz; fst.zn = nextin.zn; fst.dn = dn_next; fst.samp = samp; fst.last = nextin.last;
         fst.rec = a.rec + (int64_t)(grp * WAVES + c.wave) * a.rec_floats;
-        uint32_t cur[HR], nxt[HR];
-        pp_layer_regs<CTX, PNR_L_TRUNK0, GXR, 0, NFB, MODE_RELU, HR, (PNR_PLAN1_TRUNK0_MERGE ? NFB : 0)>(c, A, ex, dummy, cur, nullptr, s0);
-        auto trunk = [&](int l, const uint32_t (&in)[HR], uint32_t (&out)[HR], auto&& side) {
-            if (l - 1 == a.skip)
-                pp_layer_regs<CTX, PNR_L_TRUNK, GXR, HR, NFB, MODE_RELU, HR>(c, A, ex, in, out, nullptr, s0, side);
-            else
-                pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, nullptr, s0, side);
-        };
-#pragma unroll 1
-        for (int l = 1; l < a.D - 1; ++l) {
-            trunk(l, cur, nxt, NoSide{});
-#pragma unroll
-            for (int i = 0; i < HR; ++i) cur[i] = nxt[i];
-        }
-        // side work of the last trunk layer: k_mlp_pp's stages 4..7 (gamma(x) of the next sample group) in the slots k_mlp_pp gives
-        // them in the feature layer, whose width this layer has; stages 0..3 (gamma(d)) have no reader here
-        const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
-        EmbedSC esc;
-        float q0, q1, q2;
-        auto stage = [&](int k) {
-            switch (k) {
-            case 4: points(nextin, q0, q1, q2, dn_next); exn[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
-            case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &exn[1]); break;
-            case 6: embed_next_band(esc); embed_pack_band(esc, &exn[4]); embed_next_band(esc); embed_pack_band(esc, &exn[7]); break;
-            case 7: embed_next_band(esc); embed_pack_band(esc, &exn[10]); embed_next_band(esc); embed_pack_band(esc, &exn[13]); break;
-            default: break;
-            }
-        };
-        auto side = [&](int slot) {
-            if (slot == -1) {
-                // the four loads of fetch(), the youngest vector-memory operations of the phase: the next m_done() waits for all but
-                // them (k_mlp_pp's side(-1); tests/test_asm_lint.py checks the count on the compiled assembly)
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
-                nextin = fetch(g2);
-                asm volatile("; PNR_FETCH_END 4" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                c.pending_stores = 4;
-            }
-            if (slot < 0) return;
-            constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
-#pragma unroll
-            for (int j = 0; j < PER; ++j) stage(slot * PER + j);
-        };
-        trunk(a.D - 1, cur, nxt, side);
-#pragma unroll
-        for (int i = 0; i < GXR; ++i) ex[i] = exn[i];
+        uint32_t nxt[HR];
+        pp_trunk_staged<W, 4>(c, A, grp, s0, ex, nxt, [&](int g2) { nextin = fetch(g2); },
+                              [&](float& x, float& y, float& z) { sample_point(nextin, x, y, z, dn_next); });
         pp_layer_out<false, true, CTX, HR, 0>(c, A, nxt, dummy, 4, 0, samp, &fst);
 #if PNR_TRACE
         ++c.titer;
 #endif
     }
-    c.end();
-    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
-        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
+    pp_end(c, clk_c0, clk_r0);
+}
+
+// The ping-pong launch shape: three weight slots (+ the trace area) of LDS, 512 threads, one 8-wave workgroup per CU (2 x 256
+// registers per SIMD), grid-stride over the 256-sample groups.  m: the MlpArgs inside args (args itself, or FieldArgs::m), its
+// n_groups = pp_groups(S) set by the caller; attr_set: the CALLER's per-kernel "LDS attribute already set" flag (a function-local
+// thread_local of each launcher instantiation); who: the entry point's name for the error text.
+static int pp_lds_bytes(const MlpArgs& m) { return 3 * m.slot_bytes + (PNR_TRACE ? 8 * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS * 8 : 0); }
+static int pp_groups(int S) { return (S + 255) / 256; }
+template <class ARGS>
+static int launch_pp(void (*kern)(const ARGS), const ARGS& args, const MlpArgs& m, bool& attr_set, hipStream_t stream, const char* who)
+{
+    if (!attr_set) {
+        PNR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
+        attr_set = true;
     }
-#if PNR_TRACE
-    __syncthreads();
-    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 3 * a.slot_bytes);
-        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
-    }
-#endif
+    const int cap = pnr_cu_count();
+    const int grid = m.n_groups < cap ? m.n_groups : cap;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pp_lds_bytes(m), stream, args);
+    PNR_CHECK_LAUNCH(who);
+    return PNR_OK;
 }
 
 // SIGMA: k_mlp_pp_sigma<W> (plan 3) instead of k_mlp_pp -- the same weight stream, LDS slots and launch shape
@@ -972,22 +828,13 @@ template <int W, bool TRAIN, bool FUSE = false, int TAIL = 0, bool SIGMA = false
 static int launch_mlp_pp(const MlpArgs& a0, hipStream_t stream)
 {
     MlpArgs a = a0;
-    const int lds_bytes = 3 * a.slot_bytes + (PNR_TRACE ? 8 * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS * 8 : 0);
-    PNR_REQUIRE(lds_bytes <= 163840, "pnr_mlp_forward: three weight slots of %d bytes exceed the 160 KiB LDS", a.slot_bytes);
+    PNR_REQUIRE(pp_lds_bytes(a) <= 163840, "pnr_mlp_forward: three weight slots of %d bytes exceed the 160 KiB LDS", a.slot_bytes);
     PNR_REQUIRE(a.n_chunks >= 4, "pnr_mlp_forward: network too small for the weight stream");
-    a.n_groups = (a.S + 255) / 256;
+    a.n_groups = pp_groups(a.S);
     auto kern = k_mlp_pp<W, TRAIN, FUSE, TAIL>;
     if constexpr (SIGMA) kern = k_mlp_pp_sigma<W>;
     static thread_local bool attr_set = false;
-    if (!attr_set) {
-        PNR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
-        attr_set = true;
-    }
-    const int cap = pnr_cu_count();           // one 8-wave workgroup per CU (2 x 256 registers per SIMD)
-    const int grid = a.n_groups < cap ? a.n_groups : cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, a);
-    PNR_CHECK_LAUNCH("pnr_mlp_forward");
-    return PNR_OK;
+    return launch_pp(kern, a, a, attr_set, stream, "pnr_mlp_forward");
 }
 
 // ------------------------------------------------------------------------------- launcher
@@ -1027,6 +874,23 @@ static inline unsigned long long* clk_probe_of(const pnr_mlp_desc* d)
     return (unsigned long long*)(uintptr_t)(((uint64_t)(uint32_t)d->clk_probe[1] << 32) | (uint64_t)(uint32_t)d->clk_probe[0]);
 }
 
+// MlpArgs from (desc, plan, packed): the weight stream, the geometry, the clock probe and -- PNR_TRACE builds -- where the trace
+// goes.  Everything else is zero; the entry points add their inputs and outputs.
+static void mlp_args_fill(MlpArgs& a, const pnr_mlp_desc* desc, const PnrPlan& plan, const void* packed)
+{
+    memset(&a, 0, sizeof(a));
+    a.data = (const uint8_t*)packed + plan.data_off;
+    a.table = (const pnr_chunk_entry*)((const uint8_t*)packed + plan.table_off);
+    a.n_chunks = (int)plan.chunks.size();
+    a.slot_bytes = plan.max_chunk_frags * PNR_FRAG_BYTES;
+    a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
+    a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
+    a.clk = clk_probe_of(desc);
+#if PNR_TRACE
+    if (const char* e = getenv("PNR_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
+#endif
+}
+
 static int mlp_forward_impl(const pnr_mlp_desc* desc, const void* packed, const float* rays, const float* z,
                             int64_t n_rays, int n_samples, float* raw, int64_t raw_stride_s, int64_t raw_stride_c,
                             void* acts, void* stream)
@@ -1046,21 +910,11 @@ static int mlp_forward_impl(const pnr_mlp_desc* desc, const void* packed, const 
     PnrPlan plan;
     pnr_build_plan(*desc, plan);
     MlpArgs a;
-    memset(&a, 0, sizeof(a));
-    a.data = (const uint8_t*)packed + plan.data_off;
-    a.table = (const pnr_chunk_entry*)((const uint8_t*)packed + plan.table_off);
-    a.n_chunks = (int)plan.chunks.size();
-    a.slot_bytes = plan.max_chunk_frags * PNR_FRAG_BYTES;
-    a.rays = rays; a.z = z; a.S = (int)(n_rays * n_samples); a.N = n_samples; a.n_groups = 0;
+    mlp_args_fill(a, desc, plan, packed);
+    a.rays = rays; a.z = z; a.S = (int)(n_rays * n_samples); a.N = n_samples;
     pnr_set_div_magic(n_samples, a.n_magic, a.n_shift);
     a.raw = raw; a.ss = raw_stride_s; a.sc = raw_stride_c;
-    a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
-    a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
     a.acts = (uint16_t*)acts;
-#if PNR_TRACE
-    if (const char* e = getenv("PNR_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-    a.clk = clk_probe_of(desc);
     if (acts) pnr_train_layout(*desc, a.S, a.acts_off, a.dys_off, a.gate_off);
     hipStream_t st = (hipStream_t)stream;
     // bf16: 8 waves x 1 tile, registers capped at 256 (2 waves per SIMD, one workgroup per CU);
@@ -1162,23 +1016,13 @@ static int fused_mlp_launch(const pnr_mlp_desc* desc, const void* packed, const 
                 "pnr_mlp_forward_composite: rays / packed / workspace must be 16-byte aligned");
     PnrPlan plan;
     pnr_build_plan(*desc, plan);
-    memset(&a, 0, sizeof(a));
-    a.data = (const uint8_t*)packed + plan.data_off;
-    a.table = (const pnr_chunk_entry*)((const uint8_t*)packed + plan.table_off);
-    a.n_chunks = (int)plan.chunks.size();
-    a.slot_bytes = plan.max_chunk_frags * PNR_FRAG_BYTES;
+    mlp_args_fill(a, desc, plan, packed);
     a.rays = rays; a.z = z; a.S = (int)(n_rays * n_samples); a.N = n_samples;
     pnr_set_div_magic(n_samples, a.n_magic, a.n_shift);
-    a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
-    a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
     a.rec_floats = record_floats(*desc);
     a.rec = (float*)workspace;
     const int64_t tiles = ((int64_t)a.S + 255) / 256 * 8;
     a.ps = (float4*)(a.rec + tiles * a.rec_floats);           // rec_floats % 4 == 0: 16-byte aligned
-    a.clk = clk_probe_of(desc);
-#if PNR_TRACE
-    if (const char* e = getenv("PNR_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
     hipStream_t st = (hipStream_t)stream;
     const bool softmax = (desc->flags & PNR_MLP_SOFTMAX) && desc->n_sem + desc->n_inst > 0;
     if (desc->plan == 3)        // sigma only: no learned field, so PNR_MLP_SOFTMAX has nothing to act on
@@ -1363,24 +1207,15 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp_field(const FieldArgs fa)
     constexpr int NFB = W / 32, HFB = W / 64;
     constexpr int HR = NFB * 8, GR = HFB * 8, GXR = 16;
     const MlpArgs& a = fa.m;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CTX c{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
-#if PNR_PP_ABL & 16
-    c.abl_sink = u32x4{0, 0, 0, 0};
-#endif
-#if PNR_TRACE
-    c.tr = reinterpret_cast<unsigned long long*>(smem + 3 * a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
-    c.titer = 0;
-#endif
+    CTX c = pp_ctx<WAVES>(a, smem);
+    unsigned long long clk_c0, clk_r0;
+    pp_begin(c, clk_c0, clk_r0);
     const int n = c.lane & 31;
-    c.start();
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (a.clk) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 
     uint32_t dummy[1] = {0};
     u32x4 A[CTX::P];
     struct PointIn { float x, y, z; };
-    auto fetch = [&](int grp) {             // rows past the end read the last point (computed, never stored)
+    auto fetch_point = [&](int grp) {       // rows past the end read the last point (computed, never stored)
         const int s = (grp * WAVES + c.wave) * 32 + n;
         const int sl = s < a.S ? s : a.S - 1;
         const float* p = fa.pts + (int64_t)sl * 3;
@@ -1388,71 +1223,29 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp_field(const FieldArgs fa)
         in.x = p[0]; in.y = p[1]; in.z = p[2];
         return in;
     };
-    PointIn nextin = fetch(blockIdx.x < a.n_groups ? blockIdx.x : 0);
-    uint32_t ex[GXR], exn[GXR];            // gamma(x) of this sample group / of the next one (staged in the last trunk layer)
+    PointIn nextin = fetch_point(blockIdx.x < a.n_groups ? blockIdx.x : 0);
+    uint32_t ex[GXR];
     // x + 0: a -0.0 coordinate becomes +0.0, as it does in the classic pass's o + d * z at z = 0 -- the same position, bit for bit
     embed_lane<PNR_PREC_BF16, 5, 32, GXR>(__fadd_rn(nextin.x, 0.0f), __fadd_rn(nextin.y, 0.0f), __fadd_rn(nextin.z, 0.0f), c.hi, ex);
 
     for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
         const int s0 = (grp * WAVES + c.wave) * 32 + n;
         const int samp = s0 < a.S ? s0 : -1;
-        uint32_t cur[HR], nxt[HR];
-        pp_layer_regs<CTX, PNR_L_TRUNK0, GXR, 0, NFB, MODE_RELU, HR, (PNR_PLAN1_TRUNK0_MERGE ? NFB : 0)>(c, A, ex, dummy, cur, nullptr, s0);
-        auto trunk = [&](int l, const uint32_t (&in)[HR], uint32_t (&out)[HR], auto&& side) {
-            if (l - 1 == a.skip)
-                pp_layer_regs<CTX, PNR_L_TRUNK, GXR, HR, NFB, MODE_RELU, HR>(c, A, ex, in, out, nullptr, s0, side);
-            else
-                pp_layer_regs<CTX, PNR_L_TRUNK, HR, 0, NFB, MODE_RELU, HR>(c, A, in, dummy, out, nullptr, s0, side);
-        };
-#pragma unroll 1
-        for (int l = 1; l < a.D - 1; ++l) {
-            trunk(l, cur, nxt, NoSide{});
-#pragma unroll
-            for (int i = 0; i < HR; ++i) cur[i] = nxt[i];
-        }
-        // side work of the last trunk layer, as in k_mlp_pp_sigma: the next group's points are requested behind chunk 0's refill
-        // pieces and its gamma(x) is staged in the slots k_mlp_pp gives stages 4..7 in the feature layer
-        const int g2 = grp + (int)gridDim.x < a.n_groups ? grp + (int)gridDim.x : grp;
-        EmbedSC esc;
-        float q0, q1, q2;
-        auto stage = [&](int k) {
-            switch (k) {
-            case 4: q0 = __fadd_rn(nextin.x, 0.0f); q1 = __fadd_rn(nextin.y, 0.0f); q2 = __fadd_rn(nextin.z, 0.0f);
-                    exn[0] = embed_pack_xyz(q0, q1, q2, c.hi); embed_sincos<5>(q0, 0, c.hi, esc); break;
-            case 5: embed_sincos<5>(q1, 1, c.hi, esc); embed_sincos<5>(q2, 2, c.hi, esc); embed_pack_band(esc, &exn[1]); break;
-            case 6: embed_next_band(esc); embed_pack_band(esc, &exn[4]); embed_next_band(esc); embed_pack_band(esc, &exn[7]); break;
-            case 7: embed_next_band(esc); embed_pack_band(esc, &exn[10]); embed_next_band(esc); embed_pack_band(esc, &exn[13]); break;
-            default: break;
-            }
-        };
-        auto side = [&](int slot) {
-            if (slot == -1) {
-                // the loads of fetch(), the youngest vector-memory operations of the phase: the next m_done() waits for all but
-                // them (k_mlp_pp's side(-1); tests/test_asm_lint.py checks the count on the compiled assembly)
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
-                nextin = fetch(g2);
-                asm volatile("; PNR_FETCH_END " PNR_FIELD_FETCH_LOADS_S ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                c.pending_stores = PNR_FIELD_FETCH_LOADS;
-            }
-            if (slot < 0) return;
-            constexpr int PER = 8 / NFB;   // stages per slot: 1 (W = 256), 2 (W = 128)
-#pragma unroll
-            for (int j = 0; j < PER; ++j) stage(slot * PER + j);
-        };
-        trunk(a.D - 1, cur, nxt, side);
-#pragma unroll
-        for (int i = 0; i < GXR; ++i) ex[i] = exn[i];
+        uint32_t nxt[HR];
+        // one point = three floats, one vector-memory instruction (tools/asm_lint.py counts it on the compiled assembly)
+        pp_trunk_staged<W, 1>(c, A, grp, s0, ex, nxt, [&](int g2) { nextin = fetch_point(g2); }, [&](float& x, float& y, float& z) {
+            x = __fadd_rn(nextin.x, 0.0f); y = __fadd_rn(nextin.y, 0.0f); z = __fadd_rn(nextin.z, 0.0f);
+        });
         // sigma: row 3 of the block = register 3 of the hi = 0 half-wave (pnr_row_of)
         pp_field_out<CTX, HR>(c, A, nxt, 4, [&](int, const f32x16& acc) {
             if (fa.sigma && samp >= 0 && c.hi == 0) fa.sigma[samp] = acc[3];
         });
         if constexpr (HEADS) {
             if (a.head_tap) {               // the heads read feature_linear's output: it takes h's registers (h is dead)
-                pp_layer_regs<CTX, PNR_L_FEATURE, HR, 0, NFB, MODE_LINEAR, HR>(c, A, nxt, dummy, cur, nullptr, s0);
+                uint32_t ft[HR];
+                pp_layer_regs<CTX, PNR_L_FEATURE, HR, 0, NFB, MODE_LINEAR, HR>(c, A, nxt, dummy, ft, nullptr, s0);
 #pragma unroll
-                for (int i = 0; i < HR; ++i) nxt[i] = cur[i];
+                for (int i = 0; i < HR; ++i) nxt[i] = ft[i];
             }
             int lab_sem = 0, lab_inst = -1;
             // the two heads are the same code over consecutive chunks of the stream (PNR_L_SEM0 / PNR_L_INST0 chunk alike)
@@ -1497,37 +1290,16 @@ __global__ __launch_bounds__(512, 2) void k_mlp_pp_field(const FieldArgs fa)
         ++c.titer;
 #endif
     }
-    c.end();
-    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
-        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-    }
-#if PNR_TRACE
-    __syncthreads();
-    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + 3 * a.slot_bytes);
-        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
-    }
-#endif
+    pp_end(c, clk_c0, clk_r0);
 }
 
 template <int W, bool HEADS>
 static int launch_field(const FieldArgs& fa0, hipStream_t stream)
 {
     FieldArgs fa = fa0;
-    const int lds_bytes = 3 * fa.m.slot_bytes + (PNR_TRACE ? 8 * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS * 8 : 0);
-    fa.m.n_groups = (fa.m.S + 255) / 256;
-    auto kern = k_mlp_pp_field<W, HEADS>;
+    fa.m.n_groups = pp_groups(fa.m.S);
     static thread_local bool attr_set = false;
-    if (!attr_set) {
-        PNR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
-        attr_set = true;
-    }
-    const int cap = pnr_cu_count();           // one 8-wave workgroup per CU, as k_mlp_pp
-    const int grid = fa.m.n_groups < cap ? fa.m.n_groups : cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, fa);
-    PNR_CHECK_LAUNCH("pnr_mlp_query");
-    return PNR_OK;
+    return launch_pp(k_mlp_pp_field<W, HEADS>, fa, fa.m, attr_set, stream, "pnr_mlp_query");
 }
 
 PNR_EXPORT int pnr_mlp_query(const pnr_mlp_desc* desc, const void* packed, const float* points, int64_t n_points,
@@ -1556,21 +1328,13 @@ PNR_EXPORT int pnr_mlp_query(const pnr_mlp_desc* desc, const void* packed, const
     FieldArgs fa;
     memset(&fa, 0, sizeof(fa));
     MlpArgs& a = fa.m;
+    mlp_args_fill(a, desc, plan, packed);
     // the heads whose chunks the launch streams: what the outputs need, and the semantic head in front of a wanted instance head
     fa.run_inst = desc->n_inst > 0 && (inst_label || inst_logits || panoptic);
     fa.run_sem = desc->n_sem > 0 && (sem_label || sem_logits || panoptic || fa.run_inst);
-    a.data = (const uint8_t*)packed + plan.data_off;
-    a.table = (const pnr_chunk_entry*)((const uint8_t*)packed + plan.table_off);
-    a.n_chunks = pnr_field_chunks(plan, fa.run_sem, fa.run_inst);
-    a.slot_bytes = plan.max_chunk_frags * PNR_FRAG_BYTES;
+    a.n_chunks = pnr_field_chunks(plan, fa.run_sem, fa.run_inst);      // the prefix of the stream the wanted outputs need
     PNR_REQUIRE(a.n_chunks >= 4 && 3 * a.slot_bytes <= 163840, "pnr_mlp_query: weight stream does not fit (chunks=%d, slot=%d bytes)", a.n_chunks, a.slot_bytes);
     a.S = (int)n_points; a.N = 1;
-    a.D = desc->D; a.skip = desc->skip; a.n_sem = desc->n_sem; a.n_inst = desc->n_inst;
-    a.head_tap = desc->head_tap; a.head_depth = desc->head_depth == 1 ? 1 : 2;
-    a.clk = clk_probe_of(desc);
-#if PNR_TRACE
-    if (const char* e = getenv("PNR_TRACE_PTR")) a.trace = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
     fa.pts = points; fa.sigma = sigma; fa.sem_label = sem_label; fa.inst_label = inst_label; fa.panoptic = panoptic;
     fa.is_thing = is_thing; fa.sem_logits = sem_logits; fa.inst_logits = inst_logits; fa.lstride = logit_stride;
     hipStream_t st = (hipStream_t)stream;

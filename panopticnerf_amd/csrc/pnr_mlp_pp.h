@@ -90,14 +90,8 @@ __device__ __forceinline__ void pp_wait(u32x4& a)
 #endif
 // timing-only ablations (A/B builds; results are wrong): 1 = no refill pieces, 2 = no fragment reads inside the MFMA loop
 // 1: the first fragments of a layer's 2nd, 3rd, ... chunk are read right after the previous chunk's M -> L barrier
-#ifndef PNR_PP_HEAD
-#define PNR_PP_HEAD 0        /* MFMAs of a chunk issued before its L -> M barrier (soft hand-over of the matrix pipe) */
-#endif
 #ifndef PNR_PP_EARLY
 #define PNR_PP_EARLY 1
-#endif
-#ifndef PNR_PP_EARLY_BIAS
-#define PNR_PP_EARLY_BIAS 0
 #endif
 #ifndef PNR_PP_ABL
 #define PNR_PP_ABL 0
@@ -183,7 +177,6 @@ struct CtxPP {
     __device__ __forceinline__ uint32_t frag_addr() const { return lds_frag + slot_off; }
     __device__ __forceinline__ uint32_t bias_addr() const { return lds_bias + slot_off; }
     __device__ __forceinline__ uint32_t next_frag_addr() const { return lds_frag + wrap_slot(slot_off + a.slot_bytes); }
-    __device__ __forceinline__ uint32_t next_bias_addr() const { return lds_bias + wrap_slot(slot_off + a.slot_bytes); }
     // After the chunk's MFMAs: close the M phase.  BEFORE the barrier this wave waits for its own refill pieces (issued at
     // the start of its previous L, ~2 phases ago: landed long since, the wait is free) -- so that every piece is covered by
     // its issuer's vmcnt(0) AND a barrier before anybody reads it, including the other waves of the issuer's own group,
@@ -198,8 +191,8 @@ struct CtxPP {
         barrier();
         stamp(4);
     }
-    // vmcnt wait that covers every refill piece of this wave but not the `pending_stores` raw-output stores it issued
-    // AFTER them (pp_layer_out): s_waitcnt takes an immediate, hence the ladder (uniform branches, output chunks only)
+    // vmcnt wait that covers every refill piece of this wave but not the `pending_stores` vector-memory operations it issued
+    // AFTER them (the input loads behind PNR_FETCH_BEGIN): s_waitcnt takes an immediate, hence the ladder (uniform branches)
     int pending_stores;
     __device__ __forceinline__ void wait_pieces()
     {
@@ -270,6 +263,122 @@ struct CtxPP {
     }
 };
 
+// ------------------------------------------------------------------------------- kernel frame
+// What the ping-pong kernels of pnr_mlp.hip (k_mlp_pp, k_mlp_pp_sigma, k_mlp_pp_field) do around their layers, defined ONCE: the
+// bit-for-bit promises of include/pnr.h between them hang on fetch_sample() and sample_point() being the same code in all.
+// (The lock-step k_mlp_fused keeps its own per-tile fetch, point arithmetic and clock probe in its body: hipcc schedules that
+// kernel differently as soon as they become calls, and its machine code is pinned.  It shares the trace area.)
+
+// per-sample inputs of one 32-sample tile: o(3) dx | dy dz (near far unused) | z | z of the next sample | last sample of its ray
+struct SampleIn { float4 o4, d4; float zz, zn; bool last; };
+// lane n of tile `tile`; rows past the end read the last sample (computed, never stored).  NEXT: zn and last, which only the fused
+// compositing epilogue reads (one more load)
+template <bool NEXT>
+__device__ __forceinline__ SampleIn fetch_sample(const MlpArgs& a, int tile, int n)
+{
+    const int s = tile * 32 + n;
+    const int sl = s < a.S ? s : a.S - 1;
+    const int ray = pnr_div_magic(sl, a.n_magic, a.n_shift);     // sl / N without the ~40-instruction integer division
+    SampleIn in;
+    in.o4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8);
+    in.d4 = *reinterpret_cast<const float4*>(a.rays + (int64_t)ray * 8 + 4);
+    in.zz = a.z[sl];
+    in.zn = NEXT ? a.z[sl + 1 < a.S ? sl + 1 : sl] : 0.0f;     // z of the next sample (used inside a ray only)
+    in.last = NEXT ? (sl - ray * a.N + 1 == a.N) : false;      // the ray's last sample: its interval is 1e10
+    return in;
+}
+// the sample's position and |d|
+__device__ __forceinline__ void sample_point(const SampleIn& in, float& px, float& py, float& pz, float& nrm)
+{
+    const float dx = in.o4.w, dy = in.d4.x, dz = in.d4.y;
+    // pts = o + d*z: separate multiply and add, as the sampler's pnr_points does
+    px = __fadd_rn(in.o4.x, __fmul_rn(dx, in.zz));
+    py = __fadd_rn(in.o4.y, __fmul_rn(dy, in.zz));
+    pz = __fadd_rn(in.o4.z, __fmul_rn(dz, in.zz));
+    // k_composite's |d|: sqrtf((dx*dx + dy*dy) + dz*dz), contraction off
+    nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+}
+
+// clock probe (MlpArgs::clk): {shader cycles, 100 MHz ticks} of workgroup 0's first wave, from the end of the context's start().
+// The start values are the kernel's own two scalars (a struct of them changes the code hipcc makes of every k_mlp_pp).
+__device__ __forceinline__ void clk_probe_begin(const MlpArgs& a, unsigned long long& c0, unsigned long long& r0)
+{
+    c0 = r0 = 0;
+    if (a.clk) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+}
+__device__ __forceinline__ void clk_probe_end(const MlpArgs& a, unsigned long long c0, unsigned long long r0)
+{
+    if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
+        a.clk[0] = __builtin_amdgcn_s_memtime() - c0;
+        a.clk[1] = __builtin_amdgcn_s_memrealtime() - r0;
+    }
+}
+
+// PNR_TRACE builds: every wave's stamps live in the LDS behind the SLOTS weight slots (2 lock-step, 3 ping-pong); the traced
+// workgroup copies them out at the end
+template <int SLOTS, class CTX>
+__device__ __forceinline__ void trace_begin(CTX& c)
+{
+#if PNR_TRACE
+    c.tr = reinterpret_cast<unsigned long long*>(c.smem + SLOTS * c.a.slot_bytes) + c.wave * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS;
+    c.titer = 0;
+#endif
+}
+template <int SLOTS, int WAVES>
+__device__ __forceinline__ void trace_dump(const MlpArgs& a, const char* smem)
+{
+#if PNR_TRACE
+    __syncthreads();
+    if (blockIdx.x == PNR_TRACE_WG && a.trace) {
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + SLOTS * a.slot_bytes);
+        for (int i = threadIdx.x; i < WAVES * PNR_TRACE_CHUNKS * PNR_TRACE_STAMPS; i += blockDim.x) a.trace[i] = src[i];
+    }
+#endif
+}
+
+// A ping-pong kernel begins `CTX c = pp_ctx<WAVES>(a, smem); pp_begin(c, clk_c0, clk_r0);` and ends `pp_end(c, clk_c0, clk_r0);`.
+// pp_ctx returns the braced context itself: a named local returned by value changes the code of every k_mlp_pp.
+template <int WAVES>
+__device__ __forceinline__ CtxPP<WAVES> pp_ctx(const MlpArgs& a, char* smem)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return CtxPP<WAVES>{a, smem, (int)(threadIdx.x & 63), wave, (int)((threadIdx.x & 63) >> 5), wave >= WAVES / 2 ? 1 : 0, 0, 0, 0u, 0u, {0, 0}};
+}
+// slots 0..2 filled, Q one barrier behind P, the clock probe running
+template <int WAVES>
+__device__ __forceinline__ void pp_begin(CtxPP<WAVES>& c, unsigned long long& clk_c0, unsigned long long& clk_r0)
+{
+#if PNR_PP_ABL & 16
+    c.abl_sink = u32x4{0, 0, 0, 0};
+#endif
+    trace_begin<3>(c);
+    c.start();
+    clk_probe_begin(c.a, clk_c0, clk_r0);
+}
+// the last barrier, the refills issued past the last chunk, the probe, the trace
+template <int WAVES>
+__device__ __forceinline__ void pp_end(CtxPP<WAVES>& c, unsigned long long clk_c0, unsigned long long clk_r0)
+{
+    c.end();
+    clk_probe_end(c.a, clk_c0, clk_r0);
+    trace_dump<3, WAVES>(c.a, c.smem);
+}
+
+// The next sample group's input loads, requested behind the last refill piece of an L phase.  Vector-memory operations of a wave
+// complete in order, so the next m_done() may wait for "all but the youngest LOADS" -- the refill pieces -- instead of an HBM
+// round trip.  LOADS is the number of vector-memory instructions hipcc emits for request(); the markers let tools/asm_lint.py and
+// tests/test_asm_lint.py verify it, and that no LDS-DMA piece sits between them, on the compiled assembly.
+template <int LOADS, int WAVES, class REQ>
+__device__ __forceinline__ void pp_fetch_youngest(CtxPP<WAVES>& c, REQ&& request)
+{
+    __builtin_amdgcn_sched_barrier(0);     // the loads must stay the YOUNGEST operations: nothing may move across
+    asm volatile("; PNR_FETCH_BEGIN" ::: "memory");
+    request();
+    asm volatile("; PNR_FETCH_END %0" :: "n"(LOADS) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    c.pending_stores = LOADS;
+}
+
 // One chunk = FBC 32-row output blocks x KS k-steps; fragments in CONSUMPTION order i = ks*FBC + b.
 template <int FBC, int NA, int NB>
 struct PPChunk {
@@ -335,11 +444,7 @@ struct PPChunk {
         bias_finish(q, acc);
     }
 
-    // M: the chunk's MFMAs, one wave alone on its SIMD's matrix pipe.
-    // PNR_PP_HEAD > 0 (soft hand-over): the first HEAD MFMAs are issued BEFORE the L -> M barrier, at low priority.  The chunk's
-    // weights landed two phases ago and were covered by a barrier then (the L phase already reads its bias and first
-    // fragments), so only the pipe hand-over hangs on this barrier: the partner group's last MFMAs keep priority, and these
-    // fill its gaps and the ~100 cycles the barrier itself takes.
+    // M: the chunk's MFMAs, one wave alone on its SIMD's matrix pipe, behind the L -> M barrier.
     // SWAP: the fragment is the MFMA's B operand and the activations its A operand.  A weight fragment (lane = output row, 8
     // consecutive k) IS the B-operand image of the transposed weights (lane = output column, 8 consecutive k), and the
     // activation registers (lane = sample, 8 consecutive k) ARE an A operand with rows = samples: the product comes out
@@ -349,23 +454,14 @@ struct PPChunk {
     __device__ __forceinline__ static void mma(uint32_t fa, u32x4 (&A)[P], const uint32_t (&inA)[NA],
                                                const uint32_t (&inB)[NB > 0 ? NB : 1], f32x16 (&acc)[FBC], BARRIER&& barrier)
     {
-        constexpr int HEAD = PNR_PP_HEAD < NF / 2 ? PNR_PP_HEAD : NF / 2;
-        if constexpr (HEAD == 0) {
-            barrier();
+        barrier();
 #if PNR_PP_PRIO
-            __builtin_amdgcn_s_setprio(PNR_PP_PRIO);
+        __builtin_amdgcn_s_setprio(PNR_PP_PRIO);
 #endif
-        }
         pp_static_for<NF>([&](auto I) {
             constexpr int i = I;
             constexpr int ks = i / FBC, b = i % FBC;
             constexpr int younger = (NF - 1 - i) < (P - 2) ? (NF - 1 - i) : (P - 2);
-            if constexpr (HEAD > 0 && i == HEAD) {
-                barrier();
-#if PNR_PP_PRIO
-                __builtin_amdgcn_s_setprio(PNR_PP_PRIO);
-#endif
-            }
 #if PNR_TRACE_MID
             if constexpr (i == NF / 4) barrier(0);          // trace builds: the callers' functor stamps when given a number
             if constexpr (i == NF / 2) barrier(7);

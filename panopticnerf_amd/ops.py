@@ -243,6 +243,22 @@ def make_desc(D=8, W=256, skip=4, xyz_L=10, dir_L=4, n_sem=0, n_inst=0, head_W=N
     return d
 
 
+def _desc_with(desc, **fields):
+    """A copy of desc with the given fields replaced."""
+    d = MlpDesc()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc), ctypes.sizeof(d))
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+def _size_or_raise(n, what):
+    """A size the library computed (bytes / floats), or its error: a negative value means pnr_last_error has the reason."""
+    if n < 0:
+        raise RuntimeError(what + ": " + _lib.load().pnr_last_error().decode(errors="replace"))
+    return int(n)
+
+
 def fused_plan(desc, limit=None):
     """desc.plan to use for an image that only mlp_forward_composite will consume (pnr_mlp_fused_plan): 2 where the geometry has
     the two-tile assembly kernel, 1 where it has the fused-inference chunk order of the 8-wave kernel, else 0.  limit (or the
@@ -253,10 +269,7 @@ def fused_plan(desc, limit=None):
         return best
     # below the best plan: plan 1 where the library takes it (a semantic head of depth 2: the merged logit chunk), else the classic order
     if int(cap) >= 1:
-        d1 = _lib.MlpDesc()
-        ctypes.memmove(ctypes.byref(d1), ctypes.byref(desc), ctypes.sizeof(d1))
-        d1.plan = 1
-        if int(_lib.load().pnr_mlp_packed_bytes(ctypes.byref(d1))) > 0:
+        if int(_lib.load().pnr_mlp_packed_bytes(ctypes.byref(_desc_with(desc, plan=1)))) > 0:
             return 1
     return 0
 
@@ -392,9 +405,7 @@ def mlp_wgrad(desc, acts, dys, n_samples, shapes):
     acts, dys = _chk(acts, "acts", torch.bfloat16), _chk(dys, "dys", torch.bfloat16)
     lib = _lib.load()
     dev = acts.device
-    nbytes = lib.pnr_mlp_wgrad_workspace_bytes(ctypes.byref(desc), int(n_samples))
-    if nbytes < 0:
-        raise RuntimeError("pnr_mlp_wgrad_workspace_bytes: " + lib.pnr_last_error().decode(errors="replace"))
+    nbytes = _size_or_raise(lib.pnr_mlp_wgrad_workspace_bytes(ctypes.byref(desc), int(n_samples)), "pnr_mlp_wgrad_workspace_bytes")
     # per call, from torch's caching allocator: stream-ordered and graph-pool aware, so a captured step keeps its own
     # block alive and concurrent streams never share scratch (a process-global buffer did neither)
     ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
@@ -413,9 +424,7 @@ def mlp_forward_train_fp32(desc, params, rays, z):
     R, N = z.shape
     S = R * N
     lib = _lib.load()
-    n = lib.pnr_mlp_fp32_acts_floats(ctypes.byref(desc), S)
-    if n < 0:
-        raise RuntimeError("pnr_mlp_fp32_acts_floats: " + lib.pnr_last_error().decode(errors="replace"))
+    n = _size_or_raise(lib.pnr_mlp_fp32_acts_floats(ctypes.byref(desc), S), "pnr_mlp_fp32_acts_floats")
     raw = torch.empty((n_channels(desc), S), device=z.device, dtype=torch.float32)
     acts = torch.empty((int(n),), device=z.device, dtype=torch.float32)
     P, keep = _param_struct(desc, params, z.device)
@@ -434,9 +443,7 @@ def mlp_backward_fp32(desc, params, d_raw, acts, n_rays, n_samples):
         raise ValueError(f"d_raw: expected {(n_channels(desc), S)}, got {tuple(d_raw.shape)}")
     lib = _lib.load()
     dev = acts.device
-    nbytes = lib.pnr_mlp_backward_fp32_workspace_bytes(ctypes.byref(desc), S)
-    if nbytes < 0:
-        raise RuntimeError("pnr_mlp_backward_fp32_workspace_bytes: " + lib.pnr_last_error().decode(errors="replace"))
+    nbytes = _size_or_raise(lib.pnr_mlp_backward_fp32_workspace_bytes(ctypes.byref(desc), S), "pnr_mlp_backward_fp32_workspace_bytes")
     ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
     grads = {k: torch.empty_like(v, dtype=torch.float32, memory_format=torch.contiguous_format) for k, v in params.items()}
     P, keep = _param_struct(desc, params, dev)
@@ -573,10 +580,7 @@ def desc_for_mode(desc, sem_mode):
     want = _lib.MLP_SOFTMAX if int(sem_mode) == 1 else 0
     if (desc.flags & _lib.MLP_SOFTMAX) == want:
         return desc
-    d2 = _lib.MlpDesc()
-    ctypes.memmove(ctypes.byref(d2), ctypes.byref(desc), ctypes.sizeof(d2))
-    d2.flags = (desc.flags & ~_lib.MLP_SOFTMAX) | want
-    return d2
+    return _desc_with(desc, flags=(desc.flags & ~_lib.MLP_SOFTMAX) | want)
 
 
 def fused_image(sem_mode=0):
@@ -603,10 +607,7 @@ def mlp_forward_composite(desc, packed, rays, z, label_sem=None, label_inst=None
     lib = _lib.load()
     desc = desc_for_mode(desc, sem_mode)
     if wg_cap:          # PNR_MLP_WG_CAP: the plan-2 launch on a share of the compute units (Renderer's overlapped levels)
-        d2 = _lib.MlpDesc()
-        ctypes.memmove(ctypes.byref(d2), ctypes.byref(desc), ctypes.sizeof(d2))
-        d2.flags = (desc.flags & 0xFFFF) | ((int(wg_cap) & 0x1FF) << 16)
-        desc = d2
+        desc = _desc_with(desc, flags=(desc.flags & 0xFFFF) | ((int(wg_cap) & 0x1FF) << 16))
     nbytes = lib.pnr_mlp_forward_composite_workspace_bytes(ctypes.byref(desc), R, N, int(bool(want_weights)))
     if nbytes < 0:
         raise RuntimeError("pnr_mlp_forward_composite: unsupported geometry (n_samples=%d must be a multiple of 32)" % N)
@@ -629,10 +630,7 @@ def sigma_pass_supported(desc, n_samples, noise=None):
     if not (desc.precision == _lib.PREC_BF16 and noise is None and n_samples % 32 == 0 and 32 <= n_samples <= 256
             and desc.n_sem + desc.n_inst <= 128):
         return False
-    d3 = _lib.MlpDesc()
-    ctypes.memmove(ctypes.byref(d3), ctypes.byref(desc), ctypes.sizeof(d3))
-    d3.plan = 3
-    return int(_lib.load().pnr_mlp_packed_bytes(ctypes.byref(d3))) > 0
+    return int(_lib.load().pnr_mlp_packed_bytes(ctypes.byref(_desc_with(desc, plan=3)))) > 0
 
 
 @_on_device
