@@ -22,6 +22,7 @@
  *   pnr_ray_setup       a8 + a3 + a8 of the coarse level in one launch    (8a rows a3, a8)
  *   pnr_sample_pdf_labels   a7 + a8 of the fine level in one launch       (8a rows a7, a8)
  *   pnr_*_rng, pnr_rng_begin / _fill   the above with torch.rand / torch.randn drawn in the kernel (8a rows a3, a6, a7, a9)
+ *   pnr_sample_batch    the dataset's ray batches: pixel sampling, rays and targets of posed frames
  *
  * Conventions:
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
@@ -463,7 +464,8 @@ int pnr_sample_pdf_labels(const float* z, const float* weights, const float* u, 
  *   counter    sample j of global ray g = ray_base + r (r: the ray's row in the launch), stream tag t:
  *              (j >> 2 | t << 24, (uint32) g, lo32(offset), hi32(offset));  the draw is word j & 3 of the output block.
  *   tags       1 = stratified jitter (t_rand), 2 = sample_pdf uniforms (u), 3 + level = sigma noise of that level (the
- *              renderer's convention; any tag in 1..255 is accepted).
+ *              renderer's convention; any tag in 1..255 is accepted), 16 = pixel and 17 = frame draws of pnr_sample_batch
+ *              (integers, not uniforms: "training frames" below).
  *   uniform    (w >> 8) * 2^-24, in [0, 1) like torch.rand.
  *   normal     Box-Muller on the word pairs (2k, 2k + 1) of a block: u1 = ((w_2k >> 8) + 1) 2^-24, u2 = (w_2k+1 >> 8) 2^-24,
  *              r = sqrt(-2 log u1), n_2k = r cos(2 pi u2), n_2k+1 = r sin(2 pi u2);  noise = scale * n.  One Philox call gives
@@ -510,6 +512,64 @@ int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const flo
                                const float* g_inst, const float* g_weights, const int32_t* label_sem,
                                const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
                                const float* ce_sem, const float* ce_inst, float* d_raw, void* stream);
+
+/* ---- training frames: a device-resident set of posed images and the kernel that draws a ray batch from it (csrc/pnr_batch.hip;
+ * DESIGN.md "Training frames").  One launch picks n_rays (frame, pixel) pairs, builds their rays and gathers their targets.
+ * The frame table is read from DEVICE memory when the kernel RUNS, like the rng call: a captured graph's replays each draw a
+ * fresh batch, and a table edited after the capture is what later replays see.
+ *
+ * pnr_frame: one frame, 144 bytes (a multiple of 16; the array is 16-byte aligned), fields in this order:
+ *   offset   0  int32  model       PNR_CAMERA_PINHOLE | PNR_CAMERA_FISHEYE
+ *            4  int32  width, height
+ *           12  float  cam[7]      pinhole: fx, fy, cx, cy (the rest unused); fisheye: cam7 of pnr_gen_rays_fisheye
+ *           40  float  c2w[12]     3x4 row-major camera-to-world
+ *           88  float  near_, far_
+ *           96  int64  n_valid     number of drawable pixels (0: the frame is never drawn)
+ *          104  uint64 valid_pix   device address of n_valid int32 linear pixel indices j*width + i; 0 = every pixel (n_valid =
+ *                                  width*height)
+ *          112  uint64 rgb         device address of uint8 (height, width, 3); required
+ *          120  uint64 depth       device address of float (height, width); 0 = none
+ *          128  uint64 sem         device address of int16 (height, width) semantic labels; 0 = none
+ *          136  uint64 inst        device address of int16 (height, width) instance labels; 0 = none
+ * Beside the records: cum, int64[capacity + 1], cum[0] = 0 and cum[f + 1] = cum[f] + n_valid of frame f, and n_frames, one int32 = F.
+ *
+ * Draw rule (integer arithmetic only; the stream contract is the in-kernel RNG's, below).  Stream tags: PNR_TAG_PIXEL = 16 and
+ * PNR_TAG_FRAME = 17; rng_host->tag must be PNR_TAG_PIXEL.  For the launch's ray r, global ray
+ * g = ray_base + r:
+ *   (w0, w1, ., .) = the Philox block of (j = 0, tag 16, g);  W = w0 * 2^32 + w1;  mulhi64(a, b) = floor(a * b / 2^64)
+ *   mode 0 (pooled):  n = cum[F];  idx = mulhi64(W, n);  the frame is the f with cum[f] <= idx < cum[f + 1] (binary search; a frame
+ *                     with n_valid = 0 is never chosen);  k = idx - cum[f]
+ *   mode 1 (one frame per call):  (v0, v1, ., .) = the block of (j = 0, tag 17, g = 0) -- global ray 0 whatever ray_base is, so
+ *                     every rank of a step draws the same frame;  f = mulhi64(v0 * 2^32 + v1, F);  k = mulhi64(W, n_valid[f])
+ *   pixel p = valid_pix[k], or k where valid_pix is 0.
+ * Draws are WITH REPLACEMENT: two rays of a batch may be the same pixel (at 4096 rays from 10^7 pixels about one pair per batch).
+ * A ray's draw depends on (seed, offset, g) and the table only: the batches of ranks 0 .. w-1 (ray_base = rank * n_rays)
+ * concatenated are the w * n_rays batch of one rank, bit for bit.
+ *
+ * Outputs per ray (any may be NULL = not wanted):
+ *   rays (n_rays, 8), 16-byte aligned: bit for bit what pnr_gen_rays / pnr_gen_rays_fisheye write for that frame and pixel
+ *   rgb (n_rays, 3) = (float) byte / 255.0f (a division);  depth (n_rays) as stored, 0 where the frame has no depth image (what
+ *   pnr_losses reads as "no depth");  sem, inst (n_rays) int32, -1 where the frame has none;  frame_out, pix_out (n_rays) int32.
+ * What the host cannot see: F == 0, cum[F] == 0 or (mode 1) n_valid[f] == 0.  The kernel then writes rays = 0, rgb = depth = 0,
+ * labels = -1 and frame_out = pix_out = -1 for every ray; nothing is divided and no null address is read.
+ * Refused (PNR_EINVAL, before any launch): a null or misaligned table (frames 16, cum 8, n_frames 4 bytes), a mode outside 0 / 1,
+ * what every _rng entry point refuses, a tag clash -- any tag but PNR_TAG_PIXEL (1 .. 15 belong to the render streams, which may
+ * share the call; 17 is the frame stream) --, misaligned rays.  n_rays = 0 returns PNR_OK at once. */
+typedef struct pnr_frame {
+    int32_t model, width, height;
+    float cam[7];
+    float c2w[12];
+    float near_, far_;
+    int64_t n_valid;
+    uint64_t valid_pix, rgb, depth, sem, inst;
+} pnr_frame;
+#define PNR_TAG_PIXEL 16
+#define PNR_TAG_FRAME 17
+#define PNR_SAMPLE_POOLED 0
+#define PNR_SAMPLE_FRAME 1
+int pnr_sample_batch(const pnr_frame* frames, const int64_t* cum, const int32_t* n_frames, int mode, const pnr_rng* rng_host,
+                     int64_t n_rays, float* rays, float* rgb, float* depth, int32_t* sem, int32_t* inst, int32_t* frame_out,
+                     int32_t* pix_out, void* stream);
 
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable

@@ -8,7 +8,8 @@ does, and raises if it is missing (no CPU fallback)."""
 from .network import NeRF, Network, make_network  # noqa: F401
 from .renderer import Renderer, make_renderer  # noqa: F401
 from .camera import Fisheye, Pinhole  # noqa: F401
+from .data import FrameSet  # noqa: F401
 
 from .losses import NetworkWrapper  # noqa: F401,E402
 
-__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye"]
+__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "FrameSet"]

@@ -13,7 +13,9 @@ c_int = ctypes.c_int
 
 PREC_BF16, PREC_FP32 = 0, 1
 MLP_SOFTMAX, MLP_TRACE = 1, 0x7A00        # pnr_mlp_desc.flags (include/pnr.h PNR_MLP_*)
-CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1     # pnr_project_points' model word (include/pnr.h PNR_CAMERA_*)
+CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1     # pnr_project_points' / pnr_frame's model word (include/pnr.h PNR_CAMERA_*)
+TAG_PIXEL, TAG_FRAME = 16, 17             # pnr_sample_batch's stream tags (include/pnr.h PNR_TAG_*)
+SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr.h PNR_SAMPLE_*)
 
 
 class LossCfg(ctypes.Structure):
@@ -35,6 +37,14 @@ class MlpDesc(ctypes.Structure):
 class RngDesc(ctypes.Structure):
     """pnr_rng (include/pnr.h): one in-kernel stream of a launch."""
     _fields_ = [("call", ctypes.c_void_p), ("ray_base", ctypes.c_int64), ("tag", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
+class Frame(ctypes.Structure):
+    """pnr_frame (include/pnr.h "training frames"): one record of the device-resident frame table, 144 bytes."""
+    _fields_ = [("model", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("cam", ctypes.c_float * 7),
+                ("c2w", ctypes.c_float * 12), ("near_", ctypes.c_float), ("far_", ctypes.c_float), ("n_valid", ctypes.c_int64),
+                ("valid_pix", ctypes.c_uint64), ("rgb", ctypes.c_uint64), ("depth", ctypes.c_uint64), ("sem", ctypes.c_uint64),
+                ("inst", ctypes.c_uint64)]
 
 
 _fp = ctypes.POINTER(ctypes.c_float)
@@ -120,6 +130,7 @@ SIGNATURES = {
                                   c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_composite_backward_rng": (c_int, [c_f, c_i64, c_f, c_f, ctypes.POINTER(RngDesc), c_i64, c_int, c_int, c_int, c_int,
                                            c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_sample_batch": (c_int, [c_f, c_f, c_f, c_int, ctypes.POINTER(RngDesc), c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_mlp_query": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_f]),
     "pnr_mlp_query_supported": (c_int, [ctypes.POINTER(MlpDesc)]),
     "pnr_composite_combine": (c_int, [ctypes.POINTER(MlpDesc), c_f, c_f, c_i64, c_int, c_f, c_f, c_int,

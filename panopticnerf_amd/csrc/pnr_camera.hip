@@ -4,9 +4,8 @@
 // -ffp-contract=off and correctly rounded divide / sqrt): tests/_camera_ref.py restates both kernels in float32, bit for bit.
 #include <float.h>
 
+#include "pnr_camera_dev.h"
 #include "pnr_common.h"
-
-struct FisheyeCam { float xi, k1, k2, g1, g2, u0, v0; };
 
 // Un-projection: one thread per ray, two float4 stores (32 B/ray) + one byte into `valid`.
 struct GenRaysFisheyeArgs { FisheyeCam c; float c2w[12]; int width; float near_, far_; const int32_t* pix; int64_t R; float* rays; uint8_t* valid; };
@@ -16,37 +15,11 @@ __global__ __launch_bounds__(256) void k_gen_rays_fisheye(const GenRaysFisheyeAr
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = a.pix ? (int64_t)a.pix[r] : r;
         const int j = (int)(p / a.width), i = (int)(p - (int64_t)j * a.width);
-        float x = ((float)i - c.u0) / c.g1;
-        float y = ((float)j - c.v0) / c.g2;
-        const float rd = sqrtf(x * x + y * y);
-        // r (1 + k1 r^2 + k2 r^4) = rd: a fixed number of Newton steps from r = rd (a converged r is a fixed point of the step)
-        float rr = rd;
-#pragma unroll
-        for (int s = 0; s < PNR_FISHEYE_NEWTON_STEPS; ++s) {
-            const float r2 = rr * rr;
-            const float r4 = r2 * r2;
-            const float ka = c.k1 * r2, kb = c.k2 * r4;
-            const float f = rr * ((1.0f + ka) + kb) - rd;
-            const float fp = (1.0f + 3.0f * ka) + 5.0f * kb;
-            rr = rr - f / fp;
-        }
-        const float sc = rd > 0.0f ? rr / rd : 1.0f;
-        x = x * sc;
-        y = y * sc;
-        const float r2 = x * x + y * y;
-        const float disc = 1.0f + (1.0f - c.xi * c.xi) * r2;
-        const bool ok = disc >= 0.0f && r2 <= FLT_MAX;           // (both false for NaN)
-        const float lam = (c.xi + sqrtf(disc)) / (r2 + 1.0f);
-        const float dx = lam * x, dy = lam * y, dz = lam - c.xi;
-        float d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float u = a.c2w[k * 4 + 0] * dx, v = a.c2w[k * 4 + 1] * dy, w = a.c2w[k * 4 + 2] * dz;
-            d[k] = ok ? (u + v) + w : 0.0f;
-        }
+        bool ok;
+        const PnrRayRec ray = pnr_fisheye_ray(c, a.c2w, i, j, a.near_, a.far_, ok);
         float4* o = reinterpret_cast<float4*>(a.rays + r * 8);
-        o[0] = make_float4(a.c2w[3], a.c2w[7], a.c2w[11], d[0]);
-        o[1] = make_float4(d[1], d[2], ok ? a.near_ : 0.0f, ok ? a.far_ : 0.0f);
+        o[0] = ray.lo;
+        o[1] = ray.hi;
         if (a.valid) a.valid[r] = ok ? 1 : 0;
     }
 }

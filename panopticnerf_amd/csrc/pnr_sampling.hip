@@ -6,6 +6,7 @@
 // file is compiled with -ffp-contract=off and the pragma below so no mul+add pair is fused.
 // Reference functions these replace (the reference source
 // is not in the mount, include/pnr.h explains the citation form).
+#include "pnr_camera_dev.h"
 #include "pnr_common.h"
 #include "pnr_philox.h"
 #include <stdlib.h>
@@ -57,17 +58,10 @@ __global__ __launch_bounds__(256) void k_gen_rays(const GenRaysArgs a)
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = a.pix ? (int64_t)a.pix[r] : r;
         const int j = (int)(p / a.width), i = (int)(p - (int64_t)j * a.width);
-        const float x = ((float)i - a.cx) / a.fx;
-        const float y = ((float)j - a.cy) / a.fy;
-        float d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float u = a.c2w[k * 4 + 0] * x, v = a.c2w[k * 4 + 1] * y;
-            d[k] = (u + v) + a.c2w[k * 4 + 2];
-        }
+        const PnrRayRec ray = pnr_pinhole_ray(a.fx, a.fy, a.cx, a.cy, a.c2w, i, j, a.near_, a.far_);
         float4* o = reinterpret_cast<float4*>(a.rays + r * 8);
-        o[0] = make_float4(a.c2w[3], a.c2w[7], a.c2w[11], d[0]);
-        o[1] = make_float4(d[1], d[2], a.near_, a.far_);
+        o[0] = ray.lo;
+        o[1] = ray.hi;
     }
 }
 

@@ -171,6 +171,37 @@ def rng_fill(call, tag, ray_base, n_rays, n, normal=False, std=1.0):
     return out
 
 
+BATCH_OUTPUTS = (("rays", (8,), torch.float32), ("rgb", (3,), torch.float32), ("depth", (), torch.float32), ("sem", (), torch.int32),
+                 ("inst", (), torch.int32), ("frame", (), torch.int32), ("pix", (), torch.int32))
+
+
+@_on_device
+def sample_batch(frames, cum, n_frames, draw, n_rays, mode="pooled", want=None, out=None):
+    """One ray batch from a device-resident frame table (pnr_sample_batch; include/pnr.h "training frames").  frames: uint8 GPU
+    tensor of pnr_frame records (_lib.Frame), cum: (capacity + 1) int64 prefix sums of n_valid, n_frames: (1) int32 -- all read
+    when the kernel runs.  draw: the Draw of the PIXEL stream (tag _lib.TAG_PIXEL; the frame stream is _lib.TAG_FRAME).  mode:
+    "pooled" (every drawable pixel of the set alike) or "frame" (one frame per call).  Returns {rays (R,8), rgb (R,3), depth (R),
+    sem, inst, frame, pix (R) int32}, or the subset `want` names (the others are not computed: NULL outputs); `out`: a dict of
+    caller-owned tensors to write into (a captured graph's static batch)."""
+    frames, cum, n_frames = _chk(frames, "frames", torch.uint8), _chk(cum, "cum", torch.int64), _chk(n_frames, "n_frames", torch.int32)
+    if not _draw(draw):
+        raise TypeError("sample_batch: draw must be an ops.Draw")
+    if mode not in ("pooled", "frame"):
+        raise ValueError("sample_batch: mode must be 'pooled' or 'frame', not %r" % (mode,))
+    R, dev = int(n_rays), frames.device
+    names = [n for n, _, _ in BATCH_OUTPUTS]
+    want = names if want is None else list(want)
+    for n in want:
+        if n not in names:
+            raise ValueError("sample_batch: unknown output %r (one of %s)" % (n, ", ".join(names)))
+    res = {n: _own(None if out is None else out.get(n), (R,) + tail, dt, dev, "sample_batch: " + n)
+           for n, tail, dt in BATCH_OUTPUTS if n in want}
+    _lib.check(_lib.load().pnr_sample_batch(_p(frames), _p(cum), _p(n_frames), _lib.SAMPLE_POOLED if mode == "pooled" else _lib.SAMPLE_FRAME,
+                                            ctypes.byref(draw.desc()), R, *[_p(res.get(n)) for n in names], _stream()),
+               "pnr_sample_batch")
+    return res
+
+
 def _own(out, shape, dtype, dev, what):
     """`out` (a caller-owned tensor: checked) or a fresh tensor."""
     if out is None:

@@ -256,14 +256,34 @@ class GraphedStep:
     GradReducer's finish: its hooks launch nothing while a stream is being captured, so every bucket leaves from finish()) that
     runs EAGERLY between two graphs -- forward + backward | collective | optimiser -- since a collective inside a captured
     region ties the graph to one communicator state.  After training through replays call
-    `net.eval()` (or `net.invalidate_packed()`) before rendering: tensor versions do not see what a replay did to the weights."""
+    `net.eval()` (or `net.invalidate_packed()`) before rendering: tensor versions do not see what a replay did to the weights.
 
-    def __init__(self, wrapper, optimizer, example_batch, reduce=None, warmup=2):
+    A step that feeds itself: `GraphedStep(wrapper, optimizer, frames=frame_set, n_rays=4096, mode="pooled")` (data.FrameSet)
+    puts `frames.sample(n_rays, mode, rank, world, out=static batch)` at the head of the captured region (with `reduce`: of the
+    first graph), so `step()` takes no batch and copies nothing: every replay draws its own batch from the frame table as it
+    stands in device memory (frames added since the capture included).  The set's `rng_state` is restored after the warm-up
+    like the renderer's: the first replay's batch is the first `frames.sample(...)` from the state at construction.  `step.static`
+    holds the batch of the last replay (frame, pix included).  The box prior is part of the static batch: `frames.set_boxes` with the
+    same number of boxes updates it in place and later replays use the new boxes; another number of boxes needs a new GraphedStep."""
+
+    def __init__(self, wrapper, optimizer, example_batch=None, reduce=None, warmup=2, frames=None, n_rays=None, mode="pooled",
+                 rank=0, world=1):
         for grp in optimizer.param_groups:
             if "capturable" in grp and not grp["capturable"]:
                 raise ValueError("GraphedStep: build the optimizer with capturable=True (its step counters must live on the GPU)")
         self.wrapper, self.optimizer, self.reduce = wrapper, optimizer, reduce
-        self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
+        self.frames, keep_frames = frames, None
+        if frames is not None:
+            if example_batch is not None or n_rays is None:
+                raise ValueError("GraphedStep: with frames= give n_rays= and no example batch (the step draws its own)")
+            self._draw = (int(n_rays), mode, rank, world)
+            frames._alloc()
+            keep_frames = frames.rng_state.detach().clone()
+            self.static = frames.sample(*self._draw)          # allocates the static batch; its draw is undone with the warm-up's
+        elif example_batch is None:
+            raise ValueError("GraphedStep: give an example batch, or frames= and n_rays=")
+        else:
+            self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         if not any(torch.is_tensor(v) and v.is_cuda for v in self.static.values()):
             raise RuntimeError("GraphedStep: the batch must be on the GPU")
         params = [p for grp in optimizer.param_groups for p in grp["params"]]
@@ -295,6 +315,8 @@ class GraphedStep:
                             v.zero_()
             if keep_rng is not None:
                 rend.rng_state.copy_(keep_rng)
+            if keep_frames is not None:
+                frames.rng_state.copy_(keep_frames)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         self.graph_opt = None
@@ -313,12 +335,16 @@ class GraphedStep:
 
     def _fwd_bwd(self):
         self.optimizer.zero_grad(set_to_none=False)      # the gradient buffers are part of the graph: zeroed, never freed
+        if self.frames is not None:
+            self.frames.sample(*self._draw, out=self.static)
         ret, loss, stats, _ = self.wrapper(self.static)
         loss.backward()
         return ret, loss, stats
 
-    def __call__(self, batch):
-        for k, v in self.static.items():
+    def __call__(self, batch=None):
+        if (batch is None) != (self.frames is not None):
+            raise ValueError("GraphedStep: a step built with frames= takes no batch; every other step takes one")
+        for k, v in (self.static.items() if batch is not None else ()):
             if torch.is_tensor(v):
                 src = batch[k]
                 if src.shape != v.shape or src.dtype != v.dtype:
