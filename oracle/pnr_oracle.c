@@ -19,7 +19,8 @@
  * evaluate the reference's expressions -- restated from measurements against torch, bit for bit
  * (tests/test_oracle.py::test_c_oracle_is_torch_as_written):
  *   torch.linspace(0, 1, N)   step = 1/(N-1);  t_i = step*i for i < N/2, else 1 - step*(N-1-i) with ONE rounding (fma)
- *   torch.sum(x, -1)          8-lane vector partial sums, 4 of them interleaved (pnro_torch_sum below)
+ *   torch.sum(x, -1)          n >= 8: 8-lane vector partial sums, 4 of them interleaved, then a sequential scalar tail;
+ *                             n < 8 (Nc <= 9): four scalar accumulators, elements 4.. into the first (pnro_torch_sum below)
  *   torch.cumsum(x, -1)       running sum in DOUBLE, every output rounded to fp32
  * everything else is elementwise: one rounding per operation, no FMA contraction (build with
  * -ffp-contract=off).  The HIP kernels reproduce this file instruction for instruction; the
@@ -60,7 +61,7 @@ PNRO_API void pnro_gen_rays(const float* intr, const float* c2w, int width, int 
 }
 
 /* torch.linspace(0, 1, steps = N)[i], fp32, as ATen's CPU kernel computes it (RangeFactories: two-sided, the upper half from
- * the end point; the product is not rounded separately there).  Measured bit-exact against torch for N = 7 .. 192. */
+ * the end point; the product is not rounded separately there).  Measured bit-exact against torch for every N = 1 .. 512 (tests/test_oracle.py). */
 static inline float pnro_linspace01(int i, int N)
 {
     if (N <= 1) return 0.0f;
@@ -72,10 +73,23 @@ static inline float pnro_linspace01(int i, int N)
 /* torch.sum over a contiguous fp32 row of n >= 8 elements, as ATen's CPU reduction orders it: the row is cut into vectors of
  * 8 lanes; vectors 0..3 (mod 4) accumulate into four partial vectors, leftover vectors into partial 0; partials 1..3 are
  * added to partial 0; the scalar tail is summed sequentially from 0; finally the 8 lanes of partial 0 are added to that in
- * lane order.  Measured bit-exact against torch.sum for n = 30 .. 200 (tests); rows shorter than one vector: sequential. */
+ * lane order.
+ * A row SHORTER than one vector (n < 8) never reaches the vector code: ATen sums it as a scalar row with four interleaved
+ * accumulators -- a[k] = 0 + x[k] for k < 4 when n >= 4, the remaining n - 4 (or, for n < 4, all n) elements added in order
+ * into a[0], result ((a[0] + a[1]) + a[2]) + a[3].  For n <= 4 that is the sequential sum; for n = 5, 6, 7 it is not (x[4..]
+ * join a[0] before x[1] does).  Measured bit-exact against torch.sum for every n = 1 .. 254 (tests/test_oracle.py). */
 static float pnro_torch_sum(const float* x, int n)
 {
     enum { V = 8, ILP = 4 };
+    if (n < V) {
+        float a[ILP] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int i = 0;
+        if (n >= ILP)
+            for (; i < ILP; ++i) a[i] = a[i] + x[i];
+        for (; i < n; ++i) a[0] = a[0] + x[i];
+        for (int k = 1; k < ILP; ++k) a[0] = a[0] + a[k];
+        return a[0];
+    }
     const int nv = n / V;
     float part[ILP][V];
     for (int k = 0; k < ILP; ++k) for (int l = 0; l < V; ++l) part[k][l] = 0.0f;

@@ -177,6 +177,7 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
     __shared__ float s_total, s_part[32];
     const int lane = threadIdx.x;
     const int nb = Nc - 1, nw = Nc - 2, Nt = Nc + Nf;
+    const bool short4 = nw >= 4 && nw < 8;       // a row ATen sums with four scalar accumulators (see the sum below)
     int P = 1;
     while (P < Nt) P <<= 1;
     auto labels = [&](int64_t r, const float* sorted) {       // sorted: the ray's Nt merged depths in LDS (written before a barrier)
@@ -205,21 +206,26 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
         }
         __syncthreads();
         for (int k = lane; k < nb; k += 64) s_bins[k] = 0.5f * (s_z[k + 1] + s_z[k]);
-        // total = torch.sum(w) in ATen's order (pnro_torch_sum): 8-lane vectors, four partial vectors interleaved -> lane
-        // 8 k + l owns accumulator (k, l) and adds its elements in ascending order, exactly as the vector code does
+        // total = torch.sum(w) in ATen's order (pnro_torch_sum).  nw >= 8: 8-lane vectors, four partial vectors interleaved -> lane
+        // 8 k + l owns accumulator (k, l) and adds its elements in ascending order, exactly as the vector code does; then the scalar
+        // tail from 0 and the 8 lanes of partial 0.  nw < 8 (no whole vector) is ATen's scalar row sum with four accumulators: a[k] = x[k],
+        // k < 4 (when nw >= 4), x[4..] added in order into a[0], result ((a[0] + a[1]) + a[2]) + a[3].  Same code: the "tail" is then
+        // a[0] (x[0], x[4], x[5], ...), lanes 0..2 hold a[1..3] as partials (0, l) (+ 0 is exact), and the lane-order adds finish it.
         if (lane < 32) {
             const int k = lane >> 3, l = lane & 7, nv = nw / 8, groups = nv / 4;
             float pacc = 0.0f;
             for (int g = 0; g < groups; ++g) pacc = pacc + (s_w[(g * 4 + k) * 8 + l + 1] + 1e-5f);
             if (k == 0)
                 for (int v = groups * 4; v < nv; ++v) pacc = pacc + (s_w[v * 8 + l + 1] + 1e-5f);
+            if (short4 && lane < 3) pacc = pacc + (s_w[lane + 2] + 1e-5f);       // a[1..3] of the scalar row sum
             s_part[lane] = pacc;
         }
         __syncthreads();
         if (lane == 0) {
             const int nv = nw / 8;
             float total = 0.0f;
-            for (int j = nv * 8; j < nw; ++j) total = total + (s_w[j + 1] + 1e-5f);          // the scalar tail, from 0
+            // the scalar tail, from 0 (a short row's a[0]: x[0], then x[4] onwards)
+            for (int j = nv * 8; j < nw; j = (short4 && j == 0) ? 4 : j + 1) total = total + (s_w[j + 1] + 1e-5f);
             for (int l = 0; l < 8; ++l) {
                 float p0 = s_part[l];
                 p0 = p0 + s_part[8 + l]; p0 = p0 + s_part[16 + l]; p0 = p0 + s_part[24 + l];
@@ -386,6 +392,7 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
     __shared__ float s_total, s_part[32];
     const int lane = threadIdx.x;
     const int nb = Nc - 1, nw = Nc - 2, Nt = Nc + Nf;
+    const bool short4 = nw >= 4 && nw < 8;       // a row ATen sums with four scalar accumulators (see the sum below)
     int topc = 1, topf = 1;                      // the largest powers of two <= Nc, <= Nf: first strides of the bisections
     while (topc * 2 <= Nc) topc *= 2;
     while (topf * 2 <= Nf) topf *= 2;
@@ -413,20 +420,22 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
         const float zn = __shfl_down(zl, 1, 64), wn = __shfl_down(wl, 1, 64);
         s_bins[lane] = 0.5f * (zn + zl);             // bins[k] = 0.5 (z[k + 1] + z[k]), k < nb
         __syncthreads();
-        // total = torch.sum(w[1:-1] + 1e-5) in ATen's order: sample_pdf_body's code
+        // total = torch.sum(w[1:-1] + 1e-5) in ATen's order: sample_pdf_body's code (the vector order for nw >= 8, ATen's scalar row sum
+        // with four accumulators for shorter rows: lanes 0..2 hold a[1..3], the "tail" is a[0])
         if (lane < 32) {
             const int k = lane >> 3, l = lane & 7, nv = nw / 8, groups = nv / 4;
             float pacc = 0.0f;
             for (int g = 0; g < groups; ++g) pacc = pacc + (s_w[(g * 4 + k) * 8 + l + 1] + 1e-5f);
             if (k == 0)
                 for (int v = groups * 4; v < nv; ++v) pacc = pacc + (s_w[v * 8 + l + 1] + 1e-5f);
+            if (short4 && lane < 3) pacc = pacc + (s_w[lane + 2] + 1e-5f);       // a[1..3] of the scalar row sum
             s_part[lane] = pacc;
         }
         __syncthreads();
         if (lane == 0) {
             const int nv = nw / 8;
             float total = 0.0f;
-            for (int j = nv * 8; j < nw; ++j) total = total + (s_w[j + 1] + 1e-5f);
+            for (int j = nv * 8; j < nw; j = (short4 && j == 0) ? 4 : j + 1) total = total + (s_w[j + 1] + 1e-5f);
             for (int l = 0; l < 8; ++l) {
                 float p0 = s_part[l];
                 p0 = p0 + s_part[8 + l]; p0 = p0 + s_part[16 + l]; p0 = p0 + s_part[24 + l];
