@@ -18,6 +18,7 @@
  *   pnr_composite_backward   autograd backward of raw2outputs            (8a row a9)
  *   pnr_sample_pdf      sample_pdf + sorted merge with the coarse z       (8a row a7)
  *   pnr_bbox_hits       ray / 3D-bbox intersection (bbox prior)           (8a row a8)
+ *   pnr_convex_hits     ray / convex-polytope intersection (bounding primitives as half-spaces)   (8a row a8)
  *   pnr_sample_labels   per-sample fixed semantic / instance labels        (8a row a8)
  *   pnr_ray_setup       a8 + a3 + a8 of the coarse level in one launch    (8a rows a3, a8)
  *   pnr_sample_pdf_labels   a7 + a8 of the fine level in one launch       (8a rows a7, a8)
@@ -426,6 +427,39 @@ int pnr_sample_pdf(const float* z, const float* weights, const float* u, int64_t
  * pnr_sample_labels uses min(hit_count, max_hits) entries.  Bit-exact with pnro_bbox_hits. */
 int pnr_bbox_hits(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits,
                   float* hit_t, int32_t* hit_box, int32_t* hit_count, void* stream);
+
+/* ---- a8b: convex bounding primitives.  The scene's primitives as convex polytopes in half-space form -- cuboids, the prisms
+ * of an ear-clipped extruded polygon, any closed convex mesh (panopticnerf_amd/primitives.py builds the table):
+ *   planes  (P,4) float32, one (n0, n1, n2, dd) per plane, 16-byte aligned; the inside of a plane is n.x <= dd;
+ *   offsets (M+1) int32, CSR: primitive m owns planes offsets[m] .. offsets[m+1]-1.  Non-decreasing, offsets[M] <= P (the
+ *           caller's contract: the kernel reads what offsets names and checks nothing).
+ * Ids stay the (M,2) int32 table of pnr_sample_labels; the pieces of one decomposed object repeat its ids.
+ *
+ * The rule per ray (o, d, near, far) and primitive, THE CONTRACT (float32, no contraction of mul + add, one correctly rounded
+ * division; fminf / fmaxf return the other operand when one is NaN):
+ *
+ *     tmin = near; tmax = far
+ *     for each plane of the primitive, in table order:
+ *         dn = (n0*d0 + n1*d1) + n2*d2
+ *         on = (n0*o0 + n1*o1) + n2*o2
+ *         s  = dd - on
+ *         if dn > 0:  tmax = fminf(tmax, s / dn)        leaving
+ *         if dn < 0:  tmin = fmaxf(tmin, s / dn)        entering
+ *         if dn == 0 and s < 0:  tmax = -inf            parallel and outside (-0.0 counts as 0)
+ *     hit  <=>  tmin <= tmax                            (pnr_bbox_hits' comparator: a grazing ray, tmin == tmax, hits)
+ *
+ * So a primitive without planes is the whole ray [near, far]; a ray with d = 0 (an invalid fisheye pixel) hits exactly the
+ * primitives whose every plane has s >= 0 (those that contain its origin), with [near, far]; and the result does not depend on
+ * the early exit the kernel takes once a whole wave has missed a primitive.
+ *
+ * The kept list is pnr_bbox_hits': the max_hits NEAREST intervals in ascending (t_in, primitive index) order in hit_t
+ * (R,max_hits,2) / hit_box (R,max_hits) (pads 0.0f / -1), hit_count (R) the TRUE number of primitives hit.  Abutting intervals
+ * of one object's pieces are NOT merged.  max_hits >= 1 (lists of up to 8 entries are built in LDS, longer ones in the output
+ * rows).  n_rays == 0 and n_prim == 0 are valid (n_prim == 0: every list empty, every count 0; planes / offsets may be NULL).
+ * Never synchronises, never allocates: capture-safe.  The arithmetic differs from pnr_bbox_hits' slab test (which multiplies
+ * by a reciprocal in the box frame): the two agree on a cuboid to rounding, not bit for bit. */
+int pnr_convex_hits(const float* rays, int64_t n_rays, const float* planes, const int32_t* offsets, int n_prim, int max_hits,
+                    float* hit_t, int32_t* hit_box, int32_t* hit_count, void* stream);
 
 /* Sampling restricted to the bbox prior (cfg.bbox_sampling = "hull"; SURVEY.md 9 item 2 -- whether the reference samples
  * [near, far] or the hit intervals cannot be checked here, so it is a switch): rays_out = rays with near / far replaced by the

@@ -29,6 +29,12 @@ int pnrb_time_mlp_forward(const pnr_mlp_desc* desc, const void* packed, const fl
 int pnrb_time_mlp_forward_tiles(const pnr_mlp_desc* desc, const void* packed, const float* rays, const float* z, int64_t n_rays,
                                 int n_samples, void* workspace, int iters, void* scratch, float* ms_out_host,
                                 float* mhz_out_host, void* stream);
+/* Mean milliseconds per launch of pnr_bbox_hits (convex == 0: table0 = box (n,15), table1 ignored) or pnr_convex_hits (convex != 0:
+ * table0 = planes (P,4), table1 = offsets (n+1)); entry: the address of that entry point in the caller's libpnr.so.  scratch: >= 16
+ * zeroed device bytes. */
+int pnrb_time_hits(void* entry, int convex, const float* rays, int64_t n_rays, const float* table0, const int32_t* table1, int n,
+                   int max_hits, float* hit_t, int32_t* hit_box, int32_t* hit_count, int iters, void* scratch, float* ms_out_host,
+                   void* stream);
 /* What the matrix pipe of this device SUSTAINS: a register-only bf16 MFMA loop on every SIMD with constant operands
  * (random_operands = 0) or with pseudo-random operands that change from MFMA to MFMA (1: the toggle rate of real data -- on
  * MI355X the clock then drops from ~2.37 to ~1.83 GHz and the rate from ~2.46 to ~1.83 PFLOP/s).  scratch: >= 32 device bytes. */

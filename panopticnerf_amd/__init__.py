@@ -9,7 +9,9 @@ from .network import NeRF, Network, make_network  # noqa: F401
 from .renderer import Renderer, make_renderer  # noqa: F401
 from .camera import Fisheye, Pinhole  # noqa: F401
 from .data import FrameSet  # noqa: F401
+from .primitives import ConvexSet, extrude_polygon  # noqa: F401
 
 from .losses import NetworkWrapper  # noqa: F401,E402
 
-__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "FrameSet"]
+__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "FrameSet", "ConvexSet",
+           "extrude_polygon"]

@@ -113,6 +113,7 @@ SIGNATURES = {
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_bbox_hits": (c_int, [c_f, c_i64, c_f, c_int, c_int, c_f, c_f, c_f, c_f]),
+    "pnr_convex_hits": (c_int, [c_f, c_i64, c_f, c_f, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_restrict_rays": (c_int, [c_f, c_i64, c_f, c_f, c_int, c_f, c_f]),
     "pnr_sample_labels": (c_int, [c_f, c_i64, c_int, c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_f]),
     "pnr_ray_setup": (c_int, [c_f, c_i64, c_f, c_int, c_int, c_f, c_int, c_int, c_f, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),

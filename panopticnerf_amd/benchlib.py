@@ -17,6 +17,7 @@ SIGNATURES = {
     "pnrb_bind": (c_int, [c_f, c_f]),
     "pnrb_time_mlp_forward": (c_int, [ctypes.POINTER(_lib.MlpDesc), c_f, c_f, c_f, c_i64, c_int, c_f, c_i64, c_i64, c_int, c_f, _fp, _fp, c_f]),
     "pnrb_time_mlp_forward_tiles": (c_int, [ctypes.POINTER(_lib.MlpDesc), c_f, c_f, c_f, c_i64, c_int, c_f, c_int, c_f, _fp, _fp, c_f]),
+    "pnrb_time_hits": (c_int, [c_f, c_int, c_f, c_i64, c_f, c_f, c_int, c_int, c_f, c_f, c_f, c_int, c_f, _fp, c_f]),
     "pnrb_probe_mfma_peak": (c_int, [c_int, c_int, c_f, _fp, _fp, c_f]),
     "pnrb_probe_mfma_order": (c_int, [c_int, c_int, c_f, _fp, _fp, c_f]),
     "pnrb_probe_raw_read": (c_int, [c_f, c_i64, c_i64, c_int, c_int, c_int, c_f, _fp, c_f]),
@@ -85,6 +86,26 @@ def time_mlp_forward_tiles(desc, packed, rays, z, iters=5):
         _check(load().pnrb_time_mlp_forward_tiles(ctypes.byref(desc), _p(packed), _p(rays), _p(z), R, N, _p(ws), int(iters), _p(scratch),
                                                   ctypes.byref(ms), ctypes.byref(mhz), _stream()), "pnrb_time_mlp_forward_tiles")
     return float(ms.value), float(mhz.value)
+
+
+def time_hits(rays, table, max_hits=8, iters=20):
+    """Mean ms per launch of the prior's hit-list kernel on `rays`: table = box (M,15) times pnr_bbox_hits, table = (planes (P,4),
+    offsets (M+1)) times pnr_convex_hits.  hipEvents on the launch stream."""
+    convex = isinstance(table, (tuple, list))
+    t0, t1 = (table[0], table[1]) if convex else (table, None)
+    n = (t1.numel() - 1) if convex else t0.shape[0]
+    R = rays.shape[0]
+    ms = ctypes.c_float(0.0)
+    with torch.cuda.device(rays.device):
+        scratch = torch.zeros(4, device=rays.device, dtype=torch.int64)
+        hit_t = torch.empty((R, max_hits, 2), device=rays.device)
+        hit_box = torch.empty((R, max_hits), device=rays.device, dtype=torch.int32)
+        hit_count = torch.empty((R,), device=rays.device, dtype=torch.int32)
+        prod = _lib.load()
+        entry = ctypes.cast(prod.pnr_convex_hits if convex else prod.pnr_bbox_hits, ctypes.c_void_p)
+        _check(load().pnrb_time_hits(entry, int(convex), _p(rays), R, _p(t0), _p(t1), int(n), int(max_hits), _p(hit_t), _p(hit_box),
+                                     _p(hit_count), int(iters), _p(scratch), ctypes.byref(ms), _stream()), "pnrb_time_hits")
+    return float(ms.value)
 
 
 def probe_mfma_order(pattern, iters=12000, device=None):

@@ -4,6 +4,7 @@
 // libpnr.so (or an A/B build of it) itself -- the timed code is exactly the library the caller uses.
 //   pnrb_time_mlp_forward        iters x pnr_mlp_forward between two events on `stream`, + mean shader clock of the last launch
 //   pnrb_time_mlp_forward_tiles  the same for pnr_mlp_forward_tiles (the fused inference MLP launch, without the combine kernel)
+//   pnrb_time_hits               the same for pnr_bbox_hits / pnr_convex_hits (no clock probe)
 //   pnrb_probe_mfma_peak         what the matrix pipe of THIS device sustains, and at which clock (see below)
 //   pnrb_probe_raw_read          what HBM delivers for k_composite's own access pattern with no arithmetic
 #include <hip/hip_runtime.h>
@@ -117,6 +118,24 @@ PNRB_EXPORT int pnrb_time_mlp_forward_tiles(const pnr_mlp_desc* desc, const void
     const pnr_mlp_desc d = with_probe(desc, scratch);
     return time_launches([&]() { return g_tiles(&d, packed, rays, z, n_rays, n_samples, workspace, stream); },
                          iters, scratch, ms_out_host, mhz_out_host, (hipStream_t)stream);
+}
+
+// The two producers of the prior's hit lists on the same rays: pnr_bbox_hits (convex == 0: table0 = box (n,15), table1 unused) or
+// pnr_convex_hits (convex != 0: table0 = planes, table1 = offsets (n + 1)), `entry` its address in the caller's libpnr.so.  No clock
+// probe in these kernels: scratch (>= 16 zeroed device bytes) is only what time_launches reads back.
+typedef int (*fn_bbox_hits)(const float*, int64_t, const float*, int, int, float*, int32_t*, int32_t*, void*);
+typedef int (*fn_convex_hits)(const float*, int64_t, const float*, const int32_t*, int, int, float*, int32_t*, int32_t*, void*);
+PNRB_EXPORT int pnrb_time_hits(void* entry, int convex, const float* rays, int64_t n_rays, const float* table0, const int32_t* table1, int n,
+                               int max_hits, float* hit_t, int32_t* hit_box, int32_t* hit_count, int iters, void* scratch,
+                               float* ms_out_host, void* stream)
+{
+    PNR_REQUIRE(entry && scratch, "pnrb_time_hits: null entry point / scratch");
+    float mhz = 0.0f;
+    if (convex)
+        return time_launches([&]() { return ((fn_convex_hits)entry)(rays, n_rays, table0, table1, n, max_hits, hit_t, hit_box, hit_count, stream); },
+                             iters, scratch, ms_out_host, &mhz, (hipStream_t)stream);
+    return time_launches([&]() { return ((fn_bbox_hits)entry)(rays, n_rays, table0, n, max_hits, hit_t, hit_box, hit_count, stream); },
+                         iters, scratch, ms_out_host, &mhz, (hipStream_t)stream);
 }
 
 // What the matrix pipe of THIS device sustains, and at which clock:

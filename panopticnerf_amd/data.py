@@ -48,6 +48,7 @@ class FrameSet:
         self.frames = []            # host side of every record: camera, pose, bounds and the device images (kept alive here)
         self._total = 0
         self.bbox = self.bbox_ids = None
+        self.prims = None           # set_primitives: {"prim_planes", "prim_offsets", "prim_ids"} on the device
 
     def _alloc(self):
         if self.table is not None:
@@ -144,6 +145,9 @@ class FrameSet:
         call with the same number of boxes writes into the tensors of the first, so batches handed out before -- the static batch
         of a captured step -- see the new values; another number of boxes makes new tensors, which only later sample() calls return
         (a captured graph fixes shapes: a train.GraphedStep keeps the boxes it was built with)."""
+        if self.prims is not None:
+            raise ValueError("FrameSet.set_boxes: the set has primitives (set_primitives) -- one prior per set: ConvexSet.from_boxes "
+                             "turns boxes into primitives")
         bbox, bbox_ids = torch.as_tensor(bbox), torch.as_tensor(bbox_ids)
         if bbox.dim() != 2 or bbox.shape[1] != 15:
             raise ValueError("FrameSet.set_boxes: bbox must be (M, 15), not %s" % (tuple(bbox.shape),))
@@ -158,13 +162,32 @@ class FrameSet:
         else:
             self.bbox, self.bbox_ids = bbox, bbox_ids
 
+    def set_primitives(self, convex_set):
+        """The scene's prior as convex primitives (primitives.ConvexSet), returned in every batch as prim_planes (P,4),
+        prim_offsets (M+1), prim_ids (M,2) -- what Renderer.render takes instead of bbox / bbox_ids.  Like set_boxes: a second
+        call with the same numbers of planes and primitives writes into the tensors of the first (a captured step's static
+        batch sees the new table), other shapes make new tensors.  Not together with set_boxes (ConvexSet.from_boxes)."""
+        if self.bbox is not None:
+            raise ValueError("FrameSet.set_primitives: the set has boxes (set_boxes) -- one prior per set: ConvexSet.from_boxes "
+                             "turns them into primitives")
+        if not all(hasattr(convex_set, k) for k in ("planes", "offsets", "ids")):
+            raise TypeError("FrameSet.set_primitives: expected a primitives.ConvexSet")
+        new = {"prim_planes": torch.from_numpy(convex_set.planes.copy()), "prim_offsets": torch.from_numpy(convex_set.offsets.copy()),
+               "prim_ids": torch.from_numpy(convex_set.ids.copy())}
+        new = {k: v.to(self.device).contiguous() for k, v in new.items()}
+        if self.prims is not None and all(self.prims[k].shape == v.shape for k, v in new.items()):
+            for k, v in new.items():
+                self.prims[k].copy_(v)              # in place: batches handed out before see the new table
+        else:
+            self.prims = new
+
     # ------------------------------------------------------------------------------------------------ batches
     _KEYS = (("rays", "rays"), ("rgb", "rgb"), ("depth", "depth"), ("pseudo_label", "sem"), ("instance_label", "inst"),
              ("frame", "frame"), ("pix", "pix"))
 
     def sample(self, n_rays, mode="pooled", rank=0, world=1, out=None):
         """A training batch of n_rays rays: {rays (1,R,8), rgb (1,R,3), depth (1,R), pseudo_label, instance_label (1,R) int32,
-        frame, pix (R) int32} plus bbox / bbox_ids when set_boxes was called -- what NetworkWrapper takes.  mode "pooled": every
+        frame, pix (R) int32} plus bbox / bbox_ids when set_boxes was called (prim_planes / prim_offsets / prim_ids after set_primitives) -- what NetworkWrapper takes.  mode "pooled": every
         drawable pixel of the set is equally likely; "frame": one frame per call (the same on every rank), then pixels of it.
         Rank `rank` of `world` draws global rays rank * n_rays ...: the ranks' batches concatenated are, bit for bit, the
         world * n_rays batch of one rank (every rank holds the same set and state).  out: a batch this method returned before,
@@ -191,6 +214,8 @@ class FrameSet:
         batch = {k: (res[n] if k in ("frame", "pix") else res[n][None]) for k, n in self._KEYS}
         if self.bbox is not None:
             batch.update(bbox=self.bbox, bbox_ids=self.bbox_ids)
+        if self.prims is not None:
+            batch.update(self.prims)
         return batch
 
     def frame_batch(self, i):
@@ -212,4 +237,6 @@ class FrameSet:
         batch["pix"] = pix if pix is not None else torch.arange(P, dtype=torch.int32, device=dev)
         if self.bbox is not None:
             batch.update(bbox=self.bbox, bbox_ids=self.bbox_ids)
+        if self.prims is not None:
+            batch.update(self.prims)
         return batch

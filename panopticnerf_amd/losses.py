@@ -6,7 +6,7 @@ are documented in DESIGN.md 9).
     w_rgb * MSE(rgb, batch['rgb'])  +  w_depth * L1|L2(depth, batch['depth'] where > 0)
   + w_sem * CE(semantic logits, batch['pseudo_label'])  +  w_fix_sem * NLL(fixed semantic map, batch['pseudo_label'])
   + the same two terms for the instance field (batch['instance_label'])
-  + w_sem3d / w_inst3d * per-sample CE of the learned logits against the bbox labels (when batch has 'bbox')
+  + w_sem3d / w_inst3d * per-sample CE of the learned logits against the prior's labels (when batch has 'bbox' or 'prim_planes')
 with ONE fused kernel per level for the per-ray terms and their gradients (pnr_losses); the 3D term's value comes from
 pnr_ce3d and its gradient is fused into the compositing backward.  Returns (ret, loss, scalar_stats, image_stats) as
 the reference trainer expects from a wrapper.  No torch math on the path; the loss scalars stay on the GPU.

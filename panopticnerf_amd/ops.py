@@ -881,6 +881,35 @@ def bbox_hits(rays, box, max_hits=8):
     return hit_t, hit_box, hit_count
 
 
+@_on_device
+def convex_hits(rays, planes, offsets, max_hits=8, out=None):
+    """rays (R,8), planes (P,4) = (n, dd) with inside n.x <= dd, offsets (M+1) int32 CSR -> hit_t (R,mh,2), hit_box (R,mh) int32,
+    hit_count (R) int32: bbox_hits' lists for convex polytopes (pnr_convex_hits, row a8b; primitives.ConvexSet makes the table).
+    offsets must be non-decreasing with offsets[M] <= P (ConvexSet guarantees it; it lives on the device and is not read here).
+    out: (hit_t, hit_box, hit_count) caller-owned."""
+    rays, planes, offsets = _chk(rays, "rays"), _chk(planes, "planes"), _chk(offsets, "offsets", torch.int32)
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("convex_hits: rays must be (R, 8), not %s" % (tuple(rays.shape),))
+    if planes.dim() != 2 or planes.shape[1] != 4:
+        raise ValueError("convex_hits: planes must be (P, 4), not %s" % (tuple(planes.shape),))
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("convex_hits: offsets must be (M + 1,), not %s" % (tuple(offsets.shape),))
+    R, M = rays.shape[0], offsets.numel() - 1
+    max_hits = int(max_hits)
+    if max_hits < 1:
+        raise ValueError("convex_hits: max_hits must be >= 1, not %d" % max_hits)
+    dev = rays.device
+    if planes.shape[0] == 0 and M > 0:          # primitives without planes (each the whole ray): an empty tensor has no address
+        planes = planes.new_zeros((1, 4))
+    o = out if out is not None else (None, None, None)
+    hit_t = _own(o[0], (R, max_hits, 2), torch.float32, dev, "convex_hits")
+    hit_box = _own(o[1], (R, max_hits), torch.int32, dev, "convex_hits")
+    hit_count = _own(o[2], (R,), torch.int32, dev, "convex_hits")
+    _lib.check(_lib.load().pnr_convex_hits(_p(rays), R, _p(planes), _p(offsets), M, max_hits, _p(hit_t), _p(hit_box), _p(hit_count),
+                                           _stream()), "pnr_convex_hits")
+    return hit_t, hit_box, hit_count
+
+
 RAY_SETUP_MAX_HITS = 8      # pnr_ray_setup keeps the hit lists of 256 rays in LDS
 
 

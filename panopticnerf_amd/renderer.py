@@ -10,6 +10,8 @@ the compositing kernel streams.  No torch math is on the path.
 
 batch keys:  "rays" (B,N_rays,8) = o,d,near,far  (required)
              "bbox" (M,15), "bbox_ids" (M,2) int32  (optional: 3D bbox prior)
+             "prim_planes" (P,4), "prim_offsets" (M+1) int32, "prim_ids" (M,2) int32  (optional, instead of bbox: the prior as
+             convex primitives, primitives.ConvexSet.batch(); hit lists from pnr_convex_hits, everything behind them unchanged)
              "t_rand" (B,N_rays,N_samples), "u" (B,N_rays,N_importance)  (optional explicit uniforms;
              otherwise drawn when cfg.perturb > 0: with torch.rand, or inside the kernels with cfg.rng = "device")
 output keys, level l in {0 (coarse), 1 (fine)}:
@@ -17,11 +19,16 @@ output keys, level l in {0 (coarse), 1 (fine)}:
              semantic_l / fix_semantic_l (B,N_rays,C), instance_l / fix_instance_l (B,N_rays,K)
              cfg.coarse_outputs = "weights" (inference with a fine level): no rgb_0, semantic_0, instance_0
 """
+import collections
 import os
 
 import torch
 
 from . import ops
+
+
+# the 3D prior as convex primitives (batch keys prim_planes / prim_offsets): travels through render() where the box table does
+Prims = collections.namedtuple("Prims", "planes offsets")
 
 
 def _get(cfg, name, default):
@@ -127,12 +134,15 @@ class Renderer:
         """a chunk's per-ray preamble: (hits or None, z of the coarse level, its labels or None)"""
         hits = lab0 = None
         hull = self.bbox_sampling == "hull"
-        if box is not None and self.max_hits <= ops.RAY_SETUP_MAX_HITS:
+        prims = isinstance(box, Prims)
+        if box is not None and not prims and self.max_hits <= ops.RAY_SETUP_MAX_HITS:
             # rows a8 + a3 in one launch: hit lists, z and the coarse labels (pnr_ray_setup; bit for bit the separate kernels)
             hits, z, ls0, li0 = ops.ray_setup(rays, box, box_ids, self.N_samples, self.max_hits, self.lindisp, t_rand, hull, out=z_out)
             lab0 = (ls0, li0)
         else:
-            if box is not None:
+            if prims:       # convex primitives: their own producer of the hit lists, then the separate kernels (no fused twin)
+                hits = ops.convex_hits(rays, box.planes, box.offsets, self.max_hits)
+            elif box is not None:
                 hits = ops.bbox_hits(rays, box, self.max_hits)
             rays_s = ops.restrict_rays(rays, hits[0], hits[2]) if (hits is not None and hull) else rays
             z = ops.stratified(rays_s, self.N_samples, self.lindisp, t_rand, out=z_out)
@@ -333,7 +343,17 @@ class Renderer:
         R = rays.shape[0]
         box = batch.get("bbox")
         box_ids = batch.get("bbox_ids")
-        if box is not None:
+        if batch.get("prim_planes") is not None:
+            if box is not None:
+                raise ValueError("Renderer.render: the batch has both 'bbox' and 'prim_planes' -- one prior per render: turn the "
+                                 "cuboids into primitives with ConvexSet.from_boxes and join the sets with ConvexSet.concat")
+            if batch.get("prim_offsets") is None or batch.get("prim_ids") is None:
+                raise ValueError("Renderer.render: 'prim_planes' comes with 'prim_offsets' and 'prim_ids' (ConvexSet.batch())")
+            box = Prims(batch["prim_planes"].reshape(-1, 4).float().contiguous(), batch["prim_offsets"].reshape(-1).int().contiguous())
+            box_ids = batch["prim_ids"].reshape(-1, 2).int().contiguous()
+            if box_ids.shape[0] != box.offsets.numel() - 1:
+                raise ValueError("Renderer.render: prim_ids has %d rows for %d primitives" % (box_ids.shape[0], box.offsets.numel() - 1))
+        elif box is not None:
             box = box.reshape(-1, 15).float().contiguous()
             box_ids = box_ids.reshape(-1, 2).int().contiguous()
         t_rand, u = batch.get("t_rand"), batch.get("u")
@@ -398,13 +418,14 @@ class Renderer:
         return ret
 
     # --- a whole frame of a camera (panopticnerf_amd/camera.py): rays for the pixels that see anything, maps as images
-    def render_view(self, camera, c2w, near, far, bbox=None, bbox_ids=None):
+    def render_view(self, camera, c2w, near, far, bbox=None, bbox_ids=None, prims=None):
         """Render one frame of `camera` (camera.Pinhole / camera.Fisheye) at pose c2w (3x4, host values): rays are made for
         camera.valid_pix() only -- a fisheye frame skips the pixels outside the lens (and the user mask) --, rendered by
         render() (chunking, overlap and fused-plan decisions are render()'s), and every per-ray output is placed into a
         (height, width, ...) image that is 0 where a pixel sees nothing; "valid" (height, width) bool says where that is.
         Labels derived from such maps (ops.panoptic_labels, shard.label_maps) must be set to -1, the evaluator's "ignore",
-        where valid is False: the argmax of an all-zero pixel is class 0, not "nothing".  depth_* of a Fisheye frame is range
+        where valid is False: the argmax of an all-zero pixel is class 0, not "nothing".  prims: a primitives.ConvexSet as the
+        prior instead of bbox / bbox_ids (moved to the network's device on first use).  depth_* of a Fisheye frame is range
         along the unit-length ray, of a Pinhole frame z-depth (camera.py).  Inference only."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters()):
             raise RuntimeError("Renderer.render_view is inference only: call it under torch.no_grad() (training batches are made "
@@ -418,6 +439,10 @@ class Renderer:
         batch = {"rays": camera.rays(c2w, near, far, pix=None if whole else pix, device=dev)}
         if bbox is not None:
             batch.update(bbox=bbox, bbox_ids=bbox_ids)
+        if prims is not None:
+            if prims.device != dev:
+                prims.to(dev)
+            batch.update(prims.batch())
         out = self.render(batch)
         valid = torch.ones((H, W), dtype=torch.bool, device=dev)
         if whole:

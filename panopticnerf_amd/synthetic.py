@@ -80,6 +80,27 @@ def random_boxes(n_box=64, n_sem=45, n_inst=32, seed=1):
     return box, ids
 
 
+# outlines of primitive_scene's two extruded pieces, in the object's local x-y plane (metres)
+L_OUTLINE = ((-12.0, 4.0), (12.0, 4.0), (12.0, 40.0), (2.0, 40.0), (2.0, 18.0), (-12.0, 18.0))
+U_OUTLINE = ((-20.0, 50.0), (20.0, 50.0), (20.0, 70.0), (14.0, 70.0), (14.0, 56.0), (-14.0, 56.0), (-14.0, 70.0), (-20.0, 70.0))
+
+
+def primitive_scene(n_box=4, n_sem=45, n_inst=32, seed=1):
+    """A small seeded scene of bounding primitives as one primitives.ConvexSet: n_box cuboids (random_boxes), an L-shaped
+    ground slab below camera_rays' origin (4 prisms) and a U-shaped wall across the view (6 prisms).  The outlines lie in the
+    world x-z plane and are extruded along y (the camera's down axis); the seed shifts them by up to a metre.  The extruded
+    pieces' ids are (semantic, 0) with two seeded classes."""
+    from .primitives import ConvexSet, extrude_polygon
+    box, ids = random_boxes(n_box, n_sem, n_inst, seed)
+    g = torch.Generator().manual_seed(seed + 7919)
+    dx, dz = (2.0 * torch.rand(2, generator=g) - 1.0).tolist()
+    sem = torch.randint(0, max(n_sem, 1), (2,), generator=g).tolist()
+    to_world = [[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0]]         # local (x, y, z) -> world (x, z, y): orthogonal
+    ground = extrude_polygon(L_OUTLINE, 3.0, 3.5, to_world, (dx, 0.0, dz), (sem[0], 0))
+    wall = extrude_polygon(U_OUTLINE, -4.0, 3.0, to_world, (dx, 0.0, dz), (sem[1], 0))
+    return ConvexSet.concat(ConvexSet.from_boxes(box.numpy(), ids.numpy()), ground, wall)
+
+
 def trained_like_(net, sigma_bias=0.03, seed=0):
     """Shift the density bias so a useful fraction of samples has alpha > 0 (a freshly
     initialised NeRF composites to almost nothing)."""

@@ -264,7 +264,8 @@ class GraphedStep:
     stands in device memory (frames added since the capture included).  The set's `rng_state` is restored after the warm-up
     like the renderer's: the first replay's batch is the first `frames.sample(...)` from the state at construction.  `step.static`
     holds the batch of the last replay (frame, pix included).  The box prior is part of the static batch: `frames.set_boxes` with the
-    same number of boxes updates it in place and later replays use the new boxes; another number of boxes needs a new GraphedStep."""
+    same number of boxes updates it in place and later replays use the new boxes; another number of boxes needs a new GraphedStep
+    (`frames.set_primitives` likewise: same numbers of planes and primitives)."""
 
     def __init__(self, wrapper, optimizer, example_batch=None, reduce=None, warmup=2, frames=None, n_rays=None, mode="pooled",
                  rank=0, world=1):
