@@ -401,6 +401,44 @@ int pnr_gen_rays_fisheye(const float* cam7_host, const float* c2w12_host, int wi
 int pnr_project_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
                        int64_t n, float* uv, float* range, uint8_t* valid, void* stream);
 
+/* ---- cross-view reprojection (csrc/pnr_warp.hip; DESIGN.md 8 "Cross-view reprojection"): where a pixel of a source view,
+ * lifted with the source's depth image, lands in a target view, and whether the target sees it.  The reference's evaluator is
+ * not in the mount: every convention below (nearest pixel, the depth test and its default tolerance, the codes) is this
+ * build's and unpinned.  Float32 throughout, every operation a single + - * / sqrt in the order given (tests/_warp_ref.py
+ * restates the rule in float32, bit for bit).
+ *
+ * Source pixel p = pix[r] (int32, device), or p = r with pix NULL and n = width_src*height_src, as pnr_gen_rays.  The source
+ * maps (depth_src, label_src) are IMAGES indexed by p, the target maps (depth_tgt, label_tgt) images indexed by q; the
+ * outputs match (n) and uv (n, 2) are indexed by r.
+ *   1. ray (o, d) of p from the source camera and c2w_src: the ray of pnr_gen_rays / pnr_gen_rays_fisheye (near, far unused).
+ *   2. t = depth_src[p].  NOTHING TO REPROJECT (code -1) if the fisheye pixel sees nothing, or !(t > 0), or t is not finite
+ *      (or p is outside the source image).
+ *   3. X_k = o_k + t * d_k (one multiply, one add).  Right for both models: a pinhole d has z_cam = 1 and its depth is
+ *      z-depth, a fisheye d is unit length and its depth is range.
+ *   4. (u, v), |p_cam|, p_cam.z of X in the target camera with w2c_tgt: the arithmetic of pnr_project_points.  Outside the
+ *      projection's domain or outside the image the pixel LEAVES THE VIEW (code -2).
+ *   5. nearest target pixel: iu = min((int)floor(u + 0.5), width_tgt - 1), iv likewise, q = iv*width_tgt + iu (the min:
+ *      u + 0.5 may round up to width_tgt).
+ *   6. expected depth e in the TARGET's convention: p_cam.z for a pinhole target, |p_cam| for a fisheye target.  With
+ *      depth_tgt: dt = depth_tgt[q]; !(dt > 0) or dt not finite: UNKNOWN (code -3); else visible iff
+ *      |e - dt| <= tol_abs + tol_rel * e, otherwise OCCLUDED (code -4).  depth_tgt NULL: no test, the pixel is visible.
+ *   7. match[r] = q when visible, else the code.  uv[r] = (u, v) of step 4 (0, 0 outside the domain and for code -1).
+ *   8. with label_src and label_tgt (both or neither) and agree: a visible pixel whose ls = label_src[p] and lt = label_tgt[q]
+ *      are both in [0, n_classes) counts agree[ls*n_classes + lt] += 1 -- the cross-view confusion matrix; multi-view
+ *      consistency is its trace over its sum.  stats[0..4] += the number of pixels that were matched / -1 / -2 / -3 / -4.
+ *      agree (n_classes^2) and stats (5) are device int64 arrays the caller zeroes once and accumulates into over pairs
+ *      (integer atomics: exact, order-independent).  1 <= n_classes <= 8192; up to 128 through a per-block LDS histogram.
+ * cam_*_host: {fx, fy, cx, cy} or cam7 by model (PNR_CAMERA_*); c2w_src12_host, w2c_tgt12_host: 3x4 row-major, host values
+ * copied into the launch (baked into a stream capture).  Any of match, uv, agree, stats may be NULL.  Never synchronises.
+ * PNR_EINVAL before any launch: unknown model, null camera / pose / depth_src, zero focal length or gamma, bad size, labels
+ * given on one side only, agree without labels, negative or non-finite tolerance, n_classes out of range.  n == 0: PNR_OK. */
+int pnr_reproject(int model_src, const float* cam_src_host, const float* c2w_src12_host, int width_src, int height_src,
+                  const int32_t* pix, int64_t n, const float* depth_src,
+                  int model_tgt, const float* cam_tgt_host, const float* w2c_tgt12_host, int width_tgt, int height_tgt,
+                  const float* depth_tgt, float tol_abs, float tol_rel,
+                  const int32_t* label_src, const int32_t* label_tgt, int n_classes,
+                  int32_t* match, float* uv, int64_t* agree, int64_t* stats, void* stream);
+
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).
  * pnr_panoptic_labels: sem_label = argmax_c sem (lowest index on ties); inst_label = argmax_k inst where is_thing[sem_label]

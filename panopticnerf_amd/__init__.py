@@ -10,8 +10,9 @@ from .renderer import Renderer, make_renderer  # noqa: F401
 from .camera import Fisheye, Pinhole  # noqa: F401
 from .data import FrameSet  # noqa: F401
 from .primitives import ConvexSet, extrude_polygon  # noqa: F401
+from . import consistency  # noqa: F401
 
 from .losses import NetworkWrapper  # noqa: F401,E402
 
 __all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "FrameSet", "ConvexSet",
-           "extrude_polygon"]
+           "extrude_polygon", "consistency"]

@@ -1,6 +1,6 @@
 """Camera models behind one interface: Pinhole (the rectified perspective pair) and Fisheye (the side-facing cameras of a
 360 rig).  Both make rays on the GPU (`rays`), say which pixels see anything (`valid_pix`) and carry 3D points into the
-image (`project`); `Renderer.render_view` renders a frame of either.
+image (`project`); `Renderer.render_view` renders a frame of either, and `consistency.reproject` joins two such frames.
 
 The fisheye model is the unified omnidirectional (MEI) model with two radial terms as the public KITTI-360 calibration files
 parametrise it, written out in include/pnr.h ("cameras") and DESIGN.md ("Fisheye cameras"); like every convention of this
@@ -9,6 +9,7 @@ pinhole rays keep `ops.gen_rays`' convention (z_cam = 1, depth is z-depth).
 """
 import math
 
+import numpy as np
 import torch
 
 from . import ops
@@ -21,6 +22,23 @@ def _pose12(m, what):
     if t.numel() != 12:
         raise ValueError(f"{what}: expected a 3x4 (or 4x4) matrix")
     return t
+
+
+def invert_pose(c2w):
+    """w2c (3, 4) float32 of a rigid c2w = [R | t] (3x4 or 4x4): [R^T | -R^T t], computed in float64 on the host and rounded to
+    float32 once.  Every w2c of the cross-view code (consistency.py, Evaluator.evaluate_pair) is made this way, so a pose
+    pair means the same bits everywhere."""
+    if isinstance(c2w, torch.Tensor):
+        m = c2w.detach().cpu().to(torch.float64).reshape(-1)
+    else:
+        m = torch.as_tensor(np.asarray(c2w, dtype=np.float64)).reshape(-1)     # (torch would read python floats as float32)
+    if m.numel() == 16:
+        m = m[:12]
+    if m.numel() != 12:
+        raise ValueError("invert_pose: expected a 3x4 (or 4x4) matrix")
+    m = m.reshape(3, 4)
+    rt = m[:, :3].T
+    return torch.cat([rt, -(rt @ m[:, 3:])], 1).to(torch.float32)
 
 
 class _Camera:

@@ -30,38 +30,11 @@ __global__ __launch_bounds__(256) void k_project_points(const ProjectArgs a)
 {
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.P; n += (int64_t)gridDim.x * blockDim.x) {
         const float X = a.pts[n * 3 + 0], Y = a.pts[n * 3 + 1], Z = a.pts[n * 3 + 2];
-        float p[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float t0 = a.w2c[k * 4 + 0] * X, t1 = a.w2c[k * 4 + 1] * Y, t2 = a.w2c[k * 4 + 2] * Z;
-            p[k] = ((t0 + t1) + t2) + a.w2c[k * 4 + 3];
-        }
-        const float rng = sqrtf((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
-        float u, v;
-        bool dom;
-        if (a.model == PNR_CAMERA_PINHOLE) {
-            dom = p[2] > 0.0f;
-            const float x = p[0] / p[2], y = p[1] / p[2];
-            u = a.cam[0] * x + a.cam[2];
-            v = a.cam[1] * y + a.cam[3];
-        } else {
-            const float xi = a.cam[0], k1 = a.cam[1], k2 = a.cam[2];
-            const float xs = p[0] / rng, ys = p[1] / rng, zs = p[2] / rng;
-            const float den = zs + xi;
-            dom = den > 0.0f && xi * zs + 1.0f > 0.0f && rng <= FLT_MAX;       // (a range that overflowed has lost its direction)
-            const float x = xs / den, y = ys / den;
-            const float r2 = x * x + y * y;
-            const float s = (1.0f + k1 * r2) + k2 * (r2 * r2);
-            u = (a.cam[3] * x) * s + a.cam[5];
-            v = (a.cam[4] * y) * s + a.cam[6];
-        }
-        dom = dom && fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX;     // (false for NaN and Inf)
-        u = dom ? u : 0.0f;
-        v = dom ? v : 0.0f;
-        const bool inside = u >= -0.5f && u < a.umax && v >= -0.5f && v < a.vmax;
-        if (a.uv) a.uv[n] = make_float2(u, v);
-        if (a.range) a.range[n] = rng;
-        if (a.valid) a.valid[n] = (dom && inside) ? 1 : 0;
+        const PnrProj q = pnr_project_point(a.model, a.cam, a.w2c, X, Y, Z);
+        const bool inside = pnr_uv_inside(q.u, q.v, a.umax, a.vmax);
+        if (a.uv) a.uv[n] = make_float2(q.u, q.v);
+        if (a.range) a.range[n] = q.rng;
+        if (a.valid) a.valid[n] = (q.dom && inside) ? 1 : 0;
     }
 }
 

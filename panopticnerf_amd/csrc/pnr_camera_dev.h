@@ -1,6 +1,7 @@
 // Per-pixel ray arithmetic of the two camera models (include/pnr.h "ray generation" / "cameras"), shared by the kernels that make
-// rays: k_gen_rays (pnr_sampling.hip), k_gen_rays_fisheye (pnr_camera.hip) and k_sample_batch (pnr_batch.hip), which must write the
-// same bits for the same camera, pose and pixel.  Every operation is a single + - * / sqrt in one fixed order (the build has
+// rays: k_gen_rays (pnr_sampling.hip), k_gen_rays_fisheye (pnr_camera.hip), k_sample_batch (pnr_batch.hip) and k_reproject
+// (pnr_warp.hip), which must write the same bits for the same camera, pose and pixel; and the projection of a world point, shared by
+// k_project_points (pnr_camera.hip) and k_reproject.  Every operation is a single + - * / sqrt in one fixed order (the build has
 // -ffp-contract=off and correctly rounded divide / sqrt); c2w may live in kernel arguments or in device memory.
 #pragma once
 #include <float.h>
@@ -59,4 +60,44 @@ __device__ __forceinline__ PnrRayRec pnr_fisheye_ray(const FisheyeCam& c, const 
         d[k] = ok ? (u + v) + w : 0.0f;
     }
     return PnrRayRec{make_float4(c2w[3], c2w[7], c2w[11], d[0]), make_float4(d[1], d[2], ok ? near_ : 0.0f, ok ? far_ : 0.0f)};
+}
+
+// world point -> pixel coordinates of either model (include/pnr.h "cameras"): cam = pinhole {fx, fy, cx, cy} or fisheye cam7.
+// u, v are 0 outside the projection's domain (never NaN); rng = |p_cam|, z = p_cam.z.
+struct PnrProj { float u, v, rng, z; bool dom; };
+__device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam, const float* w2c, float X, float Y, float Z)
+{
+    float p[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float t0 = w2c[k * 4 + 0] * X, t1 = w2c[k * 4 + 1] * Y, t2 = w2c[k * 4 + 2] * Z;
+        p[k] = ((t0 + t1) + t2) + w2c[k * 4 + 3];
+    }
+    const float rng = sqrtf((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+    float u, v;
+    bool dom;
+    if (model == PNR_CAMERA_PINHOLE) {
+        dom = p[2] > 0.0f;
+        const float x = p[0] / p[2], y = p[1] / p[2];
+        u = cam[0] * x + cam[2];
+        v = cam[1] * y + cam[3];
+    } else {
+        const float xi = cam[0], k1 = cam[1], k2 = cam[2];
+        const float xs = p[0] / rng, ys = p[1] / rng, zs = p[2] / rng;
+        const float den = zs + xi;
+        dom = den > 0.0f && xi * zs + 1.0f > 0.0f && rng <= FLT_MAX;       // (a range that overflowed has lost its direction)
+        const float x = xs / den, y = ys / den;
+        const float r2 = x * x + y * y;
+        const float s = (1.0f + k1 * r2) + k2 * (r2 * r2);
+        u = (cam[3] * x) * s + cam[5];
+        v = (cam[4] * y) * s + cam[6];
+    }
+    dom = dom && fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX;     // (false for NaN and Inf)
+    return PnrProj{dom ? u : 0.0f, dom ? v : 0.0f, rng, p[2], dom};
+}
+
+// inside the image: pixel centres at integers, umax = width - 0.5, vmax = height - 0.5
+__device__ __forceinline__ bool pnr_uv_inside(float u, float v, float umax, float vmax)
+{
+    return u >= -0.5f && u < umax && v >= -0.5f && v < vmax;
 }

@@ -1,0 +1,172 @@
+// Cross-view reprojection (include/pnr.h "cross-view reprojection"): a source pixel is lifted with the source depth image,
+// projected into the target view, matched to the nearest target pixel and tested against the target depth image; with label
+// images on both sides the visible pairs are counted into the cross-view confusion matrix of the multi-view consistency metric.
+// A small gather-bound kernel in the style of pnr_camera.hip: one thread per source pixel, grid-stride, cameras and poses in
+// the kernel arguments.  The ray is pnr_pinhole_ray / pnr_fisheye_ray and the projection pnr_project_point (pnr_camera_dev.h),
+// the same functions the ray and projection kernels call, so the arithmetic is theirs bit for bit; tests/_warp_ref.py restates
+// the whole rule in float32.
+#include <float.h>
+
+#include "pnr_camera_dev.h"
+#include "pnr_common.h"
+
+#define PNR_WARP_LDS_CLASSES 128        // up to here `agree` is a per-block LDS histogram (k_confusion's limit: 64 KiB)
+
+struct ReprojectArgs {
+    int model_src, model_tgt;
+    float cam_src[7], cam_tgt[7];
+    float c2w[12], w2c[12];
+    int width_src, width_tgt, height_tgt;
+    int64_t npix_src;
+    float umax, vmax, tol_abs, tol_rel;
+    const int32_t* pix; int64_t R;
+    const float *depth_src, *depth_tgt;
+    const int32_t *label_src, *label_tgt;
+    int n_classes;
+    int32_t* match; float2* uv;
+    unsigned long long *agree, *stats;
+};
+
+// HIST: agree through the per-block LDS histogram h[n_classes^2] (one global atomic per non-zero cell, as k_confusion);
+// otherwise one global atomic per counted pixel (as k_confusion_big).  h holds at least 8 words in either case: after the
+// histogram is flushed its first five words collect the block's stats.
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
+{
+    extern __shared__ unsigned int h[];
+    const bool count = a.agree != nullptr;              // (the entry point refuses agree without labels)
+    const int cells = a.n_classes * a.n_classes;
+    if (HIST && count) {
+        for (int i = threadIdx.x; i < cells; i += blockDim.x) h[i] = 0;
+        __syncthreads();
+    }
+    unsigned int cnt[5] = {0, 0, 0, 0, 0};
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = a.pix ? (int64_t)a.pix[r] : r;
+        int code = -1;
+        float u = 0.0f, v = 0.0f;
+        if (p >= 0 && p < a.npix_src) {                 // an index outside the source image has nothing to reproject
+            const int j = (int)(p / a.width_src), i = (int)(p - (int64_t)j * a.width_src);
+            bool ok = true;
+            PnrRayRec ray;
+            if (a.model_src == PNR_CAMERA_PINHOLE)
+                ray = pnr_pinhole_ray(a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.c2w, i, j, 0.0f, 0.0f);
+            else
+                ray = pnr_fisheye_ray(FisheyeCam{a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.cam_src[4], a.cam_src[5], a.cam_src[6]},
+                                      a.c2w, i, j, 0.0f, 0.0f, ok);
+            const float t = a.depth_src[p];
+            if (ok && t > 0.0f && t <= FLT_MAX) {
+                const float X = ray.lo.x + t * ray.lo.w, Y = ray.lo.y + t * ray.hi.x, Z = ray.lo.z + t * ray.hi.y;
+                const PnrProj q = pnr_project_point(a.model_tgt, a.cam_tgt, a.w2c, X, Y, Z);
+                u = q.u;
+                v = q.v;
+                code = -2;
+                if (q.dom && pnr_uv_inside(u, v, a.umax, a.vmax)) {
+                    int iu = (int)floorf(u + 0.5f), iv = (int)floorf(v + 0.5f);
+                    const int wmax = a.width_tgt - 1, hmax = a.height_tgt - 1;          // (u + 0.5f may round up to width)
+                    iu = iu < wmax ? iu : wmax;
+                    iv = iv < hmax ? iv : hmax;
+                    const int tq = iv * a.width_tgt + iu;
+                    code = tq;
+                    if (a.depth_tgt) {
+                        const float e = a.model_tgt == PNR_CAMERA_PINHOLE ? q.z : q.rng;
+                        const float dt = a.depth_tgt[tq];
+                        if (!(dt > 0.0f && dt <= FLT_MAX)) code = -3;
+                        else if (!(fabsf(e - dt) <= a.tol_abs + a.tol_rel * e)) code = -4;
+                    }
+                    if (code >= 0 && count) {
+                        const int ls = a.label_src[p], lt = a.label_tgt[tq];
+                        if (ls >= 0 && ls < a.n_classes && lt >= 0 && lt < a.n_classes) {
+                            if (HIST) atomicAdd(&h[ls * a.n_classes + lt], 1u);
+                            else atomicAdd(&a.agree[(int64_t)ls * a.n_classes + lt], 1ull);
+                        }
+                    }
+                }
+            }
+        }
+        if (a.match) a.match[r] = code;
+        if (a.uv) a.uv[r] = make_float2(u, v);
+        const int slot = code >= 0 ? 0 : -code;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) cnt[k] += slot == k ? 1u : 0u;         // (constant indices: cnt stays in registers)
+    }
+    if (HIST && count) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < cells; i += blockDim.x)
+            if (h[i]) atomicAdd(&a.agree[i], (unsigned long long)h[i]);
+    }
+    if (!a.stats) return;                               // (uniform over the block)
+    __syncthreads();
+    if (threadIdx.x < 5) h[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        unsigned int c = cnt[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&h[k], c);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5 && h[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+static bool warp_camera_ok(int model, const float* cam)
+{
+    return model == PNR_CAMERA_PINHOLE ? (cam[0] != 0.0f && cam[1] != 0.0f) : (cam[3] != 0.0f && cam[4] != 0.0f);
+}
+
+PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const float* c2w_src12_host, int width_src, int height_src,
+                             const int32_t* pix, int64_t n, const float* depth_src,
+                             int model_tgt, const float* cam_tgt_host, const float* w2c_tgt12_host, int width_tgt, int height_tgt,
+                             const float* depth_tgt, float tol_abs, float tol_rel,
+                             const int32_t* label_src, const int32_t* label_tgt, int n_classes,
+                             int32_t* match, float* uv, int64_t* agree, int64_t* stats, void* stream)
+{
+    PNR_REQUIRE((model_src == PNR_CAMERA_PINHOLE || model_src == PNR_CAMERA_FISHEYE) && (model_tgt == PNR_CAMERA_PINHOLE || model_tgt == PNR_CAMERA_FISHEYE),
+                "pnr_reproject: unknown camera model %d -> %d", model_src, model_tgt);
+    PNR_REQUIRE(cam_src_host && c2w_src12_host && cam_tgt_host && w2c_tgt12_host, "pnr_reproject: null camera or pose");
+    PNR_REQUIRE(width_src >= 1 && height_src >= 1 && width_tgt >= 1 && height_tgt >= 1 && n >= 0 &&
+                (int64_t)width_src * height_src <= INT32_MAX && (int64_t)width_tgt * height_tgt <= INT32_MAX,
+                "pnr_reproject: bad size (each image holds at most 2^31 - 1 pixels)");
+    if (n == 0) return PNR_OK;                  // before the pointer checks: an empty pixel list has a null pointer
+    PNR_REQUIRE(pix || n == (int64_t)width_src * height_src, "pnr_reproject: without pixel indices n must be width_src*height_src");
+    PNR_REQUIRE(warp_camera_ok(model_src, cam_src_host) && warp_camera_ok(model_tgt, cam_tgt_host), "pnr_reproject: zero focal length or gamma");
+    PNR_REQUIRE(depth_src, "pnr_reproject: null source depth image");
+    PNR_REQUIRE(tol_abs >= 0.0f && tol_abs <= FLT_MAX && tol_rel >= 0.0f && tol_rel <= FLT_MAX,
+                "pnr_reproject: tolerances must be finite and >= 0");
+    const bool labels = label_src && label_tgt;
+    PNR_REQUIRE(labels || (!label_src && !label_tgt), "pnr_reproject: label_src and label_tgt come together");
+    PNR_REQUIRE(labels || !agree, "pnr_reproject: agree needs label images on both sides");
+    PNR_REQUIRE(!labels || (n_classes >= 1 && n_classes <= 8192), "pnr_reproject: n_classes must be in 1 .. 8192 (got %d)", n_classes);
+    PNR_REQUIRE((((uintptr_t)uv) & 7) == 0, "pnr_reproject: uv must be an 8-byte aligned device buffer");
+    ReprojectArgs a;
+    a.model_src = model_src; a.model_tgt = model_tgt;
+    const int ns = model_src == PNR_CAMERA_PINHOLE ? 4 : 7, nt = model_tgt == PNR_CAMERA_PINHOLE ? 4 : 7;
+    for (int k = 0; k < 7; ++k) {
+        a.cam_src[k] = k < ns ? cam_src_host[k] : 0.0f;
+        a.cam_tgt[k] = k < nt ? cam_tgt_host[k] : 0.0f;
+    }
+    for (int k = 0; k < 12; ++k) {
+        a.c2w[k] = c2w_src12_host[k];
+        a.w2c[k] = w2c_tgt12_host[k];
+    }
+    a.width_src = width_src; a.width_tgt = width_tgt; a.height_tgt = height_tgt; a.npix_src = (int64_t)width_src * height_src;
+    a.umax = (float)width_tgt - 0.5f; a.vmax = (float)height_tgt - 0.5f; a.tol_abs = tol_abs; a.tol_rel = tol_rel;
+    a.pix = pix; a.R = n; a.depth_src = depth_src; a.depth_tgt = depth_tgt;
+    a.label_src = labels ? label_src : nullptr; a.label_tgt = labels ? label_tgt : nullptr; a.n_classes = labels ? n_classes : 0;
+    a.match = match; a.uv = reinterpret_cast<float2*>(uv);
+    a.agree = (unsigned long long*)agree; a.stats = (unsigned long long*)stats;
+    int grid = pnr_grid_cap((n + 255) / 256);
+    if (agree && n_classes <= PNR_WARP_LDS_CLASSES) {
+        const size_t lds = (size_t)n_classes * n_classes * sizeof(unsigned int);
+        // a block zeroes and flushes n_classes^2 cells: give it at least as many trips over pixels (at most 16, as k_confusion)
+        const int64_t trips = n_classes * n_classes / 256 < 1 ? 1 : n_classes * n_classes / 256 > 16 ? 16 : n_classes * n_classes / 256;
+        const int64_t few = (n + 256 * trips - 1) / (256 * trips);
+        grid = few < grid ? (int)few : grid;
+        hipLaunchKernelGGL(k_reproject<true>, dim3(grid), dim3(256), lds < 32 ? 32 : lds, (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(k_reproject<false>, dim3(grid), dim3(256), 32, (hipStream_t)stream, a);
+    }
+    PNR_CHECK_LAUNCH("pnr_reproject");
+    return PNR_OK;
+}

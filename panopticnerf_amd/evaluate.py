@@ -10,7 +10,8 @@ import math
 
 import torch
 
-from . import ops
+from . import consistency, ops
+from .camera import invert_pose
 
 
 class Evaluator:
@@ -29,6 +30,9 @@ class Evaluator:
         self.n_inst = g("num_instances", 0)
         self.pq = None          # (C, 4) device tensor: sum of matched IoUs, TP, FP, FN per class
         self._bad_ids = None    # device counter: segments whose class index was >= n_classes (reported by summarize())
+        self.mc_agree = None    # (C, C) device int64: cross-view confusion [label in the source view, label in the target view]
+        self.mc_stats = None    # (5) device int64: source pixels matched / nothing to reproject / left the view / unknown / occluded
+        self.mc_tol = consistency.DEFAULT_TOL
 
     def evaluate(self, output, batch):
         lv = self.level if f"rgb_{self.level}" in output else 0
@@ -52,6 +56,57 @@ class Evaluator:
             pg = batch.get("panoptic_gt")
             if pg is not None:
                 self._accumulate_pq(res["panoptic_id"], pg.reshape(-1).to(dev, torch.int32).contiguous())
+        return res
+
+    def _pair_side(self, out, view, what):
+        """(camera, c2w, depth image, semantic map, valid) of one side of a pair: every check that needs no device"""
+        if not hasattr(out, "keys"):
+            raise ValueError("Evaluator.evaluate_pair: %s must be the dict Renderer.render_view returned" % what)
+        lv = self.level if f"semantic_{self.level}" in out else 0
+        if f"semantic_{lv}" not in out:
+            raise ValueError("Evaluator.evaluate_pair: %s holds no semantic map" % what)
+        if not isinstance(view, (tuple, list)) or len(view) not in (2, 3):
+            raise ValueError("Evaluator.evaluate_pair: %s must be (camera, c2w) or (camera, c2w, maps)" % what)
+        own = len(view) == 2            # the depth image comes from `out`, at the level the labels are made from
+        cam, c2w, depth = consistency.view_depth((view[0], view[1], out) if own else view, what, f"depth_{lv}" if own else None)
+        sem = out[f"semantic_{lv}"]
+        if tuple(sem.shape) != (cam.height, cam.width, self.n_classes):
+            raise ValueError("Evaluator.evaluate_pair: semantic map of %s is %s, expected (%d, %d, %d)"
+                             % (what, tuple(sem.shape), cam.height, cam.width, self.n_classes))
+        return cam, c2w, depth, sem, out.get("valid")
+
+    def _pair_labels(self, side, what):
+        """(camera, c2w, depth image, semantic label image with -1 where the frame sees nothing)"""
+        cam, c2w, depth, sem, valid = side
+        if not sem.is_cuda or not depth.is_cuda:
+            raise RuntimeError("Evaluator.evaluate_pair: %s is not on the GPU (the HIP path has no CPU fallback)" % what)
+        label = ops.panoptic_labels(sem.reshape(-1, self.n_classes).float().contiguous())[0]
+        if valid is not None:           # render_view: the argmax of a pixel that sees nothing is class 0, not "nothing"
+            label = torch.where(valid.reshape(-1).to(label.device), label, torch.full_like(label, -1))
+        return cam, c2w, depth, label.reshape(cam.height, cam.width)
+
+    def evaluate_pair(self, out_a, view_a, out_b, view_b, symmetric=True):
+        """Accumulate multi-view consistency over one pair of rendered frames.  out_*: what Renderer.render_view returned
+        (semantic and depth maps of the evaluated level, "valid"); view_*: (camera, c2w) of that frame, or (camera, c2w, maps)
+        to take the depth image from another dict.  Every pixel of A is carried into B (pnr_reproject, tolerance self.mc_tol);
+        where B sees the same surface point the two semantic labels are counted into the cross-view confusion matrix; with
+        symmetric=True the same is done from B into A.  Returns the label images and the match images; counters stay on
+        the device until summarize()."""
+        if not self.n_classes:
+            raise ValueError("Evaluator.evaluate_pair: the evaluator has no classes (n_classes = 0)")
+        a, b = self._pair_side(out_a, view_a, "view_a"), self._pair_side(out_b, view_b, "view_b")
+        a, b = self._pair_labels(a, "view_a"), self._pair_labels(b, "view_b")
+        if a[2].device != b[2].device:
+            raise ValueError("Evaluator.evaluate_pair: view_a is on %s, view_b on %s" % (a[2].device, b[2].device))
+        dev = a[2].device
+        if self.mc_agree is None:
+            self.mc_agree = torch.zeros((self.n_classes, self.n_classes), device=dev, dtype=torch.int64)
+            self.mc_stats = torch.zeros((5,), device=dev, dtype=torch.int64)
+        res = {"semantic_label_a": a[3], "semantic_label_b": b[3]}
+        for name, (s, t) in (("match_ab", (a, b)), ("match_ba", (b, a)))[: 2 if symmetric else 1]:
+            m = ops.reproject(s[0], s[1], s[2], t[0], invert_pose(t[1]), t[2], tol=self.mc_tol, label_src=s[3], label_tgt=t[3],
+                              n_classes=self.n_classes, agree=self.mc_agree, stats=self.mc_stats)["match"]
+            res[name] = m.reshape(s[0].height, s[0].width)
         return res
 
     def _accumulate_pq(self, pred_id, gt_id):
@@ -103,7 +158,7 @@ class Evaluator:
         try:
             return self._summarize()
         finally:
-            self.mse, self.conf, self.pq, self._bad_ids = [], None, None, None
+            self.mse, self.conf, self.pq, self._bad_ids, self.mc_agree, self.mc_stats = [], None, None, None, None, None
 
     def _summarize(self):
         out = {}
@@ -131,4 +186,10 @@ class Evaluator:
             out["pq"] = float(pq[seen].mean()) if seen.any() else math.nan
             out["sq"] = float((t[:, 0][seen] / t[:, 1][seen].clamp(min=1e-12))[t[:, 1][seen] > 0].mean()) if (t[:, 1] > 0).any() else math.nan
             out["rq"] = float((t[:, 1] / denom.clamp(min=1e-12))[seen].mean()) if seen.any() else math.nan
+        if self.mc_agree is not None:
+            c = self.mc_agree.double().cpu()
+            rows = c.sum(1)
+            out["mc"] = float(c.diag().sum() / c.sum()) if float(c.sum()) > 0 else math.nan
+            out["mc_per_class"] = torch.where(rows > 0, c.diag() / rows.clamp(min=1), torch.full_like(rows, float("nan"))).tolist()
+            out["mc_stats"] = [int(v) for v in self.mc_stats.cpu().tolist()]
         return out

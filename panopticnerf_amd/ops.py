@@ -120,6 +120,99 @@ def project_points(model, cam, w2c, width, height, points):
     return uv, rng, valid
 
 
+def _camera_words(cam, what):
+    """(model word, host floats, width, height) of a camera.Pinhole / camera.Fisheye"""
+    model = getattr(cam, "model", None)
+    if model == "pinhole":
+        return _lib.CAMERA_PINHOLE, _host_floats(cam.intr, 4, what), int(cam.width), int(cam.height)
+    if model == "fisheye":
+        return _lib.CAMERA_FISHEYE, _host_floats(cam.cam, 7, what), int(cam.width), int(cam.height)
+    raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye, not %r" % (what, cam))
+
+
+def _image(t, width, height, name):
+    """a (height, width) or (height * width) map of a camera, flattened; None stays None"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((height, width), (height * width,)):
+        raise ValueError("%s: expected a (%d, %d) image (or its %d flattened pixels), got %s"
+                         % (name, height, width, height * width, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t.reshape(-1) if t.is_contiguous() else t
+
+
+REPROJECT_OUTPUTS = ("match", "uv", "agree", "stats")
+
+
+@_on_device
+def reproject(src, c2w_src, depth_src, tgt, w2c_tgt, depth_tgt=None, pix=None, tol=(0.0, 0.02), label_src=None, label_tgt=None,
+              n_classes=0, agree=None, stats=None, want=("match",), out=None):
+    """Cross-view reprojection (pnr_reproject; the rule is in include/pnr.h "cross-view reprojection"): every pixel of the
+    source view -- or the int32 GPU pixel indices `pix` -- is lifted with depth_src (a (height, width) image of the source
+    camera), projected into the target view and matched to the nearest target pixel; with depth_tgt the match is tested
+    against the target's depth, |e - depth_tgt[q]| <= tol[0] + tol[1] * e.  src, tgt: camera.Pinhole / camera.Fisheye;
+    c2w_src, w2c_tgt: 3x4 host values (camera.invert_pose makes the second from a c2w).  The default tolerance (0, 0.02) is
+    this build's choice, not a pinned convention.
+
+    Returns a dict of what `want` names plus every accumulator that was passed:
+      match (R) int32: the target pixel q = row * width + column, or -1 nothing to reproject, -2 leaves the view, -3 target
+          depth unknown, -4 occluded;   uv (R, 2) float32: where the point lands (0 outside the projection's domain);
+      agree (n_classes, n_classes) int64: agree[label_src[p], label_tgt[q]] += 1 over visible pixels with both labels in
+          [0, n_classes) (label images on both sides required);   stats (5) int64: pixels matched / -1 / -2 / -3 / -4.
+    agree / stats: accumulated into when given, fresh zeroed tensors when only named in `want`.  out: {"match": ..., "uv": ...}
+    caller-owned tensors to write into."""
+    ms, cam_s, ws, hs = _camera_words(src, "reproject: src")
+    mt, cam_t, wt, ht = _camera_words(tgt, "reproject: tgt")
+    c2w_h, w2c_h = _host_floats(c2w_src, 12, "reproject: c2w_src"), _host_floats(w2c_tgt, 12, "reproject: w2c_tgt")
+    want = tuple(want)
+    for k in want:
+        if k not in REPROJECT_OUTPUTS:
+            raise ValueError("reproject: unknown output %r (one of %s)" % (k, ", ".join(REPROJECT_OUTPUTS)))
+    if depth_src is None:
+        raise ValueError("reproject: depth_src is required")
+    if (label_src is None) != (label_tgt is None):
+        raise ValueError("reproject: label_src and label_tgt come together")
+    tol_abs, tol_rel = (float(v) for v in tol)
+    if not (0.0 <= tol_abs < float("inf") and 0.0 <= tol_rel < float("inf")):
+        raise ValueError("reproject: tol = (absolute, relative) must be finite and >= 0")
+    n_classes = int(n_classes)
+    if (agree is not None or "agree" in want) and label_src is None:
+        raise ValueError("reproject: agree needs label_src and label_tgt")
+    if label_src is not None and not 1 <= n_classes <= 8192:
+        raise ValueError("reproject: n_classes must be in 1 .. 8192 with label images (got %d)" % n_classes)
+    if pix is not None and pix.dim() != 1:
+        raise ValueError("reproject: pix must be a 1-D tensor of linear pixel indices")
+    # shapes first, then dtype / device / contiguity of each
+    depth_src, depth_tgt = _image(depth_src, ws, hs, "reproject: depth_src"), _image(depth_tgt, wt, ht, "reproject: depth_tgt")
+    label_src, label_tgt = _image(label_src, ws, hs, "reproject: label_src"), _image(label_tgt, wt, ht, "reproject: label_tgt")
+    depth_src, depth_tgt = _chk(depth_src, "reproject: depth_src"), _chk(depth_tgt, "reproject: depth_tgt")
+    label_src, label_tgt = _chk(label_src, "reproject: label_src", torch.int32), _chk(label_tgt, "reproject: label_tgt", torch.int32)
+    dev = depth_src.device
+    pix = _chk(pix, "reproject: pix", torch.int32)
+    R = pix.numel() if pix is not None else ws * hs
+    if agree is None and "agree" in want:
+        agree = torch.zeros((n_classes, n_classes), device=dev, dtype=torch.int64)
+    if stats is None and "stats" in want:
+        stats = torch.zeros((5,), device=dev, dtype=torch.int64)
+    if _chk(agree, "reproject: agree", torch.int64) is not None and tuple(agree.shape) != (n_classes, n_classes):
+        raise ValueError("reproject: agree must be (n_classes, n_classes) = (%d, %d)" % (n_classes, n_classes))
+    if _chk(stats, "reproject: stats", torch.int64) is not None and tuple(stats.shape) != (5,):
+        raise ValueError("reproject: stats must be (5,)")
+    out = out or {}
+    for k in out:
+        if k not in ("match", "uv"):
+            raise ValueError("reproject: out holds %r (only 'match' and 'uv' can be caller-owned)" % (k,))
+    match = _own(out.get("match"), (R,), torch.int32, dev, "reproject: match") if "match" in want or "match" in out else None
+    uv = _own(out.get("uv"), (R, 2), torch.float32, dev, "reproject: uv") if "uv" in want or "uv" in out else None
+    for name, t in (("depth_tgt", depth_tgt), ("label_src", label_src), ("label_tgt", label_tgt), ("pix", pix), ("agree", agree), ("stats", stats)):
+        if t is not None and t.device != dev:
+            raise ValueError("reproject: %s is on %s, depth_src on %s" % (name, t.device, dev))
+    _lib.check(_lib.load().pnr_reproject(ms, cam_s, c2w_h, ws, hs, _p(pix), R, _p(depth_src), mt, cam_t, w2c_h, wt, ht, _p(depth_tgt),
+                                         tol_abs, tol_rel, _p(label_src), _p(label_tgt), n_classes if label_src is not None else 0,
+                                         _p(match), _p(uv), _p(agree), _p(stats), _stream()), "pnr_reproject")
+    ret = {"match": match, "uv": uv, "agree": agree, "stats": stats}
+    return {k: v for k, v in ret.items() if v is not None}
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global
