@@ -387,17 +387,71 @@ int pnr_gen_rays(const float* intr4_host, const float* c2w12_host, int width, in
 #define PNR_FISHEYE_NEWTON_STEPS 8      /* float32 is as close to float64 as it gets from 4 steps on (tests/test_camera_ref.py) */
 #define PNR_CAMERA_PINHOLE 0            /* pnr_project_points: cam_host = {fx, fy, cx, cy} */
 #define PNR_CAMERA_FISHEYE 1            /* pnr_project_points: cam_host = cam7 */
+#define PNR_CAMERA_EQUIRECT 3           /* pnr_project_points: cam_host = {lon0, dlon, lat0, dlat}; word 2 is unassigned and refused */
+
+/* The panoramic (equirectangular) camera (DESIGN.md 8 "Panoramic camera"): an image over longitude x latitude.
+ * cam4_host = {lon0, dlon, lat0, dlat} in HALF-TURNS (units of pi).  Pixel (i, j), camera axes as pnr_gen_rays:
+ *   lam = lon0 + ((float)i + 0.5f) * dlon      longitude, 0 along +z, positive towards +x
+ *   psi = lat0 + ((float)j + 0.5f) * dlat      downward pitch, -0.5 straight up, +0.5 straight down
+ *   (sl, cl) = sincospi(lam);  (sp, cp) = sincospi(psi);  d_cam = (cp * sl, sp, cp * cl)
+ *   d = R d_cam in the accumulation order of the fisheye ray ((R0 dx + R1 dy) + R2 dz), o = t.
+ * A full sphere is {-1, 2/W, -0.5, 1/H}.  d is UNIT LENGTH (depth along it is range, as for fisheye rays); every pixel is valid.
+ *
+ * sine, cosine and arctangent are part of the rule -- argument reduction in half-turns and the fixed float32 polynomials
+ * below, one rounding per operation, no fused multiply-add -- so tests/_pano_ref.py restates the model in numpy float32 bit
+ * for bit, like the other two:
+ *   sincospi(x):  k = rintf(2x) (ties to even);  r = x - 0.5f k (exact, |r| <= 1/4);  t = r r;
+ *                 s = r P(t),  c = Q(t),  P and Q by Horner's scheme in t from the highest coefficient down;
+ *                 q = (int)k & 3 selects (sin, cos) = (s, c), (c, -s), (-s, -c) or (-c, s).
+ *   atan2pi(y, x), in half-turns:  ax = |x|, ay = |y|, mx = max(ax, ay), mn = min(ax, ay);  mx == 0 gives 0;  a = mn / mx;
+ *                 a > PNR_TAN_PI_8:  a' = (a - 1)/(a + 1), base = 0.25;  else a' = a, base = 0;
+ *                 r = base + a' A(a' a') (Horner);  ay > ax: r = 0.5 - r;  x < 0: r = 1 - r;  y < 0: r = -r
+ *                 (comparisons: -0 counts as +0).
+ * P, Q: the Taylor coefficients of sin(pi r) / r and cos(pi r) in t = r^2; A: an odd 6-term fit of atan(a) / (pi a) in a^2 on
+ * |a| <= tan(pi/8) (relative error 6e-10 before rounding).  Written as exact float32 values.
+ *
+ * Projection of a camera-space point p (after p_cam and |p_cam| as for the other models):
+ *   lam = atan2pi(p0, p2);  h = sqrtf(p0 p0 + p2 p2);  psi = atan2pi(p1, h)
+ *   u = (lam - lon0)/dlon - 0.5f;  v = (psi - lat0)/dlat - 0.5f
+ *   longitude is periodic with per = 2.0f / fabsf(dlon) pixels:  u < -0.5f: u += per;  else u >= W - 0.5f: u -= per  (one wrap at
+ *   most: a full circle has no seam, a partial range may cross +-180 degrees)
+ *   in the domain iff |p_cam| > 0 and |p_cam| is finite in float32. */
+#define PNR_SINPI_P0 0x1.921fb6p+1f     /*  3.14159274   */
+#define PNR_SINPI_P1 -0x1.4abbcep+2f    /* -5.16771269   */
+#define PNR_SINPI_P2 0x1.466bc6p+1f     /*  2.55016398   */
+#define PNR_SINPI_P3 -0x1.32d2ccp-1f    /* -0.599264503  */
+#define PNR_SINPI_P4 0x1.507834p-4f     /*  0.0821458846 */
+#define PNR_COSPI_Q0 0x1.000000p+0f     /*  1            */
+#define PNR_COSPI_Q1 -0x1.3bd3ccp+2f    /* -4.93480206   */
+#define PNR_COSPI_Q2 0x1.03c1f0p+2f     /*  4.05871201   */
+#define PNR_COSPI_Q3 -0x1.55d3c8p+0f    /* -1.33526278   */
+#define PNR_COSPI_Q4 0x1.e1f506p-3f     /*  0.235330626  */
+#define PNR_COSPI_Q5 -0x1.a6d1f2p-6f    /* -0.0258068908 */
+#define PNR_ATANPI_A0 0x1.45f306p-2f    /*  0.318309873  */
+#define PNR_ATANPI_A1 -0x1.b29948p-4f   /* -0.106103212  */
+#define PNR_ATANPI_A2 0x1.04bc78p-4f    /*  0.0636563003 */
+#define PNR_ATANPI_A3 -0x1.7352dap-5f   /* -0.0453275926 */
+#define PNR_ATANPI_A4 0x1.13b6a6p-5f    /*  0.0336564295 */
+#define PNR_ATANPI_A5 -0x1.3ab9c6p-6f   /* -0.0192093309 */
+#define PNR_TAN_PI_8 0x1.a8279ap-2f     /*  0.41421357   */
 
 /* rays (n_rays, 8) = o d near far as pnr_gen_rays (16-byte aligned); pix / n_rays as pnr_gen_rays.  valid (n_rays) bytes or
  * NULL: 1 where the pixel sees anything.  A pixel that does not gets o, d = 0, near = far = 0 and valid = 0, never NaN. */
 int pnr_gen_rays_fisheye(const float* cam7_host, const float* c2w12_host, int width, int height, float near_, float far_,
                          const int32_t* pix, int64_t n_rays, float* rays, uint8_t* valid, void* stream);
 
+/* Panoramic rays: rays (n_rays, 8) as pnr_gen_rays_fisheye, no valid bytes (every pixel sees something); pix / n_rays as
+ * pnr_gen_rays.  PNR_EINVAL before any launch: null camera or pose, dlon == 0 or dlat == 0, a non-finite parameter, |lon0| > 1,
+ * |dlon| * width > 2 (more than a full circle), a row whose pitch leaves [-0.5, 0.5] (the edges lat0 and lat0 + height * dlat),
+ * bad sizes, n_rays != width*height without pix.  pnr_project_points and pnr_reproject check an equirect camera the same way. */
+int pnr_gen_rays_equirect(const float* cam4_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                          const int32_t* pix, int64_t n_rays, float* rays, void* stream);
+
 /* World points (n, 3) -> uv (n, 2) pixel coordinates (u = column, v = row, pixel centres at integers), range (n) = the
  * distance |p_cam| from the camera centre, valid (n) bytes = inside the projection's domain (pinhole: z_cam > 0) AND inside
  * the image (-0.5 <= u < width - 0.5, -0.5 <= v < height - 0.5).  w2c12_host: 3x4 row-major world-to-camera (host).  The
  * pinhole branch is the inverse of pnr_gen_rays: u = fx x/z + cx.  Outside the domain uv = 0; never NaN.  Any output NULL =
- * not written. */
+ * not written.  model: PNR_CAMERA_PINHOLE, _FISHEYE or _EQUIRECT (4, 7, 4 camera floats); any other word is refused. */
 int pnr_project_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
                        int64_t n, float* uv, float* range, uint8_t* valid, void* stream);
 
@@ -410,16 +464,17 @@ int pnr_project_points(int model, const float* cam_host, const float* w2c12_host
  * Source pixel p = pix[r] (int32, device), or p = r with pix NULL and n = width_src*height_src, as pnr_gen_rays.  The source
  * maps (depth_src, label_src) are IMAGES indexed by p, the target maps (depth_tgt, label_tgt) images indexed by q; the
  * outputs match (n) and uv (n, 2) are indexed by r.
- *   1. ray (o, d) of p from the source camera and c2w_src: the ray of pnr_gen_rays / pnr_gen_rays_fisheye (near, far unused).
+ *   1. ray (o, d) of p from the source camera and c2w_src: the ray of pnr_gen_rays / pnr_gen_rays_fisheye /
+ *      pnr_gen_rays_equirect (near, far unused).
  *   2. t = depth_src[p].  NOTHING TO REPROJECT (code -1) if the fisheye pixel sees nothing, or !(t > 0), or t is not finite
  *      (or p is outside the source image).
  *   3. X_k = o_k + t * d_k (one multiply, one add).  Right for both models: a pinhole d has z_cam = 1 and its depth is
- *      z-depth, a fisheye d is unit length and its depth is range.
+ *      z-depth, a fisheye or equirect d is unit length and its depth is range.
  *   4. (u, v), |p_cam|, p_cam.z of X in the target camera with w2c_tgt: the arithmetic of pnr_project_points.  Outside the
  *      projection's domain or outside the image the pixel LEAVES THE VIEW (code -2).
  *   5. nearest target pixel: iu = min((int)floor(u + 0.5), width_tgt - 1), iv likewise, q = iv*width_tgt + iu (the min:
  *      u + 0.5 may round up to width_tgt).
- *   6. expected depth e in the TARGET's convention: p_cam.z for a pinhole target, |p_cam| for a fisheye target.  With
+ *   6. expected depth e in the TARGET's convention: p_cam.z for a pinhole target, |p_cam| for a fisheye or equirect target.  With
  *      depth_tgt: dt = depth_tgt[q]; !(dt > 0) or dt not finite: UNKNOWN (code -3); else visible iff
  *      |e - dt| <= tol_abs + tol_rel * e, otherwise OCCLUDED (code -4).  depth_tgt NULL: no test, the pixel is visible.
  *   7. match[r] = q when visible, else the code.  uv[r] = (u, v) of step 4 (0, 0 outside the domain and for code -1).
@@ -428,9 +483,10 @@ int pnr_project_points(int model, const float* cam_host, const float* w2c12_host
  *      consistency is its trace over its sum.  stats[0..4] += the number of pixels that were matched / -1 / -2 / -3 / -4.
  *      agree (n_classes^2) and stats (5) are device int64 arrays the caller zeroes once and accumulates into over pairs
  *      (integer atomics: exact, order-independent).  1 <= n_classes <= 8192; up to 128 through a per-block LDS histogram.
- * cam_*_host: {fx, fy, cx, cy} or cam7 by model (PNR_CAMERA_*); c2w_src12_host, w2c_tgt12_host: 3x4 row-major, host values
+ * cam_*_host: {fx, fy, cx, cy}, cam7 or {lon0, dlon, lat0, dlat} by model (PNR_CAMERA_*); c2w_src12_host, w2c_tgt12_host: 3x4 row-major, host values
  * copied into the launch (baked into a stream capture).  Any of match, uv, agree, stats may be NULL.  Never synchronises.
- * PNR_EINVAL before any launch: unknown model, null camera / pose / depth_src, zero focal length or gamma, bad size, labels
+ * PNR_EINVAL before any launch: unknown model, null camera / pose / depth_src, zero focal length or gamma, an equirect camera
+ * that pnr_gen_rays_equirect refuses, bad size, labels
  * given on one side only, agree without labels, negative or non-finite tolerance, n_classes out of range.  n == 0: PNR_OK. */
 int pnr_reproject(int model_src, const float* cam_src_host, const float* c2w_src12_host, int width_src, int height_src,
                   const int32_t* pix, int64_t n, const float* depth_src,
@@ -591,9 +647,10 @@ int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const flo
  * fresh batch, and a table edited after the capture is what later replays see.
  *
  * pnr_frame: one frame, 144 bytes (a multiple of 16; the array is 16-byte aligned), fields in this order:
- *   offset   0  int32  model       PNR_CAMERA_PINHOLE | PNR_CAMERA_FISHEYE
+ *   offset   0  int32  model       PNR_CAMERA_PINHOLE | PNR_CAMERA_FISHEYE | PNR_CAMERA_EQUIRECT
  *            4  int32  width, height
- *           12  float  cam[7]      pinhole: fx, fy, cx, cy (the rest unused); fisheye: cam7 of pnr_gen_rays_fisheye
+ *           12  float  cam[7]      pinhole: fx, fy, cx, cy (the rest unused); fisheye: cam7 of pnr_gen_rays_fisheye; equirect:
+ *                                  lon0, dlon, lat0, dlat (the rest unused; valid_pix = 0, every pixel drawable)
  *           40  float  c2w[12]     3x4 row-major camera-to-world
  *           88  float  near_, far_
  *           96  int64  n_valid     number of drawable pixels (0: the frame is never drawn)
@@ -619,7 +676,8 @@ int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const flo
  * concatenated are the w * n_rays batch of one rank, bit for bit.
  *
  * Outputs per ray (any may be NULL = not wanted):
- *   rays (n_rays, 8), 16-byte aligned: bit for bit what pnr_gen_rays / pnr_gen_rays_fisheye write for that frame and pixel
+ *   rays (n_rays, 8), 16-byte aligned: bit for bit what pnr_gen_rays / pnr_gen_rays_fisheye / pnr_gen_rays_equirect write for
+ *   that frame and pixel
  *   rgb (n_rays, 3) = (float) byte / 255.0f (a division);  depth (n_rays) as stored, 0 where the frame has no depth image (what
  *   pnr_losses reads as "no depth");  sem, inst (n_rays) int32, -1 where the frame has none;  frame_out, pix_out (n_rays) int32.
  * What the host cannot see: F == 0, cum[F] == 0 or (mode 1) n_valid[f] == 0.  The kernel then writes rays = 0, rgb = depth = 0,

@@ -7,12 +7,12 @@ Network / Renderer interfaces.  Importing the package does not load the library;
 does, and raises if it is missing (no CPU fallback)."""
 from .network import NeRF, Network, make_network  # noqa: F401
 from .renderer import Renderer, make_renderer  # noqa: F401
-from .camera import Fisheye, Pinhole  # noqa: F401
+from .camera import Equirect, Fisheye, Pinhole  # noqa: F401
 from .data import FrameSet  # noqa: F401
 from .primitives import ConvexSet, extrude_polygon  # noqa: F401
 from . import consistency  # noqa: F401
 
 from .losses import NetworkWrapper  # noqa: F401,E402
 
-__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "FrameSet", "ConvexSet",
+__all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "Equirect", "FrameSet", "ConvexSet",
            "extrude_polygon", "consistency"]

@@ -14,6 +14,7 @@ c_int = ctypes.c_int
 PREC_BF16, PREC_FP32 = 0, 1
 MLP_SOFTMAX, MLP_TRACE = 1, 0x7A00        # pnr_mlp_desc.flags (include/pnr.h PNR_MLP_*)
 CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1     # pnr_project_points' / pnr_frame's model word (include/pnr.h PNR_CAMERA_*)
+CAMERA_EQUIRECT = 3                       # (word 2 is unassigned)
 TAG_PIXEL, TAG_FRAME = 16, 17             # pnr_sample_batch's stream tags (include/pnr.h PNR_TAG_*)
 SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr.h PNR_SAMPLE_*)
 
@@ -107,6 +108,8 @@ SIGNATURES = {
                              ctypes.c_float, c_f, c_i64, c_f, c_f]),
     "pnr_gen_rays_fisheye": (c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
                                      ctypes.c_float, c_f, c_i64, c_f, c_f, c_f]),
+    "pnr_gen_rays_equirect": (c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
+                                      ctypes.c_float, c_f, c_i64, c_f, c_f]),
     "pnr_project_points": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_i64,
                                    c_f, c_f, c_f, c_f]),
     "pnr_reproject": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_i64, c_f,

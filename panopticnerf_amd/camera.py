@@ -1,11 +1,12 @@
-"""Camera models behind one interface: Pinhole (the rectified perspective pair) and Fisheye (the side-facing cameras of a
-360 rig).  Both make rays on the GPU (`rays`), say which pixels see anything (`valid_pix`) and carry 3D points into the
-image (`project`); `Renderer.render_view` renders a frame of either, and `consistency.reproject` joins two such frames.
+"""Camera models behind one interface: Pinhole (the rectified perspective pair), Fisheye (the side-facing cameras of a
+360 rig) and Equirect (a panorama over longitude x latitude).  All make rays on the GPU (`rays`), say which pixels see anything
+(`valid_pix`) and carry 3D points into the image (`project`); `Renderer.render_view` renders a frame of any, and
+`consistency.reproject` joins two such frames.
 
 The fisheye model is the unified omnidirectional (MEI) model with two radial terms as the public KITTI-360 calibration files
 parametrise it, written out in include/pnr.h ("cameras") and DESIGN.md ("Fisheye cameras"); like every convention of this
-build it is unpinned against the reference's own 360 code.  Fisheye rays are UNIT LENGTH (depth along them is range);
-pinhole rays keep `ops.gen_rays`' convention (z_cam = 1, depth is z-depth).
+build it is unpinned against the reference's own 360 code.  Fisheye and Equirect rays are UNIT LENGTH (depth along them is
+range); pinhole rays keep `ops.gen_rays`' convention (z_cam = 1, depth is z-depth).
 """
 import math
 
@@ -42,7 +43,7 @@ def invert_pose(c2w):
 
 
 class _Camera:
-    """Shared half of the two models: the per-device cache of valid pixels and the GPU-device check."""
+    """Shared half of the models: the per-device cache of valid pixels and the GPU-device check."""
 
     def __init__(self, width, height):
         self.width, self.height = int(width), int(height)
@@ -159,4 +160,48 @@ class Fisheye(_Camera):
         """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (what depth_* of a fisheye
         render holds), valid (P) bool: a direction the lens sees and inside the image (the user mask is not consulted)."""
         uv, rng, valid = ops.project_points("fisheye", self.cam, _pose12(w2c, "Fisheye.project: w2c"), self.width, self.height, points)
+        return uv, rng, valid.bool()
+
+
+class Equirect(_Camera):
+    """A panoramic camera: columns are longitudes, rows latitudes (include/pnr.h "cameras", DESIGN.md "Panoramic camera").
+    lon = (left edge, right edge) and lat = (top edge, bottom edge) in DEGREES, longitude 0 along the camera's +z and positive
+    towards +x, latitude positive up; the default is the full sphere.  A right edge below the left one mirrors the image, a
+    left edge of e.g. 90 with a right edge of 270 crosses the +-180 degree seam.  Unit-length rays (depth is range), every pixel
+    valid; projection wraps longitude round the circle."""
+    model = "equirect"
+
+    def __init__(self, width, height, lon=(-180.0, 180.0), lat=(90.0, -90.0)):
+        super().__init__(width, height)
+        lon_l, lon_r = (float(v) for v in lon)
+        lat_t, lat_b = (float(v) for v in lat)
+        if not all(math.isfinite(v) for v in (lon_l, lon_r, lat_t, lat_b)):
+            raise ValueError("Equirect: non-finite angle")
+        if lon_l == lon_r or lat_t == lat_b:
+            raise ValueError("Equirect: zero span (lon and lat are (left, right) and (top, bottom) edges in degrees)")
+        if abs(lon_r - lon_l) > 360.0:
+            raise ValueError("Equirect: a longitude span above 360 degrees")
+        if abs(lat_t) > 90.0 or abs(lat_b) > 90.0:
+            raise ValueError("Equirect: latitude outside +-90 degrees")
+        if abs(lon_l) > 180.0:
+            raise ValueError("Equirect: the left edge must lie in +-180 degrees")
+        self.lon, self.lat = (lon_l, lon_r), (lat_t, lat_b)
+        # half-turns, pitch positive DOWN: float64 on the host, rounded to float32 once (ops._host_floats)
+        cam64 = (lon_l / 180.0, (lon_r - lon_l) / 180.0 / self.width, -lat_t / 180.0, (lat_t - lat_b) / 180.0 / self.height)
+        self.cam = tuple(float(torch.tensor(v, dtype=torch.float64).to(torch.float32)) for v in cam64)
+        if self.cam[1] == 0.0 or self.cam[3] == 0.0:
+            raise ValueError("Equirect: zero span (the step per pixel underflows float32)")
+
+    def _find_valid(self, dev):
+        return torch.arange(self.width * self.height, dtype=torch.int32, device=dev)
+
+    def rays(self, c2w, near, far, pix=None, device=None):
+        """(R, 8) rays of the whole frame or of the int32 GPU pixel indices `pix` (ops.gen_rays_equirect): unit-length d."""
+        return ops.gen_rays_equirect(self.cam, _pose12(c2w, "Equirect.rays: c2w"), self.width, self.height, near, far, pix=pix,
+                                     device=None if pix is not None else self._device(device))
+
+    def project(self, points, w2c):
+        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (what depth_* of an equirect
+        render holds), valid (P) bool: any point but the camera centre itself whose direction falls inside the image."""
+        uv, rng, valid = ops.project_points("equirect", self.cam, _pose12(w2c, "Equirect.project: w2c"), self.width, self.height, points)
         return uv, rng, valid.bool()

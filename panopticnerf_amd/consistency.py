@@ -1,7 +1,7 @@
 """Cross-view consistency: join two rendered views through depth (ops.reproject / pnr_reproject; the rule is written out in
 include/pnr.h "cross-view reprojection").
 
-A view is `(camera, c2w, maps)`: a camera.Pinhole / camera.Fisheye, its 3x4 camera-to-world pose (host values) and what
+A view is `(camera, c2w, maps)`: a camera.Pinhole / Fisheye / Equirect, its 3x4 camera-to-world pose (host values) and what
 `Renderer.render_view` returned for it -- or any dict that holds a (height, width) depth image on the GPU under `depth_key`.
 `reproject(view_a, view_b)` says for every pixel of A which pixel of B shows the same surface point (or why none does),
 `warp(image_b, match)` carries any image of B into A's pixel grid along that match.  `Evaluator.evaluate_pair` builds the

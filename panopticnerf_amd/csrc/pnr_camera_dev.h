@@ -1,8 +1,10 @@
-// Per-pixel ray arithmetic of the two camera models (include/pnr.h "ray generation" / "cameras"), shared by the kernels that make
-// rays: k_gen_rays (pnr_sampling.hip), k_gen_rays_fisheye (pnr_camera.hip), k_sample_batch (pnr_batch.hip) and k_reproject
-// (pnr_warp.hip), which must write the same bits for the same camera, pose and pixel; and the projection of a world point, shared by
-// k_project_points (pnr_camera.hip) and k_reproject.  Every operation is a single + - * / sqrt in one fixed order (the build has
-// -ffp-contract=off and correctly rounded divide / sqrt); c2w may live in kernel arguments or in device memory.
+// Per-pixel ray arithmetic of the three camera models (include/pnr.h "ray generation" / "cameras"), shared by the kernels that make
+// rays: k_gen_rays (pnr_sampling.hip), k_gen_rays_fisheye / k_gen_rays_equirect (pnr_camera.hip), k_sample_batch (pnr_batch.hip) and
+// k_reproject (pnr_warp.hip), which must write the same bits for the same camera, pose and pixel; and the projection of a world
+// point, shared by k_project_points (pnr_camera.hip) and k_reproject.  Every operation is a single + - * / sqrt in one fixed order
+// (the build has -ffp-contract=off and correctly rounded divide / sqrt); c2w may live in kernel arguments or in device memory.
+// The panoramic model's sine, cosine and arctangent are pnr_sincospi / pnr_atan2pi below -- the same kind of arithmetic, written
+// out, never the device library's -- and are called from this file only.
 #pragma once
 #include <float.h>
 
@@ -62,10 +64,89 @@ __device__ __forceinline__ PnrRayRec pnr_fisheye_ray(const FisheyeCam& c, const 
     return PnrRayRec{make_float4(c2w[3], c2w[7], c2w[11], d[0]), make_float4(d[1], d[2], ok ? near_ : 0.0f, ok ? far_ : 0.0f)};
 }
 
-// world point -> pixel coordinates of either model (include/pnr.h "cameras"): cam = pinhole {fx, fy, cx, cy} or fisheye cam7.
-// u, v are 0 outside the projection's domain (never NaN); rng = |p_cam|, z = p_cam.z.
+// sin(pi x), cos(pi x) by the rule of include/pnr.h "cameras": x in half-turns, finite
+struct PnrSinCos { float s, c; };
+__device__ __forceinline__ PnrSinCos pnr_sincospi(float x)
+{
+    const float k = __builtin_rintf(2.0f * x);          // ties to even
+    const float r = x - 0.5f * k;                       // exact, |r| <= 1/4
+    const float t = r * r;
+    float p = PNR_SINPI_P4;
+    p = p * t + PNR_SINPI_P3;
+    p = p * t + PNR_SINPI_P2;
+    p = p * t + PNR_SINPI_P1;
+    p = p * t + PNR_SINPI_P0;
+    const float s = r * p;
+    float c = PNR_COSPI_Q5;
+    c = c * t + PNR_COSPI_Q4;
+    c = c * t + PNR_COSPI_Q3;
+    c = c * t + PNR_COSPI_Q2;
+    c = c * t + PNR_COSPI_Q1;
+    c = c * t + PNR_COSPI_Q0;
+    const int q = (int)k & 3;
+    return PnrSinCos{q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c, q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s};
+}
+
+// atan2(y, x) / pi in [-1, 1] by the same rule; the sign tests are comparisons (-0 counts as +0)
+__device__ __forceinline__ float pnr_atan2pi(float y, float x)
+{
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const bool steep = ay > ax;
+    const float mx = steep ? ay : ax, mn = steep ? ax : ay;
+    const float a = mn / mx;
+    const bool upper = a > PNR_TAN_PI_8;
+    const float b = upper ? (a - 1.0f) / (a + 1.0f) : a;
+    const float t = b * b;
+    float p = PNR_ATANPI_A5;
+    p = p * t + PNR_ATANPI_A4;
+    p = p * t + PNR_ATANPI_A3;
+    p = p * t + PNR_ATANPI_A2;
+    p = p * t + PNR_ATANPI_A1;
+    p = p * t + PNR_ATANPI_A0;
+    float r = (upper ? 0.25f : 0.0f) + b * p;
+    r = mx == 0.0f ? 0.0f : r;
+    r = steep ? 0.5f - r : r;
+    r = x < 0.0f ? 1.0f - r : r;
+    return y < 0.0f ? -r : r;
+}
+
+// equirect pixel: cam = {lon0, dlon, lat0, dlat} in half-turns; d is unit length, every pixel sees something
+__device__ __forceinline__ PnrRayRec pnr_equirect_ray(float lon0, float dlon, float lat0, float dlat, const float* c2w, int i, int j,
+                                                      float near_, float far_)
+{
+    const float lam = lon0 + ((float)i + 0.5f) * dlon;
+    const float psi = lat0 + ((float)j + 0.5f) * dlat;
+    const PnrSinCos l = pnr_sincospi(lam), p = pnr_sincospi(psi);
+    const float dx = p.c * l.s, dy = p.s, dz = p.c * l.c;
+    float d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float u = c2w[k * 4 + 0] * dx, v = c2w[k * 4 + 1] * dy, w = c2w[k * 4 + 2] * dz;
+        d[k] = (u + v) + w;
+    }
+    return PnrRayRec{make_float4(c2w[3], c2w[7], c2w[11], d[0]), make_float4(d[1], d[2], near_, far_)};
+}
+
+// what every entry point that takes an equirect camera checks on the host, before any launch (include/pnr.h).  The two edge
+// tests run in double with a slack of 1e-6 half-turns: the float32 rounding of 2/W or 1/H may carry a full range past its
+// limit by W * dlon * 2^-24.
+static inline int pnr_equirect_check(const float* cam, int width, int height, const char* who)
+{
+    for (int k = 0; k < 4; ++k) PNR_REQUIRE(fabsf(cam[k]) <= FLT_MAX, "%s: non-finite equirect parameter", who);
+    PNR_REQUIRE(cam[1] != 0.0f && cam[3] != 0.0f, "%s: zero equirect step (dlon, dlat)", who);
+    PNR_REQUIRE(fabsf(cam[0]) <= 1.0f, "%s: equirect lon0 must lie in [-1, 1] half-turns", who);
+    PNR_REQUIRE(fabs((double)cam[1]) * width <= 2.0 + 1e-6, "%s: equirect longitudes span more than a full circle (|dlon| * width > 2)", who);
+    const double e0 = cam[2], e1 = (double)cam[2] + (double)cam[3] * height;
+    PNR_REQUIRE(e0 >= -0.5 - 1e-6 && e0 <= 0.5 + 1e-6 && e1 >= -0.5 - 1e-6 && e1 <= 0.5 + 1e-6,
+                "%s: equirect rows leave the pitch range [-0.5, 0.5] half-turns", who);
+    return PNR_OK;
+}
+
+// world point -> pixel coordinates of any model (include/pnr.h "cameras"): cam = pinhole {fx, fy, cx, cy}, fisheye cam7 or equirect
+// {lon0, dlon, lat0, dlat}; umax = width - 0.5 (the equirect longitude wrap).  u, v are 0 outside the projection's domain (never
+// NaN); rng = |p_cam|, z = p_cam.z.
 struct PnrProj { float u, v, rng, z; bool dom; };
-__device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam, const float* w2c, float X, float Y, float Z)
+__device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam, const float* w2c, float umax, float X, float Y, float Z)
 {
     float p[3];
 #pragma unroll
@@ -81,6 +162,15 @@ __device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam
         const float x = p[0] / p[2], y = p[1] / p[2];
         u = cam[0] * x + cam[2];
         v = cam[1] * y + cam[3];
+    } else if (model == PNR_CAMERA_EQUIRECT) {
+        const float lam = pnr_atan2pi(p[0], p[2]);
+        const float h = sqrtf(p[0] * p[0] + p[2] * p[2]);
+        const float psi = pnr_atan2pi(p[1], h);
+        dom = rng > 0.0f && rng <= FLT_MAX;
+        u = (lam - cam[0]) / cam[1] - 0.5f;
+        v = (psi - cam[2]) / cam[3] - 0.5f;
+        const float per = 2.0f / __builtin_fabsf(cam[1]);       // the longitude period in pixels: at most one wrap
+        u = u < -0.5f ? u + per : u >= umax ? u - per : u;
     } else {
         const float xi = cam[0], k1 = cam[1], k2 = cam[2];
         const float xs = p[0] / rng, ys = p[1] / rng, zs = p[2] / rng;

@@ -2,9 +2,9 @@
 // projected into the target view, matched to the nearest target pixel and tested against the target depth image; with label
 // images on both sides the visible pairs are counted into the cross-view confusion matrix of the multi-view consistency metric.
 // A small gather-bound kernel in the style of pnr_camera.hip: one thread per source pixel, grid-stride, cameras and poses in
-// the kernel arguments.  The ray is pnr_pinhole_ray / pnr_fisheye_ray and the projection pnr_project_point (pnr_camera_dev.h),
+// the kernel arguments.  The ray is pnr_pinhole_ray / pnr_fisheye_ray / pnr_equirect_ray and the projection pnr_project_point (pnr_camera_dev.h),
 // the same functions the ray and projection kernels call, so the arithmetic is theirs bit for bit; tests/_warp_ref.py restates
-// the whole rule in float32.
+// the whole rule in float32 (tests/_pano_ref.py with a panoramic view on either side).
 #include <float.h>
 
 #include "pnr_camera_dev.h"
@@ -51,13 +51,15 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
             PnrRayRec ray;
             if (a.model_src == PNR_CAMERA_PINHOLE)
                 ray = pnr_pinhole_ray(a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.c2w, i, j, 0.0f, 0.0f);
+            else if (a.model_src == PNR_CAMERA_EQUIRECT)
+                ray = pnr_equirect_ray(a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.c2w, i, j, 0.0f, 0.0f);
             else
                 ray = pnr_fisheye_ray(FisheyeCam{a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.cam_src[4], a.cam_src[5], a.cam_src[6]},
                                       a.c2w, i, j, 0.0f, 0.0f, ok);
             const float t = a.depth_src[p];
             if (ok && t > 0.0f && t <= FLT_MAX) {
                 const float X = ray.lo.x + t * ray.lo.w, Y = ray.lo.y + t * ray.hi.x, Z = ray.lo.z + t * ray.hi.y;
-                const PnrProj q = pnr_project_point(a.model_tgt, a.cam_tgt, a.w2c, X, Y, Z);
+                const PnrProj q = pnr_project_point(a.model_tgt, a.cam_tgt, a.w2c, a.umax, X, Y, Z);
                 u = q.u;
                 v = q.v;
                 code = -2;
@@ -110,8 +112,11 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
     if (threadIdx.x < 5 && h[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
 }
 
+static bool warp_model_ok(int model) { return model == PNR_CAMERA_PINHOLE || model == PNR_CAMERA_FISHEYE || model == PNR_CAMERA_EQUIRECT; }
+
 static bool warp_camera_ok(int model, const float* cam)
 {
+    if (model == PNR_CAMERA_EQUIRECT) return cam[1] != 0.0f && cam[3] != 0.0f;
     return model == PNR_CAMERA_PINHOLE ? (cam[0] != 0.0f && cam[1] != 0.0f) : (cam[3] != 0.0f && cam[4] != 0.0f);
 }
 
@@ -122,8 +127,7 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
                              const int32_t* label_src, const int32_t* label_tgt, int n_classes,
                              int32_t* match, float* uv, int64_t* agree, int64_t* stats, void* stream)
 {
-    PNR_REQUIRE((model_src == PNR_CAMERA_PINHOLE || model_src == PNR_CAMERA_FISHEYE) && (model_tgt == PNR_CAMERA_PINHOLE || model_tgt == PNR_CAMERA_FISHEYE),
-                "pnr_reproject: unknown camera model %d -> %d", model_src, model_tgt);
+    PNR_REQUIRE(warp_model_ok(model_src) && warp_model_ok(model_tgt), "pnr_reproject: unknown camera model %d -> %d", model_src, model_tgt);
     PNR_REQUIRE(cam_src_host && c2w_src12_host && cam_tgt_host && w2c_tgt12_host, "pnr_reproject: null camera or pose");
     PNR_REQUIRE(width_src >= 1 && height_src >= 1 && width_tgt >= 1 && height_tgt >= 1 && n >= 0 &&
                 (int64_t)width_src * height_src <= INT32_MAX && (int64_t)width_tgt * height_tgt <= INT32_MAX,
@@ -131,6 +135,14 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
     if (n == 0) return PNR_OK;                  // before the pointer checks: an empty pixel list has a null pointer
     PNR_REQUIRE(pix || n == (int64_t)width_src * height_src, "pnr_reproject: without pixel indices n must be width_src*height_src");
     PNR_REQUIRE(warp_camera_ok(model_src, cam_src_host) && warp_camera_ok(model_tgt, cam_tgt_host), "pnr_reproject: zero focal length or gamma");
+    if (model_src == PNR_CAMERA_EQUIRECT) {
+        const int rc = pnr_equirect_check(cam_src_host, width_src, height_src, "pnr_reproject: src");
+        if (rc) return rc;
+    }
+    if (model_tgt == PNR_CAMERA_EQUIRECT) {
+        const int rc = pnr_equirect_check(cam_tgt_host, width_tgt, height_tgt, "pnr_reproject: tgt");
+        if (rc) return rc;
+    }
     PNR_REQUIRE(depth_src, "pnr_reproject: null source depth image");
     PNR_REQUIRE(tol_abs >= 0.0f && tol_abs <= FLT_MAX && tol_rel >= 0.0f && tol_rel <= FLT_MAX,
                 "pnr_reproject: tolerances must be finite and >= 0");
@@ -141,7 +153,7 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
     PNR_REQUIRE((((uintptr_t)uv) & 7) == 0, "pnr_reproject: uv must be an 8-byte aligned device buffer");
     ReprojectArgs a;
     a.model_src = model_src; a.model_tgt = model_tgt;
-    const int ns = model_src == PNR_CAMERA_PINHOLE ? 4 : 7, nt = model_tgt == PNR_CAMERA_PINHOLE ? 4 : 7;
+    const int ns = model_src == PNR_CAMERA_FISHEYE ? 7 : 4, nt = model_tgt == PNR_CAMERA_FISHEYE ? 7 : 4;
     for (int k = 0; k < 7; ++k) {
         a.cam_src[k] = k < ns ? cam_src_host[k] : 0.0f;
         a.cam_tgt[k] = k < nt ? cam_tgt_host[k] : 0.0f;

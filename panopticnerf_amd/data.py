@@ -1,5 +1,5 @@
 """FrameSet -- a training set of posed images that lives in GPU memory, and the ray batches drawn from it (include/pnr.h
-"training frames"; DESIGN.md "Training frames").  The producer between the cameras (camera.Pinhole / camera.Fisheye) and the
+"training frames"; DESIGN.md "Training frames").  The producer between the cameras (camera.Pinhole / Fisheye / Equirect) and the
 training step: `sample()` is ONE kernel (pnr_sample_batch) that picks (frame, pixel) pairs from the set's own Philox stream,
 builds their rays and gathers rgb / depth / label targets into the batch dict NetworkWrapper takes.  The frame table is device
 memory read when the kernel runs, so a captured training step (train.GraphedStep with `frames=`) draws a fresh batch on every
@@ -16,6 +16,7 @@ from . import _lib, ops
 
 MODES = ("pooled", "frame")
 _REC = ctypes.sizeof(_lib.Frame)
+_MODELS = {"pinhole": _lib.CAMERA_PINHOLE, "fisheye": _lib.CAMERA_FISHEYE, "equirect": _lib.CAMERA_EQUIRECT}      # pnr_frame.model
 
 
 def _image(t, what, H, W, tail=()):
@@ -71,14 +72,14 @@ class FrameSet:
 
     # ------------------------------------------------------------------------------------------------ building the set
     def add(self, camera, c2w, near, far, rgb, depth=None, pseudo_label=None, instance_label=None):
-        """Append one posed image.  camera: camera.Pinhole / camera.Fisheye; c2w: 3x4 (or 4x4) camera-to-world, host values; rgb
+        """Append one posed image.  camera: camera.Pinhole / Fisheye / Equirect; c2w: 3x4 (or 4x4) camera-to-world, host values; rgb
         (H, W, 3) uint8, or float in [0, 1] (rounded to the nearest byte); depth (H, W) float, <= 0 where there is none;
         pseudo_label / instance_label (H, W) integers in the int16 range, -1 = unlabelled.  A fisheye frame draws from
-        camera.valid_pix() (lens and user mask), a pinhole frame from every pixel.  Returns the frame's index.  The record, cum
+        camera.valid_pix() (lens and user mask), a pinhole or equirect frame from every pixel.  Returns the frame's index.  The record, cum
         and n_frames are updated by stream-ordered copies: launches enqueued later (graph replays included) see the frame."""
         model = getattr(camera, "model", None)
-        if model not in ("pinhole", "fisheye"):
-            raise TypeError("FrameSet.add: camera must be a camera.Pinhole or camera.Fisheye")
+        if model not in _MODELS:
+            raise TypeError("FrameSet.add: camera must be a camera.Pinhole or camera.Fisheye (or camera.Equirect)")
         if len(self.frames) >= self.capacity:
             raise RuntimeError("FrameSet.add: the set is full (capacity = %d frames)" % self.capacity)
         H, W = camera.height, camera.width
@@ -123,9 +124,10 @@ class FrameSet:
             if pix.numel() == H * W:
                 pix = None
         n_valid = H * W if pix is None else int(pix.numel())
-        cam = list(camera.intr) + [0.0] * 3 if model == "pinhole" else list(camera.cam)
+        cam = list(camera.intr if model == "pinhole" else camera.cam)
+        cam += [0.0] * (7 - len(cam))
         ptr = lambda t: 0 if t is None else t.data_ptr()
-        rec = _lib.Frame(_lib.CAMERA_PINHOLE if model == "pinhole" else _lib.CAMERA_FISHEYE, W, H, (ctypes.c_float * 7)(*cam),
+        rec = _lib.Frame(_MODELS[model], W, H, (ctypes.c_float * 7)(*cam),
                          (ctypes.c_float * 12)(*pose.tolist()), float(near), float(far), n_valid, ptr(pix), ptr(imgs["rgb"]),
                          ptr(imgs.get("depth")), ptr(imgs.get("sem")), ptr(imgs.get("inst")))
         i = len(self.frames)

@@ -98,15 +98,39 @@ def gen_rays_fisheye(cam, c2w, width, height, near, far, pix=None, device=None, 
     return rays, valid
 
 
+def gen_rays_equirect(cam, c2w, width, height, near, far, pix=None, device=None):
+    """Panoramic ray generation on the GPU (pnr_gen_rays_equirect; the model is in include/pnr.h "cameras").  cam: lon0, dlon,
+    lat0, dlat in half-turns (camera.Equirect makes them from degrees); c2w, pix, device as gen_rays.  Returns rays (R,8):
+    UNIT-LENGTH directions like gen_rays_fisheye's (depth_* of a render on them is range), every pixel valid."""
+    cam_h, c2w_h = _host_floats(cam, 4, "gen_rays_equirect: cam"), _host_floats(c2w, 12, "gen_rays_equirect: c2w")
+    pix = _chk(pix, "pix", torch.int32)
+    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError("gen_rays_equirect: expected a GPU device (the HIP path has no CPU fallback)")
+    R = pix.numel() if pix is not None else int(width) * int(height)
+    # every refusal of the entry point comes before its first use of the device: asked first, with no memory allocated
+    _lib.check(_lib.load().pnr_gen_rays_equirect(cam_h, c2w_h, int(width), int(height), float(near), float(far), None, 0, None, None),
+               "pnr_gen_rays_equirect")
+    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pnr_gen_rays_equirect(cam_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
+                                                     _p(rays), _stream()), "pnr_gen_rays_equirect")
+    return rays
+
+
+_MODEL_WORDS = {"pinhole": (_lib.CAMERA_PINHOLE, 4), "fisheye": (_lib.CAMERA_FISHEYE, 7), "equirect": (_lib.CAMERA_EQUIRECT, 4)}
+
+
 @_on_device
 def project_points(model, cam, w2c, width, height, points):
     """World points (P,3) -> uv (P,2) pixel coordinates, range (P) = distance from the camera centre, valid (P) uint8 = inside
-    the projection's domain and inside the image (pnr_project_points).  model: "pinhole" (cam: fx, fy, cx, cy) or "fisheye"
-    (cam: xi, k1, k2, gamma1, gamma2, u0, v0); w2c: 3x4 world-to-camera (host values)."""
-    if model not in ("pinhole", "fisheye"):
-        raise ValueError("project_points: model must be 'pinhole' or 'fisheye', not %r" % (model,))
-    word = _lib.CAMERA_PINHOLE if model == "pinhole" else _lib.CAMERA_FISHEYE
-    cam_h = _host_floats(cam, 4 if model == "pinhole" else 7, "project_points: cam")
+    the projection's domain and inside the image (pnr_project_points).  model: "pinhole" (cam: fx, fy, cx, cy), "fisheye"
+    (cam: xi, k1, k2, gamma1, gamma2, u0, v0) or "equirect" (cam: lon0, dlon, lat0, dlat in half-turns; u wraps round a full
+    circle); w2c: 3x4 world-to-camera (host values)."""
+    if model not in _MODEL_WORDS:
+        raise ValueError("project_points: model must be 'pinhole', 'fisheye' or 'equirect', not %r" % (model,))
+    word, nc = _MODEL_WORDS[model]
+    cam_h = _host_floats(cam, nc, "project_points: model %r cam" % (model,))
     w2c_h = _host_floats(w2c, 12, "project_points: w2c")
     points = _chk(points, "points")
     if points.dim() != 2 or points.shape[1] != 3:
@@ -121,13 +145,15 @@ def project_points(model, cam, w2c, width, height, points):
 
 
 def _camera_words(cam, what):
-    """(model word, host floats, width, height) of a camera.Pinhole / camera.Fisheye"""
+    """(model word, host floats, width, height) of a camera.Pinhole / camera.Fisheye / camera.Equirect"""
     model = getattr(cam, "model", None)
     if model == "pinhole":
         return _lib.CAMERA_PINHOLE, _host_floats(cam.intr, 4, what), int(cam.width), int(cam.height)
     if model == "fisheye":
         return _lib.CAMERA_FISHEYE, _host_floats(cam.cam, 7, what), int(cam.width), int(cam.height)
-    raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye, not %r" % (what, cam))
+    if model == "equirect":
+        return _lib.CAMERA_EQUIRECT, _host_floats(cam.cam, 4, what), int(cam.width), int(cam.height)
+    raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye (or camera.Equirect), not %r" % (what, cam))
 
 
 def _image(t, width, height, name):
@@ -149,7 +175,7 @@ def reproject(src, c2w_src, depth_src, tgt, w2c_tgt, depth_tgt=None, pix=None, t
     """Cross-view reprojection (pnr_reproject; the rule is in include/pnr.h "cross-view reprojection"): every pixel of the
     source view -- or the int32 GPU pixel indices `pix` -- is lifted with depth_src (a (height, width) image of the source
     camera), projected into the target view and matched to the nearest target pixel; with depth_tgt the match is tested
-    against the target's depth, |e - depth_tgt[q]| <= tol[0] + tol[1] * e.  src, tgt: camera.Pinhole / camera.Fisheye;
+    against the target's depth, |e - depth_tgt[q]| <= tol[0] + tol[1] * e.  src, tgt: camera.Pinhole / Fisheye / Equirect;
     c2w_src, w2c_tgt: 3x4 host values (camera.invert_pose makes the second from a c2w).  The default tolerance (0, 0.02) is
     this build's choice, not a pinned convention.
 

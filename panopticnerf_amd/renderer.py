@@ -419,14 +419,15 @@ class Renderer:
 
     # --- a whole frame of a camera (panopticnerf_amd/camera.py): rays for the pixels that see anything, maps as images
     def render_view(self, camera, c2w, near, far, bbox=None, bbox_ids=None, prims=None):
-        """Render one frame of `camera` (camera.Pinhole / camera.Fisheye) at pose c2w (3x4, host values): rays are made for
+        """Render one frame of `camera` (camera.Pinhole / Fisheye / Equirect) at pose c2w (3x4, host values): rays are made for
         camera.valid_pix() only -- a fisheye frame skips the pixels outside the lens (and the user mask) --, rendered by
         render() (chunking, overlap and fused-plan decisions are render()'s), and every per-ray output is placed into a
         (height, width, ...) image that is 0 where a pixel sees nothing; "valid" (height, width) bool says where that is.
         Labels derived from such maps (ops.panoptic_labels, shard.label_maps) must be set to -1, the evaluator's "ignore",
         where valid is False: the argmax of an all-zero pixel is class 0, not "nothing".  prims: a primitives.ConvexSet as the
-        prior instead of bbox / bbox_ids (moved to the network's device on first use).  depth_* of a Fisheye frame is range
-        along the unit-length ray, of a Pinhole frame z-depth (camera.py).  Inference only."""
+        prior instead of bbox / bbox_ids (moved to the network's device on first use).  depth_* of a Fisheye or Equirect frame
+        is range along the unit-length ray, of a Pinhole frame z-depth (camera.py).  An Equirect frame is the panorama: every
+        map over longitude x latitude, every pixel valid.  Inference only."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters()):
             raise RuntimeError("Renderer.render_view is inference only: call it under torch.no_grad() (training batches are made "
                                "with camera.rays(pix=...) and rendered with render())")

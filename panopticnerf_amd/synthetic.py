@@ -65,6 +65,18 @@ def fisheye_camera(scale=1.0, yaw=math.pi / 2, origin=(0.0, 1.55, 0.0), mask=Non
     return cam, c2w
 
 
+def equirect_camera(scale=1.0, yaw=0.0, origin=(0.0, 1.55, 0.0)):
+    """(camera.Equirect, c2w (3,4)) for tests and examples: a full-sphere panorama at camera_rays' origin, 1408 x 704 at
+    scale = 1 (the width of the perspective frames; 2 : 1 so that a pixel spans the same angle both ways), longitude 0 turned
+    by `yaw` about y from camera_rays' forward axis."""
+    from .camera import Equirect
+    w = max(int(round(KITTI_W * scale)), 2)
+    cam = Equirect(w, max(w // 2, 1))
+    c, s = math.cos(yaw), math.sin(yaw)
+    c2w = torch.tensor([[c, 0.0, s, origin[0]], [0.0, 1.0, 0.0, origin[1]], [-s, 0.0, c, origin[2]]], dtype=torch.float32)
+    return cam, c2w
+
+
 def random_boxes(n_box=64, n_sem=45, n_inst=32, seed=1):
     """Seeded oriented boxes: (M,15) = centre, rotation rows (yaw about y), half extents; ids (M,2) int32."""
     g = torch.Generator().manual_seed(seed)
