@@ -495,6 +495,55 @@ int pnr_reproject(int model_src, const float* cam_src_host, const float* c2w_src
                   const int32_t* label_src, const int32_t* label_tgt, int n_classes,
                   int32_t* match, float* uv, int64_t* agree, int64_t* stats, void* stream);
 
+/* ---- point splatting (csrc/pnr_splat.hip; DESIGN.md 8 "Point splatting"): the forward direction of the above -- world points
+ * (a LiDAR scan, labelled 3D points, a lifted view) scattered into a view of any camera model through a z-buffer, and
+ * depth-error metrics against the depth image that makes.  Conventions (nearest pixel, square footprint, the key, the
+ * metrics' default range) are this build's and unpinned, as for reprojection.  Float32 throughout, every operation a single
+ * + - * / sqrt in the order given (tests/_splat_ref.py restates the rule in numpy, bit for bit).
+ *
+ * pnr_splat_points.  For point i of points (n, 3) (device), THE CONTRACT:
+ *   1. (u, v), |p_cam|, p_cam.z and the domain flag of the point in the camera with w2c: the arithmetic of pnr_project_points.
+ *      The point LEAVES THE VIEW unless it is in the projection's domain and -0.5 <= u < width - 0.5, -0.5 <= v < height - 0.5.
+ *      A NaN or Inf coordinate ends here by these comparisons.
+ *   2. nearest pixel as reprojection step 5: iu = min((int)floor(u + 0.5), width - 1), iv likewise.
+ *   3. depth e in the view's convention: p_cam.z for a pinhole, |p_cam| for a fisheye or equirect view.  The point is CLIPPED
+ *      unless e >= near_ && e <= far_.  0 <= near_ <= far_; far_ may be +inf (a pinhole z that overflowed then lands as +inf).
+ *   4. key = ((uint64) bits(e) << 32) | (uint32)(index_base + i).  e > 0 here, and a positive float's bits order as its value.
+ *   5. for every pixel (iu + dx, iv + dy) with |dx|, |dy| <= radius that lies inside the image:
+ *      zbuf[q] = min(zbuf[q], key), an unsigned 64-bit atomic minimum.  radius is 0, 1 or 2.  The footprint is clipped at the
+ *      image border and NEVER WRAPPED: not at the seam of a full-circle equirect image either.
+ *   6. stats[0..2] += the number of points that landed / left the view / were clipped (device int64, integer atomics).
+ * zbuf: caller-owned device int64 (height * width), initialised to all ones (-1) = empty; an empty cell can never equal a key
+ * (its high word is a NaN pattern).  It ACCUMULATES over calls: several scans, frames or chunks of one cloud use distinct
+ * index_base ranges, and the result is the same whatever their order or chunking -- the nearest point wins, a depth tie goes
+ * to the lowest index.  cam_host / w2c12_host as pnr_project_points: host values copied into the launch (baked into a stream
+ * capture).  stats may be NULL.  Never synchronises.  PNR_EINVAL before any launch: unknown model, null camera / pose / points
+ * / zbuf, zero focal length or gamma, an equirect camera that pnr_gen_rays_equirect refuses, bad size, radius outside 0 .. 2,
+ * near_ < 0 or far_ < near_ (or NaN), index_base < 0 or index_base + n > 2^31 - 1.  n == 0: PNR_OK.
+ *
+ * pnr_splat_resolve: per cell q of zbuf (n_pix), depth[q] = the float of the high word, or 0.0f where the cell is empty (the
+ * "unknown" depth of pnr_reproject: the image can go straight in as depth_tgt); index[q] = the low word as int32, or -1.
+ * Either output may be NULL.
+ *
+ * pnr_depth_metrics: pred, gt (n) float32, mask (n) uint8 or NULL.  A pixel COUNTS when (mask is NULL or mask[i] != 0) and
+ * g = gt[i] is finite and d_min <= g <= d_max (0 < d_min <= d_max, both finite).  A counted pixel whose p = pred[i] is not
+ * positive and finite adds 1 to counts[4] (missing) and nothing else.  Otherwise counts[0] += 1; in float32
+ * ratio = fmaxf(p / g, g / p) (two divisions) and counts[1..3] += ratio < 1.25f / < 1.5625f / < 1.953125f (strict); in double
+ * d = (double)p - (double)g and sums[0..4] += |d|, d*d, |d| / g, d*d / g, (log p - log g)^2 (each one operation per symbol).
+ * counts: device int64[5], integer atomics, exact.  sums: device double[5]; each term is accumulated per thread, reduced per
+ * wave and per block in a fixed order and written as a per-block partial into workspace; a one-block second kernel adds the
+ * partials in block order and the total once into sums.  No floating atomics: two calls on the same input give the same bits.
+ * Both arrays accumulate over calls (the caller zeroes them once).  workspace: pnr_depth_metrics_workspace_bytes(n) bytes,
+ * 8-byte aligned (-1 for n < 0).  PNR_EINVAL before any launch: n < 0, a bad range, a null pred / gt / sums / counts /
+ * workspace, misaligned sums / counts / workspace.  n == 0: PNR_OK. */
+int pnr_splat_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
+                     int64_t n, int64_t index_base, float near_, float far_, int radius, int64_t* zbuf, int64_t* stats,
+                     void* stream);
+int pnr_splat_resolve(const int64_t* zbuf, int64_t n_pix, float* depth, int32_t* index, void* stream);
+int64_t pnr_depth_metrics_workspace_bytes(int64_t n);
+int pnr_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int64_t n, float d_min, float d_max,
+                      double* sums, int64_t* counts, void* workspace, void* stream);
+
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).
  * pnr_panoptic_labels: sem_label = argmax_c sem (lowest index on ties); inst_label = argmax_k inst where is_thing[sem_label]

@@ -10,8 +10,8 @@ multi-view consistency metric on the same kernel.
 Conventions (this build's, unpinned like the evaluator's other conventions): nearest target pixel, no sub-pixel lookup; a
 pixel is visible when the depth B renders at the matched pixel agrees with the depth the lifted point has in B,
 |e - depth_b[q]| <= tol[0] + tol[1] * e with the default tol = (0, 0.02); depth is z-depth in a pinhole frame and range in a
-fisheye frame, as render_view writes it.  Out of scope: forward splatting with a z-buffer, bilinear lookup, depth-error
-metrics, reading poses from files, more than two views per call."""
+fisheye frame, as render_view writes it.  The forward direction (splatting with a z-buffer) and depth-error metrics live in
+pointcloud.py and Evaluator.evaluate_depth.  Out of scope: bilinear lookup, reading poses from files, more than two views per call."""
 import torch
 
 from . import ops

@@ -33,6 +33,8 @@ class Evaluator:
         self.mc_agree = None    # (C, C) device int64: cross-view confusion [label in the source view, label in the target view]
         self.mc_stats = None    # (5) device int64: source pixels matched / nothing to reproject / left the view / unknown / occluded
         self.mc_tol = consistency.DEFAULT_TOL
+        self.depth_sums = None      # (5) device float64: sums of |d|, d^2, |d|/gt, d^2/gt, (log pred - log gt)^2 (pnr_depth_metrics)
+        self.depth_counts = None    # (5) device int64: compared pixels, ratio < 1.25 / 1.25^2 / 1.25^3, missing predictions
 
     def evaluate(self, output, batch):
         lv = self.level if f"rgb_{self.level}" in output else 0
@@ -109,6 +111,28 @@ class Evaluator:
             res[name] = m.reshape(s[0].height, s[0].width)
         return res
 
+    def evaluate_depth(self, output, depth_gt, valid=None, level=None, d_range=ops.DEPTH_RANGE):
+        """Accumulate depth-error terms of a rendered depth image against a ground-truth depth image of the same shape and
+        convention (e.g. a LiDAR scan through pointcloud.splat: z-depth in a pinhole frame, range otherwise), on the device
+        (ops.depth_metrics; the rule is in include/pnr.h "point splatting").  output: what Renderer.render_view returned;
+        the depth image is depth_<level>, or with level=None the one consistency.depth_key chooses (the finest present).
+        A pixel counts where `valid` (optional bool image) is set and depth_gt is finite and inside d_range -- this build's
+        default, unpinned -- so the 0 of a splatted image's holes never counts."""
+        if not hasattr(output, "keys"):
+            raise ValueError("Evaluator.evaluate_depth: output must be the dict Renderer.render_view returned")
+        key = consistency.depth_key(output, None if level is None else "depth_%d" % int(level))
+        pred = output[key]
+        if not isinstance(pred, torch.Tensor) or not isinstance(depth_gt, torch.Tensor):
+            raise ValueError("Evaluator.evaluate_depth: %s and depth_gt must be tensors" % key)
+        if tuple(pred.shape) != tuple(depth_gt.shape):
+            raise ValueError("Evaluator.evaluate_depth: %s is %s, depth_gt %s" % (key, tuple(pred.shape), tuple(depth_gt.shape)))
+        if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != tuple(depth_gt.shape)):
+            raise ValueError("Evaluator.evaluate_depth: valid must be a bool image of depth_gt's shape %s" % (tuple(depth_gt.shape),))
+        mask = None if valid is None else (valid != 0).contiguous()
+        self.depth_sums, self.depth_counts = ops.depth_metrics(pred.float().contiguous(), depth_gt.float().contiguous(), mask, d_range,
+                                                               self.depth_sums, self.depth_counts)
+        return key
+
     def _accumulate_pq(self, pred_id, gt_id):
         """Per-frame PQ terms (Kirillov et al.): segments match when same class and IoU > 0.5 (then the match is unique).
         Panoptic ids: class*1000 + instance for things, class for stuff; < 0 = ignore.  Segment ids are re-mapped PER
@@ -159,6 +183,7 @@ class Evaluator:
             return self._summarize()
         finally:
             self.mse, self.conf, self.pq, self._bad_ids, self.mc_agree, self.mc_stats = [], None, None, None, None, None
+            self.depth_sums, self.depth_counts = None, None
 
     def _summarize(self):
         out = {}
@@ -192,4 +217,13 @@ class Evaluator:
             out["mc"] = float(c.diag().sum() / c.sum()) if float(c.sum()) > 0 else math.nan
             out["mc_per_class"] = torch.where(rows > 0, c.diag() / rows.clamp(min=1), torch.full_like(rows, float("nan"))).tolist()
             out["mc_stats"] = [int(v) for v in self.mc_stats.cpu().tolist()]
+        if self.depth_counts is not None:
+            c, s = [int(v) for v in self.depth_counts.cpu().tolist()], self.depth_sums.cpu().tolist()
+            n = c[0]
+            mean = lambda v: v / n if n else math.nan
+            out["depth_n"], out["depth_missing"] = n, c[4]
+            out["depth_mae"], out["depth_rmse"] = mean(s[0]), math.sqrt(mean(s[1])) if n else math.nan
+            out["depth_abs_rel"], out["depth_sq_rel"] = mean(s[2]), mean(s[3])
+            out["depth_rmse_log"] = math.sqrt(mean(s[4])) if n else math.nan
+            out["depth_d1"], out["depth_d2"], out["depth_d3"] = mean(c[1]), mean(c[2]), mean(c[3])
         return out

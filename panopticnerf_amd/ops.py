@@ -239,6 +239,123 @@ def reproject(src, c2w_src, depth_src, tgt, w2c_tgt, depth_tgt=None, pix=None, t
     return {k: v for k, v in ret.items() if v is not None}
 
 
+def _gpu(t, name, what="a GPU tensor"):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: expected %s, got %s" % (name, what, type(t).__name__))
+    return t
+
+
+@_on_device
+def splat_points(camera, w2c, points, zbuf=None, index_base=0, near=0.0, far=float("inf"), radius=0, stats=None):
+    """Scatter world points (P, 3) into a view through a z-buffer (pnr_splat_points; the rule is in include/pnr.h "point
+    splatting").  camera: camera.Pinhole / Fisheye / Equirect; w2c: 3x4 world-to-camera host values (camera.invert_pose).
+    Returns zbuf (height, width) int64: per pixel the packed key (depth bits << 32 | point index) of the nearest point that
+    covers it, -1 where none does -- a fresh buffer filled with -1 when `zbuf` is None, else `zbuf` itself, accumulated into
+    (several scans or chunks: give each a distinct index_base range; the result does not depend on their order).  Depth is
+    z-depth in a pinhole view and range in a fisheye / equirect view; points outside [near, far] are clipped; radius 0, 1 or 2
+    is the half width of the square footprint (clipped at the border, never wrapped).  stats: (3) int64, accumulated:
+    points landed / left the view / clipped.  splat_resolve unpacks the buffer."""
+    model, cam_h, width, height = _camera_words(camera, "splat_points: camera")
+    w2c_h = _host_floats(w2c, 12, "splat_points: w2c")
+    _gpu(points, "splat_points: points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("splat_points: points must be (P, 3)")
+    radius, index_base = int(radius), int(index_base)
+    if radius not in (0, 1, 2):
+        raise ValueError("splat_points: radius must be 0, 1 or 2 (got %d)" % radius)
+    near, far = float(near), float(far)
+    if not (0.0 <= near <= far):
+        raise ValueError("splat_points: near and far must satisfy 0 <= near <= far (far may be inf)")
+    P = points.shape[0]
+    if index_base < 0 or index_base + P > 2 ** 31 - 1:
+        raise ValueError("splat_points: index_base + the number of points must stay within 0 .. 2^31 - 1")
+    if zbuf is not None and (not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (height, width)):
+        raise ValueError("splat_points: zbuf must be a (%d, %d) int64 tensor" % (height, width))
+    if stats is not None and (not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (3,)):
+        raise ValueError("splat_points: stats must be (3,)")
+    points = _chk(points, "splat_points: points")
+    dev = points.device
+    zbuf, stats = _chk(zbuf, "splat_points: zbuf", torch.int64), _chk(stats, "splat_points: stats", torch.int64)
+    for name, t in (("zbuf", zbuf), ("stats", stats)):
+        if t is not None and t.device != dev:
+            raise ValueError("splat_points: %s is on %s, points on %s" % (name, t.device, dev))
+    if zbuf is None:
+        zbuf = torch.full((height, width), -1, device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().pnr_splat_points(model, cam_h, w2c_h, width, height, _p(points), P, index_base, near, far, radius,
+                                            _p(zbuf), _p(stats), _stream()), "pnr_splat_points")
+    return zbuf
+
+
+@_on_device
+def splat_resolve(zbuf, want=("depth", "index"), out=None):
+    """(depth, index) images of a z-buffer splat_points made (pnr_splat_resolve): depth float32 in the view's convention,
+    0 where no point landed (the "unknown" depth ops.reproject reads); index int32 = the winning point's index_base + i, -1
+    where none.  want: which of the two to make (the other is None); out: {"depth": ..., "index": ...} caller-owned tensors."""
+    _gpu(zbuf, "splat_resolve: zbuf")
+    want = tuple(want)
+    for k in want:
+        if k not in ("depth", "index"):
+            raise ValueError("splat_resolve: unknown output %r (depth, index)" % (k,))
+    out = out or {}
+    for k in out:
+        if k not in ("depth", "index"):
+            raise ValueError("splat_resolve: out holds %r (only 'depth' and 'index')" % (k,))
+    zbuf = _chk(zbuf, "splat_resolve: zbuf", torch.int64)
+    dev, shape = zbuf.device, tuple(zbuf.shape)
+    depth = _own(out.get("depth"), shape, torch.float32, dev, "splat_resolve: depth") if "depth" in want or "depth" in out else None
+    index = _own(out.get("index"), shape, torch.int32, dev, "splat_resolve: index") if "index" in want or "index" in out else None
+    _lib.check(_lib.load().pnr_splat_resolve(_p(zbuf), zbuf.numel(), _p(depth), _p(index), _stream()), "pnr_splat_resolve")
+    return depth, index
+
+
+DEPTH_RANGE = (1e-3, 80.0)          # default ground-truth range of depth_metrics: this build's, unpinned
+
+
+@_on_device
+def depth_metrics(pred, gt, mask=None, d_range=DEPTH_RANGE, sums=None, counts=None):
+    """Depth-error terms of a predicted depth image against a ground truth of the same shape (pnr_depth_metrics; the rule is
+    in include/pnr.h "point splatting").  A pixel counts where mask (bool / uint8, optional) is set and gt is finite and inside
+    d_range = (d_min, d_max).  Returns (sums (5) float64, counts (5) int64), accumulated into when given:
+      counts: compared pixels, ratio < 1.25, < 1.25^2, < 1.25^3 (ratio = max(pred/gt, gt/pred), strict), missing predictions
+      sums:   |d|, d^2, |d|/gt, d^2/gt, (log pred - log gt)^2 with d = pred - gt, over the compared pixels.
+    Deterministic: no floating atomics."""
+    _gpu(pred, "depth_metrics: pred")
+    _gpu(gt, "depth_metrics: gt")
+    if pred.shape != gt.shape:
+        raise ValueError("depth_metrics: pred is %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.shape != gt.shape):
+        raise ValueError("depth_metrics: mask must have gt's shape %s" % (tuple(gt.shape),))
+    try:
+        d_min, d_max = (float(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("depth_metrics: d_range must be (d_min, d_max)") from None
+    if not (0.0 < d_min <= d_max < float("inf")):
+        raise ValueError("depth_metrics: d_range must satisfy 0 < d_min <= d_max, both finite")
+    if sums is not None and (not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (5,)):
+        raise ValueError("depth_metrics: sums must be (5,)")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (5,)):
+        raise ValueError("depth_metrics: counts must be (5,)")
+    pred, gt = _chk(pred, "depth_metrics: pred"), _chk(gt, "depth_metrics: gt")
+    dev = gt.device
+    if mask is not None and mask.dtype == torch.bool and mask.is_cuda and mask.is_contiguous():
+        mask = mask.view(torch.uint8)
+    mask = _chk(mask, "depth_metrics: mask (bool or uint8)", torch.uint8)
+    sums, counts = _chk(sums, "depth_metrics: sums", torch.float64), _chk(counts, "depth_metrics: counts", torch.int64)
+    for name, t in (("pred", pred), ("mask", mask), ("sums", sums), ("counts", counts)):
+        if t is not None and t.device != dev:
+            raise ValueError("depth_metrics: %s is on %s, gt on %s" % (name, t.device, dev))
+    if sums is None:
+        sums = torch.zeros((5,), device=dev, dtype=torch.float64)
+    if counts is None:
+        counts = torch.zeros((5,), device=dev, dtype=torch.int64)
+    n = gt.numel()
+    ws = torch.empty((_size_or_raise(_lib.load().pnr_depth_metrics_workspace_bytes(n), "pnr_depth_metrics_workspace_bytes") // 8,),
+                     device=dev, dtype=torch.float64)
+    _lib.check(_lib.load().pnr_depth_metrics(_p(pred), _p(gt), _p(mask), n, d_min, d_max, _p(sums), _p(counts), _p(ws), _stream()),
+               "pnr_depth_metrics")
+    return sums, counts
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global

@@ -77,6 +77,40 @@ def equirect_camera(scale=1.0, yaw=0.0, origin=(0.0, 1.55, 0.0)):
     return cam, c2w
 
 
+def lidar_scan(origin=(0.0, 1.55, 0.0), sphere=((0.0, 1.55, 10.0), 30.0), ground_y=None, n_azimuth=360, n_elevation=32,
+               elevation=(-25.0, 15.0), azimuth=(-180.0, 180.0)):
+    """A spinning-LiDAR-shaped cloud with known depth, for tests and examples: n_elevation rings of n_azimuth beams from
+    `origin` -- 3 world coordinates, or a 3x4 / 4x4 sensor-to-world pose whose axes the beam angles then refer to -- hit an
+    analytic scene: the inside of `sphere` = (centre, radius), which must enclose the origin, and optionally the plane
+    y = ground_y (y points down, as in camera_rays).  Angles in degrees: azimuth 0 along +z, positive towards +x; elevation
+    positive up.  Float64 closed forms, rounded once.  Returns points (n, 3) float32 in world space and range (n) float32."""
+    o = torch.as_tensor(origin, dtype=torch.float64).reshape(-1)
+    if o.numel() == 16:
+        o = o[:12]
+    if o.numel() == 12:
+        Rm, o = o.reshape(3, 4)[:, :3], o.reshape(3, 4)[:, 3]
+    elif o.numel() == 3:
+        Rm = torch.eye(3, dtype=torch.float64)
+    else:
+        raise ValueError("lidar_scan: origin must be 3 coordinates or a 3x4 (4x4) pose")
+    centre, radius = torch.as_tensor(sphere[0], dtype=torch.float64).reshape(3), float(sphere[1])
+    oc = o - centre
+    if not float(oc @ oc) < radius * radius:
+        raise ValueError("lidar_scan: the origin must lie inside the sphere")
+    if n_azimuth < 1 or n_elevation < 1:
+        raise ValueError("lidar_scan: n_azimuth and n_elevation must be >= 1")
+    az = torch.deg2rad(azimuth[0] + (azimuth[1] - azimuth[0]) * (torch.arange(n_azimuth, dtype=torch.float64) + 0.5) / n_azimuth)
+    el = torch.deg2rad(elevation[0] + (elevation[1] - elevation[0]) * (torch.arange(n_elevation, dtype=torch.float64) + 0.5) / n_elevation)
+    el, az = torch.meshgrid(el, az, indexing="ij")
+    d = torch.stack([torch.cos(el) * torch.sin(az), -torch.sin(el), torch.cos(el) * torch.cos(az)], -1).reshape(-1, 3) @ Rm.T
+    b = d @ oc
+    t = -b + torch.sqrt(b * b - (oc @ oc - radius * radius))           # unit d: the far root, the origin is inside
+    if ground_y is not None:
+        tg = (float(ground_y) - o[1]) / d[:, 1]
+        t = torch.where((d[:, 1] != 0) & (tg > 0) & (tg < t), tg, t)
+    return (o + t[:, None] * d).float().contiguous(), t.float().contiguous()
+
+
 def random_boxes(n_box=64, n_sem=45, n_inst=32, seed=1):
     """Seeded oriented boxes: (M,15) = centre, rotation rows (yaw about y), half extents; ids (M,2) int32."""
     g = torch.Generator().manual_seed(seed)
