@@ -368,7 +368,8 @@ int pnr_ce3d(const float* raw, int64_t raw_stride_c, int first_channel, int n_cl
 int pnr_gen_rays(const float* intr4_host, const float* c2w12_host, int width, int height, float near_, float far_,
                  const int32_t* pix, int64_t n_rays, float* rays, void* stream);
 
-/* ---- cameras: fisheye ray generation and 3D -> 2D projection for both camera models (csrc/pnr_camera.hip; DESIGN.md
+/* ---- cameras: fisheye and equirect ray generation and 3D -> 2D projection for all three camera models (csrc/pnr_camera.hip,
+ * where pnr_gen_rays above lives too; what every kernel shares of a camera is csrc/pnr_camera_dev.h; DESIGN.md
  * "Fisheye cameras").  The fisheye model is the unified omnidirectional (MEI) model with two radial terms, as the public
  * KITTI-360 calibration files parametrise it; cam7_host = {xi, k1, k2, gamma1, gamma2, u0, v0}.  Camera axes as pnr_gen_rays.
  *

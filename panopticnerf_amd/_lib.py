@@ -13,8 +13,7 @@ c_int = ctypes.c_int
 
 PREC_BF16, PREC_FP32 = 0, 1
 MLP_SOFTMAX, MLP_TRACE = 1, 0x7A00        # pnr_mlp_desc.flags (include/pnr.h PNR_MLP_*)
-CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1     # pnr_project_points' / pnr_frame's model word (include/pnr.h PNR_CAMERA_*)
-CAMERA_EQUIRECT = 3                       # (word 2 is unassigned)
+CAMERA_PINHOLE, CAMERA_FISHEYE, CAMERA_EQUIRECT = 0, 1, 3     # the model word of every entry point that takes a camera and of pnr_frame (include/pnr.h PNR_CAMERA_*; word 2 is unassigned)
 TAG_PIXEL, TAG_FRAME = 16, 17             # pnr_sample_batch's stream tags (include/pnr.h PNR_TAG_*)
 SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr.h PNR_SAMPLE_*)
 

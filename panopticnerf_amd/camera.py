@@ -13,16 +13,21 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
-def _pose12(m, what):
-    t = torch.as_tensor(m, dtype=torch.float32).reshape(-1)
+def _rows3(t, msg):
+    """the 12 values of a 3x4 pose, or the first 12 of a 4x4 one, flat; anything else is refused with `msg`"""
+    t = t.reshape(-1)
     if t.numel() == 16:
         t = t[:12]
     if t.numel() != 12:
-        raise ValueError(f"{what}: expected a 3x4 (or 4x4) matrix")
+        raise ValueError(msg)
     return t
+
+
+def _pose12(m, what):
+    return _rows3(torch.as_tensor(m, dtype=torch.float32), f"{what}: expected a 3x4 (or 4x4) matrix")
 
 
 def invert_pose(c2w):
@@ -30,20 +35,19 @@ def invert_pose(c2w):
     float32 once.  Every w2c of the cross-view code (consistency.py, Evaluator.evaluate_pair) is made this way, so a pose
     pair means the same bits everywhere."""
     if isinstance(c2w, torch.Tensor):
-        m = c2w.detach().cpu().to(torch.float64).reshape(-1)
+        m = c2w.detach().cpu().to(torch.float64)
     else:
-        m = torch.as_tensor(np.asarray(c2w, dtype=np.float64)).reshape(-1)     # (torch would read python floats as float32)
-    if m.numel() == 16:
-        m = m[:12]
-    if m.numel() != 12:
-        raise ValueError("invert_pose: expected a 3x4 (or 4x4) matrix")
-    m = m.reshape(3, 4)
+        m = torch.as_tensor(np.asarray(c2w, dtype=np.float64))     # (torch would read python floats as float32)
+    m = _rows3(m, "invert_pose: expected a 3x4 (or 4x4) matrix").reshape(3, 4)
     rt = m[:, :3].T
     return torch.cat([rt, -(rt @ m[:, 3:])], 1).to(torch.float32)
 
 
 class _Camera:
-    """Shared half of the models: the per-device cache of valid pixels and the GPU-device check."""
+    """Shared half of the models: the per-device cache of valid pixels, the GPU-device check and projection.  A model adds
+    `model` (its name), `word` (the model word of include/pnr.h PNR_CAMERA_*), `params` (the camera floats that go with the
+    word), `rays` and, where not every pixel sees something, `all_valid = False` and `_find_valid`."""
+    all_valid = True
 
     def __init__(self, width, height):
         self.width, self.height = int(width), int(height)
@@ -69,40 +73,44 @@ class _Camera:
             self._valid_pix[dev] = self._find_valid(dev)
         return self._valid_pix[dev]
 
+    def _find_valid(self, dev):
+        return torch.arange(self.width * self.height, dtype=torch.int32, device=dev)
+
+    def project(self, points, w2c):
+        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre, valid (P) bool: inside
+        the model's domain (its class docstring) and inside the image."""
+        name = type(self).__name__
+        uv, rng, valid = ops.project_points(self.model, self.params, _pose12(w2c, f"{name}.project: w2c"), self.width, self.height, points)
+        return uv, rng, valid.bool()
+
 
 class Pinhole(_Camera):
-    """fx, fy, cx, cy as `ops.gen_rays`: d = R ((i - cx)/fx, (j - cy)/fy, 1), every pixel valid."""
-    model = "pinhole"
+    """fx, fy, cx, cy as `ops.gen_rays`: d = R ((i - cx)/fx, (j - cy)/fy, 1), every pixel valid.  `project`: valid where z_cam > 0
+    and inside the image; z-depth is range times the z of the unit direction, or uv back through the intrinsics."""
+    model, word = "pinhole", _lib.CAMERA_PINHOLE
 
     def __init__(self, fx, fy, cx, cy, width, height):
         super().__init__(width, height)
-        self.intr = (float(fx), float(fy), float(cx), float(cy))
+        self.intr = self.params = (float(fx), float(fy), float(cx), float(cy))
         if self.intr[0] == 0.0 or self.intr[1] == 0.0:
             raise ValueError("Pinhole: zero focal length")
-
-    def _find_valid(self, dev):
-        return torch.arange(self.width * self.height, dtype=torch.int32, device=dev)
 
     def rays(self, c2w, near, far, pix=None, device=None):
         """(R, 8) rays of the whole frame or of the int32 GPU pixel indices `pix` (ops.gen_rays)."""
         return ops.gen_rays(self.intr, _pose12(c2w, "Pinhole.rays: c2w"), self.width, self.height, near, far, pix=pix,
                             device=None if pix is not None else self._device(device))
 
-    def project(self, points, w2c):
-        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (z-depth is range times the
-        z of the unit direction, or uv back through the intrinsics), valid (P) bool: z_cam > 0 and inside the image."""
-        uv, rng, valid = ops.project_points("pinhole", self.intr, _pose12(w2c, "Pinhole.project: w2c"), self.width, self.height, points)
-        return uv, rng, valid.bool()
-
 
 class Fisheye(_Camera):
     """xi, k1, k2, gamma1, gamma2, u0, v0 of the MEI model (include/pnr.h "cameras").  mask: optional (height, width) bool /
-    0-1 array, True where the pixel is to be used (e.g. the dataset's mask of the car body); it only narrows `valid_pix`."""
-    model = "fisheye"
+    0-1 array, True where the pixel is to be used (e.g. the dataset's mask of the car body); it only narrows `valid_pix`.
+    `project`: range is what depth_* of a fisheye render holds; valid for a direction the lens sees and inside the image (the
+    user mask is not consulted)."""
+    model, word, all_valid = "fisheye", _lib.CAMERA_FISHEYE, False
 
     def __init__(self, xi, k1, k2, gamma1, gamma2, u0, v0, width, height, mask=None):
         super().__init__(width, height)
-        self.cam = tuple(float(v) for v in (xi, k1, k2, gamma1, gamma2, u0, v0))
+        self.cam = self.params = tuple(float(v) for v in (xi, k1, k2, gamma1, gamma2, u0, v0))
         if not all(math.isfinite(v) for v in self.cam):
             raise ValueError("Fisheye: non-finite parameter")
         if self.cam[0] < 0.0:
@@ -156,20 +164,15 @@ class Fisheye(_Camera):
         return ops.gen_rays_fisheye(self.cam, _pose12(c2w, "Fisheye.rays: c2w"), self.width, self.height, near, far, pix=pix,
                                     device=None if pix is not None else self._device(device), want_valid=False)[0]
 
-    def project(self, points, w2c):
-        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (what depth_* of a fisheye
-        render holds), valid (P) bool: a direction the lens sees and inside the image (the user mask is not consulted)."""
-        uv, rng, valid = ops.project_points("fisheye", self.cam, _pose12(w2c, "Fisheye.project: w2c"), self.width, self.height, points)
-        return uv, rng, valid.bool()
-
 
 class Equirect(_Camera):
     """A panoramic camera: columns are longitudes, rows latitudes (include/pnr.h "cameras", DESIGN.md "Panoramic camera").
     lon = (left edge, right edge) and lat = (top edge, bottom edge) in DEGREES, longitude 0 along the camera's +z and positive
     towards +x, latitude positive up; the default is the full sphere.  A right edge below the left one mirrors the image, a
     left edge of e.g. 90 with a right edge of 270 crosses the +-180 degree seam.  Unit-length rays (depth is range), every pixel
-    valid; projection wraps longitude round the circle."""
-    model = "equirect"
+    valid; projection wraps longitude round the circle.  `project`: range is what depth_* of an equirect render holds; valid for
+    any point but the camera centre itself whose direction falls inside the image."""
+    model, word = "equirect", _lib.CAMERA_EQUIRECT
 
     def __init__(self, width, height, lon=(-180.0, 180.0), lat=(90.0, -90.0)):
         super().__init__(width, height)
@@ -188,20 +191,11 @@ class Equirect(_Camera):
         self.lon, self.lat = (lon_l, lon_r), (lat_t, lat_b)
         # half-turns, pitch positive DOWN: float64 on the host, rounded to float32 once (ops._host_floats)
         cam64 = (lon_l / 180.0, (lon_r - lon_l) / 180.0 / self.width, -lat_t / 180.0, (lat_t - lat_b) / 180.0 / self.height)
-        self.cam = tuple(float(torch.tensor(v, dtype=torch.float64).to(torch.float32)) for v in cam64)
+        self.cam = self.params = tuple(float(torch.tensor(v, dtype=torch.float64).to(torch.float32)) for v in cam64)
         if self.cam[1] == 0.0 or self.cam[3] == 0.0:
             raise ValueError("Equirect: zero span (the step per pixel underflows float32)")
-
-    def _find_valid(self, dev):
-        return torch.arange(self.width * self.height, dtype=torch.int32, device=dev)
 
     def rays(self, c2w, near, far, pix=None, device=None):
         """(R, 8) rays of the whole frame or of the int32 GPU pixel indices `pix` (ops.gen_rays_equirect): unit-length d."""
         return ops.gen_rays_equirect(self.cam, _pose12(c2w, "Equirect.rays: c2w"), self.width, self.height, near, far, pix=pix,
                                      device=None if pix is not None else self._device(device))
-
-    def project(self, points, w2c):
-        """World points (P, 3) on the GPU -> uv (P, 2), range (P) = distance from the camera centre (what depth_* of an equirect
-        render holds), valid (P) bool: any point but the camera centre itself whose direction falls inside the image."""
-        uv, rng, valid = ops.project_points("equirect", self.cam, _pose12(w2c, "Equirect.project: w2c"), self.width, self.height, points)
-        return uv, rng, valid.bool()

@@ -1,6 +1,6 @@
 // Training frames (include/pnr.h "training frames"): one kernel draws a ray batch from a device-resident table of posed images --
-// the (frame, pixel) draw from the in-kernel Philox stream, the ray of that camera and pixel (pnr_camera_dev.h: the bits of
-// k_gen_rays / k_gen_rays_fisheye / k_gen_rays_equirect) and the gathered targets.  One thread per ray, grid-stride; per ray one Philox call, a binary
+// the (frame, pixel) draw from the in-kernel Philox stream, the ray of that camera and pixel (pnr_camera_ray of
+// pnr_camera_dev.h: the bits of k_gen_rays<model>, pnr_camera.hip) and the gathered targets.  One thread per ray, grid-stride; per ray one Philox call, a binary
 // search over the frame prefix sums, a 144-byte record read and up to five dependent gathers: latency- and gather-bound at the
 // few thousand rays of a training step.  The table (records, prefix sums, frame count) is read when the kernel runs.
 #include "pnr_camera_dev.h"
@@ -54,15 +54,8 @@ __global__ __launch_bounds__(256) void k_sample_batch(const SampleBatchArgs a)
             const int32_t* vp = reinterpret_cast<const int32_t*>(fr.valid_pix);
             p = vp ? vp[k] : (int32_t)k;
             const int j = p / fr.width, i = p - j * fr.width;
-            if (fr.model == PNR_CAMERA_FISHEYE) {
-                bool ok;
-                ray = pnr_fisheye_ray(FisheyeCam{fr.cam[0], fr.cam[1], fr.cam[2], fr.cam[3], fr.cam[4], fr.cam[5], fr.cam[6]}, fr.c2w, i, j,
-                                      fr.near_, fr.far_, ok);
-            } else if (fr.model == PNR_CAMERA_EQUIRECT) {
-                ray = pnr_equirect_ray(fr.cam[0], fr.cam[1], fr.cam[2], fr.cam[3], fr.c2w, i, j, fr.near_, fr.far_);
-            } else {
-                ray = pnr_pinhole_ray(fr.cam[0], fr.cam[1], fr.cam[2], fr.cam[3], fr.c2w, i, j, fr.near_, fr.far_);
-            }
+            bool ok;                                // (a frame's valid_pix holds no pixel outside the lens)
+            ray = pnr_camera_ray(fr.model, fr.cam, fr.c2w, i, j, fr.near_, fr.far_, ok);
             if (a.rgb) {
                 const uint8_t* px = reinterpret_cast<const uint8_t*>(fr.rgb) + (int64_t)p * 3;
                 c0 = (float)px[0] / 255.0f; c1 = (float)px[1] / 255.0f; c2 = (float)px[2] / 255.0f;

@@ -1,10 +1,12 @@
-// Per-pixel ray arithmetic of the three camera models (include/pnr.h "ray generation" / "cameras"), shared by the kernels that make
-// rays: k_gen_rays (pnr_sampling.hip), k_gen_rays_fisheye / k_gen_rays_equirect (pnr_camera.hip), k_sample_batch (pnr_batch.hip) and
-// k_reproject (pnr_warp.hip), which must write the same bits for the same camera, pose and pixel; and the projection of a world
-// point, shared by k_project_points (pnr_camera.hip) and k_reproject.  Every operation is a single + - * / sqrt in one fixed order
-// (the build has -ffp-contract=off and correctly rounded divide / sqrt); c2w may live in kernel arguments or in device memory.
-// The panoramic model's sine, cosine and arctangent are pnr_sincospi / pnr_atan2pi below -- the same kind of arithmetic, written
-// out, never the device library's -- and are called from this file only.
+// "A camera" in one place (include/pnr.h "ray generation" / "cameras"): the per-pixel ray arithmetic of the three models and
+// pnr_camera_ray, which picks among them by model word; the projection of a world point of any model; the rules a view adds to
+// it (nearest pixel, stored depth); the block reduction of per-thread counters; and the host side of a camera argument (its
+// checks, its cam[7] and pose fill).  Callers: k_gen_rays<model> and k_project_points (pnr_camera.hip), k_sample_batch
+// (pnr_batch.hip), k_reproject (pnr_warp.hip) and k_splat_points (pnr_splat.hip), which must write the same bits for the same
+// camera, pose and pixel or point -- no other file branches on the model word.  Every operation is a single + - * / sqrt in one
+// fixed order (the build has -ffp-contract=off and correctly rounded divide / sqrt); c2w may live in kernel arguments or in
+// device memory.  The panoramic model's sine, cosine and arctangent are pnr_sincospi / pnr_atan2pi below -- the same kind of
+// arithmetic, written out, never the device library's -- and are called from this file only.
 #pragma once
 #include <float.h>
 
@@ -127,6 +129,16 @@ __device__ __forceinline__ PnrRayRec pnr_equirect_ray(float lon0, float dlon, fl
     return PnrRayRec{make_float4(c2w[3], c2w[7], c2w[11], d[0]), make_float4(d[1], d[2], near_, far_)};
 }
 
+// the ray of any model: cam as pnr_project_point takes it; ok = the pixel sees anything (always, but for a fisheye).  With a
+// constant model one ray function is left.
+__device__ __forceinline__ PnrRayRec pnr_camera_ray(int model, const float* cam, const float* c2w, int i, int j, float near_, float far_, bool& ok)
+{
+    ok = true;
+    if (model == PNR_CAMERA_PINHOLE) return pnr_pinhole_ray(cam[0], cam[1], cam[2], cam[3], c2w, i, j, near_, far_);
+    if (model == PNR_CAMERA_EQUIRECT) return pnr_equirect_ray(cam[0], cam[1], cam[2], cam[3], c2w, i, j, near_, far_);
+    return pnr_fisheye_ray(FisheyeCam{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6]}, c2w, i, j, near_, far_, ok);
+}
+
 // what every entry point that takes an equirect camera checks on the host, before any launch (include/pnr.h).  The two edge
 // tests run in double with a slack of 1e-6 half-turns: the float32 rounding of 2/W or 1/H may carry a full range past its
 // limit by W * dlon * 2^-24.
@@ -140,6 +152,31 @@ static inline int pnr_equirect_check(const float* cam, int width, int height, co
     PNR_REQUIRE(e0 >= -0.5 - 1e-6 && e0 <= 0.5 + 1e-6 && e1 >= -0.5 - 1e-6 && e1 <= 0.5 + 1e-6,
                 "%s: equirect rows leave the pitch range [-0.5, 0.5] half-turns", who);
     return PNR_OK;
+}
+
+static inline bool pnr_camera_model_ok(int model) { return model == PNR_CAMERA_PINHOLE || model == PNR_CAMERA_FISHEYE || model == PNR_CAMERA_EQUIRECT; }
+
+// a camera of a known model, on the host before any launch: focal lengths / gammas / steps are divided by (`nonzero`: an entry
+// point that never refused a zero leaves it out), and an equirect camera passes pnr_equirect_check
+static inline int pnr_camera_check(int model, const float* cam, int width, int height, const char* who, bool nonzero = true)
+{
+    const bool nz = model == PNR_CAMERA_EQUIRECT ? (cam[1] != 0.0f && cam[3] != 0.0f)
+                  : model == PNR_CAMERA_PINHOLE  ? (cam[0] != 0.0f && cam[1] != 0.0f) : (cam[3] != 0.0f && cam[4] != 0.0f);
+    PNR_REQUIRE(nz || !nonzero, "%s: zero focal length or gamma", who);
+    return model == PNR_CAMERA_EQUIRECT ? pnr_equirect_check(cam, width, height, who) : PNR_OK;
+}
+
+// the model's 4 or 7 camera floats into a kernel argument's zero-padded cam[7]; returns their number
+static inline int pnr_camera_fill(int model, const float* cam_host, float* cam7)
+{
+    const int nc = model == PNR_CAMERA_FISHEYE ? 7 : 4;
+    for (int k = 0; k < 7; ++k) cam7[k] = k < nc ? cam_host[k] : 0.0f;
+    return nc;
+}
+
+static inline void pnr_pose_fill(const float* pose12_host, float* pose12)
+{
+    for (int k = 0; k < 12; ++k) pose12[k] = pose12_host[k];
 }
 
 // world point -> pixel coordinates of any model (include/pnr.h "cameras"): cam = pinhole {fx, fy, cx, cy}, fisheye cam7 or equirect
@@ -190,4 +227,34 @@ __device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam
 __device__ __forceinline__ bool pnr_uv_inside(float u, float v, float umax, float vmax)
 {
     return u >= -0.5f && u < umax && v >= -0.5f && v < vmax;
+}
+
+// nearest pixel of a coordinate inside the image (step 5 of include/pnr.h "cross-view reprojection"): floorf(u + 0.5f), clamped
+// to nmax = size - 1 because u + 0.5f may round up to the size
+__device__ __forceinline__ int pnr_nearest_pixel(float u, int nmax)
+{
+    const int i = (int)floorf(u + 0.5f);
+    return i < nmax ? i : nmax;
+}
+
+// the depth a view of this model stores for a projected point: z-depth in a pinhole view, range otherwise
+__device__ __forceinline__ float pnr_view_depth(int model, const PnrProj& q) { return model == PNR_CAMERA_PINHOLE ? q.z : q.rng; }
+
+// stats[k] += the block's sum of cnt[k], k < K: the wave's butterfly, one LDS atomic per wave, one global atomic per block and
+// non-zero counter.  Called by every thread of the block; h: K words of LDS, free to hold anything before the first barrier.
+template <int K>
+__device__ __forceinline__ void pnr_block_count_add(const unsigned int (&cnt)[K], unsigned int* h, unsigned long long* stats)
+{
+    __syncthreads();
+    if (threadIdx.x < K) h[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        unsigned int c = cnt[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&h[k], c);
+    }
+    __syncthreads();
+    if (threadIdx.x < K && h[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
 }

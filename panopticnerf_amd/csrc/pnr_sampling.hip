@@ -1,4 +1,4 @@
-// K1 / K1b / K2 / K5: per-ray sample generation, Embedder, sample_pdf + merge, bbox prior.
+// K1 / K1b / K2 / K5: per-ray sample generation, Embedder, sample_pdf + merge, bbox prior (ray generation: pnr_camera.hip).
 // gfx950 only.  The sampler, sample_pdf and bbox kernels are BIT-EXACT restatements of
 // oracle/pnr_oracle.c (pnro_stratified / pnro_points / pnro_sample_pdf / pnro_bbox_hits /
 // pnro_sample_labels), which since round 3 pins TORCH'S OWN op order (linspace two-sided, sum in
@@ -6,7 +6,6 @@
 // file is compiled with -ffp-contract=off and the pragma below so no mul+add pair is fused.
 // Reference functions these replace (the reference source
 // is not in the mount, include/pnr.h explains the citation form).
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
 #include "pnr_philox.h"
 #include <stdlib.h>
@@ -49,20 +48,6 @@ __device__ __forceinline__ float strat_sample(float nr, float fr, int i, int N, 
     const float w = up - lo;
     const float m = w * *t;
     return lo + m;
-}
-
-// Ray generation: one thread per ray, two float4 stores; write-bound (32 B/ray).
-struct GenRaysArgs { float fx, fy, cx, cy; float c2w[12]; int width; float near_, far_; const int32_t* pix; int64_t R; float* rays; };
-__global__ __launch_bounds__(256) void k_gen_rays(const GenRaysArgs a)
-{
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = a.pix ? (int64_t)a.pix[r] : r;
-        const int j = (int)(p / a.width), i = (int)(p - (int64_t)j * a.width);
-        const PnrRayRec ray = pnr_pinhole_ray(a.fx, a.fy, a.cx, a.cy, a.c2w, i, j, a.near_, a.far_);
-        float4* o = reinterpret_cast<float4*>(a.rays + r * 8);
-        o[0] = ray.lo;
-        o[1] = ray.hi;
-    }
 }
 
 // One thread per sample; HBM-bound: reads 8 B/ray amortised (+4 B t_rand), writes 4 B.
@@ -847,24 +832,6 @@ PNR_EXPORT int pnr_stratified_rng(const float* rays, int64_t n_rays, int n_sampl
     hipLaunchKernelGGL(k_stratified<PnrRngDev>, dim3(pnr_grid_cap((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        rays, n_rays, n_samples, lindisp, (const float*)nullptr, z_out, rng);
     PNR_CHECK_LAUNCH("pnr_stratified_rng");
-    return PNR_OK;
-}
-
-PNR_EXPORT int pnr_gen_rays(const float* intr4_host, const float* c2w12_host, int width, int height, float near_, float far_,
-                            const int32_t* pix, int64_t n_rays, float* rays, void* stream)
-{
-    PNR_REQUIRE(intr4_host && c2w12_host, "pnr_gen_rays: null camera");
-    PNR_REQUIRE(width >= 1 && height >= 1 && n_rays >= 0, "pnr_gen_rays: bad size");
-    if (n_rays == 0) return PNR_OK;             // before the pointer checks: an empty pixel list has a null pointer
-    PNR_REQUIRE(pix || n_rays == (int64_t)width * height, "pnr_gen_rays: without pixel indices n_rays must be width*height");
-    PNR_REQUIRE(intr4_host[0] != 0.0f && intr4_host[1] != 0.0f, "pnr_gen_rays: zero focal length");
-    PNR_REQUIRE(rays && (((uintptr_t)rays) & 15) == 0, "pnr_gen_rays: rays must be a 16-byte aligned device buffer");
-    GenRaysArgs a;
-    a.fx = intr4_host[0]; a.fy = intr4_host[1]; a.cx = intr4_host[2]; a.cy = intr4_host[3];
-    for (int k = 0; k < 12; ++k) a.c2w[k] = c2w12_host[k];
-    a.width = width; a.near_ = near_; a.far_ = far_; a.pix = pix; a.R = n_rays; a.rays = rays;
-    hipLaunchKernelGGL(k_gen_rays, dim3(pnr_grid_cap((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    PNR_CHECK_LAUNCH("pnr_gen_rays");
     return PNR_OK;
 }
 

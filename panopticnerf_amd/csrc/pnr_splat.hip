@@ -4,7 +4,7 @@
 // second kernel unpacks the buffer into a depth and an index image; a third accumulates depth-error metrics of a predicted
 // depth image against such a ground truth.  Small scatter- / gather-bound kernels in the style of pnr_warp.hip: one thread per
 // point or pixel, grid-stride, camera and pose in the kernel arguments.  The projection is pnr_project_point (pnr_camera_dev.h)
-// and nothing else, so the arithmetic is k_project_points' bit for bit; tests/_splat_ref.py restates the whole rule in numpy.
+// and nothing else, so the arithmetic is k_project_points' bit for bit (the nearest pixel and the stored depth are k_reproject's); tests/_splat_ref.py restates the whole rule in numpy.
 #include <float.h>
 
 #include "pnr_camera_dev.h"
@@ -41,11 +41,9 @@ __global__ __launch_bounds__(256) void k_splat_points(const SplatArgs a)
         const PnrProj q = pnr_project_point(a.model, a.cam, a.w2c, a.umax, X, Y, Z);
         int slot = 1;
         if (q.dom && pnr_uv_inside(q.u, q.v, a.umax, a.vmax)) {
-            int iu = (int)floorf(q.u + 0.5f), iv = (int)floorf(q.v + 0.5f);
-            const int wmax = a.width - 1, hmax = a.height - 1;                  // (u + 0.5f may round up to width)
-            iu = iu < wmax ? iu : wmax;
-            iv = iv < hmax ? iv : hmax;
-            const float e = a.model == PNR_CAMERA_PINHOLE ? q.z : q.rng;
+            const int wmax = a.width - 1, hmax = a.height - 1;
+            const int iu = pnr_nearest_pixel(q.u, wmax), iv = pnr_nearest_pixel(q.v, hmax);
+            const float e = pnr_view_depth(a.model, q);
             slot = 2;
             if (e >= a.near_ && e <= a.far_) {
                 slot = 0;
@@ -70,18 +68,7 @@ __global__ __launch_bounds__(256) void k_splat_points(const SplatArgs a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) cnt[k] += slot == k ? 1u : 0u;              // (constant indices: cnt stays in registers)
     }
-    if (!a.stats) return;                               // (uniform over the block)
-    if (threadIdx.x < 3) h[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        unsigned int c = cnt[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&h[k], c);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && h[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+    if (a.stats) pnr_block_count_add(cnt, h, a.stats);  // (uniform over the block)
 }
 
 __global__ __launch_bounds__(256) void k_splat_resolve(const unsigned long long* __restrict__ zbuf, int64_t n_pix, float* __restrict__ depth,
@@ -169,27 +156,16 @@ __global__ __launch_bounds__(64) void k_depth_metrics_final(const DepthMetricArg
     a.sums[threadIdx.x] = a.sums[threadIdx.x] + v;
 }
 
-static bool splat_model_ok(int model) { return model == PNR_CAMERA_PINHOLE || model == PNR_CAMERA_FISHEYE || model == PNR_CAMERA_EQUIRECT; }
-
-static bool splat_camera_ok(int model, const float* cam)
-{
-    if (model == PNR_CAMERA_EQUIRECT) return cam[1] != 0.0f && cam[3] != 0.0f;
-    return model == PNR_CAMERA_PINHOLE ? (cam[0] != 0.0f && cam[1] != 0.0f) : (cam[3] != 0.0f && cam[4] != 0.0f);
-}
-
 PNR_EXPORT int pnr_splat_points(int model, const float* cam_host, const float* w2c12_host, int width, int height, const float* points,
                                 int64_t n, int64_t index_base, float near_, float far_, int radius, int64_t* zbuf, int64_t* stats,
                                 void* stream)
 {
-    PNR_REQUIRE(splat_model_ok(model), "pnr_splat_points: unknown camera model %d", model);
+    PNR_REQUIRE(pnr_camera_model_ok(model), "pnr_splat_points: unknown camera model %d", model);
     PNR_REQUIRE(cam_host && w2c12_host, "pnr_splat_points: null camera or pose");
     PNR_REQUIRE(width >= 1 && height >= 1 && n >= 0 && (int64_t)width * height <= INT32_MAX,
                 "pnr_splat_points: bad size (the image holds at most 2^31 - 1 pixels)");
-    PNR_REQUIRE(splat_camera_ok(model, cam_host), "pnr_splat_points: zero focal length or gamma");
-    if (model == PNR_CAMERA_EQUIRECT) {
-        const int rc = pnr_equirect_check(cam_host, width, height, "pnr_splat_points");
-        if (rc) return rc;
-    }
+    const int rc = pnr_camera_check(model, cam_host, width, height, "pnr_splat_points");
+    if (rc) return rc;
     PNR_REQUIRE(radius >= 0 && radius <= 2, "pnr_splat_points: radius must be 0, 1 or 2 (got %d)", radius);
     PNR_REQUIRE(near_ >= 0.0f && far_ >= near_, "pnr_splat_points: near and far must satisfy 0 <= near <= far (far may be +inf)");
     PNR_REQUIRE(index_base >= 0 && index_base + n <= (int64_t)INT32_MAX, "pnr_splat_points: index_base + n must stay within 0 .. 2^31 - 1");
@@ -197,9 +173,8 @@ PNR_EXPORT int pnr_splat_points(int model, const float* cam_host, const float* w
     PNR_REQUIRE(points && zbuf, "pnr_splat_points: null points or zbuf");
     SplatArgs a;
     a.model = model;
-    const int nc = model == PNR_CAMERA_FISHEYE ? 7 : 4;
-    for (int k = 0; k < 7; ++k) a.cam[k] = k < nc ? cam_host[k] : 0.0f;
-    for (int k = 0; k < 12; ++k) a.w2c[k] = w2c12_host[k];
+    pnr_camera_fill(model, cam_host, a.cam);
+    pnr_pose_fill(w2c12_host, a.w2c);
     a.width = width; a.height = height;
     a.umax = (float)width - 0.5f; a.vmax = (float)height - 0.5f; a.near_ = near_; a.far_ = far_;
     a.points = points; a.n = n; a.index_base = (unsigned int)index_base;

@@ -2,9 +2,10 @@
 // projected into the target view, matched to the nearest target pixel and tested against the target depth image; with label
 // images on both sides the visible pairs are counted into the cross-view confusion matrix of the multi-view consistency metric.
 // A small gather-bound kernel in the style of pnr_camera.hip: one thread per source pixel, grid-stride, cameras and poses in
-// the kernel arguments.  The ray is pnr_pinhole_ray / pnr_fisheye_ray / pnr_equirect_ray and the projection pnr_project_point (pnr_camera_dev.h),
-// the same functions the ray and projection kernels call, so the arithmetic is theirs bit for bit; tests/_warp_ref.py restates
-// the whole rule in float32 (tests/_pano_ref.py with a panoramic view on either side).
+// the kernel arguments.  The ray is pnr_camera_ray and the projection pnr_project_point (pnr_camera_dev.h), the same functions
+// the ray and projection kernels call, so the arithmetic is theirs bit for bit; the nearest pixel, the depth a view stores and
+// the reduction of the stats are that header's too (shared with pnr_splat.hip).  tests/_warp_ref.py restates the whole rule in
+// float32 (tests/_pano_ref.py with a panoramic view on either side).
 #include <float.h>
 
 #include "pnr_camera_dev.h"
@@ -47,15 +48,8 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
         float u = 0.0f, v = 0.0f;
         if (p >= 0 && p < a.npix_src) {                 // an index outside the source image has nothing to reproject
             const int j = (int)(p / a.width_src), i = (int)(p - (int64_t)j * a.width_src);
-            bool ok = true;
-            PnrRayRec ray;
-            if (a.model_src == PNR_CAMERA_PINHOLE)
-                ray = pnr_pinhole_ray(a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.c2w, i, j, 0.0f, 0.0f);
-            else if (a.model_src == PNR_CAMERA_EQUIRECT)
-                ray = pnr_equirect_ray(a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.c2w, i, j, 0.0f, 0.0f);
-            else
-                ray = pnr_fisheye_ray(FisheyeCam{a.cam_src[0], a.cam_src[1], a.cam_src[2], a.cam_src[3], a.cam_src[4], a.cam_src[5], a.cam_src[6]},
-                                      a.c2w, i, j, 0.0f, 0.0f, ok);
+            bool ok;
+            const PnrRayRec ray = pnr_camera_ray(a.model_src, a.cam_src, a.c2w, i, j, 0.0f, 0.0f, ok);
             const float t = a.depth_src[p];
             if (ok && t > 0.0f && t <= FLT_MAX) {
                 const float X = ray.lo.x + t * ray.lo.w, Y = ray.lo.y + t * ray.hi.x, Z = ray.lo.z + t * ray.hi.y;
@@ -64,14 +58,10 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
                 v = q.v;
                 code = -2;
                 if (q.dom && pnr_uv_inside(u, v, a.umax, a.vmax)) {
-                    int iu = (int)floorf(u + 0.5f), iv = (int)floorf(v + 0.5f);
-                    const int wmax = a.width_tgt - 1, hmax = a.height_tgt - 1;          // (u + 0.5f may round up to width)
-                    iu = iu < wmax ? iu : wmax;
-                    iv = iv < hmax ? iv : hmax;
-                    const int tq = iv * a.width_tgt + iu;
+                    const int tq = pnr_nearest_pixel(v, a.height_tgt - 1) * a.width_tgt + pnr_nearest_pixel(u, a.width_tgt - 1);
                     code = tq;
                     if (a.depth_tgt) {
-                        const float e = a.model_tgt == PNR_CAMERA_PINHOLE ? q.z : q.rng;
+                        const float e = pnr_view_depth(a.model_tgt, q);
                         const float dt = a.depth_tgt[tq];
                         if (!(dt > 0.0f && dt <= FLT_MAX)) code = -3;
                         else if (!(fabsf(e - dt) <= a.tol_abs + a.tol_rel * e)) code = -4;
@@ -97,27 +87,7 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
         for (int i = threadIdx.x; i < cells; i += blockDim.x)
             if (h[i]) atomicAdd(&a.agree[i], (unsigned long long)h[i]);
     }
-    if (!a.stats) return;                               // (uniform over the block)
-    __syncthreads();
-    if (threadIdx.x < 5) h[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        unsigned int c = cnt[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&h[k], c);
-    }
-    __syncthreads();
-    if (threadIdx.x < 5 && h[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-}
-
-static bool warp_model_ok(int model) { return model == PNR_CAMERA_PINHOLE || model == PNR_CAMERA_FISHEYE || model == PNR_CAMERA_EQUIRECT; }
-
-static bool warp_camera_ok(int model, const float* cam)
-{
-    if (model == PNR_CAMERA_EQUIRECT) return cam[1] != 0.0f && cam[3] != 0.0f;
-    return model == PNR_CAMERA_PINHOLE ? (cam[0] != 0.0f && cam[1] != 0.0f) : (cam[3] != 0.0f && cam[4] != 0.0f);
+    if (a.stats) pnr_block_count_add(cnt, h, a.stats);  // (uniform over the block; h is free once the histogram is flushed)
 }
 
 PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const float* c2w_src12_host, int width_src, int height_src,
@@ -127,22 +97,16 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
                              const int32_t* label_src, const int32_t* label_tgt, int n_classes,
                              int32_t* match, float* uv, int64_t* agree, int64_t* stats, void* stream)
 {
-    PNR_REQUIRE(warp_model_ok(model_src) && warp_model_ok(model_tgt), "pnr_reproject: unknown camera model %d -> %d", model_src, model_tgt);
+    PNR_REQUIRE(pnr_camera_model_ok(model_src) && pnr_camera_model_ok(model_tgt), "pnr_reproject: unknown camera model %d -> %d", model_src, model_tgt);
     PNR_REQUIRE(cam_src_host && c2w_src12_host && cam_tgt_host && w2c_tgt12_host, "pnr_reproject: null camera or pose");
     PNR_REQUIRE(width_src >= 1 && height_src >= 1 && width_tgt >= 1 && height_tgt >= 1 && n >= 0 &&
                 (int64_t)width_src * height_src <= INT32_MAX && (int64_t)width_tgt * height_tgt <= INT32_MAX,
                 "pnr_reproject: bad size (each image holds at most 2^31 - 1 pixels)");
     if (n == 0) return PNR_OK;                  // before the pointer checks: an empty pixel list has a null pointer
     PNR_REQUIRE(pix || n == (int64_t)width_src * height_src, "pnr_reproject: without pixel indices n must be width_src*height_src");
-    PNR_REQUIRE(warp_camera_ok(model_src, cam_src_host) && warp_camera_ok(model_tgt, cam_tgt_host), "pnr_reproject: zero focal length or gamma");
-    if (model_src == PNR_CAMERA_EQUIRECT) {
-        const int rc = pnr_equirect_check(cam_src_host, width_src, height_src, "pnr_reproject: src");
-        if (rc) return rc;
-    }
-    if (model_tgt == PNR_CAMERA_EQUIRECT) {
-        const int rc = pnr_equirect_check(cam_tgt_host, width_tgt, height_tgt, "pnr_reproject: tgt");
-        if (rc) return rc;
-    }
+    int rc = pnr_camera_check(model_src, cam_src_host, width_src, height_src, "pnr_reproject: src");
+    if (!rc) rc = pnr_camera_check(model_tgt, cam_tgt_host, width_tgt, height_tgt, "pnr_reproject: tgt");
+    if (rc) return rc;
     PNR_REQUIRE(depth_src, "pnr_reproject: null source depth image");
     PNR_REQUIRE(tol_abs >= 0.0f && tol_abs <= FLT_MAX && tol_rel >= 0.0f && tol_rel <= FLT_MAX,
                 "pnr_reproject: tolerances must be finite and >= 0");
@@ -153,15 +117,10 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
     PNR_REQUIRE((((uintptr_t)uv) & 7) == 0, "pnr_reproject: uv must be an 8-byte aligned device buffer");
     ReprojectArgs a;
     a.model_src = model_src; a.model_tgt = model_tgt;
-    const int ns = model_src == PNR_CAMERA_FISHEYE ? 7 : 4, nt = model_tgt == PNR_CAMERA_FISHEYE ? 7 : 4;
-    for (int k = 0; k < 7; ++k) {
-        a.cam_src[k] = k < ns ? cam_src_host[k] : 0.0f;
-        a.cam_tgt[k] = k < nt ? cam_tgt_host[k] : 0.0f;
-    }
-    for (int k = 0; k < 12; ++k) {
-        a.c2w[k] = c2w_src12_host[k];
-        a.w2c[k] = w2c_tgt12_host[k];
-    }
+    pnr_camera_fill(model_src, cam_src_host, a.cam_src);
+    pnr_camera_fill(model_tgt, cam_tgt_host, a.cam_tgt);
+    pnr_pose_fill(c2w_src12_host, a.c2w);
+    pnr_pose_fill(w2c_tgt12_host, a.w2c);
     a.width_src = width_src; a.width_tgt = width_tgt; a.height_tgt = height_tgt; a.npix_src = (int64_t)width_src * height_src;
     a.umax = (float)width_tgt - 0.5f; a.vmax = (float)height_tgt - 0.5f; a.tol_abs = tol_abs; a.tol_rel = tol_rel;
     a.pix = pix; a.R = n; a.depth_src = depth_src; a.depth_tgt = depth_tgt;

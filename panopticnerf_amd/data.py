@@ -13,10 +13,10 @@ import ctypes
 import torch
 
 from . import _lib, ops
+from .camera import _Camera, _rows3
 
 MODES = ("pooled", "frame")
 _REC = ctypes.sizeof(_lib.Frame)
-_MODELS = {"pinhole": _lib.CAMERA_PINHOLE, "fisheye": _lib.CAMERA_FISHEYE, "equirect": _lib.CAMERA_EQUIRECT}      # pnr_frame.model
 
 
 def _image(t, what, H, W, tail=()):
@@ -77,19 +77,14 @@ class FrameSet:
         pseudo_label / instance_label (H, W) integers in the int16 range, -1 = unlabelled.  A fisheye frame draws from
         camera.valid_pix() (lens and user mask), a pinhole or equirect frame from every pixel.  Returns the frame's index.  The record, cum
         and n_frames are updated by stream-ordered copies: launches enqueued later (graph replays included) see the frame."""
-        model = getattr(camera, "model", None)
-        if model not in _MODELS:
+        if not isinstance(camera, _Camera):
             raise TypeError("FrameSet.add: camera must be a camera.Pinhole or camera.Fisheye (or camera.Equirect)")
         if len(self.frames) >= self.capacity:
             raise RuntimeError("FrameSet.add: the set is full (capacity = %d frames)" % self.capacity)
         H, W = camera.height, camera.width
         if H * W >= 2 ** 31:
             raise ValueError("FrameSet.add: pixel indices are int32")
-        pose = torch.as_tensor(c2w, dtype=torch.float32).reshape(-1)
-        if pose.numel() == 16:
-            pose = pose[:12]
-        if pose.numel() != 12:
-            raise ValueError("FrameSet.add: c2w must be a 3x4 (or 4x4) matrix")
+        pose = _rows3(torch.as_tensor(c2w, dtype=torch.float32), "FrameSet.add: c2w must be a 3x4 (or 4x4) matrix")
         rgb = _image(rgb, "rgb", H, W, (3,))
         if rgb.dtype != torch.uint8:
             if not rgb.dtype.is_floating_point:
@@ -118,16 +113,13 @@ class FrameSet:
         dev = self.device
         store = {"rgb": torch.uint8, "depth": torch.float32, "sem": torch.int16, "inst": torch.int16}
         imgs = {k: v.to(dev, store[k]).contiguous() for k, v in imgs.items()}
-        pix = None
-        if model == "fisheye":
-            pix = camera.valid_pix(dev)
-            if pix.numel() == H * W:
-                pix = None
+        pix = None if camera.all_valid else camera.valid_pix(dev)
+        if pix is not None and pix.numel() == H * W:
+            pix = None
         n_valid = H * W if pix is None else int(pix.numel())
-        cam = list(camera.intr if model == "pinhole" else camera.cam)
-        cam += [0.0] * (7 - len(cam))
+        cam = list(camera.params) + [0.0] * (7 - len(camera.params))
         ptr = lambda t: 0 if t is None else t.data_ptr()
-        rec = _lib.Frame(_MODELS[model], W, H, (ctypes.c_float * 7)(*cam),
+        rec = _lib.Frame(camera.word, W, H, (ctypes.c_float * 7)(*cam),
                          (ctypes.c_float * 12)(*pose.tolist()), float(near), float(far), n_valid, ptr(pix), ptr(imgs["rgb"]),
                          ptr(imgs.get("depth")), ptr(imgs.get("sem")), ptr(imgs.get("inst")))
         i = len(self.frames)

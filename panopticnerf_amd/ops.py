@@ -54,29 +54,38 @@ def _on_device(fn):
     return wrapper
 
 
+def _host_floats(v, n, what):
+    vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float32).reshape(-1).tolist()]
+    if len(vals) != n:
+        raise ValueError(f"{what}: expected {n} values, got {len(vals)}")
+    return (ctypes.c_float * n)(*vals)
+
+
+def _gen_rays(name, cam_h, c2w_h, width, height, near, far, pix, device, want_valid=None, ask_first=False):
+    """The body of the three gen_rays*: entry point pnr_<name>.  want_valid: None where the entry point takes no `valid` buffer.
+    Returns rays (R,8) and valid (R) uint8 or None."""
+    pix = _chk(pix, "pix", torch.int32)
+    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError(f"{name}: expected a GPU device (the HIP path has no CPU fallback)")
+    R = pix.numel() if pix is not None else int(width) * int(height)
+    fn, head = getattr(_lib.load(), "pnr_" + name), (cam_h, c2w_h, int(width), int(height), float(near), float(far))
+    if ask_first:       # every refusal of the entry point comes before its first use of the device: asked first, with no memory allocated
+        _lib.check(fn(*head, None, 0, None, *(() if want_valid is None else (None,)), None), "pnr_" + name)
+    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
+    valid = torch.empty((R,), device=dev, dtype=torch.uint8) if want_valid else None
+    with torch.cuda.device(dev):
+        _lib.check(fn(*head, _p(pix), R, _p(rays), *(() if want_valid is None else (_p(valid),)), _stream()), "pnr_" + name)
+    return rays, valid
+
+
 def gen_rays(intr, c2w, width, height, near, far, pix=None, device=None):
     """Pinhole ray generation on the GPU (pnr_gen_rays).  intr: fx, fy, cx, cy; c2w: 3x4 camera-to-world
     (host values); pix: int32 GPU tensor of linear pixel indices or None (whole frame).  Returns rays (R,8).  d is NOT normalised
     (z_cam = 1), so depth_* of a render on these rays is z-depth; gen_rays_fisheye's rays are unit length and its depth is range."""
     intr_h = (ctypes.c_float * 4)(*[float(v) for v in torch.as_tensor(intr, dtype=torch.float32).reshape(4).tolist()])
     c2w_h = (ctypes.c_float * 12)(*[float(v) for v in torch.as_tensor(c2w, dtype=torch.float32).reshape(12).tolist()])
-    pix = _chk(pix, "pix", torch.int32)
-    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("gen_rays: expected a GPU device (the HIP path has no CPU fallback)")
-    R = pix.numel() if pix is not None else int(width) * int(height)
-    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().pnr_gen_rays(intr_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
-                                            _p(rays), _stream()), "pnr_gen_rays")
-    return rays
-
-
-def _host_floats(v, n, what):
-    vals = [float(x) for x in torch.as_tensor(v, dtype=torch.float32).reshape(-1).tolist()]
-    if len(vals) != n:
-        raise ValueError(f"{what}: expected {n} values, got {len(vals)}")
-    return (ctypes.c_float * n)(*vals)
+    return _gen_rays("gen_rays", intr_h, c2w_h, width, height, near, far, pix, device)[0]
 
 
 def gen_rays_fisheye(cam, c2w, width, height, near, far, pix=None, device=None, want_valid=True):
@@ -85,17 +94,7 @@ def gen_rays_fisheye(cam, c2w, width, height, near, far, pix=None, device=None, 
     want_valid=False).  Unlike gen_rays' directions (z_cam = 1: depth along them is z-depth) these are UNIT LENGTH, so
     depth_* of a render on them is range along the ray.  A pixel outside the lens gets o, d = 0, near = far = 0, valid = 0."""
     cam_h, c2w_h = _host_floats(cam, 7, "gen_rays_fisheye: cam"), _host_floats(c2w, 12, "gen_rays_fisheye: c2w")
-    pix = _chk(pix, "pix", torch.int32)
-    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("gen_rays_fisheye: expected a GPU device (the HIP path has no CPU fallback)")
-    R = pix.numel() if pix is not None else int(width) * int(height)
-    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
-    valid = torch.empty((R,), device=dev, dtype=torch.uint8) if want_valid else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().pnr_gen_rays_fisheye(cam_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
-                                                    _p(rays), _p(valid), _stream()), "pnr_gen_rays_fisheye")
-    return rays, valid
+    return _gen_rays("gen_rays_fisheye", cam_h, c2w_h, width, height, near, far, pix, device, want_valid=bool(want_valid))
 
 
 def gen_rays_equirect(cam, c2w, width, height, near, far, pix=None, device=None):
@@ -103,19 +102,7 @@ def gen_rays_equirect(cam, c2w, width, height, near, far, pix=None, device=None)
     lat0, dlat in half-turns (camera.Equirect makes them from degrees); c2w, pix, device as gen_rays.  Returns rays (R,8):
     UNIT-LENGTH directions like gen_rays_fisheye's (depth_* of a render on them is range), every pixel valid."""
     cam_h, c2w_h = _host_floats(cam, 4, "gen_rays_equirect: cam"), _host_floats(c2w, 12, "gen_rays_equirect: c2w")
-    pix = _chk(pix, "pix", torch.int32)
-    dev = pix.device if pix is not None else torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("gen_rays_equirect: expected a GPU device (the HIP path has no CPU fallback)")
-    R = pix.numel() if pix is not None else int(width) * int(height)
-    # every refusal of the entry point comes before its first use of the device: asked first, with no memory allocated
-    _lib.check(_lib.load().pnr_gen_rays_equirect(cam_h, c2w_h, int(width), int(height), float(near), float(far), None, 0, None, None),
-               "pnr_gen_rays_equirect")
-    rays = torch.empty((R, 8), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().pnr_gen_rays_equirect(cam_h, c2w_h, int(width), int(height), float(near), float(far), _p(pix), R,
-                                                     _p(rays), _stream()), "pnr_gen_rays_equirect")
-    return rays
+    return _gen_rays("gen_rays_equirect", cam_h, c2w_h, width, height, near, far, pix, device, ask_first=True)[0]
 
 
 _MODEL_WORDS = {"pinhole": (_lib.CAMERA_PINHOLE, 4), "fisheye": (_lib.CAMERA_FISHEYE, 7), "equirect": (_lib.CAMERA_EQUIRECT, 4)}
@@ -146,14 +133,9 @@ def project_points(model, cam, w2c, width, height, points):
 
 def _camera_words(cam, what):
     """(model word, host floats, width, height) of a camera.Pinhole / camera.Fisheye / camera.Equirect"""
-    model = getattr(cam, "model", None)
-    if model == "pinhole":
-        return _lib.CAMERA_PINHOLE, _host_floats(cam.intr, 4, what), int(cam.width), int(cam.height)
-    if model == "fisheye":
-        return _lib.CAMERA_FISHEYE, _host_floats(cam.cam, 7, what), int(cam.width), int(cam.height)
-    if model == "equirect":
-        return _lib.CAMERA_EQUIRECT, _host_floats(cam.cam, 4, what), int(cam.width), int(cam.height)
-    raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye (or camera.Equirect), not %r" % (what, cam))
+    if not all(hasattr(cam, k) for k in ("word", "params", "width", "height")):
+        raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye (or camera.Equirect), not %r" % (what, cam))
+    return cam.word, _host_floats(cam.params, len(cam.params), what), int(cam.width), int(cam.height)
 
 
 def _image(t, width, height, name):

@@ -22,7 +22,7 @@ import torch
 import _camera_ref as cr
 from oracle import c_oracle as co
 from oracle import torch_oracle as to
-from panopticnerf_amd import Fisheye, Pinhole, make_network, make_renderer, ops, synthetic
+from panopticnerf_amd import Equirect, Fisheye, FrameSet, Pinhole, make_network, make_renderer, ops, synthetic
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from make_golden import config_case  # noqa: E402
@@ -431,3 +431,58 @@ def test_camera_ops_replay_from_a_captured_graph(dev):
     for a, b in zip(got, ref):
         assert torch.equal(a, b)
     assert not torch.equal(got[0], chain(pix_a)[0])
+
+
+# ------------------------------------------------------------------------------------------- every caller of pnr_camera_ray
+def _rotation(axis, angle):
+    """a general rotation (Rodrigues, float64)"""
+    k = np.asarray(axis, dtype=np.float64)
+    k = k / np.linalg.norm(k)
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+
+
+_SMALL = {   # 13 x 7: odd, no multiple of the wave size; the fisheye's rim (xi > 1: r^2 = 1/(xi^2 - 1) = 0.26) leaves the corners dark
+    "pinhole": lambda: Pinhole(11.0, 10.5, 6.2, 3.1, 13, 7),
+    "fisheye": lambda: Fisheye(2.2, 0.01, 0.001, 8.0, 7.5, 6.2, 3.1, 13, 7),
+    "equirect": lambda: Equirect(13, 7, lon=(-100.0, 140.0), lat=(60.0, -50.0)),
+}
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("model", list(_SMALL))
+def test_every_ray_maker_writes_the_rays_of_camera_rays_bit_for_bit(dev, model):
+    """The whole frame of Camera.rays against the pixel list, k_sample_batch and the rays k_reproject lifts: bitwise only."""
+    from panopticnerf_amd import camera as camera_mod
+    cam = _SMALL[model]()
+    n = cam.width * cam.height
+    c2w = torch.tensor(np.concatenate([_rotation((1.0, 2.0, 3.0), 0.7), [[0.4], [-1.3], [2.1]]], 1), dtype=torch.float32)
+    full = cam.rays(c2w, 0.5, 20.0, device=dev)
+    assert tuple(full.shape) == (n, 8)
+    lens = torch.zeros(n, dtype=torch.bool, device=dev)
+    lens[cam.valid_pix(dev).long()] = True
+    assert bool(lens.all()) == (model != "fisheye") and bool(lens.any())
+    # 1: the pixel list
+    listed = cam.rays(c2w, 0.5, 20.0, pix=torch.arange(n, dtype=torch.int32, device=dev))
+    assert torch.equal(_bits(listed), _bits(full))
+    # 2: a one-frame FrameSet
+    frames = FrameSet(dev, capacity=1)
+    frames.add(cam, c2w, 0.5, 20.0, torch.zeros((cam.height, cam.width, 3), dtype=torch.uint8))
+    batch = frames.sample(512)
+    pix = batch["pix"].long()
+    assert bool(lens[pix].all()) and pix.unique().numel() > n // 4
+    assert torch.equal(_bits(batch["rays"][0]), _bits(full[pix]))
+    # 3: reproject with depth 1 lifts o + d; the target is the same camera, moved and turned
+    c2w_t = torch.tensor(np.concatenate([_rotation((0.0, 1.0, 0.2), 0.5) @ _rotation((1.0, 2.0, 3.0), 0.7), [[0.5], [-1.2], [2.0]]], 1),
+                         dtype=torch.float32)
+    w2c_t = camera_mod.invert_pose(c2w_t)
+    res = ops.reproject(cam, c2w, torch.ones((cam.height, cam.width), device=dev), cam, w2c_t, want=("match", "uv"))
+    uv, _, valid = cam.project(full[:, :3] + full[:, 3:6], w2c_t)
+    match = res["match"]
+    assert torch.equal(match[~lens], torch.full_like(match[~lens], -1)) and not bool(res["uv"][~lens].any())
+    assert torch.equal(_bits(res["uv"][lens]), _bits(uv[lens]))
+    assert torch.equal(match[lens] >= 0, valid[lens]) and torch.equal(match[lens] == -2, ~valid[lens])
+    assert bool(valid[lens].any()) and not bool(valid[lens].all())          # both codes occur

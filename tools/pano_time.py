@@ -54,8 +54,8 @@ fish = Fisheye(sy.FISHEYE_XI, sy.FISHEYE_K1, sy.FISHEYE_K2, sy.FISHEYE_GAMMA1, s
 ca, cb = pose(0.0, 0.0, (0.0, 1.55, 0.0)), pose(0.05, -0.03, (0.3, 1.5, 0.4))
 dp, df = sphere_depth(pano, ca), sphere_depth(fish, cb)
 print("%d x %d panorama, %d x %d fisheye" % (pano.width, pano.height, fish.width, fish.height))
-timed("k_gen_rays_equirect, whole frame (991,232 rays)", lambda: pano.rays(ca, 0.5, 100.0, device=dev))
-timed("k_gen_rays_fisheye, whole frame (1,960,000 rays)", lambda: fish.rays(cb, 0.5, 100.0, device=dev))
+timed("k_gen_rays<equirect>, whole frame (991,232 rays)", lambda: pano.rays(ca, 0.5, 100.0, device=dev))
+timed("k_gen_rays<fisheye>, whole frame (1,960,000 rays)", lambda: fish.rays(cb, 0.5, 100.0, device=dev))
 out_p = {"match": torch.empty(pano.width * pano.height, dtype=torch.int32, device=dev)}
 out_f = {"match": torch.empty(fish.width * fish.height, dtype=torch.int32, device=dev)}
 wb, wa = camera.invert_pose(cb), camera.invert_pose(ca)
