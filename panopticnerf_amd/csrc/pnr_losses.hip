@@ -77,7 +77,9 @@ __device__ __forceinline__ float ce_row(const float* logit, int n_cls, int label
     den = group_sum(den);
     if (g)
         for (int c = l; c < n_cls; c += LS_GROUP) g[c] = scale * (expf(logit[c] - mx) / den - (c == label ? 1.0f : 0.0f));
-    return (mx + logf(den)) - logit[label];
+    // log den first, then the exact-difference mx - x_label: (mx + logf(den)) - x_label rounds at the size of mx, which made the
+    // value depend on a common shift of the row (|mx| 2^-25: 3e-5 at logits around 1000)
+    return logf(den) + (mx - logit[label]);
 }
 
 __global__ __launch_bounds__(LS_THREADS) void k_loss_maps(LossArgs a)
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_ce3d(Ce3dArgs a)
                 mx = fmaxf(mx, v);
                 if (c == lab) at = v;
             }
-            ce = (mx + logf(den)) - at;
+            ce = logf(den) + (mx - at);             // as in ce_row: invariant under a common shift of the logits
             cnt = 1.0f;
         }
     }

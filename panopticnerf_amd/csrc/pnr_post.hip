@@ -1,8 +1,8 @@
 // Label-map post-processing and evaluator counters (the step after the path in the reference's
 // `run.py evaluate` -- argmax semantic, instance assignment, panoptic merge, PSNR / mIoU).  The reference's evaluator
 // is not in the mount; conventions below are this build's and are listed in DESIGN.md 8:
-//   semantic label = argmax_c of the composited semantic map (lowest index on ties, -1 if the row is all -inf / NaN-free
-//                    maps never are);
+//   semantic label = argmax_c of the composited semantic map (lowest index on ties; a NaN reads as -inf, and a row that is
+//                    all -inf or all NaN gives index 0, as include/pnr.h and the oracle say);
 //   instance label = argmax_k of the composited instance map where the semantic class is a "thing" (is_thing[c] != 0),
 //                    -1 on "stuff";
 //   panoptic id    = class * 1000 + instance on things, class on stuff (the KITTI-360 / Cityscapes id convention).

@@ -1025,8 +1025,10 @@ def losses(weights, maps, targets, n_sem=0, n_inst=0, depth_l2=False, fix_eps=1e
     (pnr_losses; SURVEY 8f-1).  weights: dict over rgb/depth/semantic/fix_semantic/instance/fix_instance;
     maps: dict of (R,·) fp32 GPU tensors (any subset); targets: rgb (R,3), depth (R), semantic (R) int32,
     instance (R) int32.  Returns (losses (8,) device tensor: the six means, total, 0; dict of gradients)."""
-    lib = _lib.load()
     m = {k: _chk(v.detach().contiguous(), k) for k, v in maps.items() if k in _LOSS_KEYS and v is not None and v.numel()}
+    if not m:
+        raise ValueError("ops.losses: no usable map: `maps` holds none of %s with at least one ray (R = 0?)" % ", ".join(_LOSS_KEYS))
+    lib = _lib.load()
     any_map = next(iter(m.values()))
     dev, R = any_map.device, any_map.shape[0]
     t_rgb, t_depth = _chk(targets.get("rgb"), "rgb_gt"), _chk(targets.get("depth"), "depth_gt")

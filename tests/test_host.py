@@ -589,3 +589,13 @@ def test_train_eval_switch_drops_the_packed_images():
     net._packed[("fwd", 0, "cuda:0", "bf16", 0)] = (net._version(0),) + tuple(hit[1:])
     net.train()
     assert net._packed[("fwd", 0, "cuda:0", "bf16", 0)][0] is None
+
+
+def test_losses_refuses_a_call_without_a_usable_map_by_name():
+    """ops.losses takes its ray count and device from the first usable map; with none (no map, only unknown keys, only None,
+    or R = 0) it used to die of a bare StopIteration.  It says what is wrong instead, before anything reaches the GPU."""
+    from panopticnerf_amd import ops
+    tg = {"rgb": torch.zeros(0, 3), "semantic": torch.zeros(0, dtype=torch.int32)}
+    for maps in ({}, {"rgb": None}, {"weights": torch.zeros(4, 8)}, {"rgb": torch.zeros(0, 3), "semantic": torch.zeros(0, 5)}):
+        with pytest.raises(ValueError, match="no usable map"):
+            ops.losses({"rgb": 1.0}, maps, tg, 5, 0)
