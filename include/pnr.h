@@ -24,6 +24,7 @@
  *   pnr_sample_pdf_labels   a7 + a8 of the fine level in one launch       (8a rows a7, a8)
  *   pnr_*_rng, pnr_rng_begin / _fill   the above with torch.rand / torch.randn drawn in the kernel (8a rows a3, a6, a7, a9)
  *   pnr_sample_batch    the dataset's ray batches: pixel sampling, rays and targets of posed frames
+ *   pnr_census, pnr_sgm_aggregate / _select, pnr_disparity_depth   the dataset's SGM stereo depth
  *
  * Conventions:
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
@@ -544,6 +545,53 @@ int pnr_splat_resolve(const int64_t* zbuf, int64_t n_pix, float* depth, int32_t*
 int64_t pnr_depth_metrics_workspace_bytes(int64_t n);
 int pnr_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int64_t n, float d_min, float d_max,
                       double* sums, int64_t* counts, void* workspace, void* stream);
+
+/* ---- stereo matching (csrc/pnr_stereo.hip; DESIGN.md 8 "Stereo depth"): a rectified 8-bit pair -> disparity in sixteenths of a
+ * pixel -> depth, the producer of the stereo depth that the loss wrapper and the frame table consume.  The reference's matcher
+ * is not in the mount: the rule is this build's and unpinned.  Everything is integer except step 6 (tests/_sgm_ref.py restates
+ * the rule twice, bit for bit).
+ *
+ * Inputs: left, right (H, W) uint8, rectified (a match of left pixel x lies at right pixel x - d, d >= 0).  D = max_disp, a
+ * multiple of 16 in 16 .. 256.  0 < P1 <= P2 <= 192, so one path cost, at most 63 + P2, fits a byte.  paths is 4 or 8.
+ * uniqueness in 0 .. 99.  lr_tol >= 0, or -1 for "no left-right check".  THE CONTRACT:
+ *   1. CENSUS.  The window is 9 wide x 7 high with a replicated border (row and column indices clamped into the image).  The 62
+ *      neighbours are visited in row-major order from the top-left, skipping the centre: w = (w << 1) | (neighbour < centre).
+ *      The output is (H, W) 64-bit words with bits 62 and 63 zero.
+ *   2. MATCHING COST.  C(y, x, d) = popcount(cl[y, x] ^ cr[y, x - d]) for x - d >= 0, otherwise C = 63, one more than any Hamming
+ *      distance can be.
+ *   3. PATH AGGREGATION.  The directions r = (dy, dx) in this order: (0, +1), (0, -1), (+1, 0), (-1, 0); then, for 8 paths,
+ *      (+1, +1), (+1, -1), (-1, +1), (-1, -1).  Where p - r is outside the image, L_r(p, d) = C(p, d).  Otherwise
+ *        L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + P1, L_r(p-r, d+1) + P1, m + P2) - m,   m = min_k L_r(p-r, k).
+ *      Terms with d - 1 or d + 1 outside [0, D) are absent.  S = sum_r L_r is an (H, W, D) uint16 volume with d fastest, at most
+ *      8 (63 + 192) = 2040.  S is an OUTPUT of the entry point and part of the contract.
+ *   4. SELECTION.  d* = argmin_d S(p, d), the lowest d on ties; best = S(p, d*).  Right disparity:
+ *      dR(y, xr) = argmin_k S(y, xr + k, k) over k < D, xr + k < W, the lowest k on ties.  The codes are tested in this order and
+ *      the first that applies wins:
+ *        -1 when x - d* < 0;
+ *        -2 when second (100 - uniqueness) < best 100, where second = min S(p, k) over |k - d*| > 1 (no such k: the test passes);
+ *        -3 when lr_tol >= 0 and |dR(y, x - d*) - d*| > lr_tol.
+ *   5. SUB-PIXEL, in sixteenths.  The offset is 0 when d* is 0 or D - 1, or when den = S- + S+ - 2 best is 0, with S- = S(p, d* - 1)
+ *      and S+ = S(p, d* + 1).  Otherwise num = 8 (S- - S+) and offset = floor((2 num + den) / (2 den)), floored toward -inf; it
+ *      lies in -8 .. 8.  d16 (H, W) int16 = 16 d* + offset when valid, else the code.
+ *   6. DEPTH.  disp = d16 * 0.0625f (exact); depth = fb / disp with fb = fx * baseline, one float32 multiply made on the host, and
+ *      one correctly rounded float32 division.  depth = 0 where d16 <= 0 or where the quotient is not in [d_min, d_max]: the
+ *      "no depth" of the frame table.
+ *
+ * Buffers (device, caller-owned): census images int64 (H, W); S uint16 (H, W, D), 32-byte aligned, NOT required to be zeroed --
+ * the first direction stores, the others add, one launch per direction on `stream`; workspace: pnr_sgm_workspace_bytes bytes
+ * (0 in this build -- nothing is staged --, so it may be NULL; -1 for arguments pnr_sgm_aggregate refuses).  pnr_sgm_select:
+ * disp_right (H, W) int16 is an output (dR) and the left-right check's table; it may be NULL only when lr_tol < 0.
+ * pnr_disparity_depth: d16 (n) int16, depth (n) float32; fb positive and finite, 0 < d_min <= d_max (d_max may be +inf); n == 0:
+ * PNR_OK.  All capture-safe on the one stream.  PNR_EINVAL before any launch: width or height < 1 or more than 2^31 - 1 pixels,
+ * max_disp not a multiple of 16 in 16 .. 256, P1 <= 0, P1 > P2, P2 > 192, paths not 4 or 8, uniqueness outside 0 .. 99,
+ * lr_tol < -1, a null pointer (but workspace, and disp_right as above), a misaligned S, n < 0, a bad fb or range. */
+int pnr_census(const uint8_t* img, int width, int height, int64_t* out, void* stream);
+int64_t pnr_sgm_workspace_bytes(int width, int height, int max_disp, int paths);
+int pnr_sgm_aggregate(const int64_t* census_l, const int64_t* census_r, int width, int height, int max_disp, int p1, int p2,
+                      int paths, uint16_t* S, void* workspace, void* stream);
+int pnr_sgm_select(const uint16_t* S, int width, int height, int max_disp, int uniqueness, int lr_tol, int16_t* d16,
+                   int16_t* disp_right, void* stream);
+int pnr_disparity_depth(const int16_t* d16, int64_t n, float fb, float d_min, float d_max, float* depth, void* stream);
 
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).

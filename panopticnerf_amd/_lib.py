@@ -119,6 +119,11 @@ SIGNATURES = {
     "pnr_splat_resolve": (c_int, [c_f, c_i64, c_f, c_f, c_f]),
     "pnr_depth_metrics_workspace_bytes": (c_i64, [c_i64]),
     "pnr_depth_metrics": (c_int, [c_f, c_f, c_f, c_i64, ctypes.c_float, ctypes.c_float, c_f, c_f, c_f, c_f]),
+    "pnr_census": (c_int, [c_f, c_int, c_int, c_f, c_f]),
+    "pnr_sgm_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "pnr_sgm_aggregate": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_f]),
+    "pnr_sgm_select": (c_int, [c_f, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_f]),
+    "pnr_disparity_depth": (c_int, [c_f, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

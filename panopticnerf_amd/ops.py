@@ -338,6 +338,145 @@ def depth_metrics(pred, gt, mask=None, d_range=DEPTH_RANGE, sums=None, counts=No
     return sums, counts
 
 
+def _stereo_arg(t, name, dtype, shape=None, ndim=None):
+    """A tensor argument of the stereo ops: type, dtype and shape, refused by name on any device (_stereo_gpu refuses a CPU
+    tensor, after the parameters)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: expected a GPU tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise TypeError("%s: expected %s, got %s" % (name, dtype, t.dtype))
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError("%s: expected %d dimensions, got shape %s" % (name, ndim, tuple(t.shape)))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if t.numel() == 0:
+        raise ValueError("%s: empty tensor" % name)
+    return t
+
+
+def _stereo_gpu(what, **tensors):
+    """device and contiguity of every tensor given (None: absent); all on the first one's device"""
+    ref = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        _chk(t, "%s: %s" % (what, name), t.dtype)
+        if ref is None:
+            ref = t
+        elif t.device != ref.device:
+            raise ValueError("%s: %s is on %s, not on %s" % (what, name, t.device, ref.device))
+
+
+def _stereo_disp(what, max_disp):
+    max_disp = int(max_disp)
+    if max_disp < 16 or max_disp > 256 or max_disp % 16:
+        raise ValueError("%s: max_disp must be a multiple of 16 in 16 .. 256 (got %d)" % (what, max_disp))
+    return max_disp
+
+
+def sgm_aggregate_params(what, max_disp, p1, p2, paths):
+    """the parameters of pnr_sgm_aggregate as integers, or the refusal by name (`what`: the caller's name)"""
+    max_disp = _stereo_disp(what, max_disp)
+    p1, p2, paths = int(p1), int(p2), int(paths)
+    if not (0 < p1 <= p2 <= 192):
+        raise ValueError("%s: p1 and p2 must satisfy 0 < p1 <= p2 <= 192 (got %d, %d)" % (what, p1, p2))
+    if paths not in (4, 8):
+        raise ValueError("%s: paths must be 4 or 8 (got %d)" % (what, paths))
+    return max_disp, p1, p2, paths
+
+
+def sgm_select_params(what, uniqueness, lr_tol):
+    """the parameters of pnr_sgm_select as integers, or the refusal by name"""
+    uniqueness, lr_tol = int(uniqueness), int(lr_tol)
+    if not (0 <= uniqueness <= 99):
+        raise ValueError("%s: uniqueness must lie in 0 .. 99 (got %d)" % (what, uniqueness))
+    if lr_tol < -1:
+        raise ValueError("%s: lr_tol must be >= 0, or -1 for no left-right check (got %d)" % (what, lr_tol))
+    return uniqueness, lr_tol
+
+
+@_on_device
+def census(img, out=None):
+    """Census words of an (H, W) uint8 image (pnr_census; include/pnr.h "stereo matching" step 1): (H, W) int64, the 62
+    comparisons of the 9 x 7 window with a replicated border."""
+    img = _stereo_arg(img, "census: img", torch.uint8, ndim=2)
+    if out is not None:
+        out = _stereo_arg(out, "census: out", torch.int64, shape=img.shape)
+    _stereo_gpu("census", img=img, out=out)
+    if out is None:
+        out = torch.empty(tuple(img.shape), device=img.device, dtype=torch.int64)
+    H, W = img.shape
+    _lib.check(_lib.load().pnr_census(_p(img), W, H, _p(out), _stream()), "pnr_census")
+    return out
+
+
+@_on_device
+def sgm_aggregate(census_l, census_r, max_disp=128, p1=10, p2=120, paths=8, out=None):
+    """The summed path-cost volume S (H, W, max_disp) of two census images (pnr_sgm_aggregate; the rule's steps 2 and 3): the
+    header's uint16 volume held as an int16 tensor (a sum is at most 2040).  out: a caller-owned volume (it need not be
+    zeroed)."""
+    census_l = _stereo_arg(census_l, "sgm_aggregate: census_l", torch.int64, ndim=2)
+    census_r = _stereo_arg(census_r, "sgm_aggregate: census_r", torch.int64, shape=census_l.shape)
+    max_disp, p1, p2, paths = sgm_aggregate_params("sgm_aggregate", max_disp, p1, p2, paths)
+    H, W = census_l.shape
+    if out is not None:
+        out = _stereo_arg(out, "sgm_aggregate: out", torch.int16, shape=(H, W, max_disp))
+    _stereo_gpu("sgm_aggregate", census_l=census_l, census_r=census_r, out=out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((H, W, max_disp), device=census_l.device, dtype=torch.int16)
+    nbytes = _size_or_raise(lib.pnr_sgm_workspace_bytes(W, H, max_disp, paths), "pnr_sgm_workspace_bytes")
+    ws = torch.empty((nbytes,), device=census_l.device, dtype=torch.uint8) if nbytes else None
+    _lib.check(lib.pnr_sgm_aggregate(_p(census_l), _p(census_r), W, H, max_disp, p1, p2, paths, _p(out), _p(ws), _stream()),
+               "pnr_sgm_aggregate")
+    return out
+
+
+@_on_device
+def sgm_select(S, uniqueness=5, lr_tol=1, out=None, disp_right=None):
+    """(d16, disp_right) of a volume sgm_aggregate made (pnr_sgm_select; the rule's steps 4 and 5).  d16 (H, W) int16:
+    the disparity in sixteenths of a pixel, or -1 (no right pixel), -2 (not unique), -3 (left-right check).  disp_right
+    (H, W) int16: the right image's disparity; None with lr_tol = -1 (no left-right check) unless a tensor is given."""
+    S = _stereo_arg(S, "sgm_select: S", torch.int16, ndim=3)
+    H, W, D = S.shape
+    _stereo_disp("sgm_select (the last dimension of S)", D)
+    uniqueness, lr_tol = sgm_select_params("sgm_select", uniqueness, lr_tol)
+    if out is not None:
+        out = _stereo_arg(out, "sgm_select: out", torch.int16, shape=(H, W))
+    if disp_right is not None:
+        disp_right = _stereo_arg(disp_right, "sgm_select: disp_right", torch.int16, shape=(H, W))
+    _stereo_gpu("sgm_select", S=S, out=out, disp_right=disp_right)
+    if out is None:
+        out = torch.empty((H, W), device=S.device, dtype=torch.int16)
+    if disp_right is None and lr_tol >= 0:
+        disp_right = torch.empty((H, W), device=S.device, dtype=torch.int16)
+    _lib.check(_lib.load().pnr_sgm_select(_p(S), W, H, D, uniqueness, lr_tol, _p(out), _p(disp_right), _stream()), "pnr_sgm_select")
+    return out, disp_right
+
+
+@_on_device
+def disparity_depth(d16, fb, d_range=(1e-3, float("inf")), out=None):
+    """depth = fb / (d16 / 16) in float32 (pnr_disparity_depth; the rule's step 6): 0 where d16 <= 0 or the quotient is
+    outside d_range = (d_min, d_max).  fb = fx * baseline, a float32 value."""
+    d16 = _stereo_arg(d16, "disparity_depth: d16", torch.int16)
+    fb = float(fb)
+    if not (0.0 < fb < float("inf")):
+        raise ValueError("disparity_depth: fb = fx * baseline must be positive and finite (got %r)" % fb)
+    try:
+        d_min, d_max = (float(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("disparity_depth: d_range must be (d_min, d_max)") from None
+    if not (0.0 < d_min <= d_max):
+        raise ValueError("disparity_depth: d_range must satisfy 0 < d_min <= d_max (d_max may be inf)")
+    if out is not None:
+        out = _stereo_arg(out, "disparity_depth: out", torch.float32, shape=d16.shape)
+    _stereo_gpu("disparity_depth", d16=d16, out=out)
+    if out is None:
+        out = torch.empty(tuple(d16.shape), device=d16.device, dtype=torch.float32)
+    _lib.check(_lib.load().pnr_disparity_depth(_p(d16), d16.numel(), fb, d_min, d_max, _p(out), _stream()), "pnr_disparity_depth")
+    return out
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global

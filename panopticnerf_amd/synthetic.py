@@ -155,3 +155,48 @@ def trained_like_(net, sigma_bias=0.03, seed=0):
             if n is not None:
                 n.alpha_linear.bias.fill_(sigma_bias)
     return net
+
+
+STEREO_LAYERS = ((5, None), (17, (0.25, 0.75, 0.3, 0.7)))      # background at disparity 5, a central box at 17
+
+
+def stereo_pair(height, width, layers=STEREO_LAYERS, seed=0, device=None):
+    """A random-dot stereogram with integer-disparity layers, for tests and examples of `stereo`: a rectified pair whose true
+    disparity is known.  layers: (disparity, rect) from back to front, rect = (top, bottom, left, right) as fractions of the
+    LEFT image, None = the whole image; disparities must not decrease (a nearer layer hides a farther one).  The left image
+    is uniform random bytes; a left pixel at x of a layer with disparity d is seen in the right image at x - d, nearer layers
+    painted last; right pixels that no left pixel reaches keep random bytes of their own.  Made with numpy, seeded.  Returns
+    (left, right, disparity, visible): (H, W) uint8 images, the left view's disparity as int32 and the bool mask of left
+    pixels that are visible in both images -- CPU tensors, as this module's, or on `device`."""
+    import numpy as np
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError("stereo_pair: height and width must be >= 1")
+    layers = tuple(layers)
+    if not layers or layers[0][1] is not None:
+        raise ValueError("stereo_pair: the first layer must cover the image (rect None)")
+    rng = np.random.default_rng(int(seed))
+    left = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
+    right = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
+    disp = np.zeros((H, W), dtype=np.int32)
+    last = None
+    for d, rect in layers:
+        d = int(d)
+        if d < 0 or (last is not None and d < last):
+            raise ValueError("stereo_pair: disparities must be >= 0 and must not decrease from back to front")
+        last = d
+        if rect is None:
+            disp[:] = d
+        else:
+            t, b, l, r = rect
+            disp[int(round(t * H)):int(round(b * H)), int(round(l * W)):int(round(r * W))] = d
+    owner = np.full((H, W), -1, dtype=np.int64)             # the left column that each right pixel shows
+    ys, xs = np.mgrid[0:H, 0:W]
+    for d in sorted(set(int(v) for v in disp.reshape(-1))):
+        sel = (disp == d) & (xs - d >= 0)
+        right[ys[sel], xs[sel] - d] = left[ys[sel], xs[sel]]
+        owner[ys[sel], xs[sel] - d] = xs[sel]
+    xr = xs - disp
+    visible = (xr >= 0) & (owner[ys, np.clip(xr, 0, W - 1)] == xs)
+    out = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (left, right, disp, visible))
+    return out if device is None else tuple(t.to(device) for t in out)
