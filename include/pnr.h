@@ -270,12 +270,25 @@ int pnr_mlp_wgrad(const pnr_mlp_desc* desc, const void* acts, const void* dys, i
  * Linear and direction, deterministic fixed-order reductions).  Parameters are NOT packed: params_dev is a pnr_mlp_params_host
  * in host memory whose pointers are DEVICE pointers to the dense (out,in) row-major fp32 parameters (the nn.Parameter tensors
  * themselves), as for pnr_mlp_pack_device.  head_depth 1 | 2 and head_tap 0 | 1 are supported; desc.precision is ignored.
- *   acts      : fp32, pnr_mlp_fp32_acts_floats(desc, n_rays * n_samples) floats -- gamma(x), gamma(d), every layer's output,
- *               dense [S][width] (opaque to callers);
+ *   acts      : fp32, pnr_mlp_fp32_acts_floats(desc, n_rays * n_samples) floats, layout below;
  *   raw       : as pnr_mlp_forward (any strides);   d_raw: channel-major (4+n_sem+n_inst, >= S) fp32, channel stride given;
  *   grads_dev : like pnr_mlp_wgrad's -- DEVICE pointers to the fp32 gradient buffers, every one fully overwritten;
- *   workspace : pnr_mlp_backward_fp32_workspace_bytes device bytes.
- * Replaces torch autograd of the reference's Network for the fp32 case. */
+ *   workspace : pnr_mlp_backward_fp32_workspace_bytes device bytes: the gradients in flight, S (3 W + 2 (W/2)) floats, then
+ *               ceil(S / 2048) blocks of weight- and bias-gradient partial sums, each as large as the widest weight gradient
+ *               of the call (rows x columns, + rows where the Linear has a bias; with head_depth 1 a head's own W -> n Linear
+ *               counts, and is the widest at W = 128 from n around 132 upward).
+ * Replaces torch autograd of the reference's Network for the fp32 case.
+ *
+ * Layout of acts (S = n_rays * n_samples, sample s = ray * n_samples + i): regions in this order, without gaps, each dense
+ * row-major [S][width] fp32, the first at float 0 and the last ending at pnr_mlp_fp32_acts_floats:
+ *   EX       [S][3 + 6 xyz_L]  gamma(x) of the point o + d z: x, then per band k (sin(2^k x), cos(2^k x)), 3 columns each
+ *   ED       [S][3 + 6 dir_L]  gamma(d) of d / ||d||, same column order
+ *   X_1..X_D [S][W] each       post-ReLU outputs of pts_linears.0 .. D-1 (X_D is the trunk output h)
+ *   F        [S][W]            feature_linear's output (no ReLU)
+ *   G        [S][W/2]          post-ReLU output of views_linears.0
+ *   SH_sem   [S][W/2]          post-ReLU hidden layer of the semantic head: present only if n_sem > 0 and head_depth != 1
+ *   SH_inst  [S][W/2]          the same for the instance head (n_inst > 0 and head_depth != 1)
+ * The backward takes every ReLU gate from these saved outputs (x > 0). */
 int64_t pnr_mlp_fp32_acts_floats(const pnr_mlp_desc* desc, int64_t n_samples);
 int64_t pnr_mlp_backward_fp32_workspace_bytes(const pnr_mlp_desc* desc, int64_t n_samples);
 int pnr_mlp_forward_train_fp32(const pnr_mlp_desc* desc, const pnr_mlp_params_host* params_dev, const float* rays,

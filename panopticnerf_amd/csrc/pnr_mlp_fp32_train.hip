@@ -10,9 +10,8 @@
 // direction, on dense row-major fp32 tensors [S][width].  Parameters are read where they live (the nn.Parameter tensors on
 // the device, (out, in) row-major): nothing is packed.  head_depth 1 and 2, head_tap 0 and 1 are all supported.
 //
-// Saved activations (`acts`, fp32, pnr_mlp_fp32_acts_floats): EX [S][ex] gamma(x), ED [S][ed] gamma(d), X_1..X_D [S][W]
-// (post-ReLU trunk outputs), F [S][W] (feature, linear), G [S][W/2] (post-ReLU view layer), SHs / SHi [S][W/2] (post-ReLU head
-// hidden layers, head_depth 2).  ReLU gates are taken from the saved outputs (x > 0), as autograd's threshold_backward does.
+// Saved activations (`acts`, fp32): the layout include/pnr.h documents next to pnr_mlp_fp32_acts_floats (make_layout below is
+// its only implementation).  ReLU gates are taken from the saved outputs (x > 0), as autograd's threshold_backward does.
 #include <string.h>
 
 #include "pnr_common.h"
@@ -289,10 +288,30 @@ PNR_EXPORT int64_t pnr_mlp_backward_fp32_workspace_bytes(const pnr_mlp_desc* des
     if (pnr_mlp_validate(desc) != PNR_OK || n_samples < 0) return -1;
     const Layout L = make_layout(*desc, n_samples);
     const int64_t n_slab = (n_samples + KSLAB - 1) / KSLAB;
-    const int64_t kmax = L.W + (L.ex > L.ed ? L.ex : L.ed);
-    // gradients in flight: dH a/b, dF [S][W]; dG, dSH [S][W/2]; weight-gradient partials; bias partials
-    const int64_t floats = n_samples * (3 * (int64_t)L.W + 2 * (int64_t)L.H) + n_slab * (int64_t)L.W * kmax + n_slab * L.W + 16;
-    (void)kmax;
+    // one linear_wgrad launch at a time lives in the partials: n_slab x (n_out x k weight partials, then n_out bias partials
+    // where the launch has a bias).  The widest of pnr_mlp_backward_fp32's launches sizes them -- with head_depth 1 that is
+    // a head's own Linear (n_out = n_sem or n_inst <= 256, k = W), wider than any trunk layer of W = 128.
+    const int64_t W = L.W, H = L.H;
+    int64_t part = 0;
+    auto wgrad = [&](int64_t n_out, int64_t k, bool bias) {
+        const int64_t f = n_out * k + (bias ? n_out : 0);
+        if (f > part) part = f;
+    };
+    wgrad(3, H, true);                                       // rgb_linear
+    wgrad(H, W, true); wgrad(H, L.ed, false);                // views_linears.0: feature columns, gamma(d) columns
+    const bool deep = desc->head_depth != 1;
+    const int64_t heads[2] = {desc->n_sem, desc->n_inst};
+    for (int64_t n : heads) {
+        if (!n) continue;
+        if (deep) { wgrad(n, H, true); wgrad(H, W, true); }
+        else wgrad(n, W, true);
+    }
+    wgrad(W, W, true); wgrad(1, W, true);                    // feature_linear, alpha_linear
+    wgrad(W, L.ex, true);                                    // pts_linears.0
+    wgrad(W, W, true);                                       // pts_linears.l (D >= 2), trunk columns
+    if (desc->skip >= 0) wgrad(W, L.ex, false);              // the skip layer's gamma(x) columns
+    // gradients in flight: dH a/b, dF [S][W]; dG, dSH [S][W/2]; then the partials
+    const int64_t floats = n_samples * (3 * W + 2 * H) + n_slab * part;
     return floats * 4;
 }
 
