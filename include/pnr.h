@@ -629,7 +629,19 @@ int pnr_sample_pdf(const float* z, const float* weights, const float* u, int64_t
  * Per ray the max_hits NEAREST intersected boxes (smallest t_in; ties: lower box index), stored in ascending
  * (t_in, box index) order: hit_t (R,max_hits,2), hit_box (R,max_hits) int32 (-1 pad).  hit_count (R) int32 is the
  * TRUE number of intersected boxes: a value > max_hits reports that the farthest ones were dropped (grow max_hits);
- * pnr_sample_labels uses min(hit_count, max_hits) entries.  Bit-exact with pnro_bbox_hits. */
+ * pnr_sample_labels uses min(hit_count, max_hits) entries.  Bit-exact with pnro_bbox_hits.
+ *
+ * The rule per ray (o, d, near, far) and box (float32, no contraction of mul + add, one correctly rounded reciprocal):
+ *     p = o - c;  tmin = near;  tmax = far
+ *     for each box axis a (rotation row r):  ol = (r0*p0 + r1*p1) + r2*p2;  dl = (r0*d0 + r1*d1) + r2*d2;  inv = 1 / dl
+ *         t1 = (-e_a - ol) * inv;  t2 = (e_a - ol) * inv;  tmin = max(tmin, min(t1, t2));  tmax = min(tmax, max(t1, t2))
+ *     hit  <=>  tmin <= tmax
+ * a8: min / max.  Here and in the hull of pnr_restrict_rays, min / max are fminf / fmaxf with both open cases fixed: a NaN
+ * operand loses (the other one is returned), and -0.0 orders BELOW +0.0: min(-0, +0) = min(+0, -0) = -0, max = +0 (what
+ * v_min_f32 / v_max_f32 return; C leaves it open, so the oracle spells it out in pnro_fminf / pnro_fmaxf).  It decides the sign
+ * of a zero t_in -- a zero-extent box through the origin, near = 0 -- and with it the sign of z[0] under the hull switch.
+ * So along a box axis (dl = +-0) a ray inside the slab keeps its interval (t = -+inf), outside it misses, and exactly on a
+ * face it misses too (0 * inf = NaN loses against the other face's infinity); d = 0 hits the boxes that strictly contain o. */
 int pnr_bbox_hits(const float* rays, int64_t n_rays, const float* box, int n_box, int max_hits,
                   float* hit_t, int32_t* hit_box, int32_t* hit_count, void* stream);
 

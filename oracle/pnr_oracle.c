@@ -328,6 +328,23 @@ PNRO_API void pnro_merge_sorted(const float* z, const float* zs, int64_t R, int 
     }
 }
 
+/* fminf / fmaxf of the ray preamble (include/pnr.h "a8: min / max"): a NaN operand loses, and -0 orders BELOW +0 -- what the device's
+ * v_min_f32 / v_max_f32 return.  C leaves fminf(-0, +0) to the implementation, so the host's libm is not bound to that answer. */
+static inline float pnro_fminf(float a, float b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return signbit(a) ? a : b;
+    return a < b ? a : b;
+}
+static inline float pnro_fmaxf(float a, float b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return signbit(a) ? b : a;
+    return a > b ? a : b;
+}
+
 /* ---------------------------------------------------------------- a8: ray / 3D bbox prior
  * SURVEY 8a row a8.  Oriented boxes: box (M,15) = centre c(3), rotation rows Rm(9)
  * (row a = box axis a in world frame), half extents e(3);  box_ids (M,2) int32 =
@@ -335,6 +352,7 @@ PNRO_API void pnro_merge_sorted(const float* z, const float* zs, int64_t R, int 
  *   p = o - c;  ol_a = (R_a0 p0 + R_a1 p1) + R_a2 p2;  dl_a likewise with d
  *   inv = 1/dl_a; t1 = (-e_a - ol_a)*inv; t2 = (e_a - ol_a)*inv
  *   tmin = fmax(tmin, fmin(t1,t2)); tmax = fmin(tmax, fmax(t1,t2)); init tmin=near, tmax=far
+ *   (fmin / fmax: pnro_fminf / pnro_fmaxf above -- a NaN operand loses, -0 < +0)
  *   hit iff tmin <= tmax
  * Per ray the max_hits NEAREST hits (smallest t_in; ties: lower box index) in ascending (t_in, box index)
  * order: hit_t (R,max_hits,2) = (t_in,t_out), hit_box (R,max_hits) int32 (-1 = none), hit_count (R) int32 =
@@ -362,8 +380,8 @@ PNRO_API void pnro_bbox_hits(const float* rays, int64_t R, const float* box, int
                 const float inv = 1.0f / dl;
                 const float e = b[12 + a];
                 const float t1 = (-e - ol) * inv, t2 = (e - ol) * inv;
-                tmin = fmaxf(tmin, fminf(t1, t2));
-                tmax = fminf(tmax, fmaxf(t1, t2));
+                tmin = pnro_fmaxf(tmin, pnro_fminf(t1, t2));
+                tmax = pnro_fminf(tmax, pnro_fmaxf(t1, t2));
             }
             if (tmin <= tmax) {
                 /* keep the max_hits nearest intervals in ascending (t_in, box index) order */
@@ -397,8 +415,8 @@ PNRO_API void pnro_restrict_rays(const float* rays, int64_t R, const float* hit_
         if (cnt <= 0) continue;
         float lo = hit_t[(r * max_hits) * 2], hi = hit_t[(r * max_hits) * 2 + 1];
         for (int h = 1; h < cnt; ++h) {
-            lo = fminf(lo, hit_t[(r * max_hits + h) * 2]);
-            hi = fmaxf(hi, hit_t[(r * max_hits + h) * 2 + 1]);
+            lo = pnro_fminf(lo, hit_t[(r * max_hits + h) * 2]);
+            hi = pnro_fmaxf(hi, hit_t[(r * max_hits + h) * 2 + 1]);
         }
         out[r * 8 + 6] = lo;
         out[r * 8 + 7] = hi;
