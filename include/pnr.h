@@ -25,6 +25,7 @@
  *   pnr_*_rng, pnr_rng_begin / _fill   the above with torch.rand / torch.randn drawn in the kernel (8a rows a3, a6, a7, a9)
  *   pnr_sample_batch    the dataset's ray batches: pixel sampling, rays and targets of posed frames
  *   pnr_census, pnr_sgm_aggregate / _select, pnr_disparity_depth   the dataset's SGM stereo depth
+ *   pnr_mesh_count / _emit   a labelled triangle mesh of the field (no reference counterpart: the reference ships no extractor)
  *
  * Conventions:
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
@@ -605,6 +606,58 @@ int pnr_sgm_aggregate(const int64_t* census_l, const int64_t* census_r, int widt
 int pnr_sgm_select(const uint16_t* S, int width, int height, int max_disp, int uniqueness, int lr_tol, int16_t* d16,
                    int16_t* disp_right, void* stream);
 int pnr_disparity_depth(const int16_t* d16, int64_t n, float fb, float d_min, float d_max, float* depth, void* stream);
+
+/* ---- mesh extraction (csrc/pnr_mesh.hip; DESIGN.md 8 "Mesh extraction"): a lattice of field values, as Network.query_grid
+ * returns it, -> a triangle mesh of the surface field = level, with the lattice point each vertex takes its label from.  The
+ * method is marching tetrahedra on the Kuhn split: no ambiguous cases, and neighbouring cubes agree on every face diagonal, so
+ * the surface is watertight by construction.  The reference ships no extractor: the rule is this build's and unpinned
+ * (tests/_mesh_ref.py restates it twice, bit for bit).  THE CONTRACT:
+ *
+ *   LATTICE.  field is float32 (res_z, res_y, res_x).  Point (ix, iy, iz) has flat index n = (iz res_y + iy) res_x + ix and the
+ *     position lo + (i + 0.5) step per axis in float32: (float) i + 0.5f, one multiply, one add, never an FMA.  lo and step are
+ *     query_grid's: float32 lo, and step = (hi32 - lo32) / res32, one subtraction and one division.
+ *   INSIDE.  A point is inside iff field > level.  NaN is outside, +Inf inside.
+ *   CELLS.  Cube c has the corners c + {0,1}^3 and exists for c_i <= res_i - 2.  It is cut into six tetrahedra, one per
+ *     permutation pi of the axes in lexicographic order: xyz, xzy, yxz, yzx, zxy, zyx (tetrahedron 0 .. 5; parities
+ *     0 1 1 0 0 1).  Tetrahedron pi has the corners w0 = c, w1 = w0 + e_pi1, w2 = w1 + e_pi2, w3 = c + (1, 1, 1).
+ *   VERTICES.  A mesh vertex lies on a lattice edge whose two ends differ in "inside".  Every edge of the split is (a, a + off)
+ *     with off a non-zero vector of {0,1}^3: seven kinds, kind = off_x + 2 off_y + 4 off_z - 1, and the edge is OWNED by its
+ *     lower end a.  With f_a, f_b the values and p_a, p_b the positions of the owner and the far end:
+ *         t = (level - f_a) / (f_b - f_a)       two subtractions, one correctly rounded division
+ *         t = 0.5 if t is NaN, else 0 if t < 0, else 1 if t > 1
+ *         p = p_a + t (p_b - p_a)               per component: subtract, multiply, add, each rounded
+ *     always from the owner, whichever end is inside, so every tetrahedron round the edge gets the same bits.  Vertices are
+ *     numbered by (owner's flat index, kind) ascending.  src[v] = the flat index of the edge's INSIDE end.
+ *   TRIANGLES.  case = sum over k of (w_k inside) << k.  With I the inside and O the outside corners of a tetrahedron, each
+ *     ascending in w order, and (x, y) the vertex on the edge between corners x and y:
+ *         one inside corner     (I0,O0) (I0,O1) (I0,O2)
+ *         three                 (I0,O0) (I1,O0) (I2,O0)
+ *         two                   the quad q0 = (I0,O0), q1 = (I0,O1), q2 = (I1,O1), q3 = (I1,O0) as (q0, q1, q2) and (q0, q2, q3)
+ *     A triangle keeps its first vertex; its second and third are swapped where the table says so, so that
+ *     (p1 - p0) x (p2 - p0) points from the inside corners towards the outside ones.  swap[case][parity of pi]:
+ *         case    0    1    2    3    4    5    6    7    8    9   10   11   12   13   14   15
+ *         even    0    0    1    0    0    1    0    0    1    0    1    1    0    0    1    0
+ *         odd     0    1    0    1    1    0    1    1    0    1    0    0    1    1    0    0
+ *     Triangles are numbered by (the cube's flat index over the lattice, tetrahedron 0 .. 5, triangle 0 .. 1) ascending.
+ *     Zero-area triangles (a lattice value equal to level) are kept.  If any res_i < 2 there is no cube and the mesh is empty:
+ *     totals = {0, 0}, not an error.
+ *   LIMITS.  At most (2^31 - 1) / 12 = 178956970 lattice points, so that every count fits an int32 scan; faces is int32.
+ *
+ * pnr_mesh_count classifies every point, scans the counts and writes totals[0] = vertices, totals[1] = triangles (DEVICE int64[2],
+ * 8-byte aligned) and the workspace pnr_mesh_emit reads: pnr_mesh_workspace_bytes(res) bytes, 16-byte aligned, caller-owned, to
+ * be left alone between the two calls (-1 for a lattice the entry points refuse).  pnr_mesh_emit, with the same field, lattice
+ * and level, writes vertices (V, 3) float32, faces (T, 3) int32 and src (V) int64, V and T being the totals: the caller reads
+ * them between the two calls, which is the one synchronisation of an extraction and the caller's.  lo_host, step_host: three HOST
+ * floats each, copied into the launch.  src may be NULL; vertices and faces may be NULL only when their total is 0 (a NULL output
+ * is never written, and src is written only with vertices).  Neither entry point synchronises or allocates; both are
+ * capture-safe, no kernel waits on another workgroup and nothing is atomic: two calls give the same bits.
+ * PNR_EINVAL before any launch, from both: a res < 1; a lattice over the limit; a non-finite level; a null field or workspace;
+ * a misaligned field (4 bytes) or workspace (16).  pnr_mesh_count also: a null or misaligned (8) totals.  pnr_mesh_emit also: a
+ * null lo_host or step_host, a non-finite lo or step, a misaligned vertices, faces (4) or src (8). */
+int64_t pnr_mesh_workspace_bytes(int res_x, int res_y, int res_z);
+int pnr_mesh_count(const float* field, int res_x, int res_y, int res_z, float level, void* workspace, int64_t* totals, void* stream);
+int pnr_mesh_emit(const float* field, int res_x, int res_y, int res_z, float level, const float* lo_host, const float* step_host,
+                  const void* workspace, float* vertices, int32_t* faces, int64_t* src, void* stream);
 
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).

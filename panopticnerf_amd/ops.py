@@ -477,6 +477,78 @@ def disparity_depth(d16, fb, d_range=(1e-3, float("inf")), out=None):
     return out
 
 
+MESH_MAX_POINTS = (2 ** 31 - 1) // 12          # include/pnr.h "mesh extraction", LIMITS
+
+
+def _mesh_field(what, field, level):
+    """the lattice argument of the mesh ops: (res_x, res_y, res_z, level) or the refusal by name, on any device"""
+    if not isinstance(field, torch.Tensor):
+        raise ValueError("%s: field must be a GPU tensor, got %s" % (what, type(field).__name__))
+    if field.dtype != torch.float32:
+        raise ValueError("%s: field must be float32, got %s" % (what, field.dtype))
+    if field.dim() != 3 or min(field.shape) < 1:
+        raise ValueError("%s: field must be (res_z, res_y, res_x) with every res >= 1, got %s" % (what, tuple(field.shape)))
+    if field.numel() > MESH_MAX_POINTS:
+        raise ValueError("%s: field holds %d points, more than the limit of %d ((2^31 - 1) / 12)" % (what, field.numel(), MESH_MAX_POINTS))
+    level = float(level)
+    if not (abs(level) < float("inf")):
+        raise ValueError("%s: level must be finite (got %r)" % (what, level))
+    rz, ry, rx = field.shape
+    return rx, ry, rz, level
+
+
+def mesh_workspace_bytes(res_x, res_y, res_z):
+    """pnr_mesh_workspace_bytes: host arithmetic only; a lattice the entry points refuse raises"""
+    return _size_or_raise(_lib.load().pnr_mesh_workspace_bytes(int(res_x), int(res_y), int(res_z)), "pnr_mesh_workspace_bytes")
+
+
+@_on_device
+def mesh_count(field, level, workspace=None, totals=None):
+    """Classify the lattice `field` (res_z, res_y, res_x) float32 against `level` and scan the counts (pnr_mesh_count; the rule
+    is in include/pnr.h "mesh extraction").  Returns (totals, workspace): totals (2) int64 ON THE DEVICE = (vertices, triangles)
+    -- reading it is the caller's synchronisation --, workspace the uint8 buffer mesh_emit needs.  Both may be caller-owned."""
+    rx, ry, rz, level = _mesh_field("mesh_count", field, level)
+    nbytes = mesh_workspace_bytes(rx, ry, rz)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < nbytes):
+        raise ValueError("mesh_count: workspace must be a uint8 tensor of at least %d bytes" % nbytes)
+    if totals is not None and (not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (2,)):
+        raise ValueError("mesh_count: totals must be a (2,) int64 tensor")
+    _stereo_gpu("mesh_count", field=field, workspace=workspace, totals=totals)
+    if workspace is None:
+        workspace = torch.empty((nbytes,), device=field.device, dtype=torch.uint8)
+    if totals is None:
+        totals = torch.empty((2,), device=field.device, dtype=torch.int64)
+    _lib.check(_lib.load().pnr_mesh_count(_p(field), rx, ry, rz, level, _p(workspace), _p(totals), _stream()), "pnr_mesh_count")
+    return totals, workspace
+
+
+@_on_device
+def mesh_emit(field, level, lo, step, workspace, vertices, faces, src=None):
+    """Write the mesh mesh_count counted (pnr_mesh_emit): vertices (V, 3) float32, faces (T, 3) int32, src (V,) int64 or None,
+    caller-owned and sized by mesh_count's totals.  lo, step: the lattice's float32 origin and step per axis (x, y, z), host
+    values.  field, level and workspace are mesh_count's."""
+    rx, ry, rz, level = _mesh_field("mesh_emit", field, level)
+    lo_h, step_h = _host_floats(lo, 3, "mesh_emit: lo"), _host_floats(step, 3, "mesh_emit: step")
+    for name, h in (("lo", lo_h), ("step", step_h)):
+        if not all(abs(v) < float("inf") for v in h):
+            raise ValueError("mesh_emit: %s must be finite (got %r)" % (name, list(h)))
+    nbytes = mesh_workspace_bytes(rx, ry, rz)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < nbytes:
+        raise ValueError("mesh_emit: workspace must be the uint8 tensor of at least %d bytes that mesh_count filled" % nbytes)
+    for name, t, dtype, cols in (("vertices", vertices, torch.float32, 3), ("faces", faces, torch.int32, 3), ("src", src, torch.int64, 0)):
+        if t is None and name == "src":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
+            raise ValueError("mesh_emit: %s must be a %s %s tensor" % (name, "(n, 3)" if cols else "(n,)", dtype))
+    if src is not None and src.shape[0] != vertices.shape[0]:
+        raise ValueError("mesh_emit: src holds %d rows, vertices %d" % (src.shape[0], vertices.shape[0]))
+    _stereo_gpu("mesh_emit", field=field, workspace=workspace, vertices=vertices, faces=faces, src=src)
+    _lib.check(_lib.load().pnr_mesh_emit(_p(field), rx, ry, rz, level, lo_h, step_h, _p(workspace),
+                                         _p(vertices if vertices.numel() else None), _p(faces if faces.numel() else None),
+                                         _p(src if src is not None and src.numel() else None), _stream()), "pnr_mesh_emit")
+    return vertices, faces, src
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global

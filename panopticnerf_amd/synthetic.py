@@ -200,3 +200,44 @@ def stereo_pair(height, width, layers=STEREO_LAYERS, seed=0, device=None):
     visible = (xr >= 0) & (owner[ys, np.clip(xr, 0, W - 1)] == xs)
     out = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (left, right, disp, visible))
     return out if device is None else tuple(t.to(device) for t in out)
+
+
+SDF_KINDS = ("sphere", "torus", "box", "plane")
+
+
+def sdf_grid(kind, lo, hi, res, center=(0.0, 0.0, 0.0), radius=0.7, minor=0.25, half=(0.5, 0.5, 0.5), axis=0, offset=0.0, device=None):
+    """An analytic field on the lattice `Network.query_grid` defines over the box [lo, hi] (res an int or (res_x, res_y, res_z)),
+    for tests and examples of `mesh`: POSITIVE INSIDE, the negated signed distance, so its surface is the level 0.
+      sphere: radius - |p - center|;      torus: minor - the distance to the circle of `radius` round the z axis through center;
+      box: the negated signed distance of the axis-aligned box center +- half;      plane: p[axis] - offset.
+    The coordinates are query_grid's float32 cell centres, lo + (i + 0.5) * step (a multiply, then an add); the field is made
+    from them with numpy in float32, op by op.  Returns a (res_z, res_y, res_x) float32 tensor, on the CPU or on `device`."""
+    import numpy as np
+    if kind not in SDF_KINDS:
+        raise ValueError("sdf_grid: unknown kind %r (%s)" % (kind, ", ".join(SDF_KINDS)))
+    r = (int(res),) * 3 if isinstance(res, int) else tuple(int(v) for v in res)
+    if len(r) != 3 or min(r) < 1:
+        raise ValueError("sdf_grid: res must be a positive int or (res_x, res_y, res_z)")
+    lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(-1), np.asarray(hi, dtype=np.float32).reshape(-1)
+    if lo32.shape != (3,) or hi32.shape != (3,):
+        raise ValueError("sdf_grid: lo and hi must be 3-vectors")
+    if axis not in (0, 1, 2):
+        raise ValueError("sdf_grid: axis must be 0, 1 or 2")
+    step = (hi32 - lo32) / np.asarray(r, dtype=np.float32)
+    ax = [(np.arange(r[a]).astype(np.float32) + np.float32(0.5)) * step[a] + lo32[a] for a in range(3)]
+    c = np.asarray(center, dtype=np.float32).reshape(3)
+    Z, Y, X = np.meshgrid(ax[2] - c[2], ax[1] - c[1], ax[0] - c[0], indexing="ij")
+    if kind == "sphere":
+        f = np.float32(radius) - np.sqrt(X * X + Y * Y + Z * Z)
+    elif kind == "torus":
+        q = np.sqrt(X * X + Y * Y) - np.float32(radius)
+        f = np.float32(minor) - np.sqrt(q * q + Z * Z)
+    elif kind == "box":
+        h = np.asarray(half, dtype=np.float32).reshape(3)
+        d = [np.abs(X) - h[0], np.abs(Y) - h[1], np.abs(Z) - h[2]]
+        out = np.sqrt(sum(np.maximum(v, np.float32(0.0)) ** 2 for v in d))
+        f = -(out + np.minimum(np.maximum(np.maximum(d[0], d[1]), d[2]), np.float32(0.0)))
+    else:
+        f = (X, Y, Z)[axis] + c[axis] - np.float32(offset)
+    t = torch.from_numpy(np.ascontiguousarray(f.astype(np.float32)))
+    return t if device is None else t.to(device)
