@@ -11,8 +11,7 @@
 // sample_pdf's output is detached in the reference, so no gradient flows into z.
 // Fixed (bbox-prior) fields have no learnable input.  Softmax-composited fields (sem_mode 1) are
 // not differentiated here (forward-only option); the caller is told so.
-#include "pnr_common.h"
-#include "pnr_philox.h"
+#include "pnr_composite_dev.h"
 
 struct CompositeBwdArgs {
     const float* raw; int64_t sc;          // channel-major: element (s, c) at raw[c*sc + s]
@@ -29,17 +28,9 @@ struct CompositeBwdArgs {
     int sem_mode;                          // 0: logits are composited; 1: softmax(logits) per sample is composited
 };
 
-struct f4 { float v[4]; };
 // one row's arithmetic at a time: without the fence hipcc interleaves the expf chains of a whole batch of rows (8 rows x 4 samples)
 // for instruction-level parallelism and needs ~175 registers for it -- at the 128 the launch bound grants it spilled ~45 of them
-#ifndef BWD_FENCE
-#define BWD_FENCE 1
-#endif
-#if BWD_FENCE
 #define BWD_ROW_FENCE __builtin_amdgcn_sched_barrier(0)
-#else
-#define BWD_ROW_FENCE ((void)0)
-#endif
 // Per ray-group width (SUB lanes per ray): waves per SIMD the launch bound asks for, logit rows per pipelined batch (two batches
 // resident), rows in flight in the log-sum-exp / dot passes.  One ray per wave (N > 64: SUB >= 32) means R waves in all -- 4096 at the
 // training batch, 16 per CU -- so the kernel is capped at 128 VGPRs (4 waves per SIMD: the launch is resident at once; at its
@@ -57,31 +48,6 @@ struct f4 { float v[4]; };
 #define BWD_CB_OF(SUB) ((SUB) >= 32 ? 4 : 8)
 #endif
 
-__device__ __forceinline__ f4 ld4(const float* p, bool active)
-{
-    f4 o;
-    if (!active) { o.v[0] = o.v[1] = o.v[2] = o.v[3] = 0.0f; return o; }
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    o.v[0] = t.x; o.v[1] = t.y; o.v[2] = t.z; o.v[3] = t.w;
-    return o;
-}
-// Row access as (wave-uniform row pointer) + (32-bit per-lane byte offset): hipcc then selects the scalar-base form of
-// global_load / global_store (SGPR pair + one shared VGPR offset) instead of materialising a 64-bit VGPR address per row in
-// flight -- two registers per row, which is what pushed this kernel past 128 VGPRs (3 waves per SIMD instead of 4).
-__device__ __forceinline__ f4 ld4o(const float* row, uint32_t ob, bool active)
-{
-    return ld4(reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + ob), active);
-}
-__device__ __forceinline__ void st4(float* p, const f4& v, bool active);
-__device__ __forceinline__ void st4o(float* row, uint32_t ob, const f4& v, bool active)
-{
-    st4(reinterpret_cast<float*>(reinterpret_cast<char*>(row) + ob), v, active);
-}
-__device__ __forceinline__ void st4(float* p, const f4& v, bool active)
-{
-    if (active) *reinterpret_cast<float4*>(p) = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
-}
-
 // SM: softmax compositing (sem_mode 1) -- a template parameter so that the default (logit compositing) instance carries neither
 // the dot products nor their branches in its register budget
 // Rng = PnrRngDev (pnr_composite_backward_rng): the forward's sigma noise regenerated from the in-kernel stream (k_composite's lane
@@ -90,60 +56,32 @@ template <int SUB, bool SM, class... Rng>
 __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(CompositeBwdArgs a, const Rng... rng)
 {
     constexpr bool RNG = sizeof...(Rng) > 0;
-    constexpr int RPW = 64 / SUB;
     constexpr int CB = BWD_CB_OF(SUB);      // channel rows in flight per lane (log-sum-exp / dot passes)
     constexpr int BWD_PB = BWD_PB_OF(SUB);  // logit rows per pipelined batch of the main pass
-    const int lane = threadIdx.x & 63;
-    const int N = a.N, nq4 = N >> 2;
-    const int q = lane & (SUB - 1), g = lane / SUB;
-    const int64_t wave_global = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int64_t n_groups = (a.R + RPW - 1) / RPW;
+    RayLanes<SUB, 1> rl(a.R);               // the forward kernel's mapping: SUB lanes per ray x 4 samples per lane
+    const int N = a.N, q = rl.q;
     PnrRngKey key;
     if constexpr (RNG) key = pnr_rng_key(rng...);
 
-    for (int64_t grp = wave_global; grp < n_groups; grp += n_waves) {
-        const int64_t ray = grp * RPW + g;
-        const bool active = (ray < a.R) && (q < nq4);
-        const int64_t rayc = ray < a.R ? ray : a.R - 1;
-        const int64_t s0 = rayc * N + (active ? 4 * q : 0);
+    const int64_t first = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;     // this wave, and the waves of the grid
+    const int64_t step = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t grp = first; grp < rl.n_groups; grp += step) {
+        rl.at(grp, a.R, N);
+        const int64_t ray = rl.ray, rayc = rl.rayc, s0 = rl.s0;
+        const bool active = rl.act[0];
 
-        // ---- recompute alpha, T, w (as the forward kernel does)
+        // ---- recompute alpha, T, w: k_composite's own chain and scan (pnr_composite_dev.h); only the product differs -- here
+        // T = Tl excl first, since T is needed by itself
         const uint32_t ob = (uint32_t)s0 * 4u;          // byte offset of the lane's first sample in a row (R * N < 2^30: the launcher checks)
         const f4 zz = ld4o(a.z, ob, active);
         f4 sg = ld4o(a.raw + 3 * a.sc, ob, active);
-        if constexpr (RNG) {
-            if (active) {
-                float n[4];
-                pnr_rng_normal4(key, (uint32_t)ray, (uint32_t)q, n);
-                for (int k = 0; k < 4; ++k) sg.v[k] += n[k];
-            }
-        } else if (a.noise) { const f4 nz = ld4o(a.noise, ob, active); for (int k = 0; k < 4; ++k) sg.v[k] += nz.v[k]; }
-        const float dx = a.rays[rayc * 8 + 3], dy = a.rays[rayc * 8 + 4], dz = a.rays[rayc * 8 + 5];
-        const float dn = sqrtf((dx * dx + dy * dy) + dz * dz);
+        add_sigma_noise4<RNG>(sg.v, active, key, (uint32_t)ray, (uint32_t)q, a.noise, row_at(a.noise, ob));
+        const float dn = ray_dir_norm(a.rays, rayc);
         const float znext = __shfl_down(zz.v[0], 1, 64);
         f4 alpha, dist, Tl;            // Tl: product of this lane's earlier factors
-        float P = 1.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = 4 * q + k;
-            const float zn = (k < 3) ? zz.v[k + 1] : znext;
-            float d = (i + 1 < N) ? (zn - zz.v[k]) : 1e10f;
-            d *= dn;
-            dist.v[k] = d;
-            alpha.v[k] = 1.0f - expf(-(fmaxf(sg.v[k], 0.0f) * d));
-            Tl.v[k] = P;
-            P *= (1.0f - alpha.v[k]) + 1e-10f;
-        }
+        float P = alpha_chain<4>(zz.v, znext, sg.v, rl.i0, N, dn, alpha.v, Tl.v, dist.v);
         if (!active) P = 1.0f;
-        float x = P;
-#pragma unroll
-        for (int d = 1; d < SUB; d <<= 1) {
-            const float y = __shfl_up(x, d, 64);
-            if (q >= d) x *= y;
-        }
-        float excl = __shfl_up(x, 1, 64);
-        if (q == 0) excl = 1.0f;
+        const float excl = scan_excl_shfl<SUB>(P, q);
         f4 T, w;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { T.v[k] = Tl.v[k] * excl; w.v[k] = active ? alpha.v[k] * T.v[k] : 0.0f; }
@@ -156,9 +94,9 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
 #pragma unroll
             for (int k = 0; k < 4; ++k) G.v[k] = fmaf(gd, zz.v[k], ga) + gw.v[k];
         }
-        int ls[4] = {-1, -1, -1, -1}, li[4] = {-1, -1, -1, -1};
-        if (a.label_sem && active) { const int4 t = *reinterpret_cast<const int4*>(a.label_sem + s0); ls[0] = t.x; ls[1] = t.y; ls[2] = t.z; ls[3] = t.w; }
-        if (a.label_inst && active) { const int4 t = *reinterpret_cast<const int4*>(a.label_inst + s0); li[0] = t.x; li[1] = t.y; li[2] = t.z; li[3] = t.w; }
+        int ls[4], li[4];
+        ld4_labels(a.label_sem + s0, a.label_sem && active, ls);
+        ld4_labels(a.label_inst + s0, a.label_inst && active, li);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (a.g_fix_sem && ls[k] >= 0 && ls[k] < a.C) G.v[k] += a.g_fix_sem[rayc * a.C + ls[k]];
@@ -180,13 +118,7 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
                 for (int j = 0; j < CB; ++j) {
                     if (c0 + j >= nch) break;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        // online log-sum-exp with ONE expf per value: of the two factors expf(mx - m2), expf(v - m2) one is always
-                        // expf(0) = 1 (same bits as the two-expf form)
-                        const float d = v[j].v[k] - mx.v[k], e = expf(-fabsf(d));
-                        den.v[k] = d <= 0.0f ? den.v[k] + e : den.v[k] * e + 1.0f;
-                        mx.v[k] = fmaxf(mx.v[k], v[j].v[k]);
-                    }
+                    for (int k = 0; k < 4; ++k) lse_step(mx.v[k], den.v[k], v[j].v[k]);     // k_ce3d's step: this is its gradient
                     BWD_ROW_FENCE;
                 }
             }
@@ -213,7 +145,7 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
                     if (c0 + j >= nch) break;
                     const float gc = gp[rayc * nch + c0 + j];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) dot.v[k] = fmaf(gc, expf(v[j].v[k] - mx.v[k]) / den.v[k], dot.v[k]);
+                    for (int k = 0; k < 4; ++k) dot.v[k] = fmaf(gc, softmax_of(v[j].v[k], mx.v[k], den.v[k]), dot.v[k]);
                 }
             }
         };
@@ -226,7 +158,7 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
             f4 dr;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float v = 1.0f / (1.0f + expf(-r.v[k]));
+                const float v = sigmoid_of(r.v[k]);
                 G.v[k] = fmaf(gc, v, G.v[k]);
                 dr.v[k] = w.v[k] * gc * v * (1.0f - v);
             }
@@ -261,7 +193,7 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (SM && gp) {
-                        const float sc = expf(r.v[k] - (is_s ? mx_s.v[k] : mx_i.v[k])) / (is_s ? den_s.v[k] : den_i.v[k]);
+                        const float sc = softmax_of(r.v[k], is_s ? mx_s.v[k] : mx_i.v[k], is_s ? den_s.v[k] : den_i.v[k]);
                         dr.v[k] = w.v[k] * sc * (gc - (is_s ? dot_s.v[k] : dot_i.v[k]));
                     } else {
                         G.v[k] = fmaf(gc, r.v[k], G.v[k]);
@@ -275,7 +207,7 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
                     for (int k = 0; k < 4; ++k) {
                         const int lab = is_s ? ls[k] : li[k];
                         if (lab < 0 || lab >= (is_s ? a.C : a.K)) continue;
-                        const float pc = expf(r.v[k] - (is_s ? mx_s.v[k] : mx_i.v[k])) / (is_s ? den_s.v[k] : den_i.v[k]);
+                        const float pc = softmax_of(r.v[k], is_s ? mx_s.v[k] : mx_i.v[k], is_s ? den_s.v[k] : den_i.v[k]);
                         dr.v[k] += ce * (pc - (lab == cc ? 1.0f : 0.0f));
                     }
                 }
@@ -322,81 +254,19 @@ __global__ __launch_bounds__(256, BWD_WAVES(SUB)) void k_composite_bwd(Composite
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float om = 1.0f - alpha.v[k];
-            const float dalpha = G.v[k] * T.v[k] - S.v[k] / (om + 1e-10f);
+            const float dalpha = G.v[k] * T.v[k] - S.v[k] / alpha_factor(alpha.v[k]);
             ds.v[k] = (sg.v[k] > 0.0f) ? dist.v[k] * om * dalpha : 0.0f;
         }
         st4o(a.d_raw + 3 * a.sc, ob, ds, active);
     }
 }
 
-PNR_EXPORT int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                       const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
-                                       const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                       const float* g_inst, const float* g_weights, const int32_t* label_sem,
-                                       const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                       const float* ce_sem, const float* ce_inst, float* d_raw, void* stream);
-
-PNR_EXPORT int pnr_composite_backward(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                      const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
-                                      const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                      const float* g_inst, const float* g_weights, float* d_raw, void* stream)
-{
-    return pnr_composite_backward2(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, g_rgb, g_depth, g_acc,
-                                   g_sem, g_inst, g_weights, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_raw, stream);
-}
-
 static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
                                    const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
                                    const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
                                    const float* g_inst, const float* g_weights, const int32_t* label_sem,
                                    const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream, const PnrRngDev* rng = nullptr);
-
-PNR_EXPORT int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                       const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
-                                       const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                       const float* g_inst, const float* g_weights, const int32_t* label_sem,
-                                       const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                       const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
-{
-    return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, 0, g_rgb, g_depth, g_acc, g_sem,
-                                   g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream);
-}
-
-PNR_EXPORT int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                          const pnr_rng* noise_host, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
-                                          const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                          const float* g_inst, const float* g_weights, const int32_t* label_sem,
-                                          const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                          const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
-{
-    PnrRngDev rng;
-    const int rc = pnr_rng_check(noise_host, n_rays < 0 ? 0 : n_rays, "pnr_composite_backward_rng", &rng);
-    if (rc) return rc;
-    PNR_REQUIRE(sem_mode == 0 || sem_mode == 1, "pnr_composite_backward_rng: sem_mode must be 0 (logits) or 1 (softmax)");
-    return composite_backward_impl(raw, raw_stride_c, z, rays, nullptr, n_rays, n_samples, n_sem, n_inst, sem_mode, g_rgb, g_depth, g_acc,
-                                   g_sem, g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream,
-                                   &rng);
-}
-
-PNR_EXPORT int pnr_composite_backward3(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                       const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
-                                       const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                       const float* g_inst, const float* g_weights, const int32_t* label_sem,
-                                       const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                       const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
-{
-    PNR_REQUIRE(sem_mode == 0 || sem_mode == 1, "pnr_composite_backward: sem_mode must be 0 (logits) or 1 (softmax)");
-    return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, sem_mode, g_rgb, g_depth, g_acc,
-                                   g_sem, g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream);
-}
-
-static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
-                                   const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
-                                   const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
-                                   const float* g_inst, const float* g_weights, const int32_t* label_sem,
-                                   const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
-                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream, const PnrRngDev* rng)
+                                   const float* ce_sem, const float* ce_inst, float* d_raw, void* stream, const PnrRngDev* rng = nullptr)
 {
     PNR_REQUIRE(n_samples >= 4 && n_samples <= 256 && (n_samples % 4) == 0,
                 "pnr_composite_backward: n_samples=%d must be a multiple of 4 in [4,256]", n_samples);
@@ -421,26 +291,58 @@ static int composite_backward_impl(const float* raw, int64_t raw_stride_c, const
     const int64_t n_groups = (n_rays + rpw - 1) / rpw;
     const int grid = pnr_grid_cap((n_groups + 3) / 4, 8);
     hipStream_t st = (hipStream_t)stream;
-#define PNR_CB(S)                                                                                                            \
-    do {                                                                                                                     \
-        if (rng) {                                                                                                           \
-            if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<S, true, PnrRngDev>), dim3(grid), dim3(256), 0, st, a, *rng);       \
-            else hipLaunchKernelGGL((k_composite_bwd<S, false, PnrRngDev>), dim3(grid), dim3(256), 0, st, a, *rng);                 \
-        } else {                                                                                                             \
-            if (a.sem_mode) hipLaunchKernelGGL((k_composite_bwd<S, true>), dim3(grid), dim3(256), 0, st, a);                 \
-            else hipLaunchKernelGGL((k_composite_bwd<S, false>), dim3(grid), dim3(256), 0, st, a);                           \
-        }                                                                                                                    \
-    } while (0)
-    switch (sub) {
-    case 1: PNR_CB(1); break;
-    case 2: PNR_CB(2); break;
-    case 4: PNR_CB(4); break;
-    case 8: PNR_CB(8); break;
-    case 16: PNR_CB(16); break;
-    case 32: PNR_CB(32); break;
-    default: PNR_CB(64); break;
-    }
-#undef PNR_CB
+    composite_dispatch<1, 2, 4, 8, 16, 32, 64>(sub, true, sem_mode, rng, [&](auto S, auto, auto SM, const auto&... r) {
+        hipLaunchKernelGGL((k_composite_bwd<decltype(S)::value, decltype(SM)::value, std::decay_t<decltype(r)>...>), dim3(grid), dim3(256), 0, st,
+                           a, r...);
+    });
     PNR_CHECK_LAUNCH("pnr_composite_backward");
     return PNR_OK;
+}
+
+PNR_EXPORT int pnr_composite_backward(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                                      const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
+                                      const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                                      const float* g_inst, const float* g_weights, float* d_raw, void* stream)
+{
+    return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, 0, g_rgb, g_depth, g_acc, g_sem,
+                                   g_inst, g_weights, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_raw, stream);
+}
+
+PNR_EXPORT int pnr_composite_backward2(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                                       const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst,
+                                       const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                                       const float* g_inst, const float* g_weights, const int32_t* label_sem,
+                                       const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
+                                       const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
+{
+    return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, 0, g_rgb, g_depth, g_acc, g_sem,
+                                   g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream);
+}
+
+PNR_EXPORT int pnr_composite_backward3(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                                       const float* noise, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
+                                       const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                                       const float* g_inst, const float* g_weights, const int32_t* label_sem,
+                                       const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
+                                       const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
+{
+    PNR_REQUIRE(sem_mode == 0 || sem_mode == 1, "pnr_composite_backward: sem_mode must be 0 (logits) or 1 (softmax)");
+    return composite_backward_impl(raw, raw_stride_c, z, rays, noise, n_rays, n_samples, n_sem, n_inst, sem_mode, g_rgb, g_depth, g_acc,
+                                   g_sem, g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream);
+}
+
+PNR_EXPORT int pnr_composite_backward_rng(const float* raw, int64_t raw_stride_c, const float* z, const float* rays,
+                                          const pnr_rng* noise_host, int64_t n_rays, int n_samples, int n_sem, int n_inst, int sem_mode,
+                                          const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_sem,
+                                          const float* g_inst, const float* g_weights, const int32_t* label_sem,
+                                          const int32_t* label_inst, const float* g_fix_sem, const float* g_fix_inst,
+                                          const float* ce_sem, const float* ce_inst, float* d_raw, void* stream)
+{
+    PnrRngDev rng;
+    const int rc = pnr_rng_check(noise_host, n_rays < 0 ? 0 : n_rays, "pnr_composite_backward_rng", &rng);
+    if (rc) return rc;
+    PNR_REQUIRE(sem_mode == 0 || sem_mode == 1, "pnr_composite_backward_rng: sem_mode must be 0 (logits) or 1 (softmax)");
+    return composite_backward_impl(raw, raw_stride_c, z, rays, nullptr, n_rays, n_samples, n_sem, n_inst, sem_mode, g_rgb, g_depth, g_acc,
+                                   g_sem, g_inst, g_weights, label_sem, label_inst, g_fix_sem, g_fix_inst, ce_sem, ce_inst, d_raw, stream,
+                                   &rng);
 }

@@ -1,5 +1,5 @@
 // What the fused MLP epilogue (pnr_mlp_fuse.h) hands to k_composite_combine (pnr_composite.hip): record layout and the
-// fixed-point scale of the bbox-prior histograms.
+// fixed-point scale of the bbox-prior histograms (the one definition: every compositing kernel bins through pnr_composite_dev.h).
 #pragma once
 
 #define PNR_FUSE_FIX_SCALE 1073741824.0f      /* 2^30: fixed-point bins of the bbox-prior histograms (a ray's weights sum to <= 1) */

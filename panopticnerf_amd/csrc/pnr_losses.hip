@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "pnr_common.h"
+#include "pnr_composite_dev.h"
 
 #define LS_THREADS 256
 #define LS_TERMS 8        /* rgb, depth, sem, fix_sem, inst, fix_inst, (unused), (unused) */
@@ -229,9 +230,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_ce3d(Ce3dArgs a)
             float mx = -INFINITY, den = 0.0f, at = 0.0f;
             for (int c = 0; c < a.n_cls; ++c) {          // online log-sum-exp: one pass over the channel rows
                 const float v = p[(int64_t)c * a.sc];
-                const float d = v - mx, e = expf(-fabsf(d));      // one expf per value: the other factor of the online form is expf(0)
-                den = d <= 0.0f ? den + e : den * e + 1.0f;
-                mx = fmaxf(mx, v);
+                lse_step(mx, den, v);                    // the step k_composite_bwd takes for this term's gradient
                 if (c == lab) at = v;
             }
             ce = logf(den) + (mx - at);             // as in ce_row: invariant under a common shift of the logits

@@ -575,6 +575,15 @@ def _draw(x):
     return isinstance(x, Draw)
 
 
+def _twin(name, tensor, draw, rng_name=None, what=None):
+    """The call site of an op that takes a Draw in place of a tensor: the _rng twin of an entry point takes the pnr_rng* in the
+    positional slot of the float pointer it replaces.  -> (entry point, that slot's argument, its name for _lib.check)."""
+    if draw is not None:
+        rng_name = rng_name or name + "_rng"
+        return getattr(_lib.load(), rng_name), ctypes.byref(draw.desc()), rng_name
+    return getattr(_lib.load(), name), _p(tensor), what or name
+
+
 @_on_device
 def rng_begin(state, call=None):
     """pnr_rng_begin: call = state (seed, offset), then state[1] += 1, on the current stream.  state: (2,) int64 GPU tensor owned
@@ -647,16 +656,12 @@ def stratified(rays, n_samples, lindisp=False, t_rand=None, out=None):
     R = rays.shape[0]
     assert rays.shape[-1] == 8
     z = _own(out, (R, n_samples), torch.float32, rays.device, "stratified")
-    lib = _lib.load()
-    if _draw(t_rand):
-        _lib.check(lib.pnr_stratified_rng(_p(rays), R, n_samples, int(bool(lindisp)), ctypes.byref(t_rand.desc()), _p(z), _stream()),
-                   "pnr_stratified_rng")
-        return z
-    t_rand = _chk(t_rand, "t_rand")
+    draw = t_rand if _draw(t_rand) else None
+    t_rand = None if draw is not None else _chk(t_rand, "t_rand")
     if t_rand is not None:
         assert tuple(t_rand.shape) == (R, n_samples)
-    _lib.check(lib.pnr_stratified(_p(rays), R, n_samples, int(bool(lindisp)), _p(t_rand), _p(z), _stream()),
-               "pnr_stratified")
+    fn, rand, what = _twin("pnr_stratified", t_rand, draw)
+    _lib.check(fn(_p(rays), R, n_samples, int(bool(lindisp)), rand, _p(z), _stream()), what)
     return z
 
 
@@ -979,18 +984,10 @@ def composite(raw, z, rays, n_sem=0, n_inst=0, channel_major=True, noise=None, l
     dev = z.device
     out = _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev)
     g = out.get
-    if draw is not None:
-        _lib.check(_lib.load().pnr_composite_rng(_p(raw), ss, sc, _p(z), _p(rays), ctypes.byref(draw.desc()), _p(label_sem),
-                                                 _p(label_inst), R, N, n_sem, n_inst, int(sem_mode), int(bool(white_bkgd)),
-                                                 _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]), _p(g("weights")),
-                                                 _p(g("semantic")), _p(g("instance")), _p(g("fix_semantic")),
-                                                 _p(g("fix_instance")), _stream()), "pnr_composite_rng")
-        return out
-    _lib.check(_lib.load().pnr_composite(_p(raw), ss, sc, _p(z), _p(rays), _p(noise), _p(label_sem), _p(label_inst),
-                                         R, N, n_sem, n_inst, int(sem_mode), int(bool(white_bkgd)),
-                                         _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]), _p(g("weights")),
-                                         _p(g("semantic")), _p(g("instance")), _p(g("fix_semantic")),
-                                         _p(g("fix_instance")), _stream()), "pnr_composite")
+    fn, nz, what = _twin("pnr_composite", noise, draw)
+    _lib.check(fn(_p(raw), ss, sc, _p(z), _p(rays), nz, _p(label_sem), _p(label_inst), R, N, n_sem, n_inst, int(sem_mode),
+                  int(bool(white_bkgd)), _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]), _p(g("weights")), _p(g("semantic")),
+                  _p(g("instance")), _p(g("fix_semantic")), _p(g("fix_instance")), _stream()), what)
     return out
 
 
@@ -1210,20 +1207,10 @@ def composite_backward(raw, z, rays, n_sem, n_inst, grads, noise=None, label_sem
     ce_sem = None if ce_sem is None else _chk(ce_sem.reshape(1).float().contiguous(), "ce_sem")
     ce_inst = None if ce_inst is None else _chk(ce_inst.reshape(1).float().contiguous(), "ce_inst")
     d_raw = torch.empty_like(raw)
-    if draw is not None:
-        _lib.check(_lib.load().pnr_composite_backward_rng(_p(raw), R * N, _p(z), _p(rays), ctypes.byref(draw.desc()), R, N, n_sem, n_inst,
-                                                          int(sem_mode), _p(g.get("rgb")), _p(g.get("depth")), _p(g.get("acc")),
-                                                          _p(g.get("semantic")), _p(g.get("instance")), _p(g.get("weights")),
-                                                          _p(label_sem), _p(label_inst), _p(g.get("fix_semantic")),
-                                                          _p(g.get("fix_instance")), _p(ce_sem), _p(ce_inst),
-                                                          _p(d_raw), _stream()), "pnr_composite_backward_rng")
-        return d_raw
-    _lib.check(_lib.load().pnr_composite_backward3(_p(raw), R * N, _p(z), _p(rays), _p(noise), R, N, n_sem, n_inst, int(sem_mode),
-                                                   _p(g.get("rgb")), _p(g.get("depth")), _p(g.get("acc")),
-                                                   _p(g.get("semantic")), _p(g.get("instance")), _p(g.get("weights")),
-                                                   _p(label_sem), _p(label_inst), _p(g.get("fix_semantic")),
-                                                   _p(g.get("fix_instance")), _p(ce_sem), _p(ce_inst),
-                                                   _p(d_raw), _stream()), "pnr_composite_backward")
+    fn, nz, what = _twin("pnr_composite_backward3", noise, draw, rng_name="pnr_composite_backward_rng", what="pnr_composite_backward")
+    _lib.check(fn(_p(raw), R * N, _p(z), _p(rays), nz, R, N, n_sem, n_inst, int(sem_mode), _p(g.get("rgb")), _p(g.get("depth")),
+                  _p(g.get("acc")), _p(g.get("semantic")), _p(g.get("instance")), _p(g.get("weights")), _p(label_sem), _p(label_inst),
+                  _p(g.get("fix_semantic")), _p(g.get("fix_instance")), _p(ce_sem), _p(ce_inst), _p(d_raw), _stream()), what)
     return d_raw
 
 
@@ -1289,12 +1276,8 @@ def sample_pdf(z, weights, n_importance, u=None, want_samples=True, out=None):
     if want_samples:
         zs = torch.empty((R, n_importance), device=dev, dtype=torch.float32)
         inds = torch.empty((R, n_importance), device=dev, dtype=torch.int32)
-    if draw is not None:
-        _lib.check(_lib.load().pnr_sample_pdf_rng(_p(z), _p(weights), ctypes.byref(draw.desc()), R, Nc, n_importance, _p(zs), _p(inds),
-                                                  _p(z_fine), _stream()), "pnr_sample_pdf_rng")
-        return z_fine, zs, inds
-    _lib.check(_lib.load().pnr_sample_pdf(_p(z), _p(weights), _p(u), R, Nc, n_importance, _p(zs), _p(inds),
-                                          _p(z_fine), _stream()), "pnr_sample_pdf")
+    fn, uu, what = _twin("pnr_sample_pdf", u, draw)
+    _lib.check(fn(_p(z), _p(weights), uu, R, Nc, n_importance, _p(zs), _p(inds), _p(z_fine), _stream()), what)
     return z_fine, zs, inds
 
 
@@ -1366,14 +1349,9 @@ def ray_setup(rays, box, box_ids=None, n_samples=64, max_hits=8, lindisp=False, 
     if box_ids is not None:
         ls = torch.empty((R, N), device=dev, dtype=torch.int32)
         li = torch.empty((R, N), device=dev, dtype=torch.int32)
-    if draw is not None:
-        _lib.check(_lib.load().pnr_ray_setup_rng(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)),
-                                                 ctypes.byref(draw.desc()), int(bool(hull)), _p(hit_t), _p(hit_box), _p(hit_count), _p(z),
-                                                 _p(ls), _p(li), _stream()), "pnr_ray_setup_rng")
-    else:
-        _lib.check(_lib.load().pnr_ray_setup(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)), _p(t_rand),
-                                             int(bool(hull)), _p(hit_t), _p(hit_box), _p(hit_count), _p(z), _p(ls), _p(li), _stream()),
-                   "pnr_ray_setup")
+    fn, rand, what = _twin("pnr_ray_setup", t_rand, draw)
+    _lib.check(fn(_p(rays), R, _p(box), M, int(max_hits), _p(box_ids), N, int(bool(lindisp)), rand, int(bool(hull)), _p(hit_t),
+                  _p(hit_box), _p(hit_count), _p(z), _p(ls), _p(li), _stream()), what)
     return (hit_t, hit_box, hit_count), z, ls, li
 
 
@@ -1392,14 +1370,9 @@ def sample_pdf_labels(z, weights, n_importance, hits, box_ids, u=None, out=None)
     z_fine = _own(out, (R, Nt), torch.float32, dev, "sample_pdf_labels")
     ls = torch.empty((R, Nt), device=dev, dtype=torch.int32)
     li = torch.empty((R, Nt), device=dev, dtype=torch.int32)
-    if draw is not None:
-        _lib.check(_lib.load().pnr_sample_pdf_labels_rng(_p(z), _p(weights), ctypes.byref(draw.desc()), R, Nc, int(n_importance), _p(z_fine),
-                                                         _p(hit_t), _p(hit_box), _p(hit_count), hit_box.shape[1], _p(box_ids), _p(ls),
-                                                         _p(li), _stream()), "pnr_sample_pdf_labels_rng")
-    else:
-        _lib.check(_lib.load().pnr_sample_pdf_labels(_p(z), _p(weights), _p(u), R, Nc, int(n_importance), _p(z_fine), _p(hit_t),
-                                                     _p(hit_box), _p(hit_count), hit_box.shape[1], _p(box_ids), _p(ls), _p(li), _stream()),
-                   "pnr_sample_pdf_labels")
+    fn, uu, what = _twin("pnr_sample_pdf_labels", u, draw)
+    _lib.check(fn(_p(z), _p(weights), uu, R, Nc, int(n_importance), _p(z_fine), _p(hit_t), _p(hit_box), _p(hit_count), hit_box.shape[1],
+                  _p(box_ids), _p(ls), _p(li), _stream()), what)
     return z_fine, ls, li
 
 
