@@ -877,6 +877,52 @@ int pnr_sample_batch(const pnr_frame* frames, const int64_t* cum, const int32_t*
                      int64_t n_rays, float* rays, float* rgb, float* depth, int32_t* sem, int32_t* inst, int32_t* frame_out,
                      int32_t* pix_out, void* stream);
 
+/* ---- depth fusion (csrc/pnr_fusion.hip; DESIGN.md 8 "Depth fusion"): posed depth frames of a pnr_frame table -> a truncated
+ * signed distance volume (TSDF) on the lattice of query_grid and mesh extraction, with an optional mean colour and an optional
+ * majority label per lattice point: the step between the depth producers (stereo, render_view, splatting) and pnr_mesh_*.  The
+ * reference ships no fusion: the rule is this build's and unpinned.  Float32 throughout except the integer label vote, every
+ * operation a single + - * / in the order given (tests/_tsdf_ref.py restates the rule three times, twice bit for bit).
+ *
+ * LATTICE.  Point (ix, iy, iz) has flat index n = (iz res_y + iy) res_x + ix and the position X_k = lo_k + ((float)i_k + 0.5f)
+ *   step_k: one multiply, one add, never an FMA -- the positions of mesh extraction.  lo_host, step_host: three HOST floats each.
+ * VOLUME.  Caller-owned device arrays indexed by n, which ACCUMULATE over calls; the caller initialises them once:
+ *     tsdf        float32        0      the running mean of phi
+ *     weight      float32        0      the number of observations, capped at w_max
+ *     rgb         float32 (., 3) 0      optional: the running mean of the colour BYTES, 0 .. 255
+ *     rgb_weight  float32        0      optional, with rgb
+ *     label       int32         -1      optional: the packed majority key (sem << 16 | (uint16) inst), -1 = nothing voted
+ *     conf        int32          0      optional, with label: the vote's counter
+ * THE CONTRACT.  For every lattice point, the frames f = f0 .. f1 - 1 of the table are taken IN ORDER; w2c (F, 12) float32 on the
+ * device holds row f = the 3x4 row-major world-to-camera of frame f (camera.invert_pose of its c2w).  Per frame:
+ *   1. the frame is skipped if its depth address is 0.
+ *   2. (u, v), |p_cam|, p_cam.z and the domain flag of X in the frame's camera with w2c row f: the arithmetic of
+ *      pnr_project_points (umax = (float)width - 0.5f).  Skipped unless in the domain and -0.5 <= u < width - 0.5,
+ *      -0.5 <= v < height - 0.5.
+ *   3. nearest pixel as reprojection step 5: iu = min((int)floor(u + 0.5), width - 1), iv likewise, q = iv width + iu.
+ *   4. d = depth[q].  Skipped unless d > 0, d is finite and d <= max_depth (max_depth may be +inf).
+ *   5. e = the depth in the view's convention: p_cam.z for a pinhole, |p_cam| for a fisheye or equirect frame.  s = e - d.
+ *      Skipped if s > trunc: the point is hidden behind the observed surface.
+ *   6. phi = s < -trunc ? -1.0f : s / trunc.  POSITIVE MEANS BEHIND THE OBSERVED SURFACE -- the opposite of the usual sign,
+ *      because mesh extraction calls field > level inside.
+ *   7. tsdf = (tsdf * weight + phi) / (weight + 1.0f);  weight = min(weight + 1.0f, w_max).  w_max >= 1, +inf allowed.
+ *   8. if s >= -trunc and rgb is given (and the frame's rgb address is not 0): with cw = rgb_weight,
+ *      c_k = (c_k * cw + (float)byte_k) / (cw + 1.0f) for the three channels of rgb[q], then rgb_weight = min(cw + 1.0f, w_max).
+ *   9. if s >= -trunc, label is given, the frame has sem and ls = sem[q] >= 0:  key = (ls << 16) | (uint16)(inst ? inst[q] : -1),
+ *      and one step of Boyer-Moore majority voting in integers: label == key: conf = min(conf + 1, 2^30); else conf == 0:
+ *      label = key, conf = 1; else conf -= 1.
+ * The table and the pose rows are read from DEVICE memory when the kernel runs, as for pnr_sample_batch: a record edited after a
+ * capture is what later replays see.  A point's result depends on the frames and their order only, so one call over [f0, f1)
+ * equals the calls over [f0, k) and [k, f1), bit for bit.  No atomics: two runs give the same bits.  Never synchronises;
+ * capture-safe.  PNR_EINVAL before any launch: null frames, w2c, tsdf or weight; rgb without rgb_weight or the reverse, label
+ * without conf or the reverse; a misaligned table (frames, w2c: 16 bytes) or volume array (4); f0 < 0 or f1 < f0; a res < 1 or
+ * more than 2^31 - 1 points; null, non-finite lo or step, or a zero step; !(trunc > 0) or a non-finite trunc; !(max_depth > 0);
+ * !(w_max >= 1).  f0 == f1 returns PNR_OK at once.  The entry point cannot see the table's length: f1 <= F is the caller's. */
+#define PNR_TSDF_BLOCK 256              /* threads (= lattice points) a workgroup */
+#define PNR_TSDF_BLOCKS_PER_CU 8        /* the grid's cap per compute unit; the rest is walked grid-stride */
+int pnr_tsdf_integrate(const pnr_frame* frames, const float* w2c, int f0, int f1, int res_x, int res_y, int res_z,
+                       const float* lo_host, const float* step_host, float trunc, float max_depth, float w_max,
+                       float* tsdf, float* weight, float* rgb, float* rgb_weight, int32_t* label, int32_t* conf, void* stream);
+
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable
  * state -- the one diagnostic hook of the MLP kernels is a descriptor field (pnr_mlp_desc.clk_probe). */

@@ -128,6 +128,8 @@ SIGNATURES = {
     "pnr_mesh_count": (c_int, [c_f, c_int, c_int, c_int, ctypes.c_float, c_f, c_f, c_f]),
     "pnr_mesh_emit": (c_int, [c_f, c_int, c_int, c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                               c_f, c_f, c_f, c_f, c_f]),
+    "pnr_tsdf_integrate": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
-from .camera import _Camera, _rows3
+from .camera import _Camera, _rows3, invert_pose
 
 MODES = ("pooled", "frame")
 _REC = ctypes.sizeof(_lib.Frame)
@@ -48,6 +48,7 @@ class FrameSet:
         self.table = self.cum = self.n_frames = self.rng_state = None       # device memory: allocated by the first add() / sample()
         self.frames = []            # host side of every record: camera, pose, bounds and the device images (kept alive here)
         self._total = 0
+        self._w2c, self._w2c_rows = None, 0      # w2c_table(): the world-to-camera rows of the frames, on the device
         self.bbox = self.bbox_ids = None
         self.prims = None           # set_primitives: {"prim_planes", "prim_offsets", "prim_ids"} on the device
 
@@ -133,6 +134,21 @@ class FrameSet:
                             "n_valid": n_valid, **imgs})
         self._total = total
         return i
+
+    def w2c_table(self):
+        """(capacity, 12) float32 on the device: row f = camera.invert_pose of frame f's c2w, the pose table that goes with
+        `table` into ops.tsdf_integrate.  Kept on the device; a call after the set grew uploads the new rows only (a
+        stream-ordered copy, as add()'s)."""
+        self._alloc()
+        if self._w2c is None:
+            self._w2c = torch.zeros((self.capacity, 12), dtype=torch.float32, device=self.device)
+        n = len(self.frames)
+        if n > self._w2c_rows:
+            rows = torch.stack([invert_pose(fr["c2w"]).reshape(12) for fr in self.frames[self._w2c_rows:n]])
+            with torch.cuda.device(self.device):
+                self._w2c[self._w2c_rows:n].copy_(rows)
+            self._w2c_rows = n
+        return self._w2c
 
     def set_boxes(self, bbox, bbox_ids):
         """The scene's 3D box prior, returned in every batch: bbox (M, 15), bbox_ids (M, 2) (ops.bbox_hits' layout).  A second

@@ -1,0 +1,196 @@
+"""Depth fusion: posed depth frames -> a truncated signed distance volume (TSDF) -> a labelled, coloured mesh, on the GPU
+(ops.tsdf_integrate / pnr_tsdf_integrate; the rule is written out in include/pnr.h "depth fusion").  The step between the
+depth producers (stereo.depth_from_pair, Renderer.render_view, pointcloud.splat), the frames a `FrameSet` keeps on the device,
+and `mesh.extract`: images -> depth -> volume -> mesh.
+
+    vol = fusion.Volume(lo, hi, res, "cuda", color=True, labels=True)
+    fusion.integrate(vol, frames, trunc=0.2)                 # every frame of the FrameSet that has a depth image
+    m = fusion.extract(vol)                                   # mesh.Mesh with attributes sem_label, inst_label, rgb
+    m.save_ply("scene.ply", colors=m.attributes["rgb"], labels=m.attributes["sem_label"])
+
+The volume lives on the lattice of `Network.query_grid` and `mesh.extract` (cell centres lo + (i + 0.5) step of the box
+[lo, hi]).  One launch takes any number of frames: a lattice point's state stays in registers over the whole frame loop, so
+the volume is read and written once per call.  Per point the frames are taken in order, so the result is the CPU
+restatement's bit for bit and does not depend on how the frames are split over calls.
+
+Conventions (this build's, unpinned): POSITIVE tsdf is BEHIND the observed surface (mesh.extract calls field > level inside);
+nearest-pixel depth lookup; depth as render_view writes it (z-depth in a pinhole frame, range in a fisheye / equirect frame);
+every observation weighs 1; colour is the running mean of the frames' bytes; the label is a Boyer-Moore majority vote over
+(pseudo_label, instance_label) pairs.  Out of scope: per-pixel confidence weights, voxel hashing or sparse volumes, ray-cast
+rendering of the volume, frustum culling per block, reading pose files."""
+import numpy as np
+import torch
+
+from . import mesh as _mesh
+from . import ops
+
+LABEL_NONE = -1
+
+
+def pack_label(sem, inst):
+    """the key the vote stores: (sem << 16) | (uint16) inst for sem >= 0, -1 otherwise; integer tensors (any device)"""
+    sem, inst = torch.as_tensor(sem).to(torch.int32), torch.as_tensor(inst).to(torch.int32)
+    return torch.where(sem >= 0, (sem << 16) | (inst & 0xFFFF), torch.full_like(sem, LABEL_NONE))
+
+
+def unpack_label(label):
+    """(sem, inst) int32 of packed keys: sem = key >> 16, inst = the low half as an int16; both -1 where key < 0 (nothing voted)"""
+    label = torch.as_tensor(label).to(torch.int32)
+    none = label < 0
+    inst = ((label & 0xFFFF) ^ 0x8000) - 0x8000
+    return torch.where(none, torch.full_like(label, -1), label >> 16), torch.where(none, torch.full_like(label, -1), inst)
+
+
+class Volume:
+    """A TSDF volume over the box [lo, hi] at res = (res_x, res_y, res_z) cells (an int: the same on every axis).  The arrays
+    are plain tensors on `device`; integrate and extract need them on the GPU (the HIP path has no CPU fallback).
+    Arrays, (res_z, res_y, res_x) each: tsdf, weight float32; with color=True rgb (..., 3) and rgb_weight float32 (the mean of
+    the colour bytes, 0 .. 255); with labels=True label and conf int32.  lo32 / step are mesh.lattice's, so the box means the
+    same bits as in query_grid and mesh.extract."""
+
+    def __init__(self, lo, hi, res, device, color=False, labels=False):
+        try:
+            res3 = (int(res),) * 3 if np.ndim(res) == 0 else tuple(int(r) for r in res)
+        except (TypeError, ValueError):
+            raise ValueError("fusion.Volume: res must be an int or three ints (res_x, res_y, res_z)") from None
+        if len(res3) != 3 or min(res3) < 1:
+            raise ValueError("fusion.Volume: res must be an int or three ints >= 1 (res_x, res_y, res_z), got %r" % (res,))
+        if res3[0] * res3[1] * res3[2] > ops.TSDF_MAX_POINTS:
+            raise ValueError("fusion.Volume: %d x %d x %d points, more than the limit of 2^31 - 1" % res3)
+        self.lo32, self.step = _mesh.lattice(lo, hi, res3)
+        if not (self.step != 0).all():
+            raise ValueError("fusion.Volume: the box is empty along an axis (lo %r, hi %r)" % (self.lo32.tolist(), hi))
+        dev = torch.device(device)
+        self.lo, self.hi, self.res = lo, hi, res3
+        rx, ry, rz = res3
+        f32 = lambda *tail: torch.empty((rz, ry, rx) + tail, dtype=torch.float32, device=dev)
+        i32 = lambda: torch.empty((rz, ry, rx), dtype=torch.int32, device=dev)
+        self.tsdf, self.weight = f32(), f32()
+        self.rgb, self.rgb_weight = (f32(3), f32()) if color else (None, None)
+        self.label, self.conf = (i32(), i32()) if labels else (None, None)
+        self.device = self.tsdf.device
+        self.reset()
+
+    def __repr__(self):
+        return "Volume(%d x %d x %d%s%s)" % (self.res + (", color" if self.rgb is not None else "", ", labels" if self.label is not None else ""))
+
+    def reset(self):
+        """the initial values, in place: everything 0, label -1"""
+        for t in (self.tsdf, self.weight, self.rgb, self.rgb_weight, self.conf):
+            if t is not None:
+                t.zero_()
+        if self.label is not None:
+            self.label.fill_(LABEL_NONE)
+
+    def _labels(self):
+        if self.label is None:
+            raise ValueError("fusion.Volume: the volume was made without labels (labels=True)")
+        return unpack_label(self.label)
+
+    @property
+    def sem_label(self):
+        """(res_z, res_y, res_x) int32: the semantic half of the majority key, -1 where nothing voted"""
+        return self._labels()[0]
+
+    @property
+    def inst_label(self):
+        """(res_z, res_y, res_x) int32: the instance half of the majority key, -1 where nothing voted (or the frames had none)"""
+        return self._labels()[1]
+
+    def colors(self):
+        """(res_z, res_y, res_x, 3) uint8: the mean colour rounded to the nearest byte (0 where no frame coloured the point)"""
+        if self.rgb is None:
+            raise ValueError("fusion.Volume: the volume was made without colour (color=True)")
+        return self.rgb.round().clamp(0, 255).to(torch.uint8)
+
+
+def integrate(volume, frames, trunc, first=0, last=None, max_depth=float("inf"), w_max=float("inf")):
+    """Fuse frames first .. last - 1 (last=None: all) of the FrameSet `frames` into `volume`, in ONE launch.  A frame without a
+    depth image is skipped; colour comes from the frames' rgb, labels from pseudo_label / instance_label.  trunc: the band's
+    half width in world units -- see `extract` for how small it may be; max_depth: depth pixels beyond it are ignored; w_max:
+    the cap of the running weights (1 = the last frame wins, inf = a plain mean).  The world-to-camera rows come from
+    FrameSet.w2c_table (camera.invert_pose of every c2w, kept on the device).  Nothing is synchronised; with an unchanged set
+    the call is one kernel launch and can be captured in a graph."""
+    if not isinstance(volume, Volume):
+        raise TypeError("fusion.integrate: volume must be a fusion.Volume")
+    if not all(hasattr(frames, k) for k in ("table", "frames", "w2c_table")):
+        raise TypeError("fusion.integrate: frames must be a FrameSet")
+    n = len(frames)
+    first, last = int(first), n if last is None else int(last)
+    if not 0 <= first <= last <= n:
+        raise ValueError("fusion.integrate: need 0 <= first <= last <= %d (the frames of the set), got [%d, %d)" % (n, first, last))
+    trunc, max_depth, w_max = float(trunc), float(max_depth), float(w_max)
+    if not (0.0 < trunc < float("inf")):
+        raise ValueError("fusion.integrate: trunc must be positive and finite (got %r)" % trunc)
+    if not (max_depth > 0.0):
+        raise ValueError("fusion.integrate: max_depth must be positive (it may be inf; got %r)" % max_depth)
+    if not (w_max >= 1.0):
+        raise ValueError("fusion.integrate: w_max must be >= 1 (it may be inf; got %r)" % w_max)
+    if not volume.tsdf.is_cuda:
+        raise RuntimeError("fusion.integrate: the volume is not on the GPU (the HIP path has no CPU fallback)")
+    if first == last:
+        return volume
+    ops.tsdf_integrate(frames.table, frames.w2c_table(), first, last, volume.lo32, volume.step, trunc, volume.tsdf, volume.weight,
+                       rgb=volume.rgb, rgb_weight=volume.rgb_weight, label=volume.label, conf=volume.conf, max_depth=max_depth,
+                       w_max=w_max)
+    return volume
+
+
+def unobserved_near(observed):
+    """(res_z, res_y, res_x) bool: the points with an unobserved lattice point within +-1 per axis (themselves included); points
+    beyond the lattice do not count.  Torch slicing on any device: a 3 x 3 x 3 dilation of ~observed, one axis at a time."""
+    bad = ~observed
+    for axis in range(3):
+        n = bad.shape[axis]
+        grown = bad.clone()
+        if n > 1:
+            grown.narrow(axis, 0, n - 1).logical_or_(bad.narrow(axis, 1, n - 1))
+            grown.narrow(axis, 1, n - 1).logical_or_(bad.narrow(axis, 0, n - 1))
+        bad = grown
+    return bad
+
+
+def filter_mesh(vertices, faces, src, observed):
+    """The part of a mesh that lies in observed space: a vertex is kept iff every lattice point within +-1 per axis of
+    src[v] is observed, a face iff all three of its vertices are kept, and vertices of no kept face are dropped; what remains
+    keeps its order.  Returns (vertices, faces int32, src, index) with index = the old number of every remaining vertex.
+    Torch indexing on any device."""
+    keep_v = ~unobserved_near(observed).reshape(-1)[src]
+    f = faces.long()
+    keep_f = keep_v[f].all(dim=1) if f.shape[0] else torch.zeros((0,), dtype=torch.bool, device=faces.device)
+    f = f[keep_f]
+    used = torch.zeros(vertices.shape[0], dtype=torch.bool, device=vertices.device)
+    used[f.reshape(-1)] = True
+    new = torch.cumsum(used, 0) - 1
+    index = torch.nonzero(used).reshape(-1)
+    return vertices[index], new[f].to(torch.int32), src[index], index
+
+
+def extract(volume, min_weight=1.0):
+    """The mesh of the fused surface (mesh.Mesh), restricted to observed space.  field = where(weight >= min_weight, tsdf, -1)
+    goes through mesh.extract at level 0; then `filter_mesh` removes the shell between observed and never-observed space --
+    the back face at depth + trunc included.  attributes: sem_label, inst_label (volumes with labels) and rgb uint8 (volumes
+    with colour) per vertex, read at src, so save_ply(colors=m.attributes["rgb"], labels=m.attributes["sem_label"]) works
+    directly.  Torch plumbing on the device around mesh.extract; no kernel of its own.
+
+    A `trunc` below 4 x the largest lattice step ERODES REAL SURFACE: a vertex needs all 27 points round its inside point
+    observed, a neighbour of the first inside point can lie up to about 3.5 steps behind the surface (the inside end of a
+    cube-diagonal edge up to sqrt(3) steps, its diagonal neighbour sqrt(3) more), and points deeper than trunc are never
+    observed."""
+    if not isinstance(volume, Volume):
+        raise TypeError("fusion.extract: volume must be a fusion.Volume")
+    min_weight = float(min_weight)
+    if not (min_weight > 0.0):
+        raise ValueError("fusion.extract: min_weight must be positive (got %r)" % min_weight)
+    if not volume.tsdf.is_cuda:
+        raise RuntimeError("fusion.extract: the volume is not on the GPU (the HIP path has no CPU fallback)")
+    observed = volume.weight >= min_weight
+    field = torch.where(observed, volume.tsdf, torch.full_like(volume.tsdf, -1.0))
+    m = _mesh.extract(field, volume.lo, volume.hi, 0.0)
+    m.vertices, m.faces, m.src, _ = filter_mesh(m.vertices, m.faces, m.src, observed)
+    if volume.label is not None:
+        sem, inst = unpack_label(volume.label)
+        m.attributes["sem_label"], m.attributes["inst_label"] = m.labels(sem), m.labels(inst)
+    if volume.rgb is not None:
+        m.attributes["rgb"] = volume.colors().reshape(-1, 3)[m.src]
+    return m

@@ -549,6 +549,70 @@ def mesh_emit(field, level, lo, step, workspace, vertices, faces, src=None):
     return vertices, faces, src
 
 
+TSDF_MAX_POINTS = 2 ** 31 - 1                   # include/pnr.h "depth fusion"
+TSDF_BLOCK, TSDF_BLOCKS_PER_CU = 256, 8         # PNR_TSDF_BLOCK, PNR_TSDF_BLOCKS_PER_CU
+
+
+@_on_device
+def tsdf_integrate(frames, w2c, first, last, lo, step, trunc, tsdf, weight, rgb=None, rgb_weight=None, label=None, conf=None,
+                   max_depth=float("inf"), w_max=float("inf")):
+    """Fuse the depth frames first .. last - 1 of a device-resident frame table into a TSDF volume (pnr_tsdf_integrate; the rule
+    is in include/pnr.h "depth fusion").  frames: uint8 GPU tensor of pnr_frame records (FrameSet.table); w2c: (F, 12) float32,
+    row f = camera.invert_pose of frame f's c2w; both are read when the kernel runs.  lo, step: the lattice's float32 origin
+    and step per axis (x, y, z), host values (mesh.lattice).  tsdf, weight: (res_z, res_y, res_x) float32, accumulated in
+    place; rgb (res_z, res_y, res_x, 3) with rgb_weight, label with conf (int32): optional pairs.  Returns None."""
+    what = "tsdf_integrate"
+    if not isinstance(tsdf, torch.Tensor):
+        raise ValueError("%s: tsdf must be a GPU tensor, got %s" % (what, type(tsdf).__name__))
+    if tsdf.dim() != 3 or min(tsdf.shape) < 1:
+        raise ValueError("%s: tsdf must be (res_z, res_y, res_x) with every res >= 1, got %s" % (what, tuple(tsdf.shape)))
+    if tsdf.numel() > TSDF_MAX_POINTS:
+        raise ValueError("%s: tsdf holds %d points, more than the limit of 2^31 - 1" % (what, tsdf.numel()))
+    rz, ry, rx = tsdf.shape
+    if (rgb is None) != (rgb_weight is None):
+        raise ValueError("%s: rgb and rgb_weight go together (both or neither)" % what)
+    if (label is None) != (conf is None):
+        raise ValueError("%s: label and conf go together (both or neither)" % what)
+    for name, t, dtype, tail in (("tsdf", tsdf, torch.float32, ()), ("weight", weight, torch.float32, ()), ("rgb", rgb, torch.float32, (3,)),
+                                 ("rgb_weight", rgb_weight, torch.float32, ()), ("label", label, torch.int32, ()),
+                                 ("conf", conf, torch.int32, ())):
+        if t is None and name not in ("tsdf", "weight"):
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+        if tuple(t.shape) != (rz, ry, rx) + tail:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, (rz, ry, rx) + tail, tuple(t.shape)))
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1 or frames.numel() % ctypes.sizeof(_lib.Frame):
+        raise ValueError("%s: frames must be a uint8 tensor of whole pnr_frame records (%d bytes each)" % (what, ctypes.sizeof(_lib.Frame)))
+    if not isinstance(w2c, torch.Tensor) or w2c.dtype != torch.float32 or w2c.dim() != 2 or w2c.shape[1] != 12:
+        raise ValueError("%s: w2c must be an (F, 12) float32 tensor" % what)
+    first, last = int(first), int(last)
+    n_rec = min(frames.numel() // ctypes.sizeof(_lib.Frame), w2c.shape[0])
+    if not 0 <= first <= last <= n_rec:
+        raise ValueError("%s: need 0 <= first <= last <= %d (the records and w2c rows given), got [%d, %d)" % (what, n_rec, first, last))
+    lo_h, step_h = _host_floats(lo, 3, what + ": lo"), _host_floats(step, 3, what + ": step")
+    for name, h in (("lo", lo_h), ("step", step_h)):
+        if not all(abs(v) < float("inf") for v in h):
+            raise ValueError("%s: %s must be finite (got %r)" % (what, name, list(h)))
+    if not all(v != 0.0 for v in step_h):
+        raise ValueError("%s: step must be non-zero (got %r)" % (what, list(step_h)))
+    trunc, max_depth, w_max = float(trunc), float(max_depth), float(w_max)
+    if not (0.0 < trunc < float("inf")):
+        raise ValueError("%s: trunc must be positive and finite (got %r)" % (what, trunc))
+    if not (max_depth > 0.0):
+        raise ValueError("%s: max_depth must be positive (it may be inf; got %r)" % (what, max_depth))
+    if not (w_max >= 1.0):
+        raise ValueError("%s: w_max must be >= 1 (it may be inf; got %r)" % (what, w_max))
+    _stereo_gpu(what, tsdf=tsdf, weight=weight, rgb=rgb, rgb_weight=rgb_weight, label=label, conf=conf, frames=frames, w2c=w2c)
+    if first == last:
+        return
+    _lib.check(_lib.load().pnr_tsdf_integrate(_p(frames), _p(w2c), first, last, rx, ry, rz, lo_h, step_h, trunc, max_depth, w_max,
+                                              _p(tsdf), _p(weight), _p(rgb), _p(rgb_weight), _p(label), _p(conf), _stream()),
+               "pnr_tsdf_integrate")
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global
