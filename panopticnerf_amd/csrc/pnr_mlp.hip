@@ -16,7 +16,9 @@
 //  * gamma(x), gamma(d) are computed in registers by the lanes that need them (the two
 //    half-waves split the frequency bands), so the 63/27-wide encodings never exist in memory.
 //  * bf16 path: v_mfma_f32_32x32x16_bf16, fp32 accumulate, RNE conversion of activations.
-//    fp32 path (parity mode): v_mfma_f32_32x32x2_f32, bit-for-bit an fmaf chain.
+//    fp32 path (parity mode): v_mfma_f32_32x32x2_f32, bit-for-bit an fmaf chain: from the bias, per lane-vector slot v the
+//    k-slots (hi = 0, v) then (hi = 1, v) of pnr_mlp_layout.h, one fused multiply-add each (asserted on the device by
+//    tests/test_gpu_mlp_fp32_infer_sweep.py::test_the_fmaf_chain).
 //
 // HBM traffic per sample: 4 B of z (+32 B/ray) in, 4*(4+C+K) B of raw out; the kernel is
 // MFMA-bound (1.19 MFLOP/sample trunk + heads).

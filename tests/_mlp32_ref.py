@@ -189,6 +189,21 @@ def check_inputs(rep, desc, rays, z, X, trig_bound=None):
                          % (k, int((~(err <= trig_bound)).sum()), trig_bound, err.max().item()))
 
 
+def check_linear(rep, net, X, raw, name, src, dst, relu):
+    """one nn.Linear of linears(): float64 on the kernel's own input region(s) X[s] against the kernel's output region / raw rows"""
+    x = torch.cat([X[s] for s in src], 1).double()
+    w, b = net.w[name], net.b[name]
+    r, m, K = x @ w.t() + b, x.abs() @ w.abs().t() + b.abs(), x.shape[1]
+    k = X[dst] if isinstance(dst, str) else raw[:, dst[1]: dst[1] + dst[2]]
+    region = dst if isinstance(dst, str) else "raw[%s]" % name
+    if relu:
+        dead = r < -f32_bound(r, m, K + 2)
+        if (k < 0).any() or (k[dead] != 0).any():
+            rep.fail(region, "ReLU output negative, or non-zero where the pre-activation is below minus its bound")
+        r = r.clamp(min=0)
+    check_f32(rep, region, k, r, m, K + 2, key="fp32 " + ("raw" if region.startswith("raw") else region.rstrip("0123456789")))
+
+
 def check_forward(rep, desc, params, rays, z, raw, acts, trig_bound=None):
     """raw: an (S, channels) view of the kernel's image (any strides); acts: the flat fp32 buffer; rays (R, 8), z (R, N)"""
     S = z.numel()
@@ -196,17 +211,7 @@ def check_forward(rep, desc, params, rays, z, raw, acts, trig_bound=None):
     X = read_acts(desc, S, acts)
     check_inputs(rep, desc, rays, z, X, trig_bound)
     for name, src, dst, relu in linears(desc):
-        x = torch.cat([X[s] for s in src], 1).double()
-        w, b = net.w[name], net.b[name]
-        r, m, K = x @ w.t() + b, x.abs() @ w.abs().t() + b.abs(), x.shape[1]
-        k = X[dst] if isinstance(dst, str) else raw[:, dst[1]: dst[1] + dst[2]]
-        region = dst if isinstance(dst, str) else "raw[%s]" % name
-        if relu:
-            dead = r < -f32_bound(r, m, K + 2)
-            if (k < 0).any() or (k[dead] != 0).any():
-                rep.fail(region, "ReLU output negative, or non-zero where the pre-activation is below minus its bound")
-            r = r.clamp(min=0)
-        check_f32(rep, region, k, r, m, K + 2, key="fp32 " + ("raw" if region.startswith("raw") else region.rstrip("0123456789")))
+        check_linear(rep, net, X, raw, name, src, dst, relu)
     return rep
 
 
@@ -327,7 +332,7 @@ def colsum32(dy):
 def forward32(desc, params, rays, z, corrupt=None):
     """(raw (S, ch), acts flat) float32 numpy, as the kernels' order gives them; band values are float64 sin / cos of the stored
     argument rounded once.  corrupt: 'ktile' (pts_linears.0 loses the reduction rows from the last multiple of 16 on),
-    'skip_bias' (no bias in the skip layer's second launch), 'skip_order' (the skip layer reads [X, EX])."""
+    'skip_bias' (no bias in the skip layer's second launch), 'skip_order' (the skip layer reads [X, EX]), 'band_swap' (band 1 of gamma(x) stored as cos | sin)."""
     g = dims(desc)
     p = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in params.items()}
     rays, z = np.asarray(rays, np.float32), np.asarray(z, np.float32)
@@ -336,14 +341,15 @@ def forward32(desc, params, rays, z, corrupt=None):
     nrm = np.sqrt((d.astype(np.float64) ** 2).sum(1)).astype(np.float32)          # (the identity columns only need 8 u)
     vd = np.repeat((d / nrm[:, None]).astype(np.float32), N, 0)
 
-    def emb(x, L):
+    def emb(x, L, swap=False):
         cols = [x]
         for k in range(L):
             a = (x * np.float32(2.0 ** k)).astype(np.float64)
-            cols += [np.sin(a).astype(np.float32), np.cos(a).astype(np.float32)]
+            sc = [np.sin(a).astype(np.float32), np.cos(a).astype(np.float32)]
+            cols += sc[::-1] if (swap and k == 1) else sc
         return np.concatenate(cols, 1)
 
-    X = {"EX": emb(points32(rays, z), desc.xyz_L), "ED": emb(vd, desc.dir_L)}
+    X = {"EX": emb(points32(rays, z), desc.xyz_L, corrupt == "band_swap"), "ED": emb(vd, desc.dir_L)}
     raw = np.zeros((S, 4 + desc.n_sem + desc.n_inst), np.float32)
     for name, src, dst, relu in linears(desc):
         w, b = p[name + ".weight"], p[name + ".bias"]

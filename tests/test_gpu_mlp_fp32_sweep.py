@@ -35,14 +35,12 @@ import pytest
 import torch
 
 import _mlp32_ref as m32
+from _arena import GUARD, SENTINEL, Arena as _Arena
 from oracle import c_oracle as co
 from oracle import torch_oracle as to
 from panopticnerf_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -7.5e33
-GUARD = 64                      # floats on each side of every buffer
 
 _REPORT = os.environ.get("PNR_SWEEP_REPORT")
 _WORST = {}
@@ -60,31 +58,6 @@ def _report():
 
 def _p(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
-
-
-class _Arena:
-    """one device allocation filled with the sentinel; every buffer an interior view with a guard on both sides"""
-
-    def __init__(self, dev, sizes):
-        """sizes: [(name, floats, guard floats)]"""
-        self.off, o = {}, 0
-        guard_idx = []
-        for name, n, g in sizes:
-            self.off[name] = (o + g, n)
-            guard_idx += [torch.arange(o, o + g), torch.arange(o + g + n, o + 2 * g + n)]
-            o += n + 2 * g
-        self.buf = torch.full((o,), SENTINEL, device=dev, dtype=torch.float32)
-        self.guard_idx = torch.cat(guard_idx).to(dev)
-
-    def view(self, name):
-        o, n = self.off[name]
-        return self.buf[o:o + n]
-
-    def guards_intact(self):
-        return bool((self.buf[self.guard_idx] == SENTINEL).all())
-
-    def untouched(self):
-        return bool((self.buf == SENTINEL).all())
 
 
 def _rays(rng, R, near=0.5, far=8.0):
