@@ -4,6 +4,7 @@
 #include <math.h>
 
 #include "pnr_common.h"
+#include "pnr_sampling_dev.h"
 
 // One thread per ray, 256-thread blocks, grid-stride in whole blocks (the trip structure is block-uniform; the tail's surplus
 // lanes carry act = false).  The primitive loop and the plane loop are wave-uniform: offsets[] and the 16-byte plane records are
@@ -17,7 +18,10 @@
 //
 // The per-ray list: LDS = true (max_hits <= CONVEX_LDS_MAXH) keeps it in LDS as [entry][thread] (k_ray_setup's layout: a thread
 // touches only its own column, conflict-free, no barrier) and writes the output rows once at the end; LDS = false builds it in
-// the output rows as k_bbox_hits does.  Same insertion, same order: the max_hits nearest, ascending (t_in, primitive index).
+// the output rows as k_bbox_hits does, through the shared hit list of pnr_sampling_dev.h (hit_init, hit_insert).  Same insertion,
+// same order: the max_hits nearest, ascending (t_in, primitive index).  The LDS form is a kept copy on purpose, as in k_ray_setup:
+// through the shared pieces on an LDS column the kernel measured 121.3 us against 120.7 per frame, the parent's own spread being
+// 0.4 (profiles/sampling_frame/ab.txt).  Change the pieces and this together.
 #define CONVEX_LDS_MAXH 8
 
 template <bool LDS>
@@ -41,11 +45,7 @@ __global__ __launch_bounds__(256) void k_convex_hits(const float* __restrict__ r
 #pragma unroll
                 for (int h = 0; h < CONVEX_LDS_MAXH; ++h) { s_hb[h][tid] = -1; s_t[h][tid] = make_float2(0.0f, 0.0f); }
             } else {
-                for (int h = 0; h < max_hits; ++h) {
-                    hit_box[r * max_hits + h] = -1;
-                    hit_t[(r * max_hits + h) * 2 + 0] = 0.0f;
-                    hit_t[(r * max_hits + h) * 2 + 1] = 0.0f;
-                }
+                hit_init(hit_rows(hit_t, hit_box, r, max_hits), max_hits);      // the list, in the ray's output rows
             }
         }
         int cnt = 0;
@@ -66,9 +66,9 @@ __global__ __launch_bounds__(256) void k_convex_hits(const float* __restrict__ r
             }
             p = pe;
             if (act && tmin <= tmax) {
-                const int n = cnt < max_hits ? cnt : max_hits;
-                int pos = n;
-                if constexpr (LDS) {
+                if constexpr (LDS) {            // hit_insert on the LDS column: a kept copy (see the comment above the kernel)
+                    const int n = cnt < max_hits ? cnt : max_hits;
+                    int pos = n;
                     while (pos > 0 && s_t[pos - 1][tid].x > tmin) --pos;
                     if (pos < max_hits) {
                         for (int k = (n < max_hits ? n : max_hits - 1); k > pos; --k) {
@@ -78,24 +78,14 @@ __global__ __launch_bounds__(256) void k_convex_hits(const float* __restrict__ r
                         s_t[pos][tid] = make_float2(tmin, tmax);
                         s_hb[pos][tid] = m;
                     }
+                    ++cnt;
                 } else {
-                    while (pos > 0 && hit_t[(r * max_hits + pos - 1) * 2] > tmin) --pos;
-                    if (pos < max_hits) {
-                        for (int k = (n < max_hits ? n : max_hits - 1); k > pos; --k) {
-                            hit_t[(r * max_hits + k) * 2 + 0] = hit_t[(r * max_hits + k - 1) * 2 + 0];
-                            hit_t[(r * max_hits + k) * 2 + 1] = hit_t[(r * max_hits + k - 1) * 2 + 1];
-                            hit_box[r * max_hits + k] = hit_box[r * max_hits + k - 1];
-                        }
-                        hit_t[(r * max_hits + pos) * 2 + 0] = tmin;
-                        hit_t[(r * max_hits + pos) * 2 + 1] = tmax;
-                        hit_box[r * max_hits + pos] = m;
-                    }
+                    hit_insert(hit_rows(hit_t, hit_box, r, max_hits), cnt, max_hits, tmin, tmax, m);
                 }
-                ++cnt;                      // TRUE number of primitives hit: > max_hits reports the overflow
             }
         }
         if (act) {
-            hit_count[r] = cnt;
+            hit_count[r] = cnt;             // TRUE number of primitives hit: > max_hits reports the overflow
             if constexpr (LDS) {
                 for (int h = 0; h < max_hits; ++h) {
                     *reinterpret_cast<float2*>(hit_t + (r * max_hits + h) * 2) = s_t[h][tid];

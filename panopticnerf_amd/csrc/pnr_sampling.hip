@@ -2,53 +2,16 @@
 // gfx950 only.  The sampler, sample_pdf and bbox kernels are BIT-EXACT restatements of
 // oracle/pnr_oracle.c (pnro_stratified / pnro_points / pnro_sample_pdf / pnro_bbox_hits /
 // pnro_sample_labels), which since round 3 pins TORCH'S OWN op order (linspace two-sided, sum in
-// ATen's vector order, cumsum in double): same operations in the same order, one rounding each; the
-// file is compiled with -ffp-contract=off and the pragma below so no mul+add pair is fused.
+// ATen's vector order, cumsum in double): same operations in the same order, one rounding each.  The arithmetic that has to
+// be exact lives once, in pnr_sampling_dev.h (which also turns contraction off for this file); the kernels here are loops,
+// LDS layout and schedule around those pieces.
 // Reference functions these replace (the reference source
 // is not in the mount, include/pnr.h explains the citation form).
 #include "pnr_common.h"
 #include "pnr_philox.h"
+#include "pnr_sampling_dev.h"
 #include <stdlib.h>
 #include <string.h>
-
-#pragma clang fp contract(off)
-
-// torch.linspace(0, 1, N)[i] as ATen's CPU kernel computes it (two-sided; the upper half from the end point with one
-// rounding): oracle/pnr_oracle.c::pnro_linspace01, measured bit-exact against torch.  An explicit fmaf -- the file is built
-// with contraction off.
-__device__ __forceinline__ float pnr_linspace01(int i, int N)
-{
-    if (N <= 1) return 0.0f;
-    const float step = 1.0f / (float)(N - 1);
-    if (i < N / 2) return step * (float)i;
-    return fmaf(-step, (float)(N - 1 - i), 1.0f);
-}
-
-// ------------------------------------------------------------------------------- a3
-__device__ __forceinline__ float strat_z(float nr, float fr, int i, int N, int lindisp)
-{
-    const float t = pnr_linspace01(i, N);
-    const float omt = 1.0f - t;
-    if (!lindisp) {
-        const float a = nr * omt, b = fr * t;
-        return a + b;
-    }
-    const float a = (1.0f / nr) * omt, b = (1.0f / fr) * t;
-    return 1.0f / (a + b);
-}
-
-// sample i of a ray's N: the stratified depth, jittered inside its bin by *t when t is given (k_stratified, k_ray_setup)
-__device__ __forceinline__ float strat_sample(float nr, float fr, int i, int N, int lindisp, const float* t)
-{
-    const float zi = strat_z(nr, fr, i, N, lindisp);
-    if (!t) return zi;
-    const float z0 = strat_z(nr, fr, 0, N, lindisp), zl = strat_z(nr, fr, N - 1, N, lindisp);
-    const float lo = (i == 0) ? z0 : 0.5f * (zi + strat_z(nr, fr, i - 1, N, lindisp));
-    const float up = (i == N - 1) ? zl : 0.5f * (strat_z(nr, fr, i + 1, N, lindisp) + zi);
-    const float w = up - lo;
-    const float m = w * *t;
-    return lo + m;
-}
 
 // One thread per sample; HBM-bound: reads 8 B/ray amortised (+4 B t_rand), writes 4 B.
 // Rng = PnrRngDev (pnr_stratified_rng): the jitter is the in-kernel stream's uniform of the sample instead of t_rand[s]; the plain
@@ -120,23 +83,6 @@ __global__ __launch_bounds__(256) void k_embed(const float* __restrict__ x, int6
 // oracle's sequential fp32 order (the bit-exact index requirement, SURVEY.md section 7 "hard
 // parts"); everything else is lane-parallel: bins, pdf, one upper_bound per u, and a bitonic
 // sort of the Nc+Nf union in LDS (a rank-based merge when the new samples are already ascending).  LDS: 7 KiB.
-// the kept interval a sample at depth zz takes its label from: the one with the smallest t_in among those containing it (-1: none)
-template <class F>
-__device__ __forceinline__ int label_hit(float zz, int cnt, F interval)
-{
-    int best = -1;
-    float bt = 0.0f;
-    for (int h = 0; h < cnt; ++h) {
-        float ti, to;
-        interval(h, ti, to);
-        if (ti <= zz && zz <= to && (best < 0 || ti < bt)) {
-            best = h;
-            bt = ti;
-        }
-    }
-    return best;
-}
-
 // With lab.label_sem set the wave that merged a ray's samples also labels them (k_sample_labels' rule on the sorted z it still
 // holds in LDS): the fine level's labels without a second pass over z (pnr_sample_pdf_labels; one launch less per chunk).
 struct PdfLabelArgs {
@@ -145,15 +91,15 @@ struct PdfLabelArgs {
 };
 #define PDF_MAXC 256
 #define PDF_MAXT 512
-template <int MAXC, int MAXT, bool RNG = false>
+template <int MAXC, int MAXT, class... Rng>
 __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, const float* __restrict__ weights,
                                                     const float* __restrict__ u, int64_t R, int Nc, int Nf,
                                                     float* __restrict__ zs_out, int32_t* __restrict__ inds_out,
-                                                    float* __restrict__ zfine_out, const PdfLabelArgs lab,
-                                                    const PnrRngDev& rng = PnrRngDev{})
+                                                    float* __restrict__ zfine_out, const PdfLabelArgs lab, const Rng&... rng)
 {
+    constexpr bool RNG = sizeof...(Rng) > 0;
     PnrRngKey key;         // RNG: u of (ray r, sample i) is the in-kernel stream's uniform (pnr_sample_pdf_rng)
-    if constexpr (RNG) key = pnr_rng_key(rng);
+    if constexpr (RNG) key = pnr_rng_key(rng...);
     // MAXC / MAXT: the LDS footprint sets how many rays a CU has in flight, and this kernel is all latency (dependent LDS searches,
     // a dozen barriers per ray): 9.4 KiB per ray held 17 waves per CU, the <64, 256> instance (64 + 128 samples: every BASELINE
     // config) 3.4 KiB holds the CU's 32
@@ -162,9 +108,7 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
     __shared__ float s_total, s_part[32];
     const int lane = threadIdx.x;
     const int nb = Nc - 1, nw = Nc - 2, Nt = Nc + Nf;
-    const bool short4 = nw >= 4 && nw < 8;       // a row ATen sums with four scalar accumulators (see the sum below)
-    int P = 1;
-    while (P < Nt) P <<= 1;
+    const int P = pdf_padded(Nt);
     auto labels = [&](int64_t r, const float* sorted) {       // sorted: the ray's Nt merged depths in LDS (written before a barrier)
         if (!lab.label_sem) return;
         const int mh = lab.max_hits;
@@ -174,12 +118,8 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
                 ti = lab.hit_t[(r * mh + h) * 2];
                 to = lab.hit_t[(r * mh + h) * 2 + 1];
             });
-            int ls = -1, li = -1;
-            if (best >= 0) {
-                const int m = lab.hit_box[r * mh + best];
-                ls = lab.box_ids[m * 2];
-                li = lab.box_ids[m * 2 + 1];
-            }
+            int ls, li;
+            hit_ids(best, lab.hit_box + r * mh + best, lab.box_ids, &ls, &li);
             lab.label_sem[r * Nt + i] = ls;
             lab.label_inst[r * Nt + i] = li;
         }
@@ -191,67 +131,10 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
         }
         __syncthreads();
         for (int k = lane; k < nb; k += 64) s_bins[k] = 0.5f * (s_z[k + 1] + s_z[k]);
-        // total = torch.sum(w) in ATen's order (pnro_torch_sum).  nw >= 8: 8-lane vectors, four partial vectors interleaved -> lane
-        // 8 k + l owns accumulator (k, l) and adds its elements in ascending order, exactly as the vector code does; then the scalar
-        // tail from 0 and the 8 lanes of partial 0.  nw < 8 (no whole vector) is ATen's scalar row sum with four accumulators: a[k] = x[k],
-        // k < 4 (when nw >= 4), x[4..] added in order into a[0], result ((a[0] + a[1]) + a[2]) + a[3].  Same code: the "tail" is then
-        // a[0] (x[0], x[4], x[5], ...), lanes 0..2 hold a[1..3] as partials (0, l) (+ 0 is exact), and the lane-order adds finish it.
-        if (lane < 32) {
-            const int k = lane >> 3, l = lane & 7, nv = nw / 8, groups = nv / 4;
-            float pacc = 0.0f;
-            for (int g = 0; g < groups; ++g) pacc = pacc + (s_w[(g * 4 + k) * 8 + l + 1] + 1e-5f);
-            if (k == 0)
-                for (int v = groups * 4; v < nv; ++v) pacc = pacc + (s_w[v * 8 + l + 1] + 1e-5f);
-            if (short4 && lane < 3) pacc = pacc + (s_w[lane + 2] + 1e-5f);       // a[1..3] of the scalar row sum
-            s_part[lane] = pacc;
-        }
-        __syncthreads();
-        if (lane == 0) {
-            const int nv = nw / 8;
-            float total = 0.0f;
-            // the scalar tail, from 0 (a short row's a[0]: x[0], then x[4] onwards)
-            for (int j = nv * 8; j < nw; j = (short4 && j == 0) ? 4 : j + 1) total = total + (s_w[j + 1] + 1e-5f);
-            for (int l = 0; l < 8; ++l) {
-                float p0 = s_part[l];
-                p0 = p0 + s_part[8 + l]; p0 = p0 + s_part[16 + l]; p0 = p0 + s_part[24 + l];
-                total = total + p0;
-            }
-            s_total = total;
-        }
-        __syncthreads();
-        const float total = s_total;
+        const float total = pdf_torch_total(s_w, nw, s_part, &s_total, lane);
         for (int j = lane; j < nw; j += 64) s_pdf[j] = (s_w[j + 1] + 1e-5f) / total;
         __syncthreads();
-        // torch.cumsum: the running sum is kept in DOUBLE, every output rounded to fp32 -- a sequential chain of nw f64 adds
-        // (with its LDS traffic, half of this kernel's issue cycles when one lane walks it).  The pdf values are fp32 and
-        // non-negative: when every one of them is 0 or >= 2^-28, each is a multiple of 2^-51, and when their sum is < 2 so is
-        // every partial sum of ANY subset -- 52 significant bits at most: no f64 add ever rounds, and a parallel prefix scan
-        // returns the sequential chain's values bit for bit.  (pdf_j >= 1e-5 / total and sum(pdf) ~ 1: always the case for
-        // compositing weights; the sum is checked on the scan's own result, which is exact whenever the true sum is < 2.)
-        // Otherwise, and for more than 64 values, the sequential chain runs.
-        const float pl = lane < nw ? s_pdf[lane < nw ? lane : 0] : 0.0f;
-        double c = (double)pl;
-        bool exact = nw <= 64 && __all(pl == 0.0f || pl >= 0x1p-28f);
-        if (exact) {
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double o = __shfl_up(c, d, 64);
-                if (lane >= d) c += o;
-            }
-            exact = __shfl(c, 63, 64) < 1.999;
-        }
-        if (exact) {
-            if (lane == 0) s_cdf[0] = 0.0f;
-            if (lane < nw) s_cdf[lane + 1] = (float)c;
-        } else if (lane == 0) {
-            double c = 0.0;
-            s_cdf[0] = 0.0f;
-            for (int j = 0; j < nw; ++j) {
-                c += (double)s_pdf[j];
-                s_cdf[j + 1] = (float)c;
-            }
-        }
-        __syncthreads();
+        pdf_cdf(lane < nw ? s_pdf[lane < nw ? lane : 0] : 0.0f, nw, nw <= 64, s_pdf, s_cdf, lane);
         for (int i = lane; i < Nf; i += 64) {
             float uu;
             if constexpr (RNG) uu = pnr_rng_uniform_at(key, (uint32_t)r, i);
@@ -261,17 +144,9 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
                 const int mid = (lo + hi) >> 1;
                 if (s_cdf[mid] <= uu) lo = mid + 1; else hi = mid;
             }
-            const int inds = lo;
-            const int below = inds - 1 > 0 ? inds - 1 : 0;
-            const int above = inds < nb - 1 ? inds : nb - 1;
-            float denom = s_cdf[above] - s_cdf[below];
-            if (denom < 1e-5f) denom = 1.0f;
-            const float t = (uu - s_cdf[below]) / denom;
-            const float span = s_bins[above] - s_bins[below];
-            const float m = t * span;
-            const float zs = s_bins[below] + m;
+            const float zs = pdf_invert(uu, lo, nb, s_cdf, s_bins);
             if (zs_out) zs_out[r * Nf + i] = zs;
-            if (inds_out) inds_out[r * Nf + i] = inds;
+            if (inds_out) inds_out[r * Nf + i] = lo;
             s_sort[Nc + i] = zs;
         }
         if (zfine_out) {
@@ -305,21 +180,7 @@ __device__ __forceinline__ void sample_pdf_body(const float* __restrict__ z, con
             for (int i = lane; i < Nc; i += 64) s_sort[i] = s_z[i];
             for (int i = Nt + lane; i < P; i += 64) s_sort[i] = INFINITY;
             __syncthreads();
-            for (int k = 2; k <= P; k <<= 1) {
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int t = lane; t < (P >> 1); t += 64) {
-                        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                        const int p = i | j;
-                        const float a = s_sort[i], b = s_sort[p];
-                        const bool asc = (i & k) == 0;
-                        if ((a > b) == asc) {
-                            s_sort[i] = b;
-                            s_sort[p] = a;
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
+            pdf_bitonic(s_sort, P, lane);
             for (int i = lane; i < Nt; i += 64) zfine_out[r * Nt + i] = s_sort[i];
             labels(r, s_sort);
         }
@@ -343,21 +204,7 @@ __device__ __noinline__ void pdf_bitonic_fallback(float* s_sort, const float* s_
     for (int i = lane; i < Nf; i += 64) s_sort[Nc + i] = s_zs[i];
     for (int i = Nt + lane; i < P; i += 64) s_sort[i] = INFINITY;
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (P >> 1); t += 64) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int p = i | j;
-                const float a = s_sort[i], b = s_sort[p];
-                const bool asc = (i & k) == 0;
-                if ((a > b) == asc) {
-                    s_sort[i] = b;
-                    s_sort[p] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    pdf_bitonic(s_sort, P, lane);
 }
 
 #ifndef PDF_DET_WPE
@@ -377,8 +224,7 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
     __shared__ float s_total, s_part[32];
     const int lane = threadIdx.x;
     const int nb = Nc - 1, nw = Nc - 2, Nt = Nc + Nf;
-    const bool short4 = nw >= 4 && nw < 8;       // a row ATen sums with four scalar accumulators (see the sum below)
-    int topc = 1, topf = 1;                      // the largest powers of two <= Nc, <= Nf: first strides of the bisections
+    int topc = 1, topf = 1;                     // the largest powers of two <= Nc, <= Nf: first strides of the bisections
     while (topc * 2 <= Nc) topc *= 2;
     while (topf * 2 <= Nf) topf *= 2;
     const int mh = lab.max_hits;
@@ -395,9 +241,7 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
             if (lane < cnt) {
                 const float2 t2 = *reinterpret_cast<const float2*>(lab.hit_t + (r * mh + lane) * 2);
                 h_ti = t2.x; h_to = t2.y;
-                const int m = lab.hit_box[r * mh + lane];
-                h_ls = lab.box_ids[m * 2];
-                h_li = lab.box_ids[m * 2 + 1];
+                hit_ids(lane, lab.hit_box + r * mh + lane, lab.box_ids, &h_ls, &h_li);
             }
         }
         s_z[lane] = zl;
@@ -405,59 +249,12 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
         const float zn = __shfl_down(zl, 1, 64), wn = __shfl_down(wl, 1, 64);
         s_bins[lane] = 0.5f * (zn + zl);             // bins[k] = 0.5 (z[k + 1] + z[k]), k < nb
         __syncthreads();
-        // total = torch.sum(w[1:-1] + 1e-5) in ATen's order: sample_pdf_body's code (the vector order for nw >= 8, ATen's scalar row sum
-        // with four accumulators for shorter rows: lanes 0..2 hold a[1..3], the "tail" is a[0])
-        if (lane < 32) {
-            const int k = lane >> 3, l = lane & 7, nv = nw / 8, groups = nv / 4;
-            float pacc = 0.0f;
-            for (int g = 0; g < groups; ++g) pacc = pacc + (s_w[(g * 4 + k) * 8 + l + 1] + 1e-5f);
-            if (k == 0)
-                for (int v = groups * 4; v < nv; ++v) pacc = pacc + (s_w[v * 8 + l + 1] + 1e-5f);
-            if (short4 && lane < 3) pacc = pacc + (s_w[lane + 2] + 1e-5f);       // a[1..3] of the scalar row sum
-            s_part[lane] = pacc;
-        }
-        __syncthreads();
-        if (lane == 0) {
-            const int nv = nw / 8;
-            float total = 0.0f;
-            for (int j = nv * 8; j < nw; j = (short4 && j == 0) ? 4 : j + 1) total = total + (s_w[j + 1] + 1e-5f);
-            for (int l = 0; l < 8; ++l) {
-                float p0 = s_part[l];
-                p0 = p0 + s_part[8 + l]; p0 = p0 + s_part[16 + l]; p0 = p0 + s_part[24 + l];
-                total = total + p0;
-            }
-            s_total = total;
-        }
-        __syncthreads();
-        const float total = s_total;
+        const float total = pdf_torch_total(s_w, nw, s_part, &s_total, lane);
         const float pl = lane < nw ? (wn + 1e-5f) / total : 0.0f;      // pdf[j] = (w[j + 1] + 1e-5) / total
         s_pdf[lane] = pl;
-        double c = (double)pl;
-        bool exact = __all(pl == 0.0f || pl >= 0x1p-28f);
-        if (exact) {
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double o = __shfl_up(c, d, 64);
-                if (lane >= d) c += o;
-            }
-            exact = __shfl(c, 63, 64) < 1.999;
-        }
-        if (exact) {
-            if (lane == 0) s_cdf[0] = 0.0f;
-            if (lane < nw) s_cdf[lane + 1] = (float)c;
-        } else {
-            __syncthreads();
-            if (lane == 0) {
-                double cc = 0.0;
-                s_cdf[0] = 0.0f;
-                for (int j = 0; j < nw; ++j) {
-                    cc += (double)s_pdf[j];
-                    s_cdf[j + 1] = (float)cc;
-                }
-            }
-        }
-        __syncthreads();
-        // inverse CDF at the Nf deterministic u: upper bound over cdf[0 .. nb) by bisection (cdf is non-decreasing)
+        pdf_cdf(pl, nw, true, s_pdf, s_cdf, lane);       // Nc <= 64 here
+        // inverse CDF at the Nf deterministic u: upper bound over cdf[0 .. nb) by bisection (cdf is non-decreasing) -- this kernel's
+        // own search (fixed depth, branch-free), kept apart from sample_pdf_body's loop: it is the point of the instance
         bool asc = lane + 1 >= Nc || zl <= zn;
         for (int i = lane; i < Nf; i += 64) {
             const float uu = pnr_linspace01(i, Nf);
@@ -466,18 +263,7 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
                 const int p = pos + st, q = p <= nb ? p : nb;
                 pos = (p <= nb && s_cdf[q - 1] <= uu) ? p : pos;
             }
-            const int inds = pos;
-            const int below = inds - 1 > 0 ? inds - 1 : 0;
-            const int above = inds < nb - 1 ? inds : nb - 1;
-            const float cb = s_cdf[below];
-            float denom = s_cdf[above] - cb;
-            if (denom < 1e-5f) denom = 1.0f;
-            const float t = (uu - cb) / denom;
-            const float bb = s_bins[below];
-            const float span = s_bins[above] - bb;
-            const float m = t * span;
-            const float zs = bb + m;
-            s_zs[i] = zs;
+            s_zs[i] = pdf_invert(uu, pos, nb, s_cdf, s_bins);
         }
         __syncthreads();
         for (int i = lane; i + 1 < Nf; i += 64) asc = asc && (s_zs[i] <= s_zs[i + 1]);
@@ -502,11 +288,11 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
             }
             __syncthreads();
         } else {
-            int P = 1;
-            while (P < Nt) P <<= 1;
-            pdf_bitonic_fallback(s_out, s_z, s_zs, Nc, Nf, P, lane);
+            pdf_bitonic_fallback(s_out, s_z, s_zs, Nc, Nf, pdf_padded(Nt), lane);
         }
-        // the sorted union, and its labels (k_sample_labels' rule: the containing interval with the smallest t_in, lowest index first)
+        // the sorted union, and its labels (k_sample_labels' rule: the containing interval with the smallest t_in, lowest index first).
+        // A kept copy of label_hit + hit_ids on purpose: the hit loop is OUTERMOST over v_readlane broadcasts of the per-lane entries,
+        // four samples per lane in registers, ids carried along -- the shared pieces loop over hits per sample from memory
         float* __restrict__ zo = zfine_out + r * Nt;
         for (int i0 = 0; i0 < Nt; i0 += 256) {
             float zz[4];
@@ -547,33 +333,16 @@ __global__ __launch_bounds__(64) void k_sample_pdf_det(const float* __restrict__
     }
 }
 
-// two instances: <64, 256> (64 + 128 samples: every BASELINE config) at 64 registers and 3.4 KiB of LDS holds 8 waves per SIMD; the
-// general one (up to 256 + 256 samples) is bound by its 9.1 KiB of LDS per ray
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
+// four instances: <64, 256> (64 + 128 samples: every BASELINE config) held to 64 registers, with 3.4 KiB of LDS 8 waves per SIMD; the
+// general one <PDF_MAXC, PDF_MAXT> (up to 256 + 256 samples) is bound by its 9.1 KiB of LDS per ray and left to the compiler's own
+// range (1 .. 8); each with Rng = PnrRngDev, u drawn in the kernel (pnr_sample_pdf_rng / pnr_sample_pdf_labels_rng; u is then null)
+template <int MAXC, int MAXT, class... Rng>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXC <= 64 ? 8 : 1, 8)))
 void k_sample_pdf(const float* __restrict__ z, const float* __restrict__ weights, const float* __restrict__ u, int64_t R, int Nc, int Nf,
-                  float* __restrict__ zs_out, int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab)
+                  float* __restrict__ zs_out, int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab,
+                  const Rng... rng)
 {
-    sample_pdf_body<64, 256>(z, weights, u, R, Nc, Nf, zs_out, inds_out, zfine_out, lab);
-}
-__global__ __launch_bounds__(64)
-void k_sample_pdf_big(const float* __restrict__ z, const float* __restrict__ weights, const float* __restrict__ u, int64_t R, int Nc, int Nf,
-                      float* __restrict__ zs_out, int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab)
-{
-    sample_pdf_body<PDF_MAXC, PDF_MAXT>(z, weights, u, R, Nc, Nf, zs_out, inds_out, zfine_out, lab);
-}
-// the two instances with u drawn in the kernel (pnr_sample_pdf_rng / pnr_sample_pdf_labels_rng)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
-void k_sample_pdf_rng(const float* __restrict__ z, const float* __restrict__ weights, int64_t R, int Nc, int Nf, float* __restrict__ zs_out,
-                      int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab, const PnrRngDev rng)
-{
-    sample_pdf_body<64, 256, true>(z, weights, nullptr, R, Nc, Nf, zs_out, inds_out, zfine_out, lab, rng);
-}
-__global__ __launch_bounds__(64)
-void k_sample_pdf_big_rng(const float* __restrict__ z, const float* __restrict__ weights, int64_t R, int Nc, int Nf,
-                          float* __restrict__ zs_out, int32_t* __restrict__ inds_out, float* __restrict__ zfine_out, const PdfLabelArgs lab,
-                          const PnrRngDev rng)
-{
-    sample_pdf_body<PDF_MAXC, PDF_MAXT, true>(z, weights, nullptr, R, Nc, Nf, zs_out, inds_out, zfine_out, lab, rng);
+    sample_pdf_body<MAXC, MAXT>(z, weights, u, R, Nc, Nf, zs_out, inds_out, zfine_out, lab, rng...);
 }
 
 // ------------------------------------------------------------------------------- a8
@@ -585,51 +354,16 @@ __global__ __launch_bounds__(256) void k_bbox_hits(const float* __restrict__ ray
 {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R;
          r += (int64_t)gridDim.x * blockDim.x) {
-        const float o0 = rays[r * 8 + 0], o1 = rays[r * 8 + 1], o2 = rays[r * 8 + 2];
-        const float d0 = rays[r * 8 + 3], d1 = rays[r * 8 + 4], d2 = rays[r * 8 + 5];
-        const float nr = rays[r * 8 + 6], fr = rays[r * 8 + 7];
-        for (int h = 0; h < max_hits; ++h) {
-            hit_box[r * max_hits + h] = -1;
-            hit_t[(r * max_hits + h) * 2 + 0] = 0.0f;
-            hit_t[(r * max_hits + h) * 2 + 1] = 0.0f;
-        }
+        const RayRec ry = ray_load(rays, r);
+        const auto list = hit_rows(hit_t, hit_box, r, max_hits);        // built in place, in the ray's output rows
+        hit_init(list, max_hits);
         int cnt = 0;
         for (int m = 0; m < M; ++m) {
-            const float* b = box + m * 15;
-            const float p0 = o0 - b[0], p1 = o1 - b[1], p2 = o2 - b[2];
-            float tmin = nr, tmax = fr;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float r0 = b[3 + 3 * a], r1 = b[4 + 3 * a], r2 = b[5 + 3 * a];
-                const float ol = (r0 * p0 + r1 * p1) + r2 * p2;
-                const float dl = (r0 * d0 + r1 * d1) + r2 * d2;
-                const float inv = 1.0f / dl;
-                const float e = b[12 + a];
-                const float t1 = (-e - ol) * inv, t2 = (e - ol) * inv;
-                tmin = fmaxf(tmin, fminf(t1, t2));
-                tmax = fminf(tmax, fmaxf(t1, t2));
-            }
-            if (tmin <= tmax) {
-                // keep the max_hits NEAREST intervals, ascending (t_in, box index): a street-scene ray crosses more boxes
-                // than max_hits, and the near ones are the ones its samples fall in.  Insertion from the back; the
-                // farthest entry falls off the end.  (Same op order as pnro_bbox_hits: bit-exact.)
-                const int n = cnt < max_hits ? cnt : max_hits;
-                int pos = n;
-                while (pos > 0 && hit_t[(r * max_hits + pos - 1) * 2] > tmin) --pos;
-                if (pos < max_hits) {
-                    for (int k = (n < max_hits ? n : max_hits - 1); k > pos; --k) {
-                        hit_t[(r * max_hits + k) * 2 + 0] = hit_t[(r * max_hits + k - 1) * 2 + 0];
-                        hit_t[(r * max_hits + k) * 2 + 1] = hit_t[(r * max_hits + k - 1) * 2 + 1];
-                        hit_box[r * max_hits + k] = hit_box[r * max_hits + k - 1];
-                    }
-                    hit_t[(r * max_hits + pos) * 2 + 0] = tmin;
-                    hit_t[(r * max_hits + pos) * 2 + 1] = tmax;
-                    hit_box[r * max_hits + pos] = m;
-                }
-                ++cnt;                      // TRUE number of intersected boxes: > max_hits reports the overflow
-            }
+            float tmin, tmax;
+            slab_interval(box + m * 15, ry, &tmin, &tmax);
+            if (tmin <= tmax) hit_insert(list, cnt, max_hits, tmin, tmax, m);
         }
-        hit_count[r] = cnt;
+        hit_count[r] = cnt;             // TRUE number of intersected boxes
     }
 }
 
@@ -662,6 +396,9 @@ __global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a, const R
     for (int64_t base = (int64_t)blockIdx.x * 64; base < a.R; base += (int64_t)gridDim.x * 64) {
         const int64_t r = base + tid;
         if (tid < 64 && r < a.R) {              // phase 1: the block's first wave (the others are in another block's phase 2)
+            // A kept copy on purpose of ray_load, slab_interval, hit_init / hit_insert / the flush and hit_hull (pnr_sampling_dev.h), on
+            // the LDS column: assembled from the shared pieces (same registers, LDS and bits) this kernel measured 52.6 us against 50.6
+            // per 65,536 rays, the parent's own spread being 0.5 (profiles/sampling_frame/ab.txt).  Change the pieces and this together.
             const float4 ra = *reinterpret_cast<const float4*>(a.rays + r * 8), rb = *reinterpret_cast<const float4*>(a.rays + r * 8 + 4);
             const float o0 = ra.x, o1 = ra.y, o2 = ra.z, d0 = ra.w, d1 = rb.x, d2 = rb.y;
             float nr = rb.z, fr = rb.w;
@@ -682,7 +419,7 @@ __global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a, const R
                     tmin = fmaxf(tmin, fminf(t1, t2));
                     tmax = fminf(tmax, fmaxf(t1, t2));
                 }
-                if (tmin <= tmax) {             // k_bbox_hits' insertion: the max_hits nearest, ascending (t_in, box index)
+                if (tmin <= tmax) {             // hit_insert: the max_hits nearest, ascending (t_in, box index)
                     const int n = cnt < mh ? cnt : mh;
                     int pos = n;
                     while (pos > 0 && s_t[pos - 1][tid].x > tmin) --pos;
@@ -703,7 +440,7 @@ __global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a, const R
                 *reinterpret_cast<float2*>(a.hit_t + (r * mh + h) * 2) = s_t[h][tid];
                 a.hit_box[r * mh + h] = s_hb[h][tid];
             }
-            if (a.hull && kept > 0) {           // k_restrict_rays: the hull of the kept intervals replaces [near, far]
+            if (a.hull && kept > 0) {           // hit_hull: the hull of the kept intervals replaces [near, far]
                 float lo = s_t[0][tid].x, hi = s_t[0][tid].y;
                 for (int h = 1; h < kept; ++h) {
                     lo = fminf(lo, s_t[h][tid].x);
@@ -755,7 +492,9 @@ __global__ __launch_bounds__(256) void k_ray_setup(const RaySetupArgs a, const R
                         int best = -1, m = -1;
                         float bt = 0.0f;
 #pragma unroll
-                        for (int h = 0; h < SETUP_MAXH; ++h) {      // label_hit, unrolled over registers
+                        // A kept copy of label_hit + hit_ids on purpose: unrolled over the ray's entries in (scalar) REGISTERS, the
+                        // box index carried along -- label_hit's loop reads each entry through an accessor, per sample
+                        for (int h = 0; h < SETUP_MAXH; ++h) {
                             if (h >= cnt[u]) break;
                             const float ti = iv[u][h].x, to = iv[u][h].y;
                             if (ti <= zz && zz <= to && (best < 0 || ti < bt)) { best = h; bt = ti; m = hb[u][h]; }
@@ -793,6 +532,8 @@ __global__ __launch_bounds__(256) void k_sample_labels(const float* __restrict__
             ti = hit_t[(r * max_hits + h) * 2];
             to = hit_t[(r * max_hits + h) * 2 + 1];
         });
+        // hit_ids, spelled out: through the shared piece this kernel measured 14.6 us against 14.3 per 65,536 x 64 samples in three
+        // sessions, the parent's spread being 0.3 (profiles/sampling_frame/ab.txt)
         int ls = -1, li = -1;
         if (best >= 0) {
             const int m = hit_box[r * max_hits + best];
@@ -860,107 +601,79 @@ PNR_EXPORT int pnr_embed(const float* x, int64_t n, int L, float* out, void* str
     return PNR_OK;
 }
 
-// u drawn in the kernel: the instances that take u (never k_sample_pdf_det: its u is deterministic)
-static void launch_sample_pdf_rng(const float* z, const float* weights, const PnrRngDev& rng, int64_t n_rays, int n_coarse, int n_fine,
-                                  float* z_samples, int32_t* inds, float* z_fine, const PdfLabelArgs& lab, hipStream_t st)
+// The one launch of the a7 family.  k_sample_pdf_det when that is what is asked (deterministic u, merged z_fine (+ labels) only)
+// and it fits; else the general body, its small instance when the padded union does.  rng: u drawn in the kernel (never
+// k_sample_pdf_det: its u is deterministic).
+static void launch_sample_pdf(const float* z, const float* weights, const float* u, const PnrRngDev* rng, int64_t n_rays, int n_coarse,
+                              int n_fine, float* z_samples, int32_t* inds, float* z_fine, const PdfLabelArgs& lab, hipStream_t st)
 {
-    int P = 1;
-    while (P < n_coarse + n_fine) P <<= 1;
-    if (n_coarse <= 64 && P <= 256)
-        hipLaunchKernelGGL(k_sample_pdf_rng, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, n_rays, n_coarse, n_fine,
-                           z_samples, inds, z_fine, lab, rng);
+    const dim3 grid(pnr_grid_cap(n_rays, 32)), block(64);
+    const bool small = n_coarse <= 64 && pdf_padded(n_coarse + n_fine) <= 256;
+    auto go = [&](auto kernel, auto... r) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, z, weights, u, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, lab, r...);
+    };
+    // PNR_SAMPLE_PDF_GENERAL: A/B switch (tests, tools): the general body everywhere
+    if (!rng && !u && !z_samples && !inds && z_fine && small && n_fine <= 192 && lab.max_hits <= 64 && !getenv("PNR_SAMPLE_PDF_GENERAL"))
+        hipLaunchKernelGGL(k_sample_pdf_det, grid, block, 0, st, z, weights, n_rays, n_coarse, n_fine, z_fine, lab);
+    else if (rng)
+        go(small ? k_sample_pdf<64, 256, PnrRngDev> : k_sample_pdf<PDF_MAXC, PDF_MAXT, PnrRngDev>, *rng);
     else
-        hipLaunchKernelGGL(k_sample_pdf_big_rng, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, n_rays, n_coarse, n_fine,
-                           z_samples, inds, z_fine, lab, rng);
+        go(small ? k_sample_pdf<64, 256> : k_sample_pdf<PDF_MAXC, PDF_MAXT>);
 }
 
-static void launch_sample_pdf(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
-                              float* z_samples, int32_t* inds, float* z_fine, const PdfLabelArgs& lab, hipStream_t st)
+// One body behind the four entry points: name = the entry point's own (it is in every message); with_rng: rng_host is checked and u
+// drawn in the kernel; labels: the hit lists and label outputs of the _labels forms (a7 + a8: z_fine as pnr_sample_pdf, and the
+// labels pnr_sample_labels would give for it, in the same launch), null for the plain forms.
+static int sample_pdf_impl(const char* name, const float* z, const float* weights, const float* u, bool with_rng, const pnr_rng* rng_host,
+                           int64_t n_rays, int n_coarse, int n_fine, float* z_samples, int32_t* inds, float* z_fine,
+                           const PdfLabelArgs* labels, void* stream)
 {
-    int P = 1;
-    while (P < n_coarse + n_fine) P <<= 1;              // the bitonic path pads the union to a power of two
-    const bool general_only = getenv("PNR_SAMPLE_PDF_GENERAL") != nullptr;      // A/B switch (tests, tools): the general body everywhere
-    if (!u && !z_samples && !inds && z_fine && n_coarse <= 64 && n_fine <= 192 && P <= 256 && lab.max_hits <= 64 && !general_only)
-        hipLaunchKernelGGL(k_sample_pdf_det, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, n_rays, n_coarse, n_fine, z_fine, lab);
-    else if (n_coarse <= 64 && P <= 256)
-        hipLaunchKernelGGL(k_sample_pdf, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, u, n_rays, n_coarse, n_fine,
-                           z_samples, inds, z_fine, lab);
-    else
-        hipLaunchKernelGGL(k_sample_pdf_big, dim3(pnr_grid_cap(n_rays, 32)), dim3(64), 0, st, z, weights, u, n_rays, n_coarse,
-                           n_fine, z_samples, inds, z_fine, lab);
+    PnrRngDev rng;
+    if (with_rng) {
+        const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, name, &rng);
+        if (rc) return rc;
+    }
+    PNR_REQUIRE(n_rays <= 0 || (z && weights && (!labels || z_fine)), "%s: null pointer", name);
+    PNR_REQUIRE(!labels || n_rays <= 0 || (labels->hit_t && labels->hit_box && labels->hit_count && labels->box_ids && labels->label_sem &&
+                                           labels->label_inst), "%s: null pointer", name);
+    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "%s: n_coarse=%d outside [3,%d]", name, n_coarse, PDF_MAXC);
+    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "%s: n_coarse+n_fine=%d > %d", name, n_coarse + n_fine, PDF_MAXT);
+    PNR_REQUIRE(!labels || labels->max_hits >= 1, "%s: bad max_hits", name);
+    if (n_rays <= 0) return PNR_OK;
+    launch_sample_pdf(z, weights, u, with_rng ? &rng : nullptr, n_rays, n_coarse, n_fine, z_samples, inds, z_fine,
+                      labels ? *labels : PdfLabelArgs{}, (hipStream_t)stream);
+    PNR_CHECK_LAUNCH(name);
+    return PNR_OK;
 }
 
 PNR_EXPORT int pnr_sample_pdf(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse,
                               int n_fine, float* z_samples, int32_t* inds, float* z_fine, void* stream)
 {
-    PNR_REQUIRE(n_rays <= 0 || (z && weights), "pnr_sample_pdf: null pointer");
-    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
-    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf: n_coarse+n_fine=%d > %d",
-                n_coarse + n_fine, PDF_MAXT);
-    if (n_rays <= 0) return PNR_OK;
-    PdfLabelArgs lab;
-    memset(&lab, 0, sizeof(lab));
-    launch_sample_pdf(z, weights, u, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, lab, (hipStream_t)stream);
-    PNR_CHECK_LAUNCH("pnr_sample_pdf");
-    return PNR_OK;
+    return sample_pdf_impl("pnr_sample_pdf", z, weights, u, false, nullptr, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, nullptr, stream);
 }
 
 PNR_EXPORT int pnr_sample_pdf_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse,
                                   int n_fine, float* z_samples, int32_t* inds, float* z_fine, void* stream)
 {
-    PnrRngDev rng;
-    const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, "pnr_sample_pdf_rng", &rng);
-    if (rc) return rc;
-    PNR_REQUIRE(n_rays <= 0 || (z && weights), "pnr_sample_pdf_rng: null pointer");
-    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf_rng: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
-    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf_rng: n_coarse+n_fine=%d > %d", n_coarse + n_fine, PDF_MAXT);
-    if (n_rays <= 0) return PNR_OK;
-    PdfLabelArgs lab;
-    memset(&lab, 0, sizeof(lab));
-    launch_sample_pdf_rng(z, weights, rng, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, lab, (hipStream_t)stream);
-    PNR_CHECK_LAUNCH("pnr_sample_pdf_rng");
-    return PNR_OK;
+    return sample_pdf_impl("pnr_sample_pdf_rng", z, weights, nullptr, true, rng_host, n_rays, n_coarse, n_fine, z_samples, inds, z_fine, nullptr,
+                           stream);
+}
+
+PNR_EXPORT int pnr_sample_pdf_labels(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
+                                     float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
+                                     int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream)
+{
+    const PdfLabelArgs lab{hit_t, hit_box, hit_count, max_hits, box_ids, label_sem, label_inst};
+    return sample_pdf_impl("pnr_sample_pdf_labels", z, weights, u, false, nullptr, n_rays, n_coarse, n_fine, nullptr, nullptr, z_fine, &lab, stream);
 }
 
 PNR_EXPORT int pnr_sample_pdf_labels_rng(const float* z, const float* weights, const pnr_rng* rng_host, int64_t n_rays, int n_coarse,
                                          int n_fine, float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
                                          int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream)
 {
-    PnrRngDev rng;
-    const int rc = pnr_rng_check(rng_host, n_rays < 0 ? 0 : n_rays, "pnr_sample_pdf_labels_rng", &rng);
-    if (rc) return rc;
-    PNR_REQUIRE(n_rays <= 0 || (z && weights && z_fine), "pnr_sample_pdf_labels_rng: null pointer");
-    PNR_REQUIRE(n_rays <= 0 || (hit_t && hit_box && hit_count && box_ids && label_sem && label_inst), "pnr_sample_pdf_labels_rng: null pointer");
-    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf_labels_rng: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
-    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf_labels_rng: n_coarse+n_fine=%d > %d", n_coarse + n_fine,
-                PDF_MAXT);
-    PNR_REQUIRE(max_hits >= 1, "pnr_sample_pdf_labels_rng: bad max_hits");
-    if (n_rays <= 0) return PNR_OK;
-    PdfLabelArgs lab;
-    lab.hit_t = hit_t; lab.hit_box = hit_box; lab.hit_count = hit_count; lab.max_hits = max_hits; lab.box_ids = box_ids;
-    lab.label_sem = label_sem; lab.label_inst = label_inst;
-    launch_sample_pdf_rng(z, weights, rng, n_rays, n_coarse, n_fine, nullptr, nullptr, z_fine, lab, (hipStream_t)stream);
-    PNR_CHECK_LAUNCH("pnr_sample_pdf_labels_rng");
-    return PNR_OK;
-}
-
-// a7 + a8: z_fine as pnr_sample_pdf, and the labels pnr_sample_labels would give for it, in the same launch
-PNR_EXPORT int pnr_sample_pdf_labels(const float* z, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_fine,
-                                     float* z_fine, const float* hit_t, const int32_t* hit_box, const int32_t* hit_count,
-                                     int max_hits, const int32_t* box_ids, int32_t* label_sem, int32_t* label_inst, void* stream)
-{
-    PNR_REQUIRE(n_rays <= 0 || (z && weights && z_fine), "pnr_sample_pdf_labels: null pointer");
-    PNR_REQUIRE(n_rays <= 0 || (hit_t && hit_box && hit_count && box_ids && label_sem && label_inst), "pnr_sample_pdf_labels: null pointer");
-    PNR_REQUIRE(n_coarse >= 3 && n_coarse <= PDF_MAXC, "pnr_sample_pdf_labels: n_coarse=%d outside [3,%d]", n_coarse, PDF_MAXC);
-    PNR_REQUIRE(n_fine >= 1 && n_coarse + n_fine <= PDF_MAXT, "pnr_sample_pdf_labels: n_coarse+n_fine=%d > %d", n_coarse + n_fine, PDF_MAXT);
-    PNR_REQUIRE(max_hits >= 1, "pnr_sample_pdf_labels: bad max_hits");
-    if (n_rays <= 0) return PNR_OK;
-    PdfLabelArgs lab;
-    lab.hit_t = hit_t; lab.hit_box = hit_box; lab.hit_count = hit_count; lab.max_hits = max_hits; lab.box_ids = box_ids;
-    lab.label_sem = label_sem; lab.label_inst = label_inst;
-    launch_sample_pdf(z, weights, u, n_rays, n_coarse, n_fine, nullptr, nullptr, z_fine, lab, (hipStream_t)stream);
-    PNR_CHECK_LAUNCH("pnr_sample_pdf_labels");
-    return PNR_OK;
+    const PdfLabelArgs lab{hit_t, hit_box, hit_count, max_hits, box_ids, label_sem, label_inst};
+    return sample_pdf_impl("pnr_sample_pdf_labels_rng", z, weights, nullptr, true, rng_host, n_rays, n_coarse, n_fine, nullptr, nullptr, z_fine,
+                           &lab, stream);
 }
 
 // a8 + a3 (+ a8): hit lists as pnr_bbox_hits, z as pnr_stratified (over the hull of the kept intervals with hull != 0:
@@ -1055,14 +768,7 @@ __global__ __launch_bounds__(256) void k_restrict_rays(const float* __restrict__
         const float4 a = *reinterpret_cast<const float4*>(rays + r * 8);
         float4 b = *reinterpret_cast<const float4*>(rays + r * 8 + 4);
         const int cnt = hit_count[r] < max_hits ? hit_count[r] : max_hits;
-        if (cnt > 0) {
-            float lo = hit_t[(r * max_hits) * 2], hi = hit_t[(r * max_hits) * 2 + 1];
-            for (int h = 1; h < cnt; ++h) {
-                lo = fminf(lo, hit_t[(r * max_hits + h) * 2]);
-                hi = fmaxf(hi, hit_t[(r * max_hits + h) * 2 + 1]);
-            }
-            b.z = lo; b.w = hi;
-        }
+        if (cnt > 0) hit_hull(HitRows<const float, const int32_t>{hit_t + r * max_hits * 2, nullptr}, cnt, &b.z, &b.w);
         *reinterpret_cast<float4*>(out + r * 8) = a;
         *reinterpret_cast<float4*>(out + r * 8 + 4) = b;
     }

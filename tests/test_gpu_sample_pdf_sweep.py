@@ -1,7 +1,8 @@
 """sample_pdf at EVERY coarse sample count, against the C oracle, bit for bit (COVERAGE.md row a7).
 
-pnr_sampling.hip has five sampler kernels -- sample_pdf_body<64, 256>, <256, 512>, their in-kernel-u twins and the inference
-instance k_sample_pdf_det -- whose code depends on the shape in many places: the ATen-ordered sum (groups of 32 weights,
+pnr_sampling.hip has five sampler kernels -- k_sample_pdf<64, 256>, <256, 512> (one template over sample_pdf_body), their
+in-kernel-u twins <..., PnrRngDev> and the inference instance k_sample_pdf_det, all assembled from the pieces of
+pnr_sampling_dev.h -- whose code depends on the shape in many places: the ATen-ordered sum (groups of 32 weights,
 leftover vectors of 8, a scalar tail; four scalar accumulators for rows shorter than 8), the CDF (an exact parallel scan for
 nw = Nc - 2 <= 64 well-conditioned values, a sequential double chain otherwise), fixed-depth bisections that start at the largest
 power of two <= Nc / <= Nf, loops that stride by 64 lanes, a bitonic sort padded to a power of two, the dispatch on Nc <= 64,
