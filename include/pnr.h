@@ -923,6 +923,65 @@ int pnr_tsdf_integrate(const pnr_frame* frames, const float* w2c, int f0, int f1
                        const float* lo_host, const float* step_host, float trunc, float max_depth, float w_max,
                        float* tsdf, float* weight, float* rgb, float* rgb_weight, int32_t* label, int32_t* conf, void* stream);
 
+/* ---- volume ray casting (csrc/pnr_fusion.hip; DESIGN.md 8 "Volume ray casting"): a TSDF volume seen from any camera -- the way
+ * back from the volume of "depth fusion" to an image: depth, surface normal and the nearest lattice point per pixel.  The
+ * reference ships no fusion: the rule is this build's and unpinned.  Float32 throughout, every operation a single + - * /,
+ * floor, sqrt, min or max in the order given, never an FMA (tests/_raycast_ref.py restates the rule three times, twice bit for
+ * bit).  min and max are fminf / fmaxf.
+ *
+ * INPUTS.  The camera (model, cam_host, c2w12_host, width, height) as pnr_project_points takes its camera, but the pose is
+ *   camera-to-world; near_, far_; the lattice (res, lo_host, step_host) and the device arrays tsdf, weight of "depth fusion";
+ *   min_weight; dt = the march step in units of the ray parameter; max_steps.
+ * OUTPUTS.  Caller-owned device arrays, one element per pixel q = j width + i:
+ *     depth   float32        0 unless HIT
+ *     normal  float32 (., 3) 0 unless HIT     optional (NULL: not written)
+ *     src     int32         -1 unless HIT     optional (NULL: not written)
+ *     code    uint8          PNR_RAYCAST_HIT, _NO_RAY (pnr_camera_ray says the pixel sees nothing), _MISSED (the ray does not meet
+ *                            the lattice between near and far) or _NO_SURFACE (the ray left the lattice, passed far or used up
+ *                            max_steps without a crossing)
+ * THE RULE, per pixel (i, j):
+ *   1. RAY.  o, d, near, far = pnr_camera_ray(model, cam, c2w, i, j, near_, far_, ok), unchanged: the ray of pnr_gen_rays*.  A
+ *      pinhole d is not normalised (the parameter is z-depth), a fisheye or equirect d is unit length (the parameter is range),
+ *      so depth is in the convention of render_view.  !ok: NO_RAY.
+ *   2. LATTICE COORDINATES, once per ray:  og_k = (o_k - lo_k) / step_k - 0.5f,  dg_k = d_k / step_k.  A sample at parameter t has
+ *      g_k = og_k + t * dg_k; trilinear interpolation is defined for 0 <= g_k <= res_k - 1, hence every res_k >= 2.
+ *   3. CLIP.  t_in = near, t_out = far; per axis k = x, y, z: if dg_k == 0 the ray misses when og_k < 0 or og_k > (float)(res_k - 1);
+ *      otherwise ta = (0 - og_k) / dg_k, tb = ((float)(res_k - 1) - og_k) / dg_k, t_in = max(t_in, min(ta, tb)), t_out =
+ *      min(t_out, max(ta, tb)).  MISSED unless t_in <= t_out.
+ *   4. MARCH.  Samples n = 0, 1, ... at t_n = t_in + (float)n * dt while t_n <= t_out and n < max_steps.
+ *   5. SAMPLE at t.  Per axis: c_k = clamp((int)floor(g_k), 0, res_k - 2) -- the floor is clamped to [0, 2^30] as a float before
+ *      the conversion, which is then in range whatever g_k is -- and f_k = clamp(g_k - (float)c_k, 0, 1) = min(max(., 0), 1).  The
+ *      eight corners are the lattice points (c_x + a, c_y + b, c_z + c), a, b, c in {0, 1}.  The sample is OBSERVED iff all eight
+ *      have weight >= min_weight.  Its value: the lerp p + f * (q - p) along x for the four x-pairs, then along y for the two
+ *      pairs of results, then along z.  The value of an unobserved sample is never used: NaN or garbage in tsdf where weight
+ *      fails the test cannot leak.
+ *   6. CROSSING.  The sign is depth fusion's: positive is BEHIND the surface.  The first n >= 1 whose samples n - 1 and n are both
+ *      observed with v_{n-1} < 0 <= v_n is the hit; otherwise marching goes on.  So a ray that starts behind a surface, a crossing
+ *      with an unobserved sample on either side, and the back of the band (+ to -) are no hits.  No hit: NO_SURFACE.
+ *   7. HIT.  r = v_{n-1} / (v_{n-1} - v_n);  depth = t* = t_{n-1} + (t_n - t_{n-1}) * r.  One more sample is taken at t*: cell c*,
+ *      fraction f*.  src = the flat index ("depth fusion") of the nearest corner (c*_k + (f*_k >= 0.5f ? 1 : 0)), whether or not
+ *      that sample is observed.  If it is observed: the gradient of the trilinear interpolant -- for x the difference q - p of
+ *      each x-pair, lerped along y then z; for y the y-pairs, lerped along x then z; for z the z-pairs, lerped along x then y --,
+ *      each component divided by step_k, len = sqrt((gx gx + gy gy) + gz gz), normal = (-gx / len, -gy / len, -gz / len): a
+ *      world-space unit vector out of the surface, towards observed free space.  Not observed, or len not positive and finite:
+ *      normal = 0, and the pixel is still a HIT.
+ * The camera and the pose are host values baked into the launch; the volume is read when the kernel runs (a captured launch sees
+ * what was integrated since).  No atomics: two runs give the same bits.  Never synchronises; capture-safe.  PNR_EINVAL before any
+ * launch: an unknown model; null camera or pose; null tsdf, weight, depth or code; a misaligned array (4 bytes); width or height
+ * < 1 or more than 2^31 - 1 pixels; a camera the model's checks refuse (a zero focal length, gamma or step; pnr_gen_rays_equirect's);
+ * a res < 2 or more than 2^31 - 1 points; null, non-finite lo or step, or a zero step; !(dt > 0) or a non-finite dt; max_steps
+ * < 0; !(min_weight > 0); !(near_ >= 0); !(far_ > near_). */
+#define PNR_RAYCAST_HIT 0
+#define PNR_RAYCAST_NO_RAY 1
+#define PNR_RAYCAST_MISSED 2
+#define PNR_RAYCAST_NO_SURFACE 3
+#define PNR_RAYCAST_TILE 8              /* a wave is a TILE x TILE block of pixels */
+#define PNR_RAYCAST_BLOCK 256           /* threads (= pixels) a workgroup: four tiles side by side */
+int pnr_tsdf_raycast(int model, const float* cam_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                     int res_x, int res_y, int res_z, const float* lo_host, const float* step_host, const float* tsdf,
+                     const float* weight, float min_weight, float dt, int max_steps, float* depth, float* normal, int32_t* src,
+                     uint8_t* code, void* stream);
+
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable
  * state -- the one diagnostic hook of the MLP kernels is a descriptor field (pnr_mlp_desc.clk_probe). */

@@ -130,6 +130,9 @@ SIGNATURES = {
                               c_f, c_f, c_f, c_f, c_f]),
     "pnr_tsdf_integrate": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_tsdf_raycast": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
+                                 ctypes.c_float, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                 c_f, c_f, ctypes.c_float, ctypes.c_float, c_int, c_f, c_f, c_f, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

@@ -139,3 +139,213 @@ PNR_EXPORT int pnr_tsdf_integrate(const pnr_frame* frames, const float* w2c, int
     PNR_CHECK_LAUNCH("pnr_tsdf_integrate");
     return PNR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Volume ray casting (include/pnr.h "volume ray casting"): the volume seen from any camera.  tests/_raycast_ref.py restates the
+// rule in numpy; everything here equals it bit for bit.
+//
+// One thread per pixel; a wave is an 8 x 8 pixel TILE, not 64 pixels of a row, so the rays of a wave walk neighbouring cells and
+// its gathers fall into few cache lines; a block is four tiles side by side, one block per four tiles (no cap: a ray's work runs
+// from nothing to max_steps samples, and the hardware's dispatcher balances what a tile-stride loop would fix).  Partial tiles at
+// the right and bottom edges are masked.  The ray is pnr_camera_ray's, the bits of the ray kernels.  Inside the march the eight
+// corner values and the observed flag of the current cell stay in registers and are gathered again only when the cell changes,
+// which cannot change a bit: the same numbers enter the same operations.  The only stores are the pixel's own outputs after the
+// loop.  No atomics, no LDS, nothing waits on anything.
+struct RaycastArgs {
+    int model, width, height, max_steps;
+    float cam[7], c2w[12];
+    float near_, far_, min_weight, dt;
+    int res[3];
+    float lo[3], step[3];
+    unsigned int tiles_x;
+    int64_t n_tiles;
+    const float *tsdf, *weight;
+    float *depth, *normal;
+    int32_t* src;
+    uint8_t* code;
+};
+
+// the eight corners of a cell, index a + 2 b + 4 c for the corner (cx + a, cy + b, cz + c), and whether all eight are observed
+struct RaycastCell {
+    float v[8];
+    bool obs;
+};
+
+__device__ __forceinline__ void raycast_load(const RaycastArgs& a, int cx, int cy, int cz, RaycastCell& cell)
+{
+    const size_t rx = (size_t)a.res[0], sz = rx * (size_t)a.res[1];
+    const size_t base = ((size_t)cz * (size_t)a.res[1] + (size_t)cy) * rx + (size_t)cx;      // every corner < res_x res_y res_z
+    bool obs = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const size_t at = base + (k & 1) + ((k >> 1) & 1) * rx + (k >> 2) * sz;
+        cell.v[k] = a.tsdf[at];
+        obs = obs && a.weight[at] >= a.min_weight;
+    }
+    cell.obs = obs;
+}
+
+// c = clamp((int)floor(g), 0, res - 2) and f = clamp(g - (float)c, 0, 1); the floor is clamped as a float first, so the
+// conversion is in range whatever g is (NaN gives 0)
+__device__ __forceinline__ void raycast_cell_of(float g, int res, int& c, float& f)
+{
+    const float fl = fminf(fmaxf(floorf(g), 0.0f), 1073741824.0f);
+    const int ci = (int)fl;
+    c = ci < res - 2 ? ci : res - 2;
+    f = fminf(fmaxf(g - (float)c, 0.0f), 1.0f);
+}
+
+__device__ __forceinline__ float raycast_lerp(float p, float q, float f)
+{
+    const float d = q - p;
+    const float m = f * d;                                          // a multiply, then an add: never an FMA
+    return p + m;
+}
+
+__device__ __forceinline__ float raycast_value(const RaycastCell& c, float fx, float fy, float fz)
+{
+    const float x00 = raycast_lerp(c.v[0], c.v[1], fx), x10 = raycast_lerp(c.v[2], c.v[3], fx);
+    const float x01 = raycast_lerp(c.v[4], c.v[5], fx), x11 = raycast_lerp(c.v[6], c.v[7], fx);
+    return raycast_lerp(raycast_lerp(x00, x10, fy), raycast_lerp(x01, x11, fy), fz);
+}
+
+__global__ __launch_bounds__(PNR_RAYCAST_BLOCK) void k_tsdf_raycast(const RaycastArgs a)
+{
+    const int64_t tile = (int64_t)blockIdx.x * (PNR_RAYCAST_BLOCK / 64) + (threadIdx.x >> 6);
+    if (tile >= a.n_tiles) return;
+    const unsigned int tj = (unsigned int)(tile / a.tiles_x), ti = (unsigned int)(tile - (int64_t)tj * a.tiles_x);
+    const unsigned int lane = threadIdx.x & 63;
+    const int64_t i64 = (int64_t)ti * PNR_RAYCAST_TILE + (lane & (PNR_RAYCAST_TILE - 1));
+    const int64_t j64 = (int64_t)tj * PNR_RAYCAST_TILE + (lane >> 3);
+    if (i64 >= a.width || j64 >= a.height) return;                  // the partial tiles of the right and bottom edges
+    const int i = (int)i64, j = (int)j64;
+    const size_t q = (size_t)j * (size_t)a.width + (size_t)i;
+
+    float depth = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    int32_t src = -1;
+    uint8_t code = PNR_RAYCAST_NO_RAY;
+    bool ok;
+    const PnrRayRec ray = pnr_camera_ray(a.model, a.cam, a.c2w, i, j, a.near_, a.far_, ok);
+    if (ok) {
+        const float o[3] = {ray.lo.x, ray.lo.y, ray.lo.z}, d[3] = {ray.lo.w, ray.hi.x, ray.hi.y};
+        float og[3], dg[3];
+        float t_in = ray.hi.z, t_out = ray.hi.w;
+        bool miss = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            og[k] = (o[k] - a.lo[k]) / a.step[k] - 0.5f;
+            dg[k] = d[k] / a.step[k];
+            const float top = (float)(a.res[k] - 1);
+            if (dg[k] == 0.0f) {
+                miss = miss || og[k] < 0.0f || og[k] > top;
+            } else {
+                const float ta = (0.0f - og[k]) / dg[k], tb = (top - og[k]) / dg[k];
+                t_in = fmaxf(t_in, fminf(ta, tb));
+                t_out = fminf(t_out, fmaxf(ta, tb));
+            }
+        }
+        code = PNR_RAYCAST_MISSED;
+        if (!miss && t_in <= t_out) {
+            code = PNR_RAYCAST_NO_SURFACE;
+            RaycastCell cell;
+            int cx = -1, cy = -1, cz = -1;                          // no cell is loaded yet
+            float t_prev = 0.0f, v_prev = 0.0f;
+            bool obs_prev = false;
+            for (int n = 0; n < a.max_steps; ++n) {
+                const float adv = (float)n * a.dt;
+                const float t = t_in + adv;
+                if (!(t <= t_out)) break;
+                const float m0 = t * dg[0], m1 = t * dg[1], m2 = t * dg[2];
+                int c0, c1, c2;
+                float f0, f1, f2;
+                raycast_cell_of(og[0] + m0, a.res[0], c0, f0);
+                raycast_cell_of(og[1] + m1, a.res[1], c1, f1);
+                raycast_cell_of(og[2] + m2, a.res[2], c2, f2);
+                if (c0 != cx || c1 != cy || c2 != cz) {               // the cell changed: gather its eight corners again
+                    cx = c0; cy = c1; cz = c2;
+                    raycast_load(a, cx, cy, cz, cell);
+                }
+                const float v = raycast_value(cell, f0, f1, f2);
+                if (obs_prev && cell.obs && v_prev < 0.0f && 0.0f <= v) {      // n >= 1: obs_prev is false at n = 0
+                    const float r = v_prev / (v_prev - v);
+                    const float w = (t - t_prev) * r;
+                    depth = t_prev + w;
+                    code = PNR_RAYCAST_HIT;
+                    break;
+                }
+                t_prev = t; v_prev = v; obs_prev = cell.obs;
+            }
+            if (code == PNR_RAYCAST_HIT) {
+                const float m0 = depth * dg[0], m1 = depth * dg[1], m2 = depth * dg[2];
+                int c0, c1, c2;
+                float f0, f1, f2;
+                raycast_cell_of(og[0] + m0, a.res[0], c0, f0);
+                raycast_cell_of(og[1] + m1, a.res[1], c1, f1);
+                raycast_cell_of(og[2] + m2, a.res[2], c2, f2);
+                const int64_t s0 = c0 + (f0 >= 0.5f ? 1 : 0), s1 = c1 + (f1 >= 0.5f ? 1 : 0), s2 = c2 + (f2 >= 0.5f ? 1 : 0);
+                src = (int32_t)((s2 * a.res[1] + s1) * a.res[0] + s0);
+                if (a.normal) {
+                    if (c0 != cx || c1 != cy || c2 != cz) raycast_load(a, c0, c1, c2, cell);
+                    if (cell.obs) {
+                        const float* v = cell.v;
+                        // the gradient of the trilinear interpolant: the differences along an axis, lerped along the other two
+                        // in the order x, y, z
+                        float gx = raycast_lerp(raycast_lerp(v[1] - v[0], v[3] - v[2], f1), raycast_lerp(v[5] - v[4], v[7] - v[6], f1), f2);
+                        float gy = raycast_lerp(raycast_lerp(v[2] - v[0], v[3] - v[1], f0), raycast_lerp(v[6] - v[4], v[7] - v[5], f0), f2);
+                        float gz = raycast_lerp(raycast_lerp(v[4] - v[0], v[5] - v[1], f0), raycast_lerp(v[6] - v[2], v[7] - v[3], f0), f1);
+                        gx = gx / a.step[0]; gy = gy / a.step[1]; gz = gz / a.step[2];
+                        const float xx = gx * gx, yy = gy * gy, zz = gz * gz;
+                        const float len = sqrtf((xx + yy) + zz);
+                        if (len > 0.0f && len <= FLT_MAX) { nx = -gx / len; ny = -gy / len; nz = -gz / len; }
+                    }
+                }
+            }
+        }
+    }
+    a.depth[q] = depth;
+    a.code[q] = code;
+    if (a.normal) { a.normal[q * 3 + 0] = nx; a.normal[q * 3 + 1] = ny; a.normal[q * 3 + 2] = nz; }
+    if (a.src) a.src[q] = src;
+}
+
+PNR_EXPORT int pnr_tsdf_raycast(int model, const float* cam_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                                int res_x, int res_y, int res_z, const float* lo_host, const float* step_host, const float* tsdf,
+                                const float* weight, float min_weight, float dt, int max_steps, float* depth, float* normal, int32_t* src,
+                                uint8_t* code, void* stream)
+{
+    PNR_REQUIRE(pnr_camera_model_ok(model), "pnr_tsdf_raycast: unknown camera model %d", model);
+    PNR_REQUIRE(cam_host && c2w12_host, "pnr_tsdf_raycast: null camera or pose (cam_host, c2w12_host)");
+    PNR_REQUIRE(tsdf && weight, "pnr_tsdf_raycast: null tsdf or weight");
+    PNR_REQUIRE(depth && code, "pnr_tsdf_raycast: null depth or code");
+    PNR_REQUIRE(((((uintptr_t)tsdf) | ((uintptr_t)weight) | ((uintptr_t)depth) | ((uintptr_t)normal) | ((uintptr_t)src)) & 3) == 0,
+                "pnr_tsdf_raycast: misaligned array (tsdf, weight, depth, normal, src: 4 bytes)");
+    PNR_REQUIRE(width >= 1 && height >= 1 && (int64_t)width * height <= INT32_MAX,
+                "pnr_tsdf_raycast: bad image %d x %d (width, height >= 1, at most 2^31 - 1 pixels)", width, height);
+    const int rc = pnr_camera_check(model, cam_host, width, height, "pnr_tsdf_raycast");
+    if (rc) return rc;
+    PNR_REQUIRE(res_x >= 2 && res_y >= 2 && res_z >= 2 && (int64_t)res_x * res_y <= INT32_MAX && (int64_t)res_x * res_y * res_z <= INT32_MAX,
+                "pnr_tsdf_raycast: bad lattice %d x %d x %d (every res >= 2, at most 2^31 - 1 points)", res_x, res_y, res_z);
+    PNR_REQUIRE(lo_host && step_host, "pnr_tsdf_raycast: null lo or step");
+    for (int k = 0; k < 3; ++k)
+        PNR_REQUIRE(isfinite(lo_host[k]) && isfinite(step_host[k]) && step_host[k] != 0.0f,
+                    "pnr_tsdf_raycast: lo and step must be finite and step non-zero (axis %d)", k);
+    PNR_REQUIRE(dt > 0.0f && isfinite(dt), "pnr_tsdf_raycast: dt must be positive and finite");
+    PNR_REQUIRE(max_steps >= 0, "pnr_tsdf_raycast: max_steps must be >= 0 (got %d)", max_steps);
+    PNR_REQUIRE(min_weight > 0.0f, "pnr_tsdf_raycast: min_weight must be positive");
+    PNR_REQUIRE(near_ >= 0.0f && far_ > near_, "pnr_tsdf_raycast: need 0 <= near < far");
+    RaycastArgs a;
+    a.model = model; a.width = width; a.height = height; a.max_steps = max_steps;
+    pnr_camera_fill(model, cam_host, a.cam);
+    pnr_pose_fill(c2w12_host, a.c2w);
+    a.near_ = near_; a.far_ = far_; a.min_weight = min_weight; a.dt = dt;
+    a.res[0] = res_x; a.res[1] = res_y; a.res[2] = res_z;
+    for (int k = 0; k < 3; ++k) { a.lo[k] = lo_host[k]; a.step[k] = step_host[k]; }
+    const int64_t tiles_x = ((int64_t)width + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE, tiles_y = ((int64_t)height + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE;
+    a.tiles_x = (unsigned int)tiles_x;
+    a.n_tiles = tiles_x * tiles_y;                                  // at most 2^28 + 2^25: the grid below fits a launch
+    a.tsdf = tsdf; a.weight = weight; a.depth = depth; a.normal = normal; a.src = src; a.code = code;
+    const int64_t blocks = (a.n_tiles + PNR_RAYCAST_BLOCK / 64 - 1) / (PNR_RAYCAST_BLOCK / 64);
+    hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned int)blocks), dim3(PNR_RAYCAST_BLOCK), 0, (hipStream_t)stream, a);
+    PNR_CHECK_LAUNCH("pnr_tsdf_raycast");
+    return PNR_OK;
+}

@@ -1,4 +1,4 @@
-"""Depth fusion: posed depth frames -> a truncated signed distance volume (TSDF) -> a labelled, coloured mesh, on the GPU
+"""Depth fusion: posed depth frames -> a truncated signed distance volume (TSDF) -> a labelled, coloured mesh or image, on the GPU
 (ops.tsdf_integrate / pnr_tsdf_integrate; the rule is written out in include/pnr.h "depth fusion").  The step between the
 depth producers (stereo.depth_from_pair, Renderer.render_view, pointcloud.splat), the frames a `FrameSet` keeps on the device,
 and `mesh.extract`: images -> depth -> volume -> mesh.
@@ -16,8 +16,16 @@ restatement's bit for bit and does not depend on how the frames are split over c
 Conventions (this build's, unpinned): POSITIVE tsdf is BEHIND the observed surface (mesh.extract calls field > level inside);
 nearest-pixel depth lookup; depth as render_view writes it (z-depth in a pinhole frame, range in a fisheye / equirect frame);
 every observation weighs 1; colour is the running mean of the frames' bytes; the label is a Boyer-Moore majority vote over
-(pseudo_label, instance_label) pairs.  Out of scope: per-pixel confidence weights, voxel hashing or sparse volumes, ray-cast
-rendering of the volume, frustum culling per block, reading pose files."""
+(pseudo_label, instance_label) pairs.  Out of scope: per-pixel confidence weights, voxel hashing or sparse volumes, frustum
+culling per block, reading pose files.
+
+The way back from the volume to an image is `raycast` (ops.tsdf_raycast / pnr_tsdf_raycast; include/pnr.h "volume ray casting"):
+
+    maps = fusion.raycast(vol, camera, c2w, near, far)       # depth, normal, code, src, valid, sem_label, inst_label, rgb
+    consistency.reproject((camera, c2w, maps), other_view)    # (camera, c2w, maps) is a view like render_view's
+
+Out of scope there: steps that adapt to the tsdf value, block-level empty-space skipping, trilinear colour, shading, sub-lists
+of pixels, pose refinement (ICP) against the ray-cast."""
 import numpy as np
 import torch
 
@@ -194,3 +202,60 @@ def extract(volume, min_weight=1.0):
     if volume.rgb is not None:
         m.attributes["rgb"] = volume.colors().reshape(-1, 3)[m.src]
     return m
+
+
+HIT, NO_RAY, MISSED, NO_SURFACE = ops.RAYCAST_HIT, ops.RAYCAST_NO_RAY, ops.RAYCAST_MISSED, ops.RAYCAST_NO_SURFACE
+_MODEL_NAMES = {word: name for name, (word, _) in ops._MODEL_WORDS.items()}
+
+
+def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps=None, normals=True, attributes=True):
+    """Render `volume` into (camera, c2w): the way back from a fused volume to an image, in ONE launch (ops.tsdf_raycast; the rule
+    is in include/pnr.h "volume ray casting").  camera: camera.Pinhole / Fisheye / Equirect; c2w: 3x4 camera-to-world.  A ray is
+    marched through the lattice in steps of `step` (units of the ray parameter; None: half the volume's smallest lattice step)
+    for at most max_steps samples (None: enough for the lattice's diagonal); the first crossing from in front of the surface to
+    behind it, between two samples whose eight lattice points all have weight >= min_weight, is the hit.  Returns a maps dict
+    of (height, width, ...) images on the volume's device, which (camera, c2w, maps) makes a view for consistency.reproject,
+    pointcloud.lift and Evaluator.evaluate_depth:
+        depth   float32   in render_view's convention (z-depth in a pinhole, range in a fisheye / equirect); 0 off the surface
+        code    uint8     HIT, NO_RAY, MISSED or NO_SURFACE;  valid  bool = code == HIT
+        src     int32     the flat index of the lattice point nearest the hit, -1 off the surface
+        normal  float32 (., 3)  with normals: the world-space unit normal towards free space, 0 off the surface
+        sem_label, inst_label int32 (-1 off the surface; volumes with labels) and rgb uint8 (0 off the surface; volumes with
+        colour), with attributes: gathered at src with torch indexing.
+    Nothing is synchronised; the launch can be captured in a graph, and a replay sees what was integrated since."""
+    if not isinstance(volume, Volume):
+        raise TypeError("fusion.raycast: volume must be a fusion.Volume")
+    if not all(hasattr(camera, k) for k in ("word", "params", "width", "height")) or camera.word not in _MODEL_NAMES:
+        raise TypeError("fusion.raycast: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (camera,))
+    if min(volume.res) < 2:
+        raise ValueError("fusion.raycast: the volume is %d x %d x %d; ray casting needs every res >= 2" % volume.res)
+    near, far, min_weight = float(near), float(far), float(min_weight)
+    if not (near >= 0.0 and far > near):
+        raise ValueError("fusion.raycast: need 0 <= near < far (got %r, %r)" % (near, far))
+    if not (min_weight > 0.0):
+        raise ValueError("fusion.raycast: min_weight must be positive (got %r)" % min_weight)
+    dt = ops.raycast_default_dt(volume.step) if step is None else float(step)
+    if not (0.0 < dt < float("inf")):
+        raise ValueError("fusion.raycast: step must be positive and finite (got %r)" % dt)
+    max_steps = ops.raycast_default_max_steps(volume.res, volume.step, dt) if max_steps is None else int(max_steps)
+    if max_steps < 0:
+        raise ValueError("fusion.raycast: max_steps must be >= 0 (got %d)" % max_steps)
+    if not volume.tsdf.is_cuda:
+        raise RuntimeError("fusion.raycast: the volume is not on the GPU (the HIP path has no CPU fallback)")
+    dev, h, w = volume.device, int(camera.height), int(camera.width)
+    maps = {"depth": torch.empty((h, w), dtype=torch.float32, device=dev), "code": torch.empty((h, w), dtype=torch.uint8, device=dev),
+            "src": torch.empty((h, w), dtype=torch.int32, device=dev)}
+    if normals:
+        maps["normal"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    ops.tsdf_raycast(_MODEL_NAMES[camera.word], camera.params, c2w, w, h, near, far, volume.lo32, volume.step, volume.tsdf, volume.weight,
+                     maps["depth"], maps["code"], normal=maps.get("normal"), src=maps["src"], min_weight=min_weight, dt=dt,
+                     max_steps=max_steps)
+    maps["valid"] = maps["code"] == HIT
+    if attributes:
+        at = maps["src"].clamp(min=0).long()
+        if volume.label is not None:
+            for name, lab in zip(("sem_label", "inst_label"), unpack_label(volume.label)):
+                maps[name] = torch.where(maps["valid"], lab.reshape(-1)[at], torch.full_like(maps["src"], -1))
+        if volume.rgb is not None:
+            maps["rgb"] = torch.where(maps["valid"][..., None], volume.colors().reshape(-1, 3)[at], torch.zeros((), dtype=torch.uint8, device=dev))
+    return maps

@@ -613,6 +613,82 @@ def tsdf_integrate(frames, w2c, first, last, lo, step, trunc, tsdf, weight, rgb=
                "pnr_tsdf_integrate")
 
 
+RAYCAST_HIT, RAYCAST_NO_RAY, RAYCAST_MISSED, RAYCAST_NO_SURFACE = 0, 1, 2, 3      # PNR_RAYCAST_* (include/pnr.h "volume ray casting")
+RAYCAST_MAX_PIXELS = 2 ** 31 - 1
+
+
+@_on_device
+def tsdf_raycast(camera_model, cam, c2w, width, height, near, far, lo, step, tsdf, weight, depth, code, normal=None, src=None,
+                 min_weight=1.0, dt=None, max_steps=None):
+    """Render a TSDF volume into a camera (pnr_tsdf_raycast; the rule is in include/pnr.h "volume ray casting").  camera_model:
+    "pinhole", "fisheye" or "equirect" with cam as project_points takes it; c2w: 3x4 camera-to-world (host values).  lo, step: the
+    lattice's float32 origin and step per axis (x, y, z), host values (mesh.lattice); tsdf, weight: (res_z, res_y, res_x) float32,
+    every res >= 2, read when the kernel runs.  Outputs, caller-owned (height, width) images: depth float32, code uint8, and
+    optionally normal (height, width, 3) float32 and src int32.  dt: the march step in units of the ray parameter (None: half the
+    smallest |step|); max_steps: the most samples a ray takes (None: enough for the lattice's diagonal at that dt).  Returns None."""
+    what = "tsdf_raycast"
+    if camera_model not in _MODEL_WORDS:
+        raise ValueError("%s: camera_model must be 'pinhole', 'fisheye' or 'equirect', not %r" % (what, camera_model))
+    word, nc = _MODEL_WORDS[camera_model]
+    cam_h = _host_floats(cam, nc, "%s: model %r cam" % (what, camera_model))
+    c2w_h = _host_floats(c2w, 12, what + ": c2w")
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or width * height > RAYCAST_MAX_PIXELS:
+        raise ValueError("%s: bad image %d x %d (width, height >= 1, at most 2^31 - 1 pixels)" % (what, width, height))
+    if not isinstance(tsdf, torch.Tensor):
+        raise ValueError("%s: tsdf must be a GPU tensor, got %s" % (what, type(tsdf).__name__))
+    if tsdf.dim() != 3 or min(tsdf.shape) < 2:
+        raise ValueError("%s: tsdf must be (res_z, res_y, res_x) with every res >= 2, got %s" % (what, tuple(tsdf.shape)))
+    if tsdf.numel() > TSDF_MAX_POINTS:
+        raise ValueError("%s: tsdf holds %d points, more than the limit of 2^31 - 1" % (what, tsdf.numel()))
+    rz, ry, rx = tsdf.shape
+    for name, t, dtype, shape, needed in (("tsdf", tsdf, torch.float32, (rz, ry, rx), True), ("weight", weight, torch.float32, (rz, ry, rx), True),
+                                          ("depth", depth, torch.float32, (height, width), True), ("code", code, torch.uint8, (height, width), True),
+                                          ("normal", normal, torch.float32, (height, width, 3), False),
+                                          ("src", src, torch.int32, (height, width), False)):
+        if t is None and not needed:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
+    lo_h, step_h = _host_floats(lo, 3, what + ": lo"), _host_floats(step, 3, what + ": step")
+    for name, h in (("lo", lo_h), ("step", step_h)):
+        if not all(abs(v) < float("inf") for v in h):
+            raise ValueError("%s: %s must be finite (got %r)" % (what, name, list(h)))
+    if not all(v != 0.0 for v in step_h):
+        raise ValueError("%s: step must be non-zero (got %r)" % (what, list(step_h)))
+    near, far, min_weight = float(near), float(far), float(min_weight)
+    if not (near >= 0.0 and far > near):
+        raise ValueError("%s: need 0 <= near < far (got %r, %r)" % (what, near, far))
+    if not (min_weight > 0.0):
+        raise ValueError("%s: min_weight must be positive (got %r)" % (what, min_weight))
+    dt = raycast_default_dt(step_h) if dt is None else float(dt)
+    if not (0.0 < dt < float("inf")):
+        raise ValueError("%s: dt must be positive and finite (got %r)" % (what, dt))
+    max_steps = raycast_default_max_steps((rx, ry, rz), step_h, dt) if max_steps is None else int(max_steps)
+    if max_steps < 0:
+        raise ValueError("%s: max_steps must be >= 0 (got %d)" % (what, max_steps))
+    _stereo_gpu(what, tsdf=tsdf, weight=weight, depth=depth, code=code, normal=normal, src=src)
+    _lib.check(_lib.load().pnr_tsdf_raycast(word, cam_h, c2w_h, width, height, near, far, rx, ry, rz, lo_h, step_h, _p(tsdf), _p(weight),
+                                            min_weight, dt, max_steps, _p(depth), _p(normal), _p(src), _p(code), _stream()),
+               "pnr_tsdf_raycast")
+
+
+def raycast_default_dt(step):
+    """half the smallest |step| of the lattice, as a float32: roughly every second sample stays in its cell"""
+    return float(torch.tensor([abs(float(s)) for s in step], dtype=torch.float32).min() * 0.5)
+
+
+def raycast_default_max_steps(res, step, dt):
+    """samples enough for the lattice's diagonal at march step dt: a ray's parameter never runs faster than arc length (|d| >= 1
+    in every model), so no ray inside the lattice takes more"""
+    diag = sum(((int(r) - 1) * float(s)) ** 2 for r, s in zip(res, step)) ** 0.5
+    return min(int(diag / float(dt)) + 2, 2 ** 31 - 1)
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global
