@@ -982,6 +982,90 @@ int pnr_tsdf_raycast(int model, const float* cam_host, const float* c2w12_host, 
                      const float* weight, float min_weight, float dt, int max_steps, float* depth, float* normal, int32_t* src,
                      uint8_t* code, void* stream);
 
+/* ---- pose tracking (csrc/pnr_icp.hip; DESIGN.md 8 "Pose tracking"): the pose of a live depth frame refined against a model view
+ * -- a view (camera M, c2w_M, depth, world-space normal) as pnr_tsdf_raycast writes it -- by projective association and a
+ * point-to-plane Gauss-Newton iteration.  The reference ships no tracker: the rule is this build's and unpinned.  The pose lives
+ * in DEVICE memory (pose12: 12 float32, the 3x4 row-major camera-to-world of the live frame) and is read and updated there, so a
+ * chain of accumulate / solve launches needs no host read.  Per pixel float32, every operation a single + - * / sqrt, fminf or
+ * fmaxf in the order given, never an FMA; the sums and the solve are IEEE double, one operation per symbol (tests/_icp_ref.py
+ * restates the rule: per pixel twice, bit for bit; the solve in Python floats, bit for bit).
+ *
+ * pnr_icp_accumulate: one linearisation.  Per live pixel q = j width_l + i, IN THIS ORDER; the first failing test gives the code:
+ *   1. t = depth_l[q].  NO_DEPTH unless t > 0 and t is finite.  (o, d) = pnr_camera_ray(model_l, cam_l, IDENTITY pose, i, j): o = 0
+ *      and d is the model's own direction; !ok (a fisheye pixel outside the lens): NO_DEPTH.  p_cam = (t d_x, t d_y, t d_z).
+ *   2. with the rows (r0 r1 r2 | T) of pose12:  qv_k = (r0 x + r1 y) + r2 z of p_cam,  p_k = qv_k + T_k.
+ *   3. (u, v) and the domain flag of p in the model view with w2c_m: the arithmetic of pnr_project_points (umax = (float)width_m
+ *      - 0.5f).  OUTSIDE unless in the domain and -0.5 <= u < width_m - 0.5, -0.5 <= v < height_m - 0.5.  Nearest pixel as
+ *      reprojection step 5: a = min((int)floor(u + 0.5), width_m - 1), b likewise, mq = b width_m + a.
+ *   4. dm = depth_m[mq], n = normal_m[mq].  NO_MODEL unless dm > 0 and dm is finite, every component of n is finite and not all
+ *      three are 0 (pnr_tsdf_raycast writes depth 0 and normal 0 off the surface: no code image is needed).
+ *   5. (o_m, d_m) = pnr_camera_ray(model_m, cam_m, c2w_m, a, b); !ok: NO_MODEL.  m_k = o_m,k + dm d_m,k;  e_k = m_k - p_k.
+ *      TOO_FAR unless (e_x e_x + e_y e_y) + e_z e_z <= dist_max * dist_max (so a NaN is TOO_FAR).
+ *   6. BACK_FACING if (n_x qv_x + n_y qv_y) + n_z qv_z >= 0: the model surface does not face the live camera.
+ *   7. MATCH:  r = (n_x e_x + n_y e_y) + n_z e_z;  c = qv x n, each component one a b - c d: c_x = qv_y n_z - qv_z n_y,
+ *      c_y = qv_z n_x - qv_x n_z, c_z = qv_x n_y - qv_y n_x;  J = (c_x, c_y, c_z, n_x, n_y, n_z).  The twist x = (omega, v) is about
+ *      the live camera's centre: p' = R_delta qv + T + v, so r' = r - J x to first order.
+ * SUMS over the MATCH pixels, in double: A_ab += (double)J_a (double)J_b for a <= b, row by row (slots 0 .. 20: A_00 A_01 .. A_05
+ *   A_11 .. A_55), g_a += (double)J_a (double)r (slots 21 .. 26), E += (double)r (double)r (slot 27); the products are exact.  An
+ *   exact integer count (slot 28, an int64).  A thread takes the pixels q = first + k stride in that order, a wave reduces by the
+ *   xor butterfly (32, 16, .. 1), the four waves of a workgroup add as ((w0 + w1) + w2) + w3, and every workgroup writes ONE ROW of
+ *   PNR_ICP_ROW 8-byte slots.  No floating atomics: two runs give the same bits.
+ * WORKSPACE: pnr_icp_workspace_bytes(n_pix) bytes (-1 for n_pix < 1 or > 2^31 - 1), 8-byte aligned: slot 0 = the number of rows
+ *   written (int64, the grid: at most PNR_ICP_MAX_BLOCKS and one workgroup per compute unit), then the rows in block order.
+ * OPTIONAL per-pixel outputs (NULL: not written): code uint8 (PNR_ICP_*), residual float32 (r, 0 unless MATCH).
+ * The cameras, c2w_m and w2c_m (camera.invert_pose of c2w_m: float64 on the host, rounded once) are host values baked into the
+ * launch; pose12, the depth images and the normals are read when the kernel runs.  Never synchronises; capture-safe.  PNR_EINVAL
+ * before any launch: an unknown model; a null camera or model pose; width or height < 1 or more than 2^31 - 1 pixels on either
+ * side; a camera the model's checks refuse; null depth_l, pose12, depth_m, normal_m or workspace; pose12, the images or residual
+ * misaligned (4 bytes) or workspace (8); dist_max not positive, or its square not finite.
+ *
+ * pnr_icp_solve: ONE workgroup.  n_pix is pnr_icp_accumulate's width_l * height_l (it bounds the rows read whatever slot 0 holds).
+ *   1. COMBINE: every slot of the rows is added in block order from 0.0 (the count in integers).
+ *   2. count < min_matches: TOO_FEW.  With update == 0 the entry point stops here: status OK, nothing solved, pose12 untouched
+ *      (the last row of a track: count and E at the final pose).
+ *   3. CHOLESKY A = L L^T, column j = 0 .. 5:  s = A_jj;  s = s - L_jk L_jk for k = 0 .. j - 1;  DEGENERATE unless
+ *      s > 2^-30 A_jj (the pivot against its own diagonal entry of A);  L_jj = sqrt(s);  for i = j + 1 .. 5:  s = A_ij;
+ *      s = s - L_ik L_jk for k = 0 .. j - 1;  L_ij = s / L_jj.
+ *   4. FORWARD  y_i = (g_i - sum) / L_ii, i = 0 .. 5, the sum subtracted term by term: s = g_i; s = s - L_ik y_k for k = 0 .. i - 1.
+ *      BACK  x_i = s / L_ii, i = 5 .. 0:  s = y_i;  s = s - L_ki x_k for k = i + 1 .. 5.   omega = x_0..2, v = x_3..5.
+ *   5. w2 = (omega_x omega_x + omega_y omega_y) + omega_z omega_z, v2 likewise.  STEP_TOO_LARGE unless w2 <= max_rot max_rot and
+ *      v2 <= max_trans max_trans (doubles; a NaN is too large).
+ *   6. a = sin(theta) / theta and b = (1 - cos(theta)) / theta^2 as their power series in s = w2, PNR_ICP_SERIES_TERMS terms in
+ *      Horner form:  a = ca_7;  a = a s + ca_k for k = 6 .. 0, with ca_k = (-1)^k / (2k + 1)!;  b the same with
+ *      cb_k = (-1)^k / (2k + 2)! -- each coefficient the correctly rounded quotient of 1.0 and the (exact) factorial.  No sqrt and
+ *      no libm call.  The first dropped terms at the cap s = 0.25 are 2^-64.4 and 2^-68.5.
+ *      R_delta:  diagonal  D_ii = 1.0 + b (omega_i omega_i - s);  off the diagonal  D_ij = a K_ij + b (omega_i omega_j)  with
+ *      K = [omega]x: K_01 = -omega_z, K_02 = omega_y, K_10 = omega_z, K_12 = -omega_x, K_20 = -omega_y, K_21 = omega_x.
+ *   7. R'_ij = (D_i0 R_0j + D_i1 R_1j) + D_i2 R_2j  and  T'_i = T_i + v_i  in double on the float32 pose, each rounded to float32
+ *      once at the store: R' = R_delta R, T' = T + v.  The kernel does not re-orthonormalise.
+ *   history row (5 doubles, device): count, E, w2, v2, status.  w2 and v2 are 0 where nothing was solved (TOO_FEW, DEGENERATE,
+ *   update == 0).  pose12 is left bit for bit unchanged unless the status is OK and update != 0.
+ * Never synchronises; capture-safe.  PNR_EINVAL before any launch: null or misaligned workspace, history (8 bytes) or pose12 (4);
+ * n_pix < 1 or > 2^31 - 1; min_matches < 1; !(max_rot > 0) or max_rot > PNR_ICP_MAX_ROT (the series' cap); !(max_trans > 0)
+ * (+inf allowed). */
+#define PNR_ICP_MATCH 0
+#define PNR_ICP_NO_DEPTH 1
+#define PNR_ICP_OUTSIDE 2
+#define PNR_ICP_NO_MODEL 3
+#define PNR_ICP_TOO_FAR 4
+#define PNR_ICP_BACK_FACING 5
+#define PNR_ICP_OK 0
+#define PNR_ICP_TOO_FEW 1
+#define PNR_ICP_DEGENERATE 2
+#define PNR_ICP_STEP_TOO_LARGE 3
+#define PNR_ICP_SUMS 28                 /* 21 of A, 6 of g, E */
+#define PNR_ICP_ROW 29                  /* 8-byte slots a workgroup writes: the sums and the count */
+#define PNR_ICP_MAX_BLOCKS 256          /* the grid's limit: what pnr_icp_workspace_bytes sizes for */
+#define PNR_ICP_SERIES_TERMS 8
+#define PNR_ICP_MAX_ROT 0.5f            /* radians: the largest max_rot pnr_icp_solve accepts */
+int64_t pnr_icp_workspace_bytes(int64_t n_pix);
+int pnr_icp_accumulate(int model_l, const float* cam_l_host, int width_l, int height_l, const float* depth_l, const float* pose12,
+                       int model_m, const float* cam_m_host, const float* c2w_m12_host, const float* w2c_m12_host, int width_m,
+                       int height_m, const float* depth_m, const float* normal_m, float dist_max, void* workspace, uint8_t* code,
+                       float* residual, void* stream);
+int pnr_icp_solve(const void* workspace, int64_t n_pix, int64_t min_matches, float max_rot, float max_trans, int update,
+                  float* pose12, double* history_row, void* stream);
+
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable
  * state -- the one diagnostic hook of the MLP kernels is a descriptor field (pnr_mlp_desc.clk_probe). */

@@ -133,6 +133,11 @@ SIGNATURES = {
     "pnr_tsdf_raycast": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
                                  ctypes.c_float, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                  c_f, c_f, ctypes.c_float, ctypes.c_float, c_int, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_icp_workspace_bytes": (c_i64, [c_i64]),
+    "pnr_icp_accumulate": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_f, c_int, ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_f, ctypes.c_float,
+                                   c_f, c_f, c_f, c_f]),
+    "pnr_icp_solve": (c_int, [c_f, c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_f, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

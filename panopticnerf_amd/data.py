@@ -150,6 +150,30 @@ class FrameSet:
             self._w2c_rows = n
         return self._w2c
 
+    def set_pose(self, i, c2w):
+        """Replace the pose of frame i: c2w a 3x4 (or 4x4) camera-to-world, host values (a tracked pose comes back from the device
+        with .cpu(): the one read a tracking loop needs per frame).  The frame's record on the device, the host copy and --
+        once w2c_table() has been made -- its row there are updated by stream-ordered copies, as add()'s: launches enqueued
+        later (graph replays included) see the new pose, launches enqueued before see the old one."""
+        try:
+            i = int(i)
+        except (TypeError, ValueError):
+            raise TypeError("FrameSet.set_pose: i must be a frame index") from None
+        if not 0 <= i < len(self.frames):
+            raise IndexError("FrameSet.set_pose: frame %d of a set of %d" % (i, len(self.frames)))
+        pose = torch.as_tensor(c2w)
+        if pose.is_cuda:
+            raise TypeError("FrameSet.set_pose: c2w must be host values (a device pose: c2w.cpu())")
+        pose = _rows3(pose.to(torch.float32), "FrameSet.set_pose: c2w must be a 3x4 (or 4x4) matrix").clone()
+        if not bool(torch.isfinite(pose).all()):
+            raise ValueError("FrameSet.set_pose: c2w must be finite")
+        off = i * _REC + _lib.Frame.c2w.offset
+        with torch.cuda.device(self.device):
+            self.table[off:off + 48].copy_(pose.view(torch.uint8))
+            if self._w2c is not None and i < self._w2c_rows:
+                self._w2c[i].copy_(invert_pose(pose).reshape(12))
+        self.frames[i]["c2w"] = pose.reshape(3, 4)
+
     def set_boxes(self, bbox, bbox_ids):
         """The scene's 3D box prior, returned in every batch: bbox (M, 15), bbox_ids (M, 2) (ops.bbox_hits' layout).  A second
         call with the same number of boxes writes into the tensors of the first, so batches handed out before -- the static batch

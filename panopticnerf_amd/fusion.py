@@ -25,7 +25,16 @@ The way back from the volume to an image is `raycast` (ops.tsdf_raycast / pnr_ts
     consistency.reproject((camera, c2w, maps), other_view)    # (camera, c2w, maps) is a view like render_view's
 
 Out of scope there: steps that adapt to the tsdf value, block-level empty-space skipping, trilinear colour, shading, sub-lists
-of pixels, pose refinement (ICP) against the ray-cast."""
+of pixels.
+
+The ray-cast is also the model a new frame is aligned to: `track` (ops.icp_accumulate / ops.icp_solve; include/pnr.h "pose
+tracking") refines a pose guess by point-to-plane ICP on the device, and FrameSet.set_pose writes it back, which closes the loop:
+
+    view = (camera, c2w_prev, fusion.raycast(vol, camera, c2w_prev, near, far))
+    c2w, info = fusion.track(view, camera, depth, c2w_prev)   # device (3, 4); info["history"]: count, E, |w|^2, |v|^2, status per iteration
+    frames.set_pose(i, c2w.cpu()); fusion.integrate(vol, frames, trunc, first=i, last=i + 1)
+
+Out of scope there: image pyramids, robust weights, live normals and a normal-angle gate, colour terms, stopping early."""
 import numpy as np
 import torch
 
@@ -259,3 +268,99 @@ def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps
         if volume.rgb is not None:
             maps["rgb"] = torch.where(maps["valid"][..., None], volume.colors().reshape(-1, 3)[at], torch.zeros((), dtype=torch.uint8, device=dev))
     return maps
+
+
+MATCH, NO_DEPTH, OUTSIDE, NO_MODEL, TOO_FAR, BACK_FACING = (ops.ICP_MATCH, ops.ICP_NO_DEPTH, ops.ICP_OUTSIDE, ops.ICP_NO_MODEL,
+                                                            ops.ICP_TOO_FAR, ops.ICP_BACK_FACING)
+ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = ops.ICP_OK, ops.ICP_TOO_FEW, ops.ICP_DEGENERATE, ops.ICP_STEP_TOO_LARGE
+
+
+def _is_camera(camera):
+    return all(hasattr(camera, k) for k in ("word", "params", "width", "height")) and camera.word in _MODEL_NAMES
+
+
+def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=64, max_rot=0.25, max_trans=0.5, maps=True):
+    """Refine the pose of a live depth frame against a model view by point-to-plane ICP with projective association (the rule is
+    in include/pnr.h "pose tracking"): frame-to-model alignment, the step that closes raycast -> track -> set_pose -> integrate.
+    model_view: (camera_M, c2w_M, maps) with maps["depth"] and the world-space maps["normal"], as `raycast` returns them (c2w_M: host
+    values); camera, depth: the live frame, depth a (height, width) float32 GPU image in render_view's convention; c2w: the guess,
+    3x4 (or 4x4) host values or a device tensor (a host guess is uploaded by a stream-ordered copy: inside a graph capture pass a
+    device tensor).  Cameras of any model on either side.  Each of the `iters` iterations is one ops.icp_accumulate and one
+    ops.icp_solve on a pose that stays in device memory; a last accumulate at the final pose fills history row `iters` and, with
+    maps, the images.  dist_max: matches farther apart (world units) are dropped; an iteration with fewer than min_matches, a
+    degenerate system, or a step beyond max_rot (radians, at most 0.5) / max_trans leaves the pose as it was.
+    Returns (c2w, info): c2w a device (3, 4) float32; info["history"] a device (iters + 1, 5) float64 of count, E = sum r^2,
+    |omega|^2, |v|^2, status (ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE) per iteration; with maps info["code"] uint8
+    (MATCH, NO_DEPTH, OUTSIDE, NO_MODEL, TOO_FAR, BACK_FACING), info["residual"] float32 and info["valid"] = code == MATCH.
+    Nothing is synchronised and nothing is read back: the 2 iters + 2 launches can be captured in a graph, and a replay sees the
+    depth image's and the model maps' current contents."""
+    try:
+        cam_m, c2w_m, mmaps = model_view
+    except (TypeError, ValueError):
+        raise TypeError("fusion.track: model_view must be (camera, c2w, maps), a view as fusion.raycast makes it") from None
+    if not _is_camera(cam_m):
+        raise TypeError("fusion.track: the model view's camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (cam_m,))
+    if not _is_camera(camera):
+        raise TypeError("fusion.track: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (camera,))
+    if not hasattr(mmaps, "keys") or "depth" not in mmaps:
+        raise ValueError("fusion.track: the model view's maps need 'depth'")
+    if mmaps.get("normal") is None:
+        raise ValueError("fusion.track: the model view's maps need 'normal' (fusion.raycast with normals=True)")
+    c2w_m = torch.as_tensor(c2w_m, dtype=torch.float32).reshape(-1)
+    if c2w_m.numel() not in (12, 16):
+        raise ValueError("fusion.track: the model view's c2w must be a 3x4 (or 4x4) matrix")
+    c2w_m = c2w_m[:12]
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("fusion.track: iters must be >= 0 (got %d)" % iters)
+    # the scalars the two ops would refuse, refused here: before anything is allocated or launched
+    dist_max, min_matches, max_rot, max_trans = float(dist_max), int(min_matches), float(max_rot), float(max_trans)
+    if not (0.0 < dist_max < 1.8e19):
+        raise ValueError("fusion.track: dist_max must be positive with a finite float32 square (got %r)" % dist_max)
+    if min_matches < 1:
+        raise ValueError("fusion.track: min_matches must be >= 1 (got %d)" % min_matches)
+    if not (0.0 < max_rot <= ops.ICP_MAX_ROT):
+        raise ValueError("fusion.track: max_rot must lie in (0, %g] radians (got %r)" % (ops.ICP_MAX_ROT, max_rot))
+    if not (max_trans > 0.0):
+        raise ValueError("fusion.track: max_trans must be positive (it may be inf; got %r)" % max_trans)
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError("fusion.track: depth must be a GPU tensor, got %s" % type(depth).__name__)
+    if not depth.is_cuda:
+        raise RuntimeError("fusion.track: depth is not on the GPU (the HIP path has no CPU fallback)")
+    dev, h, w = depth.device, int(camera.height), int(camera.width)
+    hm, wm = int(cam_m.height), int(cam_m.width)
+    for name, t, shape in (("depth", depth, (h, w)), ("the model view's depth", mmaps["depth"], (hm, wm)),
+                           ("the model view's normal", mmaps["normal"], (hm, wm, 3))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError("fusion.track: %s must be a float32 tensor of shape %s, got %s"
+                             % (name, shape, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.is_contiguous():
+            raise ValueError("fusion.track: %s must be contiguous" % name)
+        if t.device != dev:
+            raise ValueError("fusion.track: %s is on %s, depth on %s" % (name, t.device, dev))
+    if isinstance(c2w, torch.Tensor) and c2w.is_cuda:
+        if c2w.numel() not in (12, 16):
+            raise ValueError("fusion.track: c2w must be a 3x4 (or 4x4) matrix")
+        pose = c2w.to(dev, torch.float32).reshape(-1)[:12].clone()
+    else:
+        host = torch.as_tensor(c2w, dtype=torch.float32).reshape(-1)
+        if host.numel() not in (12, 16):
+            raise ValueError("fusion.track: c2w must be a 3x4 (or 4x4) matrix")
+        pose = host[:12].to(dev)
+    ws = ops.icp_workspace(w * h, dev)
+    history = torch.zeros((iters + 1, 5), dtype=torch.float64, device=dev)
+    live = (_MODEL_NAMES[camera.word], camera.params, w, h, depth, pose)
+    model = (_MODEL_NAMES[cam_m.word], cam_m.params, c2w_m, int(cam_m.width), int(cam_m.height), mmaps["depth"], mmaps["normal"])
+    solve = dict(min_matches=min_matches, max_rot=max_rot, max_trans=max_trans)
+    for k in range(iters):
+        ops.icp_accumulate(*live, *model, dist_max, ws)
+        ops.icp_solve(ws, w * h, pose, history[k], **solve)
+    info = {"history": history}
+    if maps:
+        info["code"] = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        info["residual"] = torch.empty((h, w), dtype=torch.float32, device=dev)
+    ops.icp_accumulate(*live, *model, dist_max, ws, code=info.get("code"), residual=info.get("residual"))
+    ops.icp_solve(ws, w * h, pose, history[iters], update=False, **solve)
+    if maps:
+        info["valid"] = info["code"] == MATCH
+    return pose.reshape(3, 4), info

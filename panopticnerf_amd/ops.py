@@ -689,6 +689,116 @@ def raycast_default_max_steps(res, step, dt):
     return min(int(diag / float(dt)) + 2, 2 ** 31 - 1)
 
 
+# PNR_ICP_* (include/pnr.h "pose tracking"): the per-pixel codes and the solve's status
+ICP_MATCH, ICP_NO_DEPTH, ICP_OUTSIDE, ICP_NO_MODEL, ICP_TOO_FAR, ICP_BACK_FACING = 0, 1, 2, 3, 4, 5
+ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = 0, 1, 2, 3
+ICP_MAX_ROT = 0.5
+ICP_MAX_PIXELS = 2 ** 31 - 1
+
+
+def icp_workspace(n_pix, device):
+    """the workspace of icp_accumulate / icp_solve for a live frame of n_pix pixels: a float64 tensor on `device`"""
+    n = _size_or_raise(_lib.load().pnr_icp_workspace_bytes(int(n_pix)), "pnr_icp_workspace_bytes")
+    return torch.empty((n // 8,), dtype=torch.float64, device=device)
+
+
+def _icp_pose(pose12, what):
+    if not isinstance(pose12, torch.Tensor):
+        raise ValueError("%s: pose12 must be a GPU tensor of 12 float32 (the 3x4 camera-to-world, updated in place), got %s"
+                         % (what, type(pose12).__name__))
+    _chk(pose12, what + ": pose12")
+    if pose12.numel() != 12:
+        raise ValueError("%s: pose12 must hold 12 values (3x4 row-major), got %s" % (what, tuple(pose12.shape)))
+    return pose12
+
+
+def _icp_workspace(workspace, n_pix, what):
+    if not isinstance(workspace, torch.Tensor):
+        raise ValueError("%s: workspace must be a GPU tensor (ops.icp_workspace), got %s" % (what, type(workspace).__name__))
+    _chk(workspace, what + ": workspace", torch.float64)
+    need = _size_or_raise(_lib.load().pnr_icp_workspace_bytes(n_pix), "pnr_icp_workspace_bytes") // 8
+    if workspace.dim() != 1 or workspace.numel() < need:
+        raise ValueError("%s: workspace must be a flat float64 tensor of at least %d elements (ops.icp_workspace), got %s"
+                         % (what, need, tuple(workspace.shape)))
+    return workspace
+
+
+@_on_device
+def icp_accumulate(camera_model, cam, width, height, depth, pose12, model_camera_model, model_cam, model_c2w, model_width, model_height,
+                   model_depth, model_normal, dist_max, workspace, code=None, residual=None):
+    """One linearisation of point-to-plane ICP (pnr_icp_accumulate; the rule is in include/pnr.h "pose tracking").  The live side:
+    camera_model / cam / width / height as project_points takes a camera, depth a (height, width) float32 image, pose12 the
+    DEVICE pose (12 float32, 3x4 camera-to-world), read when the kernel runs.  The model side: its camera, model_c2w (3x4 host
+    values; the w2c is camera.invert_pose of it), model_depth (model_height, model_width) and model_normal (., ., 3) float32 as
+    fusion.raycast writes them.  workspace: ops.icp_workspace(width * height, device); it receives one row of partial sums per
+    workgroup, which icp_solve adds.  Optional outputs: code (height, width) uint8, residual (height, width) float32.  Returns None."""
+    what = "icp_accumulate"
+    for name, m in (("camera_model", camera_model), ("model_camera_model", model_camera_model)):
+        if m not in _MODEL_WORDS:
+            raise ValueError("%s: %s must be 'pinhole', 'fisheye' or 'equirect', not %r" % (what, name, m))
+    (word_l, nc_l), (word_m, nc_m) = _MODEL_WORDS[camera_model], _MODEL_WORDS[model_camera_model]
+    cam_l = _host_floats(cam, nc_l, "%s: model %r cam" % (what, camera_model))
+    cam_m = _host_floats(model_cam, nc_m, "%s: model %r model_cam" % (what, model_camera_model))
+    c2w_m = _host_floats(model_c2w, 12, what + ": model_c2w")
+    from .camera import invert_pose
+    w2c_m = _host_floats(invert_pose(torch.tensor(list(c2w_m), dtype=torch.float32)), 12, what + ": model w2c")
+    width, height, wm, hm = int(width), int(height), int(model_width), int(model_height)
+    for w, h, side in ((width, height, "the live image"), (wm, hm, "the model image")):
+        if w < 1 or h < 1 or w * h > ICP_MAX_PIXELS:
+            raise ValueError("%s: bad size of %s, %d x %d (width, height >= 1, at most 2^31 - 1 pixels)" % (what, side, w, h))
+    for name, t, dtype, shape, needed in (("depth", depth, torch.float32, (height, width), True),
+                                          ("model_depth", model_depth, torch.float32, (hm, wm), True),
+                                          ("model_normal", model_normal, torch.float32, (hm, wm, 3), True),
+                                          ("code", code, torch.uint8, (height, width), False),
+                                          ("residual", residual, torch.float32, (height, width), False)):
+        if t is None and not needed:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
+    dist_max = float(dist_max)
+    if not (0.0 < dist_max < 1.8e19):
+        raise ValueError("%s: dist_max must be positive with a finite float32 square (got %r)" % (what, dist_max))
+    _icp_pose(pose12, what)
+    _icp_workspace(workspace, width * height, what)
+    _stereo_gpu(what, depth=depth, pose12=pose12, model_depth=model_depth, model_normal=model_normal, workspace=workspace, code=code,
+                residual=residual)
+    _lib.check(_lib.load().pnr_icp_accumulate(word_l, cam_l, width, height, _p(depth), _p(pose12), word_m, cam_m, c2w_m, w2c_m, wm, hm,
+                                              _p(model_depth), _p(model_normal), dist_max, _p(workspace), _p(code), _p(residual),
+                                              _stream()), "pnr_icp_accumulate")
+
+
+@_on_device
+def icp_solve(workspace, n_pix, pose12, history_row, min_matches=6, max_rot=ICP_MAX_ROT, max_trans=float("inf"), update=True):
+    """Add the rows icp_accumulate left in `workspace`, solve the 6 x 6 normal equations and update the device pose in place
+    (pnr_icp_solve; one workgroup).  n_pix: the live frame's width * height; pose12: 12 float32 on the GPU; history_row: (5,)
+    float64 on the GPU, which receives count, E, |omega|^2, |v|^2, status (ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE,
+    ICP_STEP_TOO_LARGE).  The pose changes only with status ICP_OK.  update=False: count and E only, nothing is solved."""
+    what = "icp_solve"
+    n_pix, min_matches, max_rot, max_trans = int(n_pix), int(min_matches), float(max_rot), float(max_trans)
+    if n_pix < 1 or n_pix > ICP_MAX_PIXELS:
+        raise ValueError("%s: n_pix must lie in 1 .. 2^31 - 1 (got %d)" % (what, n_pix))
+    if min_matches < 1:
+        raise ValueError("%s: min_matches must be >= 1 (got %d)" % (what, min_matches))
+    if not (0.0 < max_rot <= ICP_MAX_ROT):
+        raise ValueError("%s: max_rot must lie in (0, %g] radians (got %r)" % (what, ICP_MAX_ROT, max_rot))
+    if not (max_trans > 0.0):
+        raise ValueError("%s: max_trans must be positive (it may be inf; got %r)" % (what, max_trans))
+    _icp_pose(pose12, what)
+    _icp_workspace(workspace, n_pix, what)
+    if not isinstance(history_row, torch.Tensor):
+        raise ValueError("%s: history_row must be a GPU tensor of 5 float64, got %s" % (what, type(history_row).__name__))
+    _chk(history_row, what + ": history_row", torch.float64)
+    if tuple(history_row.shape) != (5,):
+        raise ValueError("%s: history_row must be (5,), got %s" % (what, tuple(history_row.shape)))
+    _stereo_gpu(what, workspace=workspace, pose12=pose12, history_row=history_row)
+    _lib.check(_lib.load().pnr_icp_solve(_p(workspace), n_pix, min_matches, max_rot, max_trans, 1 if update else 0, _p(pose12),
+                                         _p(history_row), _stream()), "pnr_icp_solve")
+
+
 class Draw:
     """One in-kernel random stream of a launch (include/pnr.h "in-kernel RNG", pnr_rng): `call` is the (2,) int64 GPU tensor
     {seed, offset} that rng_begin wrote, `tag` the stream (1 = t_rand, 2 = u, 3 + level = sigma noise), `ray_base` the global

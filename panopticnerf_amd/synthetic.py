@@ -241,3 +241,72 @@ def sdf_grid(kind, lo, hi, res, center=(0.0, 0.0, 0.0), radius=0.7, minor=0.25, 
         f = (X, Y, Z)[axis] + c[axis] - np.float32(offset)
     t = torch.from_numpy(np.ascontiguousarray(f.astype(np.float32)))
     return t if device is None else t.to(device)
+
+
+def camera_directions(camera):
+    """(height, width, 3) float64 camera-space ray directions of a camera.Pinhole / Fisheye / Equirect and (height, width) bool
+    = the pixel sees anything, in closed form on the CPU (the fisheye polynomial by Newton's method run until nothing moves): a
+    pinhole direction has z = 1 (its parameter is z-depth), a fisheye or equirect direction is unit length (its parameter is
+    range), the conventions of render_view.  For analytic test scenes; the GPU rays are ops.gen_rays*."""
+    h, w = int(camera.height), int(camera.width)
+    j, i = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    # the float32 parameters the kernels get (ops._host_floats), widened: the scene is exact for the camera the GPU sees
+    par = [float(v) for v in torch.tensor(camera.params, dtype=torch.float32).tolist()]
+    if camera.model == "pinhole":
+        fx, fy, cx, cy = par
+        return torch.stack([(i - cx) / fx, (j - cy) / fy, torch.ones_like(i)], -1), torch.ones((h, w), dtype=torch.bool)
+    if camera.model == "equirect":
+        lon0, dlon, lat0, dlat = par
+        lam, psi = math.pi * (lon0 + (i + 0.5) * dlon), math.pi * (lat0 + (j + 0.5) * dlat)
+        return torch.stack([torch.cos(psi) * torch.sin(lam), torch.sin(psi), torch.cos(psi) * torch.cos(lam)], -1), torch.ones((h, w), dtype=torch.bool)
+    if camera.model != "fisheye":
+        raise ValueError("camera_directions: unknown camera model %r" % (camera.model,))
+    xi, k1, k2, g1, g2, u0, v0 = par
+    x, y = (i - u0) / g1, (j - v0) / g2
+    rd = torch.sqrt(x * x + y * y)
+    r = rd.clone()
+    for _ in range(100):
+        r2 = r * r
+        step = (r * (1.0 + k1 * r2 + k2 * r2 * r2) - rd) / (1.0 + 3.0 * k1 * r2 + 5.0 * k2 * r2 * r2)
+        r = r - step
+        if not bool((step.abs() > 1e-16 * r.abs().clamp(min=1.0)).any()):
+            break
+    sc = torch.where(rd > 0, r / rd.clamp(min=1e-300), torch.ones_like(rd))
+    x, y = x * sc, y * sc
+    r2 = x * x + y * y
+    disc = 1.0 + (1.0 - xi * xi) * r2
+    ok = disc >= 0
+    lam = (xi + torch.sqrt(disc.clamp(min=0.0))) / (r2 + 1.0)
+    d = torch.stack([lam * x, lam * y, lam - xi], -1)
+    return torch.where(ok[..., None], d, torch.zeros_like(d)), ok
+
+
+def room_depth(camera, c2w, lo, hi, normals=False):
+    """The analytic depth image of the axis-aligned box [lo, hi] seen from INSIDE, for a camera of any model at the 3x4 (or 4x4)
+    pose c2w: (height, width) float32 in render_view's convention (z-depth in a pinhole, range in a fisheye / equirect frame), 0
+    where a fisheye pixel sees nothing.  A room is not symmetric, so -- unlike a sphere -- it pins all six degrees of freedom of
+    a pose: the scene of the tracking tests.  Float64 closed form on the CPU, rounded once.  normals=True: also the (height,
+    width, 3) float32 world-space unit normal of the wall each pixel sees, pointing into the room (0 where depth is 0)."""
+    m = torch.as_tensor(c2w, dtype=torch.float64).reshape(-1)
+    if m.numel() == 16:
+        m = m[:12]
+    if m.numel() != 12:
+        raise ValueError("room_depth: c2w must be a 3x4 (or 4x4) matrix")
+    m = m.reshape(3, 4)
+    lo64, hi64 = torch.as_tensor(lo, dtype=torch.float64).reshape(-1), torch.as_tensor(hi, dtype=torch.float64).reshape(-1)
+    if lo64.numel() != 3 or hi64.numel() != 3:
+        raise ValueError("room_depth: lo and hi must be 3-vectors")
+    o = m[:, 3]
+    if not bool(((lo64 < o) & (o < hi64)).all()):
+        raise ValueError("room_depth: the camera centre %r must lie strictly inside the box" % (o.tolist(),))
+    dc, ok = camera_directions(camera)
+    d = dc @ m[:, :3].T
+    wall = torch.where(d > 0, hi64, lo64)                                # the wall each axis' component runs towards
+    t = torch.where(d != 0, (wall - o) / torch.where(d != 0, d, torch.ones_like(d)), torch.full_like(d, float("inf")))
+    depth, axis = t.min(dim=-1)
+    depth = torch.where(ok, depth, torch.zeros_like(depth)).to(torch.float32)
+    if not normals:
+        return depth
+    n = torch.zeros_like(d)
+    n.scatter_(-1, axis[..., None], -torch.sign(torch.gather(d, -1, axis[..., None])))
+    return depth, torch.where(ok[..., None], n, torch.zeros_like(n)).to(torch.float32)
