@@ -43,6 +43,11 @@ def invert_pose(c2w):
     return torch.cat([rt, -(rt @ m[:, 3:])], 1).to(torch.float32)
 
 
+def is_camera(cam):
+    """a Pinhole / Fisheye / Equirect, or an object with what the ops and their wrappers read of one (the attributes below)"""
+    return all(hasattr(cam, k) for k in ("model", "word", "params", "width", "height"))
+
+
 class _Camera:
     """Shared half of the models: the per-device cache of valid pixels, the GPU-device check and projection.  A model adds
     `model` (its name), `word` (the model word of include/pnr.h PNR_CAMERA_*), `params` (the camera floats that go with the

@@ -40,6 +40,7 @@ import torch
 
 from . import mesh as _mesh
 from . import ops
+from .camera import is_camera
 
 LABEL_NONE = -1
 
@@ -136,13 +137,7 @@ def integrate(volume, frames, trunc, first=0, last=None, max_depth=float("inf"),
     first, last = int(first), n if last is None else int(last)
     if not 0 <= first <= last <= n:
         raise ValueError("fusion.integrate: need 0 <= first <= last <= %d (the frames of the set), got [%d, %d)" % (n, first, last))
-    trunc, max_depth, w_max = float(trunc), float(max_depth), float(w_max)
-    if not (0.0 < trunc < float("inf")):
-        raise ValueError("fusion.integrate: trunc must be positive and finite (got %r)" % trunc)
-    if not (max_depth > 0.0):
-        raise ValueError("fusion.integrate: max_depth must be positive (it may be inf; got %r)" % max_depth)
-    if not (w_max >= 1.0):
-        raise ValueError("fusion.integrate: w_max must be >= 1 (it may be inf; got %r)" % w_max)
+    trunc, max_depth, w_max = ops.integrate_params("fusion.integrate", trunc, max_depth, w_max)
     if not volume.tsdf.is_cuda:
         raise RuntimeError("fusion.integrate: the volume is not on the GPU (the HIP path has no CPU fallback)")
     if first == last:
@@ -214,7 +209,6 @@ def extract(volume, min_weight=1.0):
 
 
 HIT, NO_RAY, MISSED, NO_SURFACE = ops.RAYCAST_HIT, ops.RAYCAST_NO_RAY, ops.RAYCAST_MISSED, ops.RAYCAST_NO_SURFACE
-_MODEL_NAMES = {word: name for name, (word, _) in ops._MODEL_WORDS.items()}
 
 
 def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps=None, normals=True, attributes=True):
@@ -234,21 +228,12 @@ def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps
     Nothing is synchronised; the launch can be captured in a graph, and a replay sees what was integrated since."""
     if not isinstance(volume, Volume):
         raise TypeError("fusion.raycast: volume must be a fusion.Volume")
-    if not all(hasattr(camera, k) for k in ("word", "params", "width", "height")) or camera.word not in _MODEL_NAMES:
+    if not is_camera(camera):
         raise TypeError("fusion.raycast: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (camera,))
     if min(volume.res) < 2:
         raise ValueError("fusion.raycast: the volume is %d x %d x %d; ray casting needs every res >= 2" % volume.res)
-    near, far, min_weight = float(near), float(far), float(min_weight)
-    if not (near >= 0.0 and far > near):
-        raise ValueError("fusion.raycast: need 0 <= near < far (got %r, %r)" % (near, far))
-    if not (min_weight > 0.0):
-        raise ValueError("fusion.raycast: min_weight must be positive (got %r)" % min_weight)
-    dt = ops.raycast_default_dt(volume.step) if step is None else float(step)
-    if not (0.0 < dt < float("inf")):
-        raise ValueError("fusion.raycast: step must be positive and finite (got %r)" % dt)
-    max_steps = ops.raycast_default_max_steps(volume.res, volume.step, dt) if max_steps is None else int(max_steps)
-    if max_steps < 0:
-        raise ValueError("fusion.raycast: max_steps must be >= 0 (got %d)" % max_steps)
+    near, far, min_weight, dt, max_steps = ops.raycast_params("fusion.raycast", near, far, min_weight, step, max_steps, volume.res,
+                                                              volume.step, dt_name="step")
     if not volume.tsdf.is_cuda:
         raise RuntimeError("fusion.raycast: the volume is not on the GPU (the HIP path has no CPU fallback)")
     dev, h, w = volume.device, int(camera.height), int(camera.width)
@@ -256,7 +241,7 @@ def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps
             "src": torch.empty((h, w), dtype=torch.int32, device=dev)}
     if normals:
         maps["normal"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-    ops.tsdf_raycast(_MODEL_NAMES[camera.word], camera.params, c2w, w, h, near, far, volume.lo32, volume.step, volume.tsdf, volume.weight,
+    ops.tsdf_raycast(camera.model, camera.params, c2w, w, h, near, far, volume.lo32, volume.step, volume.tsdf, volume.weight,
                      maps["depth"], maps["code"], normal=maps.get("normal"), src=maps["src"], min_weight=min_weight, dt=dt,
                      max_steps=max_steps)
     maps["valid"] = maps["code"] == HIT
@@ -273,10 +258,6 @@ def raycast(volume, camera, c2w, near, far, step=None, min_weight=1.0, max_steps
 MATCH, NO_DEPTH, OUTSIDE, NO_MODEL, TOO_FAR, BACK_FACING = (ops.ICP_MATCH, ops.ICP_NO_DEPTH, ops.ICP_OUTSIDE, ops.ICP_NO_MODEL,
                                                             ops.ICP_TOO_FAR, ops.ICP_BACK_FACING)
 ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = ops.ICP_OK, ops.ICP_TOO_FEW, ops.ICP_DEGENERATE, ops.ICP_STEP_TOO_LARGE
-
-
-def _is_camera(camera):
-    return all(hasattr(camera, k) for k in ("word", "params", "width", "height")) and camera.word in _MODEL_NAMES
 
 
 def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=64, max_rot=0.25, max_trans=0.5, maps=True):
@@ -298,9 +279,9 @@ def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=6
         cam_m, c2w_m, mmaps = model_view
     except (TypeError, ValueError):
         raise TypeError("fusion.track: model_view must be (camera, c2w, maps), a view as fusion.raycast makes it") from None
-    if not _is_camera(cam_m):
+    if not is_camera(cam_m):
         raise TypeError("fusion.track: the model view's camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (cam_m,))
-    if not _is_camera(camera):
+    if not is_camera(camera):
         raise TypeError("fusion.track: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (camera,))
     if not hasattr(mmaps, "keys") or "depth" not in mmaps:
         raise ValueError("fusion.track: the model view's maps need 'depth'")
@@ -314,15 +295,8 @@ def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=6
     if iters < 0:
         raise ValueError("fusion.track: iters must be >= 0 (got %d)" % iters)
     # the scalars the two ops would refuse, refused here: before anything is allocated or launched
-    dist_max, min_matches, max_rot, max_trans = float(dist_max), int(min_matches), float(max_rot), float(max_trans)
-    if not (0.0 < dist_max < 1.8e19):
-        raise ValueError("fusion.track: dist_max must be positive with a finite float32 square (got %r)" % dist_max)
-    if min_matches < 1:
-        raise ValueError("fusion.track: min_matches must be >= 1 (got %d)" % min_matches)
-    if not (0.0 < max_rot <= ops.ICP_MAX_ROT):
-        raise ValueError("fusion.track: max_rot must lie in (0, %g] radians (got %r)" % (ops.ICP_MAX_ROT, max_rot))
-    if not (max_trans > 0.0):
-        raise ValueError("fusion.track: max_trans must be positive (it may be inf; got %r)" % max_trans)
+    dist_max = ops.icp_accumulate_params("fusion.track", dist_max)
+    min_matches, max_rot, max_trans = ops.icp_solve_params("fusion.track", min_matches, max_rot, max_trans)
     if not isinstance(depth, torch.Tensor):
         raise TypeError("fusion.track: depth must be a GPU tensor, got %s" % type(depth).__name__)
     if not depth.is_cuda:
@@ -349,8 +323,8 @@ def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=6
         pose = host[:12].to(dev)
     ws = ops.icp_workspace(w * h, dev)
     history = torch.zeros((iters + 1, 5), dtype=torch.float64, device=dev)
-    live = (_MODEL_NAMES[camera.word], camera.params, w, h, depth, pose)
-    model = (_MODEL_NAMES[cam_m.word], cam_m.params, c2w_m, int(cam_m.width), int(cam_m.height), mmaps["depth"], mmaps["normal"])
+    live = (camera.model, camera.params, w, h, depth, pose)
+    model = (cam_m.model, cam_m.params, c2w_m, int(cam_m.width), int(cam_m.height), mmaps["depth"], mmaps["normal"])
     solve = dict(min_matches=min_matches, max_rot=max_rot, max_trans=max_trans)
     for k in range(iters):
         ops.icp_accumulate(*live, *model, dist_max, ws)

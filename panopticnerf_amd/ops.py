@@ -5,11 +5,13 @@ PyTorch is used only for device memory and the current HIP stream: every op take
 All ops fail loudly off-GPU; nothing here computes on the CPU.
 """
 import ctypes
+import functools
 import os
 
 import torch
 
 from . import _lib
+from . import camera as _camera          # camera imports this module at its top: the module, not a name from it
 from ._lib import MlpDesc, MlpParamsHost
 
 
@@ -36,8 +38,6 @@ def _p(t):
 def _on_device(fn):
     """Run `fn` with the device of its first GPU-tensor argument current, so that `_stream()` is THAT device's current
     stream (a tensor on cuda:1 while cuda:0 is current would otherwise be launched on the wrong device's stream)."""
-    import functools
-
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         cand = []
@@ -59,6 +59,120 @@ def _host_floats(v, n, what):
     if len(vals) != n:
         raise ValueError(f"{what}: expected {n} values, got {len(vals)}")
     return (ctypes.c_float * n)(*vals)
+
+
+# The argument checks of the geometry ops.  Each takes the caller's name `what` first and refuses in that name, so an op and the
+# wrapper above it (fusion.*, mesh.extract, stereo.sgm) state a rule once; the ops call them in the order their refusals come.
+_INF = float("inf")
+MAX_PIXELS = 2 ** 31 - 1                        # of any image the ops take
+_MODEL_WORDS = {"pinhole": (_lib.CAMERA_PINHOLE, 4), "fisheye": (_lib.CAMERA_FISHEYE, 7), "equirect": (_lib.CAMERA_EQUIRECT, 4)}
+
+
+def _is_tensor(t, dtype=None, shape=None):
+    return isinstance(t, torch.Tensor) and (dtype is None or t.dtype == dtype) and (shape is None or tuple(t.shape) == tuple(shape))
+
+
+def _gpu(t, name):
+    if not _is_tensor(t):
+        raise ValueError("%s: expected a GPU tensor, got %s" % (name, type(t).__name__))
+
+
+def _tensor(what, name, t, must_be="a GPU tensor"):
+    """the other spelling of _gpu's test, with room for what the tensor holds"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be %s, got %s" % (what, name, must_be, type(t).__name__))
+
+
+def _tensor_table(what, needed, optional=()):
+    """rows of (name, tensor, dtype, shape): type, then dtype, then shape of each, on any device; a None among `optional` is absent"""
+    for rows, may_be_none in ((needed, False), (optional, True)):
+        for name, t, dtype, shape in rows:
+            if t is None and may_be_none:
+                continue
+            _tensor(what, name, t)
+            if t.dtype != dtype:
+                raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
+
+
+def _same_device(what, **tensors):
+    """device and contiguity of every tensor given (None: absent); all on the first one's device"""
+    ref = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        _chk(t, "%s: %s" % (what, name), t.dtype)
+        if ref is None:
+            ref = t
+        elif t.device != ref.device:
+            raise ValueError("%s: %s is on %s, not on %s" % (what, name, t.device, ref.device))
+
+
+def _on(what, dev, ref_name, **tensors):
+    """every tensor given (None: absent) is on `dev`, the device of the argument `ref_name`; for the ops that _chk each tensor"""
+    for name, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise ValueError("%s: %s is on %s, %s on %s" % (what, name, t.device, ref_name, dev))
+
+
+def _lattice_shape(what, name, t, min_res, max_points=2 ** 31 - 1, limit="2^31 - 1"):
+    """(res_x, res_y, res_z) of the (res_z, res_y, res_x) tensor `t`, the volume of the TSDF ops or the field of the mesh ops"""
+    _tensor(what, name, t)
+    if t.dim() != 3 or min(t.shape) < min_res:
+        raise ValueError("%s: %s must be (res_z, res_y, res_x) with every res >= %d, got %s" % (what, name, min_res, tuple(t.shape)))
+    if t.numel() > max_points:
+        raise ValueError("%s: %s holds %d points, more than the limit of %s" % (what, name, t.numel(), limit))
+    rz, ry, rx = t.shape
+    return rx, ry, rz
+
+
+def _lattice_floats(what, lo, step, nonzero_step=True):
+    """the lattice's origin and step per axis as host floats"""
+    lo_h, step_h = _host_floats(lo, 3, what + ": lo"), _host_floats(step, 3, what + ": step")
+    for name, h in (("lo", lo_h), ("step", step_h)):
+        if not all(abs(v) < _INF for v in h):
+            raise ValueError("%s: %s must be finite (got %r)" % (what, name, list(h)))
+    if nonzero_step and not all(v != 0.0 for v in step_h):
+        raise ValueError("%s: step must be non-zero (got %r)" % (what, list(step_h)))
+    return lo_h, step_h
+
+
+def _model_word(what, name, model):
+    """(model word, number of camera floats) of the model name given as argument `name`"""
+    if model not in _MODEL_WORDS:
+        raise ValueError("%s: %s must be 'pinhole', 'fisheye' or 'equirect', not %r" % (what, name, model))
+    return _MODEL_WORDS[model]
+
+
+def _camera_model(what, name, model, cam, cam_name="cam"):
+    """(model word, host floats) of a camera given as a model name (argument `name`) and its floats (argument `cam_name`)"""
+    word, n = _model_word(what, name, model)
+    return word, _host_floats(cam, n, "%s: model %r %s" % (what, model, cam_name))
+
+
+def _image_size(what, width, height, of="image"):
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or width * height > MAX_PIXELS:
+        raise ValueError("%s: bad %s %d x %d (width, height >= 1, at most 2^31 - 1 pixels)" % (what, of, width, height))
+    return width, height
+
+
+def _d_range(what, d_range, may_be_inf):
+    try:
+        d_min, d_max = (float(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("%s: d_range must be (d_min, d_max)" % what) from None
+    if not (0.0 < d_min <= d_max) or (d_max == _INF and not may_be_inf):
+        raise ValueError("%s: d_range must satisfy 0 < d_min <= d_max%s" % (what, " (d_max may be inf)" if may_be_inf else ", both finite"))
+    return d_min, d_max
+
+
+def _names(what, keys, known, refusal):
+    """every key is one of `known`, or the refusal: a template of %(key)s and %(known)s"""
+    for k in keys:
+        if k not in known:
+            raise ValueError("%s: %s" % (what, refusal % {"key": repr(k), "known": ", ".join(known)}))
 
 
 def _gen_rays(name, cam_h, c2w_h, width, height, near, far, pix, device, want_valid=None, ask_first=False):
@@ -105,19 +219,13 @@ def gen_rays_equirect(cam, c2w, width, height, near, far, pix=None, device=None)
     return _gen_rays("gen_rays_equirect", cam_h, c2w_h, width, height, near, far, pix, device, ask_first=True)[0]
 
 
-_MODEL_WORDS = {"pinhole": (_lib.CAMERA_PINHOLE, 4), "fisheye": (_lib.CAMERA_FISHEYE, 7), "equirect": (_lib.CAMERA_EQUIRECT, 4)}
-
-
 @_on_device
 def project_points(model, cam, w2c, width, height, points):
     """World points (P,3) -> uv (P,2) pixel coordinates, range (P) = distance from the camera centre, valid (P) uint8 = inside
     the projection's domain and inside the image (pnr_project_points).  model: "pinhole" (cam: fx, fy, cx, cy), "fisheye"
     (cam: xi, k1, k2, gamma1, gamma2, u0, v0) or "equirect" (cam: lon0, dlon, lat0, dlat in half-turns; u wraps round a full
     circle); w2c: 3x4 world-to-camera (host values)."""
-    if model not in _MODEL_WORDS:
-        raise ValueError("project_points: model must be 'pinhole', 'fisheye' or 'equirect', not %r" % (model,))
-    word, nc = _MODEL_WORDS[model]
-    cam_h = _host_floats(cam, nc, "project_points: model %r cam" % (model,))
+    word, cam_h = _camera_model("project_points", "model", model, cam)
     w2c_h = _host_floats(w2c, 12, "project_points: w2c")
     points = _chk(points, "points")
     if points.dim() != 2 or points.shape[1] != 3:
@@ -133,7 +241,7 @@ def project_points(model, cam, w2c, width, height, points):
 
 def _camera_words(cam, what):
     """(model word, host floats, width, height) of a camera.Pinhole / camera.Fisheye / camera.Equirect"""
-    if not all(hasattr(cam, k) for k in ("word", "params", "width", "height")):
+    if not _camera.is_camera(cam):
         raise ValueError("%s: expected a camera.Pinhole or camera.Fisheye (or camera.Equirect), not %r" % (what, cam))
     return cam.word, _host_floats(cam.params, len(cam.params), what), int(cam.width), int(cam.height)
 
@@ -142,9 +250,9 @@ def _image(t, width, height, name):
     """a (height, width) or (height * width) map of a camera, flattened; None stays None"""
     if t is None:
         return None
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((height, width), (height * width,)):
+    if not _is_tensor(t) or tuple(t.shape) not in ((height, width), (height * width,)):
         raise ValueError("%s: expected a (%d, %d) image (or its %d flattened pixels), got %s"
-                         % (name, height, width, height * width, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+                         % (name, height, width, height * width, tuple(t.shape) if _is_tensor(t) else type(t).__name__))
     return t.reshape(-1) if t.is_contiguous() else t
 
 
@@ -172,15 +280,13 @@ def reproject(src, c2w_src, depth_src, tgt, w2c_tgt, depth_tgt=None, pix=None, t
     mt, cam_t, wt, ht = _camera_words(tgt, "reproject: tgt")
     c2w_h, w2c_h = _host_floats(c2w_src, 12, "reproject: c2w_src"), _host_floats(w2c_tgt, 12, "reproject: w2c_tgt")
     want = tuple(want)
-    for k in want:
-        if k not in REPROJECT_OUTPUTS:
-            raise ValueError("reproject: unknown output %r (one of %s)" % (k, ", ".join(REPROJECT_OUTPUTS)))
+    _names("reproject", want, REPROJECT_OUTPUTS, "unknown output %(key)s (one of %(known)s)")
     if depth_src is None:
         raise ValueError("reproject: depth_src is required")
     if (label_src is None) != (label_tgt is None):
         raise ValueError("reproject: label_src and label_tgt come together")
     tol_abs, tol_rel = (float(v) for v in tol)
-    if not (0.0 <= tol_abs < float("inf") and 0.0 <= tol_rel < float("inf")):
+    if not (0.0 <= tol_abs < _INF and 0.0 <= tol_rel < _INF):
         raise ValueError("reproject: tol = (absolute, relative) must be finite and >= 0")
     n_classes = int(n_classes)
     if (agree is not None or "agree" in want) and label_src is None:
@@ -206,25 +312,15 @@ def reproject(src, c2w_src, depth_src, tgt, w2c_tgt, depth_tgt=None, pix=None, t
     if _chk(stats, "reproject: stats", torch.int64) is not None and tuple(stats.shape) != (5,):
         raise ValueError("reproject: stats must be (5,)")
     out = out or {}
-    for k in out:
-        if k not in ("match", "uv"):
-            raise ValueError("reproject: out holds %r (only 'match' and 'uv' can be caller-owned)" % (k,))
+    _names("reproject", out, ("match", "uv"), "out holds %(key)s (only 'match' and 'uv' can be caller-owned)")
     match = _own(out.get("match"), (R,), torch.int32, dev, "reproject: match") if "match" in want or "match" in out else None
     uv = _own(out.get("uv"), (R, 2), torch.float32, dev, "reproject: uv") if "uv" in want or "uv" in out else None
-    for name, t in (("depth_tgt", depth_tgt), ("label_src", label_src), ("label_tgt", label_tgt), ("pix", pix), ("agree", agree), ("stats", stats)):
-        if t is not None and t.device != dev:
-            raise ValueError("reproject: %s is on %s, depth_src on %s" % (name, t.device, dev))
+    _on("reproject", dev, "depth_src", depth_tgt=depth_tgt, label_src=label_src, label_tgt=label_tgt, pix=pix, agree=agree, stats=stats)
     _lib.check(_lib.load().pnr_reproject(ms, cam_s, c2w_h, ws, hs, _p(pix), R, _p(depth_src), mt, cam_t, w2c_h, wt, ht, _p(depth_tgt),
                                          tol_abs, tol_rel, _p(label_src), _p(label_tgt), n_classes if label_src is not None else 0,
                                          _p(match), _p(uv), _p(agree), _p(stats), _stream()), "pnr_reproject")
     ret = {"match": match, "uv": uv, "agree": agree, "stats": stats}
     return {k: v for k, v in ret.items() if v is not None}
-
-
-def _gpu(t, name, what="a GPU tensor"):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s: expected %s, got %s" % (name, what, type(t).__name__))
-    return t
 
 
 @_on_device
@@ -251,18 +347,15 @@ def splat_points(camera, w2c, points, zbuf=None, index_base=0, near=0.0, far=flo
     P = points.shape[0]
     if index_base < 0 or index_base + P > 2 ** 31 - 1:
         raise ValueError("splat_points: index_base + the number of points must stay within 0 .. 2^31 - 1")
-    if zbuf is not None and (not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (height, width)):
+    if zbuf is not None and not _is_tensor(zbuf, shape=(height, width)):
         raise ValueError("splat_points: zbuf must be a (%d, %d) int64 tensor" % (height, width))
-    if stats is not None and (not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (3,)):
+    if stats is not None and not _is_tensor(stats, shape=(3,)):
         raise ValueError("splat_points: stats must be (3,)")
     points = _chk(points, "splat_points: points")
     dev = points.device
     zbuf, stats = _chk(zbuf, "splat_points: zbuf", torch.int64), _chk(stats, "splat_points: stats", torch.int64)
-    for name, t in (("zbuf", zbuf), ("stats", stats)):
-        if t is not None and t.device != dev:
-            raise ValueError("splat_points: %s is on %s, points on %s" % (name, t.device, dev))
-    if zbuf is None:
-        zbuf = torch.full((height, width), -1, device=dev, dtype=torch.int64)
+    _on("splat_points", dev, "points", zbuf=zbuf, stats=stats)
+    zbuf = torch.full((height, width), -1, device=dev, dtype=torch.int64) if zbuf is None else zbuf
     _lib.check(_lib.load().pnr_splat_points(model, cam_h, w2c_h, width, height, _p(points), P, index_base, near, far, radius,
                                             _p(zbuf), _p(stats), _stream()), "pnr_splat_points")
     return zbuf
@@ -274,14 +367,9 @@ def splat_resolve(zbuf, want=("depth", "index"), out=None):
     0 where no point landed (the "unknown" depth ops.reproject reads); index int32 = the winning point's index_base + i, -1
     where none.  want: which of the two to make (the other is None); out: {"depth": ..., "index": ...} caller-owned tensors."""
     _gpu(zbuf, "splat_resolve: zbuf")
-    want = tuple(want)
-    for k in want:
-        if k not in ("depth", "index"):
-            raise ValueError("splat_resolve: unknown output %r (depth, index)" % (k,))
-    out = out or {}
-    for k in out:
-        if k not in ("depth", "index"):
-            raise ValueError("splat_resolve: out holds %r (only 'depth' and 'index')" % (k,))
+    want, out = tuple(want), out or {}
+    _names("splat_resolve", want, ("depth", "index"), "unknown output %(key)s (%(known)s)")
+    _names("splat_resolve", out, ("depth", "index"), "out holds %(key)s (only 'depth' and 'index')")
     zbuf = _chk(zbuf, "splat_resolve: zbuf", torch.int64)
     dev, shape = zbuf.device, tuple(zbuf.shape)
     depth = _own(out.get("depth"), shape, torch.float32, dev, "splat_resolve: depth") if "depth" in want or "depth" in out else None
@@ -305,31 +393,21 @@ def depth_metrics(pred, gt, mask=None, d_range=DEPTH_RANGE, sums=None, counts=No
     _gpu(gt, "depth_metrics: gt")
     if pred.shape != gt.shape:
         raise ValueError("depth_metrics: pred is %s, gt %s" % (tuple(pred.shape), tuple(gt.shape)))
-    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.shape != gt.shape):
+    if mask is not None and not _is_tensor(mask, shape=gt.shape):
         raise ValueError("depth_metrics: mask must have gt's shape %s" % (tuple(gt.shape),))
-    try:
-        d_min, d_max = (float(v) for v in d_range)
-    except (TypeError, ValueError):
-        raise ValueError("depth_metrics: d_range must be (d_min, d_max)") from None
-    if not (0.0 < d_min <= d_max < float("inf")):
-        raise ValueError("depth_metrics: d_range must satisfy 0 < d_min <= d_max, both finite")
-    if sums is not None and (not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (5,)):
-        raise ValueError("depth_metrics: sums must be (5,)")
-    if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (5,)):
-        raise ValueError("depth_metrics: counts must be (5,)")
+    d_min, d_max = _d_range("depth_metrics", d_range, may_be_inf=False)
+    for name, t in (("sums", sums), ("counts", counts)):
+        if t is not None and not _is_tensor(t, shape=(5,)):
+            raise ValueError("depth_metrics: %s must be (5,)" % name)
     pred, gt = _chk(pred, "depth_metrics: pred"), _chk(gt, "depth_metrics: gt")
     dev = gt.device
     if mask is not None and mask.dtype == torch.bool and mask.is_cuda and mask.is_contiguous():
         mask = mask.view(torch.uint8)
     mask = _chk(mask, "depth_metrics: mask (bool or uint8)", torch.uint8)
     sums, counts = _chk(sums, "depth_metrics: sums", torch.float64), _chk(counts, "depth_metrics: counts", torch.int64)
-    for name, t in (("pred", pred), ("mask", mask), ("sums", sums), ("counts", counts)):
-        if t is not None and t.device != dev:
-            raise ValueError("depth_metrics: %s is on %s, gt on %s" % (name, t.device, dev))
-    if sums is None:
-        sums = torch.zeros((5,), device=dev, dtype=torch.float64)
-    if counts is None:
-        counts = torch.zeros((5,), device=dev, dtype=torch.int64)
+    _on("depth_metrics", dev, "gt", pred=pred, mask=mask, sums=sums, counts=counts)
+    sums = torch.zeros((5,), device=dev, dtype=torch.float64) if sums is None else sums
+    counts = torch.zeros((5,), device=dev, dtype=torch.int64) if counts is None else counts
     n = gt.numel()
     ws = torch.empty((_size_or_raise(_lib.load().pnr_depth_metrics_workspace_bytes(n), "pnr_depth_metrics_workspace_bytes") // 8,),
                      device=dev, dtype=torch.float64)
@@ -338,11 +416,12 @@ def depth_metrics(pred, gt, mask=None, d_range=DEPTH_RANGE, sums=None, counts=No
     return sums, counts
 
 
-def _stereo_arg(t, name, dtype, shape=None, ndim=None):
-    """A tensor argument of the stereo ops: type, dtype and shape, refused by name on any device (_stereo_gpu refuses a CPU
-    tensor, after the parameters)."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s: expected a GPU tensor, got %s" % (name, type(t).__name__))
+def _stereo_arg(t, name, dtype, shape=None, ndim=None, optional=False):
+    """A tensor argument of the stereo ops (None: an absent `optional` one): type, dtype and shape, refused by name on any device.
+    Not _tensor_table's rows: the messages say "expected", and there are ndim and empty."""
+    if t is None and optional:
+        return None
+    _gpu(t, name)
     if t.dtype != dtype:
         raise TypeError("%s: expected %s, got %s" % (name, dtype, t.dtype))
     if ndim is not None and t.dim() != ndim:
@@ -352,19 +431,6 @@ def _stereo_arg(t, name, dtype, shape=None, ndim=None):
     if t.numel() == 0:
         raise ValueError("%s: empty tensor" % name)
     return t
-
-
-def _stereo_gpu(what, **tensors):
-    """device and contiguity of every tensor given (None: absent); all on the first one's device"""
-    ref = None
-    for name, t in tensors.items():
-        if t is None:
-            continue
-        _chk(t, "%s: %s" % (what, name), t.dtype)
-        if ref is None:
-            ref = t
-        elif t.device != ref.device:
-            raise ValueError("%s: %s is on %s, not on %s" % (what, name, t.device, ref.device))
 
 
 def _stereo_disp(what, max_disp):
@@ -400,11 +466,9 @@ def census(img, out=None):
     """Census words of an (H, W) uint8 image (pnr_census; include/pnr.h "stereo matching" step 1): (H, W) int64, the 62
     comparisons of the 9 x 7 window with a replicated border."""
     img = _stereo_arg(img, "census: img", torch.uint8, ndim=2)
-    if out is not None:
-        out = _stereo_arg(out, "census: out", torch.int64, shape=img.shape)
-    _stereo_gpu("census", img=img, out=out)
-    if out is None:
-        out = torch.empty(tuple(img.shape), device=img.device, dtype=torch.int64)
+    out = _stereo_arg(out, "census: out", torch.int64, shape=img.shape, optional=True)
+    _same_device("census", img=img, out=out)
+    out = torch.empty(tuple(img.shape), device=img.device, dtype=torch.int64) if out is None else out
     H, W = img.shape
     _lib.check(_lib.load().pnr_census(_p(img), W, H, _p(out), _stream()), "pnr_census")
     return out
@@ -419,12 +483,10 @@ def sgm_aggregate(census_l, census_r, max_disp=128, p1=10, p2=120, paths=8, out=
     census_r = _stereo_arg(census_r, "sgm_aggregate: census_r", torch.int64, shape=census_l.shape)
     max_disp, p1, p2, paths = sgm_aggregate_params("sgm_aggregate", max_disp, p1, p2, paths)
     H, W = census_l.shape
-    if out is not None:
-        out = _stereo_arg(out, "sgm_aggregate: out", torch.int16, shape=(H, W, max_disp))
-    _stereo_gpu("sgm_aggregate", census_l=census_l, census_r=census_r, out=out)
+    out = _stereo_arg(out, "sgm_aggregate: out", torch.int16, shape=(H, W, max_disp), optional=True)
+    _same_device("sgm_aggregate", census_l=census_l, census_r=census_r, out=out)
     lib = _lib.load()
-    if out is None:
-        out = torch.empty((H, W, max_disp), device=census_l.device, dtype=torch.int16)
+    out = torch.empty((H, W, max_disp), device=census_l.device, dtype=torch.int16) if out is None else out
     nbytes = _size_or_raise(lib.pnr_sgm_workspace_bytes(W, H, max_disp, paths), "pnr_sgm_workspace_bytes")
     ws = torch.empty((nbytes,), device=census_l.device, dtype=torch.uint8) if nbytes else None
     _lib.check(lib.pnr_sgm_aggregate(_p(census_l), _p(census_r), W, H, max_disp, p1, p2, paths, _p(out), _p(ws), _stream()),
@@ -441,13 +503,10 @@ def sgm_select(S, uniqueness=5, lr_tol=1, out=None, disp_right=None):
     H, W, D = S.shape
     _stereo_disp("sgm_select (the last dimension of S)", D)
     uniqueness, lr_tol = sgm_select_params("sgm_select", uniqueness, lr_tol)
-    if out is not None:
-        out = _stereo_arg(out, "sgm_select: out", torch.int16, shape=(H, W))
-    if disp_right is not None:
-        disp_right = _stereo_arg(disp_right, "sgm_select: disp_right", torch.int16, shape=(H, W))
-    _stereo_gpu("sgm_select", S=S, out=out, disp_right=disp_right)
-    if out is None:
-        out = torch.empty((H, W), device=S.device, dtype=torch.int16)
+    out = _stereo_arg(out, "sgm_select: out", torch.int16, shape=(H, W), optional=True)
+    disp_right = _stereo_arg(disp_right, "sgm_select: disp_right", torch.int16, shape=(H, W), optional=True)
+    _same_device("sgm_select", S=S, out=out, disp_right=disp_right)
+    out = torch.empty((H, W), device=S.device, dtype=torch.int16) if out is None else out
     if disp_right is None and lr_tol >= 0:
         disp_right = torch.empty((H, W), device=S.device, dtype=torch.int16)
     _lib.check(_lib.load().pnr_sgm_select(_p(S), W, H, D, uniqueness, lr_tol, _p(out), _p(disp_right), _stream()), "pnr_sgm_select")
@@ -460,19 +519,12 @@ def disparity_depth(d16, fb, d_range=(1e-3, float("inf")), out=None):
     outside d_range = (d_min, d_max).  fb = fx * baseline, a float32 value."""
     d16 = _stereo_arg(d16, "disparity_depth: d16", torch.int16)
     fb = float(fb)
-    if not (0.0 < fb < float("inf")):
+    if not (0.0 < fb < _INF):
         raise ValueError("disparity_depth: fb = fx * baseline must be positive and finite (got %r)" % fb)
-    try:
-        d_min, d_max = (float(v) for v in d_range)
-    except (TypeError, ValueError):
-        raise ValueError("disparity_depth: d_range must be (d_min, d_max)") from None
-    if not (0.0 < d_min <= d_max):
-        raise ValueError("disparity_depth: d_range must satisfy 0 < d_min <= d_max (d_max may be inf)")
-    if out is not None:
-        out = _stereo_arg(out, "disparity_depth: out", torch.float32, shape=d16.shape)
-    _stereo_gpu("disparity_depth", d16=d16, out=out)
-    if out is None:
-        out = torch.empty(tuple(d16.shape), device=d16.device, dtype=torch.float32)
+    d_min, d_max = _d_range("disparity_depth", d_range, may_be_inf=True)
+    out = _stereo_arg(out, "disparity_depth: out", torch.float32, shape=d16.shape, optional=True)
+    _same_device("disparity_depth", d16=d16, out=out)
+    out = torch.empty(tuple(d16.shape), device=d16.device, dtype=torch.float32) if out is None else out
     _lib.check(_lib.load().pnr_disparity_depth(_p(d16), d16.numel(), fb, d_min, d_max, _p(out), _stream()), "pnr_disparity_depth")
     return out
 
@@ -482,18 +534,13 @@ MESH_MAX_POINTS = (2 ** 31 - 1) // 12          # include/pnr.h "mesh extraction"
 
 def _mesh_field(what, field, level):
     """the lattice argument of the mesh ops: (res_x, res_y, res_z, level) or the refusal by name, on any device"""
-    if not isinstance(field, torch.Tensor):
-        raise ValueError("%s: field must be a GPU tensor, got %s" % (what, type(field).__name__))
-    if field.dtype != torch.float32:
+    _tensor(what, "field", field)
+    if field.dtype != torch.float32:            # a ValueError that says "float32": not _tensor_table's TypeError
         raise ValueError("%s: field must be float32, got %s" % (what, field.dtype))
-    if field.dim() != 3 or min(field.shape) < 1:
-        raise ValueError("%s: field must be (res_z, res_y, res_x) with every res >= 1, got %s" % (what, tuple(field.shape)))
-    if field.numel() > MESH_MAX_POINTS:
-        raise ValueError("%s: field holds %d points, more than the limit of %d ((2^31 - 1) / 12)" % (what, field.numel(), MESH_MAX_POINTS))
+    rx, ry, rz = _lattice_shape(what, "field", field, 1, MESH_MAX_POINTS, "%d ((2^31 - 1) / 12)" % MESH_MAX_POINTS)
     level = float(level)
-    if not (abs(level) < float("inf")):
+    if not (abs(level) < _INF):
         raise ValueError("%s: level must be finite (got %r)" % (what, level))
-    rz, ry, rx = field.shape
     return rx, ry, rz, level
 
 
@@ -509,15 +556,13 @@ def mesh_count(field, level, workspace=None, totals=None):
     -- reading it is the caller's synchronisation --, workspace the uint8 buffer mesh_emit needs.  Both may be caller-owned."""
     rx, ry, rz, level = _mesh_field("mesh_count", field, level)
     nbytes = mesh_workspace_bytes(rx, ry, rz)
-    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < nbytes):
+    if workspace is not None and (not _is_tensor(workspace, torch.uint8) or workspace.numel() < nbytes):
         raise ValueError("mesh_count: workspace must be a uint8 tensor of at least %d bytes" % nbytes)
-    if totals is not None and (not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (2,)):
+    if totals is not None and not _is_tensor(totals, torch.int64, (2,)):
         raise ValueError("mesh_count: totals must be a (2,) int64 tensor")
-    _stereo_gpu("mesh_count", field=field, workspace=workspace, totals=totals)
-    if workspace is None:
-        workspace = torch.empty((nbytes,), device=field.device, dtype=torch.uint8)
-    if totals is None:
-        totals = torch.empty((2,), device=field.device, dtype=torch.int64)
+    _same_device("mesh_count", field=field, workspace=workspace, totals=totals)
+    workspace = torch.empty((nbytes,), device=field.device, dtype=torch.uint8) if workspace is None else workspace
+    totals = torch.empty((2,), device=field.device, dtype=torch.int64) if totals is None else totals
     _lib.check(_lib.load().pnr_mesh_count(_p(field), rx, ry, rz, level, _p(workspace), _p(totals), _stream()), "pnr_mesh_count")
     return totals, workspace
 
@@ -528,21 +573,19 @@ def mesh_emit(field, level, lo, step, workspace, vertices, faces, src=None):
     caller-owned and sized by mesh_count's totals.  lo, step: the lattice's float32 origin and step per axis (x, y, z), host
     values.  field, level and workspace are mesh_count's."""
     rx, ry, rz, level = _mesh_field("mesh_emit", field, level)
-    lo_h, step_h = _host_floats(lo, 3, "mesh_emit: lo"), _host_floats(step, 3, "mesh_emit: step")
-    for name, h in (("lo", lo_h), ("step", step_h)):
-        if not all(abs(v) < float("inf") for v in h):
-            raise ValueError("mesh_emit: %s must be finite (got %r)" % (name, list(h)))
+    lo_h, step_h = _lattice_floats("mesh_emit", lo, step, nonzero_step=False)
     nbytes = mesh_workspace_bytes(rx, ry, rz)
-    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < nbytes:
+    if not _is_tensor(workspace, torch.uint8) or workspace.numel() < nbytes:
         raise ValueError("mesh_emit: workspace must be the uint8 tensor of at least %d bytes that mesh_count filled" % nbytes)
+    # one message for type, dtype and shape, and n is free: not _tensor_table's rows
     for name, t, dtype, cols in (("vertices", vertices, torch.float32, 3), ("faces", faces, torch.int32, 3), ("src", src, torch.int64, 0)):
         if t is None and name == "src":
             continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
+        if not _is_tensor(t, dtype) or t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
             raise ValueError("mesh_emit: %s must be a %s %s tensor" % (name, "(n, 3)" if cols else "(n,)", dtype))
     if src is not None and src.shape[0] != vertices.shape[0]:
         raise ValueError("mesh_emit: src holds %d rows, vertices %d" % (src.shape[0], vertices.shape[0]))
-    _stereo_gpu("mesh_emit", field=field, workspace=workspace, vertices=vertices, faces=faces, src=src)
+    _same_device("mesh_emit", field=field, workspace=workspace, vertices=vertices, faces=faces, src=src)
     _lib.check(_lib.load().pnr_mesh_emit(_p(field), rx, ry, rz, level, lo_h, step_h, _p(workspace),
                                          _p(vertices if vertices.numel() else None), _p(faces if faces.numel() else None),
                                          _p(src if src is not None and src.numel() else None), _stream()), "pnr_mesh_emit")
@@ -551,6 +594,18 @@ def mesh_emit(field, level, lo, step, workspace, vertices, faces, src=None):
 
 TSDF_MAX_POINTS = 2 ** 31 - 1                   # include/pnr.h "depth fusion"
 TSDF_BLOCK, TSDF_BLOCKS_PER_CU = 256, 8         # PNR_TSDF_BLOCK, PNR_TSDF_BLOCKS_PER_CU
+
+
+def integrate_params(what, trunc, max_depth, w_max):
+    """the scalars of pnr_tsdf_integrate as floats, or the refusal by name (`what`: the caller's name)"""
+    trunc, max_depth, w_max = float(trunc), float(max_depth), float(w_max)
+    if not (0.0 < trunc < _INF):
+        raise ValueError("%s: trunc must be positive and finite (got %r)" % (what, trunc))
+    if not (max_depth > 0.0):
+        raise ValueError("%s: max_depth must be positive (it may be inf; got %r)" % (what, max_depth))
+    if not (w_max >= 1.0):
+        raise ValueError("%s: w_max must be >= 1 (it may be inf; got %r)" % (what, w_max))
+    return trunc, max_depth, w_max
 
 
 @_on_device
@@ -562,50 +617,26 @@ def tsdf_integrate(frames, w2c, first, last, lo, step, trunc, tsdf, weight, rgb=
     and step per axis (x, y, z), host values (mesh.lattice).  tsdf, weight: (res_z, res_y, res_x) float32, accumulated in
     place; rgb (res_z, res_y, res_x, 3) with rgb_weight, label with conf (int32): optional pairs.  Returns None."""
     what = "tsdf_integrate"
-    if not isinstance(tsdf, torch.Tensor):
-        raise ValueError("%s: tsdf must be a GPU tensor, got %s" % (what, type(tsdf).__name__))
-    if tsdf.dim() != 3 or min(tsdf.shape) < 1:
-        raise ValueError("%s: tsdf must be (res_z, res_y, res_x) with every res >= 1, got %s" % (what, tuple(tsdf.shape)))
-    if tsdf.numel() > TSDF_MAX_POINTS:
-        raise ValueError("%s: tsdf holds %d points, more than the limit of 2^31 - 1" % (what, tsdf.numel()))
-    rz, ry, rx = tsdf.shape
+    rx, ry, rz = _lattice_shape(what, "tsdf", tsdf, 1)
     if (rgb is None) != (rgb_weight is None):
         raise ValueError("%s: rgb and rgb_weight go together (both or neither)" % what)
     if (label is None) != (conf is None):
         raise ValueError("%s: label and conf go together (both or neither)" % what)
-    for name, t, dtype, tail in (("tsdf", tsdf, torch.float32, ()), ("weight", weight, torch.float32, ()), ("rgb", rgb, torch.float32, (3,)),
-                                 ("rgb_weight", rgb_weight, torch.float32, ()), ("label", label, torch.int32, ()),
-                                 ("conf", conf, torch.int32, ())):
-        if t is None and name not in ("tsdf", "weight"):
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
-        if t.dtype != dtype:
-            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
-        if tuple(t.shape) != (rz, ry, rx) + tail:
-            raise ValueError("%s: %s must be %s, got %s" % (what, name, (rz, ry, rx) + tail, tuple(t.shape)))
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 1 or frames.numel() % ctypes.sizeof(_lib.Frame):
+    res = (rz, ry, rx)
+    _tensor_table(what, (("tsdf", tsdf, torch.float32, res), ("weight", weight, torch.float32, res)),
+                  (("rgb", rgb, torch.float32, res + (3,)), ("rgb_weight", rgb_weight, torch.float32, res),
+                   ("label", label, torch.int32, res), ("conf", conf, torch.int32, res)))
+    if not _is_tensor(frames, torch.uint8) or frames.dim() != 1 or frames.numel() % ctypes.sizeof(_lib.Frame):
         raise ValueError("%s: frames must be a uint8 tensor of whole pnr_frame records (%d bytes each)" % (what, ctypes.sizeof(_lib.Frame)))
-    if not isinstance(w2c, torch.Tensor) or w2c.dtype != torch.float32 or w2c.dim() != 2 or w2c.shape[1] != 12:
+    if not _is_tensor(w2c, torch.float32) or w2c.dim() != 2 or w2c.shape[1] != 12:
         raise ValueError("%s: w2c must be an (F, 12) float32 tensor" % what)
     first, last = int(first), int(last)
     n_rec = min(frames.numel() // ctypes.sizeof(_lib.Frame), w2c.shape[0])
     if not 0 <= first <= last <= n_rec:
         raise ValueError("%s: need 0 <= first <= last <= %d (the records and w2c rows given), got [%d, %d)" % (what, n_rec, first, last))
-    lo_h, step_h = _host_floats(lo, 3, what + ": lo"), _host_floats(step, 3, what + ": step")
-    for name, h in (("lo", lo_h), ("step", step_h)):
-        if not all(abs(v) < float("inf") for v in h):
-            raise ValueError("%s: %s must be finite (got %r)" % (what, name, list(h)))
-    if not all(v != 0.0 for v in step_h):
-        raise ValueError("%s: step must be non-zero (got %r)" % (what, list(step_h)))
-    trunc, max_depth, w_max = float(trunc), float(max_depth), float(w_max)
-    if not (0.0 < trunc < float("inf")):
-        raise ValueError("%s: trunc must be positive and finite (got %r)" % (what, trunc))
-    if not (max_depth > 0.0):
-        raise ValueError("%s: max_depth must be positive (it may be inf; got %r)" % (what, max_depth))
-    if not (w_max >= 1.0):
-        raise ValueError("%s: w_max must be >= 1 (it may be inf; got %r)" % (what, w_max))
-    _stereo_gpu(what, tsdf=tsdf, weight=weight, rgb=rgb, rgb_weight=rgb_weight, label=label, conf=conf, frames=frames, w2c=w2c)
+    lo_h, step_h = _lattice_floats(what, lo, step)
+    trunc, max_depth, w_max = integrate_params(what, trunc, max_depth, w_max)
+    _same_device(what, tsdf=tsdf, weight=weight, rgb=rgb, rgb_weight=rgb_weight, label=label, conf=conf, frames=frames, w2c=w2c)
     if first == last:
         return
     _lib.check(_lib.load().pnr_tsdf_integrate(_p(frames), _p(w2c), first, last, rx, ry, rz, lo_h, step_h, trunc, max_depth, w_max,
@@ -614,7 +645,22 @@ def tsdf_integrate(frames, w2c, first, last, lo, step, trunc, tsdf, weight, rgb=
 
 
 RAYCAST_HIT, RAYCAST_NO_RAY, RAYCAST_MISSED, RAYCAST_NO_SURFACE = 0, 1, 2, 3      # PNR_RAYCAST_* (include/pnr.h "volume ray casting")
-RAYCAST_MAX_PIXELS = 2 ** 31 - 1
+
+
+def raycast_params(what, near, far, min_weight, dt, max_steps, res, step, dt_name="dt"):
+    """the scalars of pnr_tsdf_raycast with the defaults of dt and max_steps filled in, or the refusal by name (dt_name: the caller's)"""
+    near, far, min_weight = float(near), float(far), float(min_weight)
+    if not (near >= 0.0 and far > near):
+        raise ValueError("%s: need 0 <= near < far (got %r, %r)" % (what, near, far))
+    if not (min_weight > 0.0):
+        raise ValueError("%s: min_weight must be positive (got %r)" % (what, min_weight))
+    dt = raycast_default_dt(step) if dt is None else float(dt)
+    if not (0.0 < dt < _INF):
+        raise ValueError("%s: %s must be positive and finite (got %r)" % (what, dt_name, dt))
+    max_steps = raycast_default_max_steps(res, step, dt) if max_steps is None else int(max_steps)
+    if max_steps < 0:
+        raise ValueError("%s: max_steps must be >= 0 (got %d)" % (what, max_steps))
+    return near, far, min_weight, dt, max_steps
 
 
 @_on_device
@@ -627,51 +673,16 @@ def tsdf_raycast(camera_model, cam, c2w, width, height, near, far, lo, step, tsd
     optionally normal (height, width, 3) float32 and src int32.  dt: the march step in units of the ray parameter (None: half the
     smallest |step|); max_steps: the most samples a ray takes (None: enough for the lattice's diagonal at that dt).  Returns None."""
     what = "tsdf_raycast"
-    if camera_model not in _MODEL_WORDS:
-        raise ValueError("%s: camera_model must be 'pinhole', 'fisheye' or 'equirect', not %r" % (what, camera_model))
-    word, nc = _MODEL_WORDS[camera_model]
-    cam_h = _host_floats(cam, nc, "%s: model %r cam" % (what, camera_model))
+    word, cam_h = _camera_model(what, "camera_model", camera_model, cam)
     c2w_h = _host_floats(c2w, 12, what + ": c2w")
-    width, height = int(width), int(height)
-    if width < 1 or height < 1 or width * height > RAYCAST_MAX_PIXELS:
-        raise ValueError("%s: bad image %d x %d (width, height >= 1, at most 2^31 - 1 pixels)" % (what, width, height))
-    if not isinstance(tsdf, torch.Tensor):
-        raise ValueError("%s: tsdf must be a GPU tensor, got %s" % (what, type(tsdf).__name__))
-    if tsdf.dim() != 3 or min(tsdf.shape) < 2:
-        raise ValueError("%s: tsdf must be (res_z, res_y, res_x) with every res >= 2, got %s" % (what, tuple(tsdf.shape)))
-    if tsdf.numel() > TSDF_MAX_POINTS:
-        raise ValueError("%s: tsdf holds %d points, more than the limit of 2^31 - 1" % (what, tsdf.numel()))
-    rz, ry, rx = tsdf.shape
-    for name, t, dtype, shape, needed in (("tsdf", tsdf, torch.float32, (rz, ry, rx), True), ("weight", weight, torch.float32, (rz, ry, rx), True),
-                                          ("depth", depth, torch.float32, (height, width), True), ("code", code, torch.uint8, (height, width), True),
-                                          ("normal", normal, torch.float32, (height, width, 3), False),
-                                          ("src", src, torch.int32, (height, width), False)):
-        if t is None and not needed:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
-        if t.dtype != dtype:
-            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
-        if tuple(t.shape) != shape:
-            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
-    lo_h, step_h = _host_floats(lo, 3, what + ": lo"), _host_floats(step, 3, what + ": step")
-    for name, h in (("lo", lo_h), ("step", step_h)):
-        if not all(abs(v) < float("inf") for v in h):
-            raise ValueError("%s: %s must be finite (got %r)" % (what, name, list(h)))
-    if not all(v != 0.0 for v in step_h):
-        raise ValueError("%s: step must be non-zero (got %r)" % (what, list(step_h)))
-    near, far, min_weight = float(near), float(far), float(min_weight)
-    if not (near >= 0.0 and far > near):
-        raise ValueError("%s: need 0 <= near < far (got %r, %r)" % (what, near, far))
-    if not (min_weight > 0.0):
-        raise ValueError("%s: min_weight must be positive (got %r)" % (what, min_weight))
-    dt = raycast_default_dt(step_h) if dt is None else float(dt)
-    if not (0.0 < dt < float("inf")):
-        raise ValueError("%s: dt must be positive and finite (got %r)" % (what, dt))
-    max_steps = raycast_default_max_steps((rx, ry, rz), step_h, dt) if max_steps is None else int(max_steps)
-    if max_steps < 0:
-        raise ValueError("%s: max_steps must be >= 0 (got %d)" % (what, max_steps))
-    _stereo_gpu(what, tsdf=tsdf, weight=weight, depth=depth, code=code, normal=normal, src=src)
+    width, height = _image_size(what, width, height)
+    rx, ry, rz = _lattice_shape(what, "tsdf", tsdf, 2)
+    _tensor_table(what, (("tsdf", tsdf, torch.float32, (rz, ry, rx)), ("weight", weight, torch.float32, (rz, ry, rx)),
+                         ("depth", depth, torch.float32, (height, width)), ("code", code, torch.uint8, (height, width))),
+                  (("normal", normal, torch.float32, (height, width, 3)), ("src", src, torch.int32, (height, width))))
+    lo_h, step_h = _lattice_floats(what, lo, step)
+    near, far, min_weight, dt, max_steps = raycast_params(what, near, far, min_weight, dt, max_steps, (rx, ry, rz), step_h)
+    _same_device(what, tsdf=tsdf, weight=weight, depth=depth, code=code, normal=normal, src=src)
     _lib.check(_lib.load().pnr_tsdf_raycast(word, cam_h, c2w_h, width, height, near, far, rx, ry, rz, lo_h, step_h, _p(tsdf), _p(weight),
                                             min_weight, dt, max_steps, _p(depth), _p(normal), _p(src), _p(code), _stream()),
                "pnr_tsdf_raycast")
@@ -693,7 +704,26 @@ def raycast_default_max_steps(res, step, dt):
 ICP_MATCH, ICP_NO_DEPTH, ICP_OUTSIDE, ICP_NO_MODEL, ICP_TOO_FAR, ICP_BACK_FACING = 0, 1, 2, 3, 4, 5
 ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = 0, 1, 2, 3
 ICP_MAX_ROT = 0.5
-ICP_MAX_PIXELS = 2 ** 31 - 1
+
+
+def icp_accumulate_params(what, dist_max):
+    """the scalar of pnr_icp_accumulate as a float, or the refusal by name (`what`: the caller's name)"""
+    dist_max = float(dist_max)
+    if not (0.0 < dist_max < 1.8e19):
+        raise ValueError("%s: dist_max must be positive with a finite float32 square (got %r)" % (what, dist_max))
+    return dist_max
+
+
+def icp_solve_params(what, min_matches, max_rot, max_trans):
+    """the scalars of pnr_icp_solve, or the refusal by name"""
+    min_matches, max_rot, max_trans = int(min_matches), float(max_rot), float(max_trans)
+    if min_matches < 1:
+        raise ValueError("%s: min_matches must be >= 1 (got %d)" % (what, min_matches))
+    if not (0.0 < max_rot <= ICP_MAX_ROT):
+        raise ValueError("%s: max_rot must lie in (0, %g] radians (got %r)" % (what, ICP_MAX_ROT, max_rot))
+    if not (max_trans > 0.0):
+        raise ValueError("%s: max_trans must be positive (it may be inf; got %r)" % (what, max_trans))
+    return min_matches, max_rot, max_trans
 
 
 def icp_workspace(n_pix, device):
@@ -703,24 +733,19 @@ def icp_workspace(n_pix, device):
 
 
 def _icp_pose(pose12, what):
-    if not isinstance(pose12, torch.Tensor):
-        raise ValueError("%s: pose12 must be a GPU tensor of 12 float32 (the 3x4 camera-to-world, updated in place), got %s"
-                         % (what, type(pose12).__name__))
+    _tensor(what, "pose12", pose12, "a GPU tensor of 12 float32 (the 3x4 camera-to-world, updated in place)")
     _chk(pose12, what + ": pose12")
     if pose12.numel() != 12:
         raise ValueError("%s: pose12 must hold 12 values (3x4 row-major), got %s" % (what, tuple(pose12.shape)))
-    return pose12
 
 
 def _icp_workspace(workspace, n_pix, what):
-    if not isinstance(workspace, torch.Tensor):
-        raise ValueError("%s: workspace must be a GPU tensor (ops.icp_workspace), got %s" % (what, type(workspace).__name__))
+    _tensor(what, "workspace", workspace, "a GPU tensor (ops.icp_workspace)")
     _chk(workspace, what + ": workspace", torch.float64)
     need = _size_or_raise(_lib.load().pnr_icp_workspace_bytes(n_pix), "pnr_icp_workspace_bytes") // 8
     if workspace.dim() != 1 or workspace.numel() < need:
         raise ValueError("%s: workspace must be a flat float64 tensor of at least %d elements (ops.icp_workspace), got %s"
                          % (what, need, tuple(workspace.shape)))
-    return workspace
 
 
 @_on_device
@@ -733,39 +758,21 @@ def icp_accumulate(camera_model, cam, width, height, depth, pose12, model_camera
     fusion.raycast writes them.  workspace: ops.icp_workspace(width * height, device); it receives one row of partial sums per
     workgroup, which icp_solve adds.  Optional outputs: code (height, width) uint8, residual (height, width) float32.  Returns None."""
     what = "icp_accumulate"
-    for name, m in (("camera_model", camera_model), ("model_camera_model", model_camera_model)):
-        if m not in _MODEL_WORDS:
-            raise ValueError("%s: %s must be 'pinhole', 'fisheye' or 'equirect', not %r" % (what, name, m))
-    (word_l, nc_l), (word_m, nc_m) = _MODEL_WORDS[camera_model], _MODEL_WORDS[model_camera_model]
-    cam_l = _host_floats(cam, nc_l, "%s: model %r cam" % (what, camera_model))
-    cam_m = _host_floats(model_cam, nc_m, "%s: model %r model_cam" % (what, model_camera_model))
+    _model_word(what, "camera_model", camera_model), _model_word(what, "model_camera_model", model_camera_model)     # both names first
+    word_l, cam_l = _camera_model(what, "camera_model", camera_model, cam)
+    word_m, cam_m = _camera_model(what, "model_camera_model", model_camera_model, model_cam, "model_cam")
     c2w_m = _host_floats(model_c2w, 12, what + ": model_c2w")
-    from .camera import invert_pose
-    w2c_m = _host_floats(invert_pose(torch.tensor(list(c2w_m), dtype=torch.float32)), 12, what + ": model w2c")
-    width, height, wm, hm = int(width), int(height), int(model_width), int(model_height)
-    for w, h, side in ((width, height, "the live image"), (wm, hm, "the model image")):
-        if w < 1 or h < 1 or w * h > ICP_MAX_PIXELS:
-            raise ValueError("%s: bad size of %s, %d x %d (width, height >= 1, at most 2^31 - 1 pixels)" % (what, side, w, h))
-    for name, t, dtype, shape, needed in (("depth", depth, torch.float32, (height, width), True),
-                                          ("model_depth", model_depth, torch.float32, (hm, wm), True),
-                                          ("model_normal", model_normal, torch.float32, (hm, wm, 3), True),
-                                          ("code", code, torch.uint8, (height, width), False),
-                                          ("residual", residual, torch.float32, (height, width), False)):
-        if t is None and not needed:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a GPU tensor, got %s" % (what, name, type(t).__name__))
-        if t.dtype != dtype:
-            raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
-        if tuple(t.shape) != shape:
-            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
-    dist_max = float(dist_max)
-    if not (0.0 < dist_max < 1.8e19):
-        raise ValueError("%s: dist_max must be positive with a finite float32 square (got %r)" % (what, dist_max))
+    w2c_m = _host_floats(_camera.invert_pose(torch.tensor(list(c2w_m), dtype=torch.float32)), 12, what + ": model w2c")
+    width, height = _image_size(what, width, height, "size of the live image,")
+    wm, hm = _image_size(what, model_width, model_height, "size of the model image,")
+    _tensor_table(what, (("depth", depth, torch.float32, (height, width)), ("model_depth", model_depth, torch.float32, (hm, wm)),
+                         ("model_normal", model_normal, torch.float32, (hm, wm, 3))),
+                  (("code", code, torch.uint8, (height, width)), ("residual", residual, torch.float32, (height, width))))
+    dist_max = icp_accumulate_params(what, dist_max)
     _icp_pose(pose12, what)
     _icp_workspace(workspace, width * height, what)
-    _stereo_gpu(what, depth=depth, pose12=pose12, model_depth=model_depth, model_normal=model_normal, workspace=workspace, code=code,
-                residual=residual)
+    _same_device(what, depth=depth, pose12=pose12, model_depth=model_depth, model_normal=model_normal, workspace=workspace, code=code,
+                 residual=residual)
     _lib.check(_lib.load().pnr_icp_accumulate(word_l, cam_l, width, height, _p(depth), _p(pose12), word_m, cam_m, c2w_m, w2c_m, wm, hm,
                                               _p(model_depth), _p(model_normal), dist_max, _p(workspace), _p(code), _p(residual),
                                               _stream()), "pnr_icp_accumulate")
@@ -778,23 +785,17 @@ def icp_solve(workspace, n_pix, pose12, history_row, min_matches=6, max_rot=ICP_
     float64 on the GPU, which receives count, E, |omega|^2, |v|^2, status (ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE,
     ICP_STEP_TOO_LARGE).  The pose changes only with status ICP_OK.  update=False: count and E only, nothing is solved."""
     what = "icp_solve"
-    n_pix, min_matches, max_rot, max_trans = int(n_pix), int(min_matches), float(max_rot), float(max_trans)
-    if n_pix < 1 or n_pix > ICP_MAX_PIXELS:
+    n_pix = int(n_pix)
+    if n_pix < 1 or n_pix > MAX_PIXELS:
         raise ValueError("%s: n_pix must lie in 1 .. 2^31 - 1 (got %d)" % (what, n_pix))
-    if min_matches < 1:
-        raise ValueError("%s: min_matches must be >= 1 (got %d)" % (what, min_matches))
-    if not (0.0 < max_rot <= ICP_MAX_ROT):
-        raise ValueError("%s: max_rot must lie in (0, %g] radians (got %r)" % (what, ICP_MAX_ROT, max_rot))
-    if not (max_trans > 0.0):
-        raise ValueError("%s: max_trans must be positive (it may be inf; got %r)" % (what, max_trans))
+    min_matches, max_rot, max_trans = icp_solve_params(what, min_matches, max_rot, max_trans)
     _icp_pose(pose12, what)
     _icp_workspace(workspace, n_pix, what)
-    if not isinstance(history_row, torch.Tensor):
-        raise ValueError("%s: history_row must be a GPU tensor of 5 float64, got %s" % (what, type(history_row).__name__))
+    _tensor(what, "history_row", history_row, "a GPU tensor of 5 float64")
     _chk(history_row, what + ": history_row", torch.float64)
     if tuple(history_row.shape) != (5,):
         raise ValueError("%s: history_row must be (5,), got %s" % (what, tuple(history_row.shape)))
-    _stereo_gpu(what, workspace=workspace, pose12=pose12, history_row=history_row)
+    _same_device(what, workspace=workspace, pose12=pose12, history_row=history_row)
     _lib.check(_lib.load().pnr_icp_solve(_p(workspace), n_pix, min_matches, max_rot, max_trans, 1 if update else 0, _p(pose12),
                                          _p(history_row), _stream()), "pnr_icp_solve")
 
@@ -879,9 +880,7 @@ def sample_batch(frames, cum, n_frames, draw, n_rays, mode="pooled", want=None, 
     R, dev = int(n_rays), frames.device
     names = [n for n, _, _ in BATCH_OUTPUTS]
     want = names if want is None else list(want)
-    for n in want:
-        if n not in names:
-            raise ValueError("sample_batch: unknown output %r (one of %s)" % (n, ", ".join(names)))
+    _names("sample_batch", want, names, "unknown output %(key)s (one of %(known)s)")
     res = {n: _own(None if out is None else out.get(n), (R,) + tail, dt, dev, "sample_batch: " + n)
            for n, tail, dt in BATCH_OUTPUTS if n in want}
     _lib.check(_lib.load().pnr_sample_batch(_p(frames), _p(cum), _p(n_frames), _lib.SAMPLE_POOLED if mode == "pooled" else _lib.SAMPLE_FRAME,
@@ -938,7 +937,6 @@ def default_schedule():
     """pnr_mlp_desc.schedule of new descriptors: 0 (ping-pong inference / lock-step training forward) unless the A/B tools'
     environment variable PNR_MLP_VARIANT asks otherwise (its historical values: 0 = lock-step everywhere -> schedule 1,
     1 = the default -> 0, 2 = ping-pong everywhere -> 2).  Read here, on the Python side: libpnr.so keeps no process-global."""
-    import os
     return {"0": 1, "1": 0, "2": 2}.get(os.environ.get("PNR_MLP_VARIANT", "1"), 0)
 
 

@@ -13,6 +13,7 @@ import torch
 from panopticnerf_amd import Equirect, Fisheye, FrameSet, Pinhole, _lib, fusion, ops, synthetic
 
 import _icp_ref as ir
+from _fake_gpu import _FakeCuda, _fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(64)          # ONE: non-null, aligned, never dereferenced -- validation fails first
@@ -148,30 +149,6 @@ def _solve_args(**over):
 def test_icp_solve_refusals(over, exc, message):
     with pytest.raises(exc, match=message):
         ops.icp_solve(**_solve_args(**over))
-
-
-class _FakeCuda(torch.Tensor):
-    """a CPU tensor that says it is on the GPU (and, with `device`, on which): lets the checks behind `is_cuda` run without one"""
-    @staticmethod
-    def __new__(cls, t, device=None):
-        self = torch.Tensor._make_subclass(cls, t)
-        self._says = device
-        return self
-
-    def __init__(self, t, device=None):
-        pass
-
-    @property
-    def is_cuda(self):
-        return True
-
-    @property
-    def device(self):
-        return torch.device(self._says) if self._says else torch.device("cpu")
-
-
-def _fake(t, device=None):
-    return _FakeCuda(t, device)
 
 
 def _fake_acc(**over):
