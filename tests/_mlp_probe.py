@@ -18,6 +18,9 @@ _mlp32_ref.acts_regions:
             column per launch.
   G         rgb_linear rows e_i, e_j, e_k: three columns per launch, H / 3 launches (full_G).
 
+probes(prec="bf16") builds the same networks for the bf16 inference kernels, where the read-out is the bf16 activation the next
+Linear reads (tests/_mlp_probe_bf16.py).
+
 Everything sits behind launch(desc, params, rays, z) -> raw (S, channels): the same code runs against _mlp32_ref.forward32 on the
 CPU (tests/test_mlp_probe.py) and against the kernel on the GPU (tests/test_gpu_mlp_fp32_infer_sweep.py).
 
@@ -53,15 +56,16 @@ def _take(params, prefix):
     return {prefix + ".weight": params[prefix + ".weight"], prefix + ".bias": params[prefix + ".bias"]}
 
 
-def probes(desc, params, full_G=False, need=None):
-    """the probe launches of one case; need: region names to read (None: all, G only with full_G)"""
+def probes(desc, params, full_G=False, need=None, prec="fp32"):
+    """the probe launches of one case; need: region names to read (None: all, G only with full_G); prec: the precision of the
+    probe descriptors (every probe matrix holds only 0 and +-1, exact in bf16 too: tests/_mlp_probe_bf16.py)"""
     g = m32.dims(desc)
     W, H, D, skip, ex, ed = g["W"], g["H"], g["D"], g["skip"], g["ex"], g["ed"]
     tapname = "feature" if g["tap"] else "trunk"
     want = lambda r: need is None or r in need                                       # noqa: E731
 
     def mk(D_, skip_, C=0, K=0, tap="trunk", depth=1):
-        return ops.make_desc(D_, W, skip_, desc.xyz_L, desc.dir_L, C, K, H, "fp32", tap, depth)
+        return ops.make_desc(D_, W, skip_, desc.xyz_L, desc.dir_L, C, K, H, prec, tap, depth)
 
     base = {}
     for nm in ("alpha_linear", "feature_linear", "views_linears.0", "rgb_linear"):

@@ -4,6 +4,8 @@ k_wgrad + k_wgrad_reduce), and the one comparison every check uses.  Not part of
 Layer-local: every layer of the reference reads the KERNEL's own saved bf16 input of that layer (acts) or its own stored
 upstream gradient (dys), so kernel and reference see the same ReLU gates and the same rounded operands.  What is left between
 them is the order of the fp32 accumulation and one rounding to bf16, which is bounded below from first principles.
+The forward half (check_forward) works on feature-ordered regions, whoever produced them: check_training hands it Buffers.feat(...),
+the inference sweep (tests/_mlp_probe_bf16.py, test_gpu_mlp_bf16_infer_sweep.py) the regions its probe networks read out.
 
 Bounds (u = 2^-24, the unit roundoff of fp32; C_ACC = 2):
   * A fp32 sum of K exact products plus an fp32 bias (bf16 x bf16 products are exact in fp32) differs from the exact sum by at
@@ -209,15 +211,19 @@ class Net:
         if region != "raw":
             name, x = self.fwd_inputs(region, X)
             return self.lin(name, x)
-        D = self.D
-        tapx = X["F"] if self.tap else X["X%d" % D]
-        parts = [self.lin("rgb_linear", X["G"]), self.lin("alpha_linear", X["X%d" % D])]
-        if self.C:
-            parts.append(self.lin(self.sem[0], X["SH_sem"]) if self.depth == 2 else self.lin(self.sem[1], tapx))
-        if self.K:
-            parts.append(self.lin(self.inst[0], X["SH_inst"]) if self.depth == 2 else self.lin(self.inst[1], tapx))
+        parts = [self.lin(name, X[src]) for name, _, _, src in self.raw_parts()]
         K = torch.tensor([float(p[2]) for p in parts for _ in range(p[0].shape[1])], dtype=torch.float64, device=self.dev)
         return torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1), K
+
+    def raw_parts(self):
+        """[(Linear name, first raw channel, rows, input region)] of the fp32 rows, in channel order"""
+        xd = "X%d" % self.D
+        tap = "F" if self.tap else xd
+        out = [("rgb_linear", 0, 3, "G"), ("alpha_linear", 3, 1, xd)]
+        for (last, first), c0, n, sh in ((self.sem, 4, self.C, "SH_sem"), (self.inst, 4 + self.C, self.K, "SH_inst")):
+            if n:
+                out.append((last, c0, n, sh) if self.depth == 2 else (first, c0, n, tap))
+        return out
 
     def regions_fwd(self):
         out = ["X%d" % (l + 1) for l in range(self.D)] + ["F", "G"]
@@ -300,9 +306,10 @@ def _band_err(j):
     return e
 
 
-def embed_ref(p, nf):
+def embed_ref(p, nf, dir_arg_err=0.0):
     """p (S, 3) float64 -> (values, delta) (S, 6 nf + 3) in canonical column order with ALL 2 nf bands (the kernel computes
-    every band; pnr_seg_col hides those >= L from the weights).  delta: the E_j of the header."""
+    every band; pnr_seg_col hides those >= L from the weights).  delta: the E_j of the header.
+    dir_arg_err: relative error of p itself (gamma(d): the fp32 normalisation), added as 2^f * it to band f."""
     S = p.shape[0]
     vals, dl = [p], [torch.zeros_like(p)]
     for f in range(2 * nf):
@@ -311,17 +318,17 @@ def embed_ref(p, nf):
         e = _band_err(f % nf)
         dl += [torch.full((S, 6), e, dtype=torch.float64, device=p.device)]
     v = torch.cat([vals[0]] + [torch.cat([vals[1 + 2 * f], vals[2 + 2 * f]], 1) for f in range(2 * nf)], 1)
-    return v, torch.cat(dl, 1)
-
-
-def embed_slot_ref(p, nf, dir_arg_err=0.0):
-    """(values, delta) of a saved EX (nf = 5, 64 slots) / ED (nf = 2, 32 slots) region in SLOT order; pads are exactly 0.
-    dir_arg_err: relative error of p itself (gamma(d): the fp32 normalisation), added as 2^f * it to band f."""
-    v, dl = embed_ref(p, nf)
+    dl = torch.cat(dl, 1)
     if dir_arg_err:
         dl[:, :3] += dir_arg_err
         for f in range(2 * nf):
             dl[:, 3 + 6 * f: 9 + 6 * f] += 2.0 ** f * dir_arg_err
+    return v, dl
+
+
+def embed_slot_ref(p, nf, dir_arg_err=0.0):
+    """(values, delta) of a saved EX (nf = 5, 64 slots) / ED (nf = 2, 32 slots) region in SLOT order; pads are exactly 0."""
+    v, dl = embed_ref(p, nf, dir_arg_err)
     idx = embed_slots(nf, 2 * nf, str(p.device))               # every band's slot
     ok = idx >= 0
     vs = torch.zeros((p.shape[0], idx.numel()), dtype=torch.float64, device=p.device)
@@ -384,6 +391,34 @@ def wgrad_slabs(desc, S):
 
 
 # ------------------------------------------------------------------------------------------------------------ the check
+def check_forward(rep, net, X, raw=None, pts=None, vd64=None, s0=0, regions=None, parts=None):
+    """The forward half of the layer-local check over FEATURE-ordered regions, whoever produced them (the training forward's saved
+    buffers through Buffers.feat, or the inference kernels' probe read-out of tests/_mlp_probe_bf16.py).
+    X: region -> (S, width) float64 kernel values; raw: (S, channels) fp32 rows, or None.  pts (S, 3) fp32 sample points and vd64
+    (S, 3) float64 unit view directions: where given, EX / ED are checked over the bands the weights see (identity columns of EX =
+    bf16-RNE of pts bit for bit, bands inside the E_j of the header, ED with the 8 u direction term).  regions: the hidden regions
+    to check (default: those of net.regions_fwd() that X holds); parts: the Linear names of raw_parts() to check (default: all).
+    Every region is checked against float64 on the kernel's OWN input region(s), which X must hold."""
+    if pts is not None:
+        ex = 3 + 6 * net.Lx
+        if not torch.equal(X["EX"][:, :3], pts.to(torch.bfloat16).double()):
+            rep.fail("EX", "the xyz columns are not bf16 of the sample points (fp32 points differ from k_points?)")
+        v, dl = embed_ref(pts.double(), 5)
+        check_bf16(rep, "EX", X["EX"], v[:, :ex], dl[:, :ex], s0=s0)
+    if vd64 is not None:
+        ed = 3 + 6 * net.Ld
+        v, dl = embed_ref(vd64, 2, dir_arg_err=8 * U)
+        check_bf16(rep, "ED", X["ED"], v[:, :ed], dl[:, :ed], s0=s0)
+    for nm in [r for r in net.regions_fwd() if r in X] if regions is None else regions:
+        r, m, K = net.fwd(nm, X)
+        check_bf16(rep, nm, X[nm], r, C_ACC * K * U * m, relu=nm != "F", s0=s0)
+    if raw is not None:
+        for name, c0, n, src in net.raw_parts():
+            if parts is None or name in parts:
+                r, m, K = net.lin(name, X[src])
+                check_f32(rep, "raw[%s]" % name, raw[:, c0:c0 + n], r, m, K, key="fp32 raw")
+
+
 def check_training(desc, params, pts, rays, raw, acts, dys=None, d_raw=None, grads=None, chunk=1 << 16, rep=None):
     """Every region of a training forward (raw, acts with gates), and if given of the data-gradient pass (dys) and of the
     weight gradients (grads), against the float64 layer-local reference.  pts (S, 3) fp32 sample points (bit-exact with the
@@ -423,7 +458,9 @@ def check_training(desc, params, pts, rays, raw, acts, dys=None, d_raw=None, gra
     for s0 in range(0, S, chunk):
         s1 = min(S, s0 + chunk)
         X = {k: v[s0:s1].double() for k, v in Xb.items()}
-        # embeddings (slot order: pads and every band, also those the weights do not see)
+        # the feature-ordered half: visible embedding columns, every hidden region, every raw row
+        check_forward(rep, net, X, raw[:, s0:s1].t(), pts[s0:s1].to(dev), vd64[s0:s1], s0=s0, regions=fwd_regions)
+        # embeddings once more in slot order: pads and every band, also those the weights do not see
         v, dl = embed_slot_ref(p64[s0:s1], 5)
         xyz = ex_slots[s0:s1, [0, 1, 32]].double()
         if not torch.equal(xyz, pts[s0:s1].to(dev).to(torch.bfloat16).double()):
@@ -432,15 +469,10 @@ def check_training(desc, params, pts, rays, raw, acts, dys=None, d_raw=None, gra
         v, dl = embed_slot_ref(vd64[s0:s1], 2, dir_arg_err=8 * U)
         check_bf16(rep, "ED", ed_slots[s0:s1], v, dl, s0=s0)
         for nm in fwd_regions:
-            r, m, K = net.fwd(nm, X)
-            relu = nm != "F"
-            check_bf16(rep, nm, X[nm], r, C_ACC * K * U * m, relu=relu, s0=s0)
-            if relu:
+            if nm != "F":
                 g = Gb[nm][s0:s1]
                 if not torch.equal(g, X[nm] > 0):
                     rep.fail("gate_" + nm, "%d gate bits differ from [X > 0]" % int((g != (X[nm] > 0)).sum()))
-        r, m, K = net.fwd("raw", X)
-        check_f32(rep, "raw", raw[:, s0:s1].t(), r, m, K)
         if bwd:
             Y = {k: v[s0:s1].double() for k, v in Yb.items()}
             dr = d_raw[:, s0:s1].t()

@@ -2,8 +2,9 @@
 k_composite_combine) against the float64 reference of tests/_fused_ref.py, at every sample count it takes, on every plan, in both
 compositing modes.  SURVEY.md 8a rows a5 + a6.
 
-The reference input is the kernels' own fp32 raw: ops.mlp_forward on the plan-0 image of the same network (checked layer by layer
-against float64 in tests/test_gpu_mlp_sweep.py), in float64.  Three layers:
+The reference input is the kernels' own fp32 raw: ops.mlp_forward on the plan-0 image of the same network (the inference kernels'
+raw is checked layer by layer against float64 in tests/test_gpu_mlp_bf16_infer_sweep.py, the training forward's in
+tests/test_gpu_mlp_sweep.py), in float64.  Three layers:
   A  the epilogue records (pnr_mlp_forward_tiles): Q, lw and the logit sums S against tiles64; the quadruples' r, g, b must be
      raw's colour channels BIT FOR BIT (the fused kernels and mlp_forward run the same MLP arithmetic);
   B  k_composite_combine (pnr_composite_combine) on records and quadruples written by hand -- Q = 0, subnormal, 1 - 2^-24, local

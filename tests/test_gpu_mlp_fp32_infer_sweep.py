@@ -85,6 +85,10 @@ class Launch:
     def __init__(self, dev, layout="channel", pad=24):
         self.dev, self.layout, self.pad, self.bad, self.calls, self.arena = dev, layout, pad, [], 0, None
 
+    def image(self, desc, params):
+        """the packed image on the device (a subclass may cache it)"""
+        return ops.pack_mlp(desc, params).to(self.dev)
+
     def __call__(self, desc, params, rays, z, n_rays=None):
         lib = _lib.load()
         R, N = z.shape
@@ -98,7 +102,7 @@ class Launch:
         self.arena = ar = Arena(self.dev, [("rays", 8 * R, GUARD), ("z", S, GUARD), ("raw", n_raw, g_raw)])
         ar.view("rays").copy_(rays.reshape(-1).to(self.dev))
         ar.view("z").copy_(z.reshape(-1).to(self.dev))
-        img = ops.pack_mlp(desc, params).to(self.dev)
+        img = self.image(desc, params)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.pnr_mlp_forward(ctypes.byref(desc), _p(img), _p(ar.view("rays")), _p(ar.view("z")), R if n_rays is None else n_rays, N,
                                        _p(ar.view("raw")), ss, sc, stream), "pnr_mlp_forward")
