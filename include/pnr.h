@@ -1066,6 +1066,61 @@ int pnr_icp_accumulate(int model_l, const float* cam_l_host, int width_l, int he
 int pnr_icp_solve(const void* workspace, int64_t n_pix, int64_t min_matches, float max_rot, float max_trans, int update,
                   float* pose12, double* history_row, void* stream);
 
+/* ---- depth front end (csrc/pnr_depth.hip; DESIGN.md 8 "Depth front end"): what turns any depth image into a view -- an
+ * edge-preserving filter with a speckle rule, then vertices and normals, so that "pose tracking" can take a depth frame as its
+ * model view.  The reference ships neither: the rule is this build's and unpinned.  Float32 throughout, every operation a single
+ * + - * /, sqrt or comparison in the order given, never an FMA (tests/_depth_ref.py restates both rules three times, twice bit
+ * for bit).  A depth t is VALID iff t > 0 and t is finite (so a NaN is not).  No atomics: two runs give the same bits.  Neither
+ * entry point synchronises; both are capture-safe, and the images are read when the kernel runs.
+ *
+ * pnr_depth_filter.  g_host[0 .. radius]: the spatial weights by |offset|, made by the host (exp(-k k / (2 sigma_space^2)) in
+ *   float64, rounded once: the kernel calls no exp).  Per pixel (i, j) with centre depth c = depth_in[j width + i]:
+ *   1. c not valid: depth_out = 0, support = 0.  Holes are not filled.
+ *   2. sigma = sigma_a + sigma_b * c;  acc = ws = 0, count = 0.
+ *   3. the window row-major: dy = -radius .. radius outside, dx = -radius .. radius inside.  The neighbour t = depth_in at
+ *      (i + dx, j + dy) is USED iff it lies inside the image, t is valid, and u > 0 with x = (t - c) / sigma, u = 1 - x * x (a NaN
+ *      is not used; the centre has x = 0 and is always used).  Then w = (g[|dy|] * g[|dx|]) * (u * u);  acc = acc + w * t;
+ *      ws = ws + w;  count = count + 1.  The range weight is a compact biweight: no transcendental.
+ *   4. depth_out = acc / ws if count >= min_support, else 0 (the speckle rule: an isolated pixel has no support).
+ *      support (int16, optional; NULL: not written) = count, at most (2 radius + 1)^2 = 289.
+ *   PNR_EINVAL before any launch: width or height < 1 or more than 2^31 - 1 pixels; null depth_in, depth_out or g_host; depth_in
+ *   or depth_out misaligned (4 bytes) or support (2); depth_in == depth_out; radius outside 0 .. PNR_DEPTH_MAX_RADIUS; a g entry
+ *   that is not positive and finite; sigma_a or sigma_b negative or not finite, or both 0; min_support < 1.
+ *
+ * pnr_depth_normals.  The camera (model, cam_host, c2w12_host, width, height) as pnr_tsdf_raycast takes it; mc2 = min_cos^2,
+ *   rounded on the host.  Per pixel q = (i, j) with t = depth[q], IN THIS ORDER; the first failing test gives the code:
+ *   1. (o, d) = pnr_camera_ray(model, cam, c2w, i, j).  NO_DEPTH unless t is valid and the ray is ok.  v_k = t * d_k;
+ *      vertex_k = o_k + v_k.
+ *   2. the neighbours one pixel left, right, up and down.  One is USABLE iff it lies inside the image (no longitude wrap), its own
+ *      test 1 passes, and |t_nb - t| <= jump_a + jump_b * t.
+ *   3. per image axis (x: left / right, y: up / down):  both usable: D = v(next) - v(previous);  one usable: v(next) - v or
+ *      v - v(previous);  neither, on either axis: NO_NEIGHBOUR.  The differences are of v, never of vertex: the camera's origin
+ *      would cost the low bits at large world coordinates.
+ *   4. c = Dx x Dy, each component one a b - c d:  c_x = Dx_y Dy_z - Dx_z Dy_y,  c_y = Dx_z Dy_x - Dx_x Dy_z,
+ *      c_z = Dx_x Dy_y - Dx_y Dy_x.  cc = (c_x c_x + c_y c_y) + c_z c_z;  len = sqrt(cc).  DEGENERATE unless len > 0 and finite.
+ *   5. s = (c_x v_x + c_y v_y) + c_z v_z;  vv = (v_x v_x + v_y v_y) + v_z v_z.  GRAZING if s * s < (mc2 * cc) * vv.
+ *   6. OK:  n_k = c_k / len, negated if s > 0: the normal faces the camera, pnr_tsdf_raycast's convention, which
+ *      pnr_icp_accumulate's BACK_FACING test expects.
+ *   OUTPUTS.  normal float32 (., 3): 0 unless OK.  vertex float32 (., 3), optional: o + v wherever test 1 passed, 0 elsewhere.
+ *   code uint8, optional: PNR_NORMAL_*.
+ *   PNR_EINVAL before any launch: an unknown model; null camera or pose; width or height < 1 or more than 2^31 - 1 pixels; a camera
+ *   the model's checks refuse; null depth or normal; depth, normal or vertex misaligned (4 bytes); jump_a or jump_b negative or NaN
+ *   (+inf allowed: no gate); mc2 outside [0, 1]. */
+#define PNR_DEPTH_MAX_RADIUS 8
+#define PNR_DEPTH_TILE_X 32             /* pixels a workgroup of k_depth_filter: TILE_X x TILE_Y, one thread each */
+#define PNR_DEPTH_TILE_Y 8
+#define PNR_NORMALS_TILE_X 32           /* the same of k_depth_normals */
+#define PNR_NORMALS_TILE_Y 8
+#define PNR_NORMAL_OK 0
+#define PNR_NORMAL_NO_DEPTH 1
+#define PNR_NORMAL_NO_NEIGHBOUR 2
+#define PNR_NORMAL_DEGENERATE 3
+#define PNR_NORMAL_GRAZING 4
+int pnr_depth_filter(int width, int height, const float* depth_in, int radius, const float* g_host, float sigma_a, float sigma_b,
+                     int min_support, float* depth_out, int16_t* support, void* stream);
+int pnr_depth_normals(int model, const float* cam_host, const float* c2w12_host, int width, int height, const float* depth,
+                      float jump_a, float jump_b, float mc2, float* normal, float* vertex, uint8_t* code, void* stream);
+
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable
  * state -- the one diagnostic hook of the MLP kernels is a descriptor field (pnr_mlp_desc.clk_probe). */

@@ -16,6 +16,8 @@ MLP_SOFTMAX, MLP_TRACE = 1, 0x7A00        # pnr_mlp_desc.flags (include/pnr.h PN
 CAMERA_PINHOLE, CAMERA_FISHEYE, CAMERA_EQUIRECT = 0, 1, 3     # the model word of every entry point that takes a camera and of pnr_frame (include/pnr.h PNR_CAMERA_*; word 2 is unassigned)
 TAG_PIXEL, TAG_FRAME = 16, 17             # pnr_sample_batch's stream tags (include/pnr.h PNR_TAG_*)
 SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr.h PNR_SAMPLE_*)
+NORMAL_OK, NORMAL_NO_DEPTH, NORMAL_NO_NEIGHBOUR, NORMAL_DEGENERATE, NORMAL_GRAZING = 0, 1, 2, 3, 4    # pnr_depth_normals' codes (PNR_NORMAL_*)
+DEPTH_MAX_RADIUS = 8                      # pnr_depth_filter's largest radius (PNR_DEPTH_MAX_RADIUS)
 
 
 class LossCfg(ctypes.Structure):
@@ -138,6 +140,9 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, c_f, ctypes.c_float,
                                    c_f, c_f, c_f, c_f]),
     "pnr_icp_solve": (c_int, [c_f, c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_int, c_f, c_f, c_f]),
+    "pnr_depth_filter": (c_int, [c_int, c_int, c_f, c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float, c_int, c_f, c_f, c_f]),
+    "pnr_depth_normals": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, c_f, ctypes.c_float,
+                                  ctypes.c_float, ctypes.c_float, c_f, c_f, c_f, c_f]),
     "pnr_panoptic_labels": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),
     "pnr_confusion": (c_int, [c_f, c_f, c_i64, c_int, c_f, c_f]),
     "pnr_sample_pdf": (c_int, [c_f, c_f, c_f, c_i64, c_int, c_int, c_f, c_f, c_f, c_f]),

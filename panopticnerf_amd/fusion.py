@@ -34,10 +34,17 @@ tracking") refines a pose guess by point-to-plane ICP on the device, and FrameSe
     c2w, info = fusion.track(view, camera, depth, c2w_prev)   # device (3, 4); info["history"]: count, E, |w|^2, |v|^2, status per iteration
     frames.set_pose(i, c2w.cpu()); fusion.integrate(vol, frames, trunc, first=i, last=i + 1)
 
-Out of scope there: image pyramids, robust weights, live normals and a normal-angle gate, colour terms, stopping early."""
+Out of scope there: image pyramids, robust weights, a normal-angle gate, colour terms, stopping early.
+
+Before a volume exists, a depth frame is its own model: depth.view gives any depth image the normals `track` needs, and `odometry`
+chains frame-to-frame tracks into poses good enough to integrate the first frames:
+
+    poses, info = fusion.odometry(camera, depths, filter=dict(radius=3, min_support=4))     # device (F, 3, 4); nothing read back
+    for i, p in enumerate(poses.cpu()): frames.set_pose(i, p)"""
 import numpy as np
 import torch
 
+from . import depth as _depth
 from . import mesh as _mesh
 from . import ops
 from .camera import is_camera
@@ -338,3 +345,76 @@ def track(model_view, camera, depth, c2w, iters=10, dist_max=0.25, min_matches=6
     if maps:
         info["valid"] = info["code"] == MATCH
     return pose.reshape(3, 4), info
+
+
+def _compose(a, b):
+    """a o b of two (3, 4) float64 device poses by elementwise arithmetic (the package calls no BLAS):
+    R_ic = (a_i0 b_0c + a_i1 b_1c) + a_i2 b_2c, and the translation column with a's own added last"""
+    out = (a[:, 0:1] * b[0:1, :] + a[:, 1:2] * b[1:2, :]) + a[:, 2:3] * b[2:3, :]
+    return torch.cat([out[:, :3], out[:, 3:] + a[:, 3:]], dim=1)
+
+
+def odometry(camera, depths, c2w0=None, filter=None, guess="identity", **track_args):
+    """Poses for a sequence of depth images of one camera, with no volume: frame k is tracked against the view of frame k - 1
+    (depth.view of it in its OWN camera frame, pose identity -- so no host value depends on a device result), which gives the pose
+    of camera k in camera k - 1; the absolute poses are composed on the device, in float64, by elementwise arithmetic.
+    depths: a sequence of F >= 1 (height, width) float32 GPU images (or one (F, height, width) tensor); c2w0: the pose of frame 0,
+    3x4 (or 4x4) host values or a device tensor (None: identity; inside a graph capture pass None or a device tensor); filter: None
+    or depth.filter's arguments as a dict, applied to every frame -- the filtered image is both the live frame and the next model;
+    guess: "identity" (every step starts from no motion) or "velocity" (from the previous step's relative pose); track_args:
+    iters, dist_max, min_matches, max_rot, max_trans of `track`.
+    Returns (poses, info): poses a device (F, 3, 4) float32; info["relative"] (F - 1, 3, 4) float32, row k - 1 the pose of camera k
+    in camera k - 1, and info["history"] (F - 1, iters + 1, 5) float64, `track`'s history of every step.  A failed step keeps its
+    guess: its status is not ICP_OK, its relative pose is the guess, and both are there to see in info.  Nothing is synchronised
+    and nothing is read back: the whole call can be captured in a graph."""
+    what = "fusion.odometry"
+    if not is_camera(camera):
+        raise TypeError("%s: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (what, camera))
+    if guess not in ("identity", "velocity"):
+        raise ValueError("%s: guess must be 'identity' or 'velocity', not %r" % (what, guess))
+    ops._names(what, track_args, ("iters", "dist_max", "min_matches", "max_rot", "max_trans"),
+               "unknown argument %(key)s (the arguments of fusion.track it passes on: %(known)s)")
+    if isinstance(depths, torch.Tensor):
+        if depths.dim() != 3:
+            raise ValueError("%s: depths must be a sequence of (height, width) images or one (F, height, width) tensor, got %s" % (what, tuple(depths.shape)))
+        depths = list(depths.unbind(0))
+    try:
+        depths = list(depths)
+    except TypeError:
+        raise TypeError("%s: depths must be a sequence of (height, width) images or one (F, height, width) tensor" % what) from None
+    if not depths:
+        raise ValueError("%s: depths is empty (at least one frame)" % what)
+    _depth._filter_args(what, filter)
+    iters = int(track_args.get("iters", 10))
+    if iters < 0:
+        raise ValueError("%s: iters must be >= 0 (got %d)" % (what, iters))
+    ops.icp_accumulate_params(what, track_args.get("dist_max", 0.25))
+    ops.icp_solve_params(what, track_args.get("min_matches", 64), track_args.get("max_rot", 0.25), track_args.get("max_trans", 0.5))
+    for k, d in enumerate(depths):
+        _depth._image("%s: frame %d" % (what, k), d, camera)
+        if d.device != depths[0].device:
+            raise ValueError("%s: frame %d is on %s, frame 0 on %s" % (what, k, d.device, depths[0].device))
+    dev = depths[0].device
+    if c2w0 is None:
+        first = torch.eye(3, 4, dtype=torch.float64, device=dev)
+    else:
+        c2w0 = c2w0 if isinstance(c2w0, torch.Tensor) else torch.as_tensor(c2w0, dtype=torch.float32)
+        if c2w0.numel() not in (12, 16):
+            raise ValueError("%s: c2w0 must be a 3x4 (or 4x4) matrix" % what)
+        first = c2w0.reshape(-1)[:12].reshape(3, 4).to(dev, torch.float64)
+    eye = torch.eye(4)[:3]
+    views = [_depth.view(camera, eye, d, filter=filter) for d in depths]
+    ident = torch.eye(3, 4, dtype=torch.float32, device=dev)
+    absolute, relative, history = [first], [], []
+    start = ident
+    for k in range(1, len(views)):
+        rel, info = track(views[k - 1], camera, views[k][2]["depth"], start, maps=False, **track_args)
+        relative.append(rel)
+        history.append(info["history"])
+        absolute.append(_compose(absolute[-1], rel.to(torch.float64)))
+        if guess == "velocity":
+            start = rel
+    poses = torch.stack(absolute).to(torch.float32)
+    info = {"relative": torch.stack(relative) if relative else torch.zeros((0, 3, 4), dtype=torch.float32, device=dev),
+            "history": torch.stack(history) if history else torch.zeros((0, iters + 1, 5), dtype=torch.float64, device=dev)}
+    return poses, info

@@ -6,6 +6,7 @@ All ops fail loudly off-GPU; nothing here computes on the CPU.
 """
 import ctypes
 import functools
+import math
 import os
 
 import torch
@@ -798,6 +799,100 @@ def icp_solve(workspace, n_pix, pose12, history_row, min_matches=6, max_rot=ICP_
     _same_device(what, workspace=workspace, pose12=pose12, history_row=history_row)
     _lib.check(_lib.load().pnr_icp_solve(_p(workspace), n_pix, min_matches, max_rot, max_trans, 1 if update else 0, _p(pose12),
                                          _p(history_row), _stream()), "pnr_icp_solve")
+
+
+# PNR_NORMAL_* and PNR_DEPTH_MAX_RADIUS (include/pnr.h "depth front end")
+NORMAL_OK, NORMAL_NO_DEPTH, NORMAL_NO_NEIGHBOUR, NORMAL_DEGENERATE, NORMAL_GRAZING = (
+    _lib.NORMAL_OK, _lib.NORMAL_NO_DEPTH, _lib.NORMAL_NO_NEIGHBOUR, _lib.NORMAL_DEGENERATE, _lib.NORMAL_GRAZING)
+DEPTH_MAX_RADIUS = _lib.DEPTH_MAX_RADIUS
+
+
+def _pair(what, name, v, meaning):
+    try:
+        a, b = (float(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s must be (a, b): %s" % (what, name, meaning)) from None
+    return a, b
+
+
+def depth_filter_params(what, radius, sigma_space, sigma_range, min_support):
+    """the scalars of pnr_depth_filter, or the refusal by name (`what`: the caller's name): (radius, g, sigma_a, sigma_b, min_support)
+    with g the radius + 1 spatial weights exp(-k^2 / (2 sigma_space^2)), made in float64 and rounded to float32 once"""
+    radius, sigma_space, min_support = int(radius), float(sigma_space), int(min_support)
+    if not 0 <= radius <= DEPTH_MAX_RADIUS:
+        raise ValueError("%s: radius must lie in 0 .. %d (got %d)" % (what, DEPTH_MAX_RADIUS, radius))
+    if not (0.0 < sigma_space < _INF):
+        raise ValueError("%s: sigma_space must be positive and finite (got %r)" % (what, sigma_space))
+    g = [float(torch.tensor(math.exp(-(k * k) / (2.0 * sigma_space * sigma_space)), dtype=torch.float64).to(torch.float32)) for k in range(radius + 1)]
+    if not all(v > 0.0 for v in g):
+        raise ValueError("%s: sigma_space %r is too small for radius %d (the weight at the window's edge rounds to 0)" % (what, sigma_space, radius))
+    sigma_a, sigma_b = _pair(what, "sigma_range", sigma_range, "sigma = a + b * depth")
+    if not (0.0 <= sigma_a < _INF and 0.0 <= sigma_b < _INF and (sigma_a > 0.0 or sigma_b > 0.0)):
+        raise ValueError("%s: sigma_range must be non-negative and finite, not both 0 (got %r)" % (what, (sigma_a, sigma_b)))
+    if min_support < 1:
+        raise ValueError("%s: min_support must be >= 1 (got %d)" % (what, min_support))
+    return radius, g, sigma_a, sigma_b, min_support
+
+
+def depth_normals_params(what, jump, min_cos):
+    """the scalars of pnr_depth_normals, or the refusal by name: (jump_a, jump_b, mc2) with mc2 = min_cos^2 in float64 (the entry
+    point's float argument rounds it once)"""
+    jump_a, jump_b = _pair(what, "jump", jump, "a neighbour is used while |difference| <= a + b * depth")
+    if not (jump_a >= 0.0 and jump_b >= 0.0):
+        raise ValueError("%s: jump must be non-negative (it may be inf; got %r)" % (what, (jump_a, jump_b)))
+    min_cos = float(min_cos)
+    if not (0.0 <= min_cos <= 1.0):
+        raise ValueError("%s: min_cos must lie in [0, 1] (got %r)" % (what, min_cos))
+    return jump_a, jump_b, min_cos * min_cos
+
+
+def _depth_image(what, name, depth):
+    """(width, height) of a 2-D depth image of any dtype and device: the shape the other images are held to"""
+    _tensor(what, name, depth)
+    if depth.dim() != 2:
+        raise ValueError("%s: %s must be a (height, width) image, got %s" % (what, name, tuple(depth.shape)))
+    return _image_size(what, depth.shape[1], depth.shape[0])
+
+
+@_on_device
+def depth_filter(depth, out, radius=3, sigma_space=1.5, sigma_range=(0.0, 0.03), min_support=1, support=None):
+    """Edge-preserving smoothing of a depth image with a speckle rule (pnr_depth_filter; the rule is in include/pnr.h "depth front
+    end").  depth: (height, width) float32; out: the same shape, another tensor; support: optional int16 image of the number of
+    pixels each result was averaged over.  radius: the window's half width, at most DEPTH_MAX_RADIUS; sigma_space: the spatial
+    Gaussian's sigma in pixels; sigma_range = (a, b): a neighbour counts while |difference| < a + b * depth of the centre, weighted by
+    a biweight; min_support: a pixel with fewer counted neighbours (itself included) becomes 0.  Invalid pixels (0, negative, NaN,
+    Inf) stay 0: holes are not filled.  Returns None."""
+    what = "depth_filter"
+    width, height = _depth_image(what, "depth", depth)
+    _tensor_table(what, (("depth", depth, torch.float32, (height, width)), ("out", out, torch.float32, (height, width))),
+                  (("support", support, torch.int16, (height, width)),))
+    radius, g, sigma_a, sigma_b, min_support = depth_filter_params(what, radius, sigma_space, sigma_range, min_support)
+    _same_device(what, depth=depth, out=out, support=support)
+    if depth.data_ptr() == out.data_ptr():
+        raise ValueError("%s: out must not be depth itself (a pixel reads its neighbours)" % what)
+    g_h = (ctypes.c_float * len(g))(*g)
+    _lib.check(_lib.load().pnr_depth_filter(width, height, _p(depth), radius, g_h, sigma_a, sigma_b, min_support, _p(out), _p(support),
+                                            _stream()), "pnr_depth_filter")
+
+
+@_on_device
+def depth_normals(camera_model, cam, c2w, width, height, depth, normal, jump=(0.0, 0.05), min_cos=0.1, vertex=None, code=None):
+    """World-space vertices and normals of a depth image (pnr_depth_normals; the rule is in include/pnr.h "depth front end").
+    camera_model / cam / c2w / width / height as tsdf_raycast takes its camera (c2w: host values); depth: (height, width) float32 in
+    render_view's convention.  Outputs, caller-owned: normal (height, width, 3) float32, the unit normal towards the camera, 0 where
+    there is none; optional vertex (height, width, 3) float32 and code (height, width) uint8 (NORMAL_OK, NORMAL_NO_DEPTH,
+    NORMAL_NO_NEIGHBOUR, NORMAL_DEGENERATE, NORMAL_GRAZING).  jump = (a, b): a neighbour is differenced against while its depth lies
+    within a + b * depth; min_cos: normals at a steeper angle to the ray are dropped as GRAZING.  Returns None."""
+    what = "depth_normals"
+    word, cam_h = _camera_model(what, "camera_model", camera_model, cam)
+    c2w_h = _host_floats(c2w, 12, what + ": c2w")
+    width, height = _image_size(what, width, height)
+    _tensor_table(what, (("depth", depth, torch.float32, (height, width)), ("normal", normal, torch.float32, (height, width, 3))),
+                  (("vertex", vertex, torch.float32, (height, width, 3)), ("code", code, torch.uint8, (height, width))))
+    jump_a, jump_b, mc2 = depth_normals_params(what, jump, min_cos)
+    _same_device(what, depth=depth, normal=normal, vertex=vertex, code=code)
+    _lib.check(_lib.load().pnr_depth_normals(word, cam_h, c2w_h, width, height, _p(depth), jump_a, jump_b, mc2, _p(normal), _p(vertex),
+                                             _p(code), _stream()), "pnr_depth_normals")
 
 
 class Draw:
