@@ -37,9 +37,6 @@ def _get(cfg, name, default):
 
 CHUNK_QUANTUM = 1024     # rays: at 64 and at 192 samples per ray a multiple of 1024 rays is a whole number of rounds of the
                          # MLP kernels' persistent grid (256 workgroups x 256 samples)
-
-
-PREAMBLE_EARLY = os.environ.get("PNR_OVERLAP_PRE", "1") != "0"     # (A/B) overlapped frames: a chunk's ray_setup in front of the fine MLP two chunks before
 CHUNK_TAIL = 8           # a tail of at most chunk_size / CHUNK_TAIL rays joins the other chunks instead of becoming a chunk
 
 
@@ -66,6 +63,49 @@ def chunk_plan(n_rays, chunk_size):
         out.append((s, e))
         s = e
     return out
+
+
+def _keyed(res, z, lv):
+    """a level's dict (the ops' key names) and its z as render keys: rgb -> rgb_<lv>, ..., z_vals_<lv>"""
+    return {**{f"{k}_{lv}": v for k, v in res.items()}, f"z_vals_{lv}": z}
+
+
+def _level_out(out, lv):
+    """the inverse, for out=: level lv's caller-owned tensors of `out` under the ops' key names (z_vals is not the level's to write)"""
+    return {k[:-2]: v for k, v in out.items() if k.endswith(f"_{lv}") and k != f"z_vals_{lv}"}
+
+
+def _fill_rows(rows, o):
+    """rows: a chunk's row slices of the frame, o: what the chunk returned -- anything it did not write in place (an output
+    without an out= route) is copied in"""
+    for k, v in o.items():
+        if v.data_ptr() != rows[k].data_ptr():
+            rows[k].copy_(v)
+
+
+def _unflatten(maps, lead):
+    """per-ray maps (R, ...) -> (*lead, ...); the training path's scalars as they are"""
+    return {k: v if v.dim() == 0 else v.reshape(*lead, *v.shape[1:]) for k, v in maps.items()}
+
+
+def merge_chunks(outs):
+    """The chunks' render_rays dicts as one: per-ray maps concatenated; of the training path's per-level scalars,
+    ce3d_<field>_n_<lv> (a chunk's number of LABELLED samples) is summed and ce3d_<field>_<lv> (the mean over them) is weighted
+    by that count."""
+    if len(outs) == 1:
+        return outs[0]
+    ret = {}
+    for k in outs[0]:
+        vs = [o[k] for o in outs]
+        head, lv = k.rsplit("_", 1)
+        if vs[0].dim() > 0:
+            ret[k] = torch.cat(vs, 0)
+        elif head.endswith("_n"):
+            ret[k] = torch.stack(vs).sum()
+        else:
+            n = torch.stack([o[f"{head}_n_{lv}"] for o in outs])
+            ret[k] = (torch.stack(vs) * n).sum() / n.sum().clamp(min=1.0)
+    return ret
 
 
 class Renderer:
@@ -148,110 +188,109 @@ class Renderer:
             z = ops.stratified(rays_s, self.N_samples, self.lindisp, t_rand, out=z_out)
         return hits, z, lab0
 
-    # --- one chunk of rays: the reference's render_rays (row a2)
-    def render_rays(self, rays, box=None, box_ids=None, t_rand=None, u=None, train=False, grad=False, out=None, sched=None, rng=None):
-        """rng: (call, ray_base) of the device RNG (cfg.rng = "device": render() issued the call, ray_base = this chunk's first row
-        of the flattened batch) -- t_rand, u and the sigma noise are then drawn inside the kernels.  out: optional {output key: caller-owned tensor of this chunk's shape} (inference only) -- render() passes row slices
-        of the frame-sized maps, so the chunks of a frame are never concatenated.  sched: _render_overlapped's hooks for this
-        chunk -- {"wait": event the coarse MLP launch waits for, "caps": (coarse, fine) workgroup caps, "pdf_done": filled with the
-        event recorded behind sample_pdf}."""
-        net, Nc, Nf = self.net, self.N_samples, self.N_importance
+    # --- the stages of one chunk; render_rays composes them on the caller's stream, _render_overlapped on its side streams
+    def _labels(self, z, hits, box_ids, lab=None):
+        """(semantic, instance) labels of the samples z: `lab` where the kernel that made z labelled them, (None, None) without a prior"""
+        if lab is not None:
+            return lab
+        return ops.sample_labels(z, hits[0], hits[1], hits[2], box_ids) if hits is not None else (None, None)
+
+    def _noise(self, lv, z, train, rng):
+        """the sigma noise of a training level: a tensor, an ops.Draw (device RNG) or None"""
+        if not (self.raw_noise_std > 0 and train):
+            return None
+        if rng is not None:
+            return ops.Draw(rng[0], 3 + lv, rng[1], self.raw_noise_std)
+        return torch.randn(z.shape, device=z.device) * self.raw_noise_std
+
+    def _need_weights(self, lv):
+        return self.keep_weights or (lv == 0 and self.N_importance > 0)     # (the fine level samples the coarse weights)
+
+    def _level(self, lv, rays, z, labels, noise, out, grad, wg_cap=0):
+        """One level of one chunk: the MLP and the compositing of the samples z -> the level's dict under the ops' key names.
+        out: the level's caller-owned tensors (_level_out; inference only).  wg_cap: the fused plan-2 launch on at most that many
+        workgroups (_render_overlapped)."""
+        net, dev = self.net, rays.device
+        ls, li = labels
         n0 = net.nerf(0)
-        C, K = n0.n_sem, n0.n_inst
+        if grad:
+            from . import train as _train       # autograd path (SURVEY 8a row a9)
+            return _train.level_train(self, lv, rays, z, ls, li, noise)
+        weights_only = lv == 0 and self.coarse_outputs == "weights"
+        need_w = self._need_weights(lv)
+        d = net.nerf(lv).desc(net.precision)
+        if weights_only and self.fuse and ops.sigma_pass_supported(d, z.shape[1], noise):
+            desc, img = net.packed(0, dev, fused="sigma")          # trunk + sigma only (pnr_mlp_forward_composite, plan 3)
+            return ops.mlp_forward_weights(desc, img, rays, z, ls, li, out=out)
+        if not weights_only and self.fuse and ops.fused_supported(d, z.shape[1], self.sem_mode, noise):
+            # rows a5 + a6 in one pass: no raw image round trip (pnr_mlp_forward_composite, its own chunk order)
+            desc, img = net.packed(lv, dev, fused=ops.fused_image(self.sem_mode))
+            return ops.mlp_forward_composite(desc, img, rays, z, ls, li, self.white_bkgd, need_w, out=out, sem_mode=self.sem_mode,
+                                             wg_cap=wg_cap)
+        # the two-kernel level.  Weights only (fp32, sigma noise, an N the sigma pass does not take): the full level, its maps dropped
+        desc, img = net.packed(lv, dev)
+        raw = ops.mlp_forward(desc, img, rays, z, channel_major=True)
+        res = ops.composite(raw, z, rays, n0.n_sem, n0.n_inst, True, noise, ls, li, self.sem_mode, self.white_bkgd, need_w, out=out)
+        return {k: v for k, v in res.items() if k not in ops.WEIGHTS_ONLY_DROPS} if weights_only else res
+
+    def _resample(self, z, weights, hits, box_ids, u, z_out):
+        """(z of the fine level, its labels or None) from the coarse level's z and weights"""
+        w0 = weights.detach().contiguous()
+        if hits is not None:        # rows a7 + a8 in one launch: the wave that merged a ray's samples labels them
+            z_fine, ls1, li1 = ops.sample_pdf_labels(z, w0, self.N_importance, hits, box_ids, u, out=z_out)
+            return z_fine, (ls1, li1)
+        z_fine, _, _ = ops.sample_pdf(z, w0, self.N_importance, u, want_samples=False, out=z_out)
+        return z_fine, None
+
+    # --- one chunk of rays: the reference's render_rays (row a2)
+    def render_rays(self, rays, box=None, box_ids=None, t_rand=None, u=None, train=False, grad=False, out=None, rng=None):
+        """rng: (call, ray_base) of the device RNG (cfg.rng = "device": render() issued the call, ray_base = this chunk's first row
+        of the flattened batch) -- t_rand, u and the sigma noise are then drawn inside the kernels.  out: optional {output key:
+        caller-owned tensor of this chunk's shape} (inference only) -- render() passes row slices of the frame-sized maps, so the
+        chunks of a frame are never concatenated.  Every launch goes to the caller's stream and no event is made: a call can be
+        captured in a HIP graph."""
+        Nc, Nf = self.N_samples, self.N_importance
         dev = rays.device
-        ret = {}
-        hits = lab0 = None
-        if t_rand is None and self.perturb > 0 and train:
+        out = out if (out and not grad) else {}
+        draw = self.perturb > 0 and train
+        if t_rand is None and draw:
             t_rand = ops.Draw(rng[0], 1, rng[1]) if rng is not None else torch.rand((rays.shape[0], Nc), device=dev)
-        own = (lambda key: out.get(key)) if (out and not grad) else (lambda key: None)
-        if sched is not None and sched.get("pre") is not None:
-            hits, z, lab0 = sched["pre"]                    # this chunk's preamble was issued earlier on this stream (_render_overlapped)
-        else:
-            hits, z, lab0 = self._preamble(rays, box, box_ids, t_rand, own("z_vals_0"))
+        hits, z, lab0 = self._preamble(rays, box, box_ids, t_rand, out.get("z_vals_0"))
         if hits is not None and self.strict_hits:          # accumulated on the device; checked ONCE at the end of render() (a single sync)
             over = torch.stack([(hits[2] > self.max_hits).sum(), hits[2].max()])
             self._overflow = over if self._overflow is None else torch.stack([self._overflow[0] + over[0],
                                                                               torch.maximum(self._overflow[1], over[1])])
-
-        def level(lv, zz, labels=None):
-            ls = li = None
-            if labels is not None:
-                ls, li = labels
-            elif hits is not None:
-                ls, li = ops.sample_labels(zz, hits[0], hits[1], hits[2], box_ids)
-            noise = None
-            if self.raw_noise_std > 0 and train:
-                if rng is not None:
-                    noise = ops.Draw(rng[0], 3 + lv, rng[1], self.raw_noise_std)
-                else:
-                    noise = torch.randn(zz.shape, device=dev) * self.raw_noise_std
-            if grad:
-                from . import train as _train       # autograd path (SURVEY 8a row a9)
-                res = _train.level_train(self, lv, rays, zz, ls, li, noise)
-            elif lv == 0 and self.coarse_outputs == "weights":
-                mine = {k: own(f"{k}_0") for k in ("depth", "acc", "weights", "fix_semantic", "fix_instance")}
-                mine = {k: v for k, v in mine.items() if v is not None}
-                if self.fuse and ops.sigma_pass_supported(n0.desc(net.precision), zz.shape[1], noise):
-                    desc, img = net.packed(0, dev, fused="sigma")          # trunk + sigma only (pnr_mlp_forward_composite, plan 3)
-                    res = ops.mlp_forward_weights(desc, img, rays, zz, ls, li, out=mine)
-                else:       # fp32, sigma noise, an N the fused pass does not take: the full level, its maps dropped
-                    desc, img = net.packed(0, dev)
-                    raw = ops.mlp_forward(desc, img, rays, zz, channel_major=True)
-                    res = ops.composite(raw, zz, rays, C, K, True, noise, ls, li, self.sem_mode, self.white_bkgd, True, out=mine)
-                    res = {k: v for k, v in res.items() if k not in ops.WEIGHTS_ONLY_DROPS}
-            else:
-                need_w = self.keep_weights or (lv == 0 and Nf > 0)
-                mine = {k: own(f"{k}_{lv}") for k in ("rgb", "depth", "acc", "weights", "semantic", "instance", "fix_semantic", "fix_instance")}
-                mine = {k: v for k, v in mine.items() if v is not None}
-                if self.fuse and ops.fused_supported(net.nerf(lv).desc(net.precision), zz.shape[1], self.sem_mode, noise):
-                    # rows a5 + a6 in one pass: no raw image round trip (pnr_mlp_forward_composite, its own chunk order)
-                    desc, img = net.packed(lv, dev, fused=ops.fused_image(self.sem_mode))
-                    if sched is not None and lv == 0 and sched.get("wait") is not None:
-                        torch.cuda.current_stream(dev).wait_event(sched["wait"])      # start beside the other chunk's fine level
-                    res = ops.mlp_forward_composite(desc, img, rays, zz, ls, li, self.white_bkgd, need_w, out=mine, sem_mode=self.sem_mode,
-                                                    wg_cap=0 if sched is None else sched["caps"][lv])
-                else:
-                    desc, img = net.packed(lv, dev)
-                    raw = ops.mlp_forward(desc, img, rays, zz, channel_major=True)
-                    res = ops.composite(raw, zz, rays, C, K, True, noise, ls, li, self.sem_mode, self.white_bkgd, need_w, out=mine)
-            for k, v in res.items():
-                ret[f"{k}_{lv}"] = v
-            ret[f"z_vals_{lv}"] = zz
-            return res
-
-        o0 = level(0, z, lab0)
+        lab0 = self._labels(z, hits, box_ids, lab0)
+        o0 = self._level(0, rays, z, lab0, self._noise(0, z, train, rng), _level_out(out, 0), grad)
+        ret = _keyed(o0, z, 0)
         if Nf > 0:
-            if u is None and self.perturb > 0 and train:
+            if u is None and draw:
                 u = ops.Draw(rng[0], 2, rng[1]) if rng is not None else torch.rand((rays.shape[0], Nf), device=dev)
-            w0 = o0["weights"].detach().contiguous()
-            if hits is not None:        # rows a7 + a8 in one launch: the wave that merged a ray's samples labels them
-                z_fine, ls1, li1 = ops.sample_pdf_labels(z, w0, Nf, hits, box_ids, u, out=own("z_vals_1"))
-                lab1 = (ls1, li1)
-            else:
-                z_fine, _, _ = ops.sample_pdf(z, w0, Nf, u, want_samples=False, out=own("z_vals_1"))
-                lab1 = None
-            if sched is not None:
-                sched["pdf_done"] = torch.cuda.Event()
-                sched["pdf_done"].record(torch.cuda.current_stream(dev))
-                if sched.get("before_fine") is not None:
-                    sched["before_fine"]()                  # the preamble of the chunk after next, in front of this chunk's fine MLP
-            level(1, z_fine, lab1)
+            z_fine, lab1 = self._resample(z, o0["weights"], hits, box_ids, u, out.get("z_vals_1"))
+            lab1 = self._labels(z_fine, hits, box_ids, lab1)
+            o1 = self._level(1, rays, z_fine, lab1, self._noise(1, z_fine, train, rng), _level_out(out, 1), grad)
+            ret.update(_keyed(o1, z_fine, 1))
+        return ret
+
+    def _output_maps(self, R, has_box, dev, grad=False):
+        """THE maps of a render of R rays -- keys, shapes and dtypes as render_rays returns them, both levels, allocated and not
+        written: what a frame of several chunks is rendered into (every chunk gets its row slices as out=) and, at R = 0, what
+        a render of no rays returns.  fix_* only with a prior; no level 1 without a fine level; cfg.coarse_outputs = "weights"
+        (inference: not grad) drops the coarse maps that mode does not make."""
+        n0 = self.net.nerf(0)
+        lab = True if has_box else None
+        Nc, Nf = self.N_samples, self.N_importance
+        ret = {}
+        for lv, N in ((0, Nc), (1, Nc + Nf)) if Nf > 0 else ((0, Nc),):
+            drop = ops.WEIGHTS_ONLY_DROPS if (lv == 0 and not grad and self.coarse_outputs == "weights") else ()
+            m = ops._maps(None, R, N, n0.n_sem, n0.n_inst, lab, lab, self._need_weights(lv), dev, drop=drop)
+            ret.update(_keyed(m, torch.empty((R, N), device=dev, dtype=torch.float32), lv))
         return ret
 
     def _empty_outputs(self, lead, has_box, dev, grad=False):
         """render() of zero rays: every output key of a non-empty call, with zero rows and no launch (the edge case a caller
         hits with an empty shard: n_rays < world, or a mask that selects nothing)."""
-        n0 = self.net.nerf(0)
-        C, K = n0.n_sem, n0.n_inst
-        ret = {}
-        for lv, N in ((0, self.N_samples),) + (((1, self.N_samples + self.N_importance),) if self.N_importance > 0 else ()):
-            need_w = self.keep_weights or (lv == 0 and self.N_importance > 0)
-            drop = ops.WEIGHTS_ONLY_DROPS if (lv == 0 and not grad and self.coarse_outputs == "weights") else ()
-            m = ops._maps(None, 0, N, C, K, True if has_box else None, True if has_box else None, need_w, dev, drop=drop)
-            m["z_vals"] = torch.empty((0, N), device=dev, dtype=torch.float32)
-            for k, v in m.items():
-                ret[f"{k}_{lv}"] = v.reshape(*lead, *v.shape[1:])
-        return ret
+        return _unflatten(self._output_maps(0, has_box, dev, grad), lead)
 
     # --- inference frames of several chunks: the levels of neighbouring chunks side by side
     def _overlap_caps(self, dev, plan, grad, train, has_box, t_rand, u):
@@ -277,29 +316,17 @@ class Renderer:
             return None
         return cap_c, cap_f
 
-    def _frame_maps(self, R, has_box, dev):
-        """frame-sized output maps, keys and shapes as render_rays returns them"""
-        n0 = self.net.nerf(0)
-        C, K = n0.n_sem, n0.n_inst
-        frame = {}
-        for lv, N in ((0, self.N_samples), (1, self.N_samples + self.N_importance)):
-            need_w = self.keep_weights or lv == 0
-            m = ops._maps(None, R, N, C, K, True if has_box else None, True if has_box else None, need_w, dev)
-            m["z_vals"] = torch.empty((R, N), device=dev, dtype=torch.float32)
-            for k, v in m.items():
-                frame[f"{k}_{lv}"] = v
-        return frame
-
     def _render_overlapped(self, rays, box, box_ids, plan, caps, lead):
         """Chunks alternate between two side streams; a chunk's whole chain (ray_setup, coarse MLP, combine, sample_pdf + labels, fine
         MLP, combine) stays on its stream, and ONE cross-stream rule aligns the pipeline: the coarse MLP of chunk c + 1 (on cap_c
         workgroups) waits for chunk c's sample_pdf, i.e. starts together with chunk c's fine MLP (on cap_f workgroups).  The first
         coarse and the last fine launch have the device to themselves.  Same kernels on the same inputs as the serial frame: every
-        map is the same bits (tests/test_gpu_configs.py::test_full_frame_in_one_launch_equals_the_chunked_frame)."""
+        map is the same bits (tests/test_gpu_configs.py::test_full_frame_in_one_launch_equals_the_chunked_frame).  However the loop
+        ends, the caller's stream waits for both side streams: rays, boxes and the frame go back to the allocator on that stream."""
         dev = rays.device
-        R = rays.shape[0]
         cap_c, cap_f = caps
-        frame = self._frame_maps(R, box is not None, dev)
+        last = len(plan) - 1
+        frame = self._output_maps(rays.shape[0], box is not None, dev)
         main = torch.cuda.current_stream(dev)
         if dev not in self._side_streams:
             self._side_streams[dev] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
@@ -309,26 +336,35 @@ class Renderer:
         for st in side:
             st.wait_event(start)           # rays, boxes, the frame maps: everything the side streams read or write exists
         prev_pdf = None
-        pre = {}
+        pre = {}                        # chunk -> its preamble, where that was issued early
 
-        def preamble(cj):               # issued on chunk cj's stream two chunks early: in front of chunk cj - 2's fine MLP
+        def preamble(cj):
             sj, ej = plan[cj]
-            pre[cj] = self._preamble(rays[sj:ej], box, box_ids, None, frame["z_vals_0"][sj:ej])
-        for ci, (s, e) in enumerate(plan):
-            sched = {"wait": prev_pdf, "caps": (0 if ci == 0 else cap_c, 0 if ci == len(plan) - 1 else cap_f), "pdf_done": None,
-                     "pre": pre.pop(ci, None),
-                     "before_fine": (lambda cj=ci + 2: preamble(cj)) if (PREAMBLE_EARLY and ci + 2 < len(plan)) else None}
-            with torch.cuda.stream(side[ci & 1]):
-                o = self.render_rays(rays[s:e], box, box_ids, None, None, False, False, out={k: v[s:e] for k, v in frame.items()}, sched=sched)
-                for k, v in o.items():          # anything a chunk did not write in place (an output without an out= route)
-                    if v.data_ptr() != frame[k][s:e].data_ptr():
-                        frame[k][s:e].copy_(v)
-            prev_pdf = sched["pdf_done"]
-        for st in side:
-            done = torch.cuda.Event()
-            done.record(st)
-            main.wait_event(done)
-        return {k: v.reshape(*lead, *v.shape[1:]) for k, v in frame.items()}
+            return self._preamble(rays[sj:ej], box, box_ids, None, frame["z_vals_0"][sj:ej])
+        try:
+            for ci, (s, e) in enumerate(plan):
+                r, st = rays[s:e], side[ci & 1]
+                out = {k: v[s:e] for k, v in frame.items()}
+                with torch.cuda.stream(st):
+                    hits, z, lab0 = pre.pop(ci) if ci in pre else preamble(ci)
+                    lab0 = self._labels(z, hits, box_ids, lab0)
+                    if prev_pdf is not None:
+                        st.wait_event(prev_pdf)             # the coarse MLP starts beside the other chunk's fine level
+                    o0 = self._level(0, r, z, lab0, None, _level_out(out, 0), False, 0 if ci == 0 else cap_c)
+                    z_fine, lab1 = self._resample(z, o0["weights"], hits, box_ids, None, out["z_vals_1"])
+                    prev_pdf = torch.cuda.Event()
+                    prev_pdf.record(st)
+                    if ci + 2 <= last:
+                        pre[ci + 2] = preamble(ci + 2)      # of the chunk after next, in front of this chunk's fine MLP
+                    lab1 = self._labels(z_fine, hits, box_ids, lab1)
+                    o1 = self._level(1, r, z_fine, lab1, None, _level_out(out, 1), False, 0 if ci == last else cap_f)
+                    _fill_rows(out, {**_keyed(o0, z, 0), **_keyed(o1, z_fine, 1)})
+        finally:
+            for st in side:
+                done = torch.cuda.Event()
+                done.record(st)
+                main.wait_event(done)
+        return _unflatten(frame, lead)
 
     # --- the plugin entry point (row a1)
     def render(self, batch):
@@ -374,48 +410,26 @@ class Renderer:
             if self.rng_state.device != rays.device:
                 self.rng_state = self.rng_state.to(rays.device)
             call = ops.rng_begin(self.rng_state)        # one offset per call; every chunk and level draws from it
+        # inference frames of several chunks: frame-sized maps, every chunk writes its own rows
+        frame = self._output_maps(R, box is not None, rays.device) if (len(plan) > 1 and not grad and self.frame_outputs) else None
         outs = []
-        frame = None        # inference frames of several chunks: frame-sized maps, every later chunk writes its own rows
         for s, e in plan:
+            rows = None if frame is None else {k: v[s:e] for k, v in frame.items()}
             o = self.render_rays(rays[s:e], box, box_ids,
                                  None if t_rand is None else t_rand[s:e],
-                                 None if u is None else u[s:e], train, grad,
-                                 out=None if frame is None else {k: v[s:e] for k, v in frame.items()},
+                                 None if u is None else u[s:e], train, grad, out=rows,
                                  rng=None if call is None else (call, s))
-            if s == 0 and e < R and not grad and self.frame_outputs and all(v.dim() >= 1 and v.shape[0] == e for v in o.values()):
-                frame = {k: torch.empty((R,) + tuple(v.shape[1:]), device=v.device, dtype=v.dtype) for k, v in o.items()}
-                for k, v in o.items():
-                    frame[k][:e].copy_(v)
-            elif frame is not None:
-                for k, v in o.items():      # anything a chunk did not write in place (an output without an out= route)
-                    if v.data_ptr() != frame[k][s:e].data_ptr():
-                        frame[k][s:e].copy_(v)
-            outs.append(o)
+            if frame is not None:
+                _fill_rows(rows, o)
+            else:
+                outs.append(o)
         if self._overflow is not None:
             n_over, worst = (int(v) for v in self._overflow.tolist())         # the one device sync of strict_hits
             self._overflow = None
             if n_over > 0:
                 raise RuntimeError("Renderer.render: %d ray(s) cross more than max_hits = %d boxes (up to %d): the farthest "
                                    "intervals were dropped -- raise cfg.max_hits" % (n_over, self.max_hits, worst))
-        if frame is not None:
-            return {k: v.reshape(*lead, *v.shape[1:]) for k, v in frame.items()}
-        ret = {}
-        for k in outs[0]:
-            if outs[0][k].dim() == 0:
-                # per-level scalars of the training path: ce3d_<field>_<lv> is a mean over the chunk's LABELLED samples,
-                # ce3d_<field>_n_<lv> their number -> the frame's mean weights every chunk by its count
-                if len(outs) == 1:
-                    ret[k] = outs[0][k]
-                elif k.rsplit("_", 1)[0].endswith("_n"):
-                    ret[k] = torch.stack([o[k] for o in outs]).sum()
-                else:
-                    head, lv = k.rsplit("_", 1)
-                    n = torch.stack([o[f"{head}_n_{lv}"] for o in outs])
-                    ret[k] = (torch.stack([o[k] for o in outs]) * n).sum() / n.sum().clamp(min=1.0)
-                continue
-            v = outs[0][k] if len(outs) == 1 else torch.cat([o[k] for o in outs], 0)
-            ret[k] = v.reshape(*lead, *v.shape[1:])
-        return ret
+        return _unflatten(frame if frame is not None else merge_chunks(outs), lead)
 
     # --- a whole frame of a camera (panopticnerf_amd/camera.py): rays for the pixels that see anything, maps as images
     def render_view(self, camera, c2w, near, far, bbox=None, bbox_ids=None, prims=None):

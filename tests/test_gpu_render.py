@@ -295,15 +295,59 @@ def test_overlapped_levels_equal_the_serial_frame(dev, heads, with_box, act):
         r_over = make_renderer(cfg, net)
         assert r_over._overlap_caps(dev, [(0, 1), (1, 2)], False, False, with_box, None, None) == (64, 192)
         over = r_over.render(b)
+        assert r_over._side_streams                  # the overlapped path really ran
         over2 = r_over.render(b)
         cfg.overlap_levels = False
         r_ser = make_renderer(cfg, net)
         assert r_ser._overlap_caps(dev, [(0, 1), (1, 2)], False, False, with_box, None, None) is None
         ser = r_ser.render(b)
+        assert r_ser._side_streams == {}
     torch.cuda.synchronize()
     assert set(over) == set(ser)
     for k in ser:
         assert over[k].shape == ser[k].shape and torch.equal(over[k], ser[k]) and torch.equal(over2[k], ser[k]), k
+
+
+def test_overlapped_frame_joins_its_streams_when_a_chunk_raises(dev, monkeypatch):
+    """A chunk that raises in the middle of an overlapped frame (here a host exception out of the third sample_pdf_labels call: no
+    kernel misbehaves) leaves work on both side streams that reads the rays and writes the frame, all of it allocated on the
+    caller's stream.  _render_overlapped makes the caller's stream wait for both side streams on every way out, so once the
+    caller's stream has drained, both side streams have; the exception arrives unchanged, and the next render on the same renderer
+    is the serial frame bit for bit.  3,500 rays in 4 chunks of 875: both side streams busy, an early preamble issued and never
+    used, a ragged tile count.  This checks the join; it is no race detector -- without the join the side streams may
+    happen to be done first and query() still answers True."""
+    from panopticnerf_amd import renderer as R_
+    cfg = NS(N_samples=64, N_importance=128, num_classes=45, num_instances=32, precision="bf16", chunk_size=1024, keep_weights=True,
+             semantic_activation="none", overlap_levels=True)
+    torch.manual_seed(5)
+    net = make_network(cfg).to(dev).eval()
+    synthetic.trained_like_(net, 0.05)
+    rays = synthetic.camera_rays()[::29][:3500].contiguous().to(dev)
+    box, ids = synthetic.random_boxes(16, 45, 32)
+    b = {"rays": rays[None], "bbox": box.to(dev), "bbox_ids": ids.to(dev)}
+    assert [e - s for s, e in R_.chunk_plan(3500, 1024)] == [875] * 4
+    rend = make_renderer(cfg, net)
+    inner, calls = ops.sample_pdf_labels, []
+
+    def third_call_raises(*a, **k):
+        calls.append(1)
+        if len(calls) == 3:
+            raise RuntimeError("boom")
+        return inner(*a, **k)
+    with torch.no_grad():
+        with monkeypatch.context() as m:
+            m.setattr(R_.ops, "sample_pdf_labels", third_call_raises)
+            with pytest.raises(RuntimeError, match="^boom$"):
+                rend.render(b)
+        torch.cuda.current_stream(dev).synchronize()
+        assert len(rend._side_streams[dev]) == 2 and all(st.query() for st in rend._side_streams[dev])
+        again = rend.render(b)
+        cfg.overlap_levels = False
+        ser = make_renderer(cfg, net).render(b)
+    torch.cuda.synchronize()
+    assert len(calls) == 3 and set(again) == set(ser)
+    for k in ser:
+        assert again[k].shape == ser[k].shape and torch.equal(again[k], ser[k]), k
 
 
 def test_a_ranks_share_of_the_frame_is_one_chunk(dev):

@@ -119,6 +119,75 @@ def test_chunk_plan_is_balanced_and_whole_rounds():
         assert len(plan) <= R // c + 1
 
 
+def test_merge_chunks_concatenates_maps_and_weights_the_means_by_their_counts():
+    """renderer.merge_chunks, the end of a training render of several chunks: per-ray maps are concatenated in chunk order,
+    ce3d_<field>_n_<lv> counts are summed, and ce3d_<field>_<lv> means are weighted by those counts (0.0, not NaN, where no
+    chunk had a labelled sample).  One chunk comes back as it is."""
+    from panopticnerf_amd.renderer import merge_chunks
+
+    def chunk(rows, first, mean, n):
+        return {"rgb_0": torch.arange(first, first + rows * 3, dtype=torch.float32).reshape(rows, 3),
+                "depth_0": torch.arange(first, first + rows, dtype=torch.float32),
+                "ce3d_semantic_0": torch.tensor(mean), "ce3d_semantic_n_0": torch.tensor(n)}
+    a, b, c = chunk(2, 0, 2.0, 1.0), chunk(3, 100, 4.0, 3.0), chunk(2, 200, 7.0, 0.0)
+    assert merge_chunks([a]) is a
+    for outs, rows in (([a, b], 5), ([a, b, c], 7)):
+        m = merge_chunks(outs)
+        assert set(m) == set(a)
+        assert m["rgb_0"].shape == (rows, 3) and m["depth_0"].shape == (rows,)
+        assert torch.equal(m["rgb_0"], torch.cat([o["rgb_0"] for o in outs])) and torch.equal(m["rgb_0"][2:5], b["rgb_0"])
+        assert torch.equal(m["depth_0"], torch.cat([o["depth_0"] for o in outs]))
+        assert m["ce3d_semantic_0"].item() == 3.5 and m["ce3d_semantic_n_0"].item() == 4.0        # (2 * 1 + 4 * 3 [+ 7 * 0]) / 4
+    z = merge_chunks([chunk(2, 0, 0.0, 0.0), chunk(3, 0, 0.0, 0.0)])
+    assert z["ce3d_semantic_0"].item() == 0.0 and z["ce3d_semantic_n_0"].item() == 0.0
+
+
+@pytest.mark.parametrize("prior", [False, True])
+@pytest.mark.parametrize("C,K", [(5, 3), (5, 0), (0, 0)])
+def test_the_output_spec_of_a_render_against_a_table(C, K, prior):
+    """Renderer._output_maps gives the maps of every render -- the empty one, the serial frame, the overlapped frame --, so its
+    keys and trailing shapes are checked here against a table written out by hand: with and without a prior, heads, kept
+    weights, coarse_outputs and a fine level."""
+    for keep, mode, Nf in [(k, m, n) for k in (True, False) for m in ("all", "weights") for n in (0, 16)]:
+        cfg = NS(D=2, W=128, skips=[], N_samples=32, N_importance=Nf, num_classes=C, num_instances=K, keep_weights=keep, coarse_outputs=mode)
+        net = make_network(cfg)
+        if mode == "weights" and Nf == 0:
+            with pytest.raises(ValueError):
+                make_renderer(cfg, net)
+            continue
+        got = make_renderer(cfg, net)._output_maps(7, prior, "cpu")
+        want = {"depth_0": (), "acc_0": (), "z_vals_0": (32,)}
+        if mode == "all":
+            want["rgb_0"] = (3,)
+        if keep or Nf:
+            want["weights_0"] = (32,)
+        if Nf:
+            want.update({"rgb_1": (3,), "depth_1": (), "acc_1": (), "z_vals_1": (48,)})
+            if keep:
+                want["weights_1"] = (48,)
+        for lv in (0, 1) if Nf else (0,):
+            for field, n in (("semantic", C), ("instance", K)):
+                if n and (lv == 1 or mode == "all"):
+                    want[f"{field}_{lv}"] = (n,)
+                if n and prior:
+                    want[f"fix_{field}_{lv}"] = (n,)
+        what = (C, K, prior, keep, mode, Nf)
+        assert {k: tuple(v.shape) for k, v in got.items()} == {k: (7,) + s for k, s in want.items()}, what
+        assert all(v.dtype == torch.float32 and v.device.type == "cpu" for v in got.values())
+        # the properties the callers rely on, stated once more on their own
+        if mode == "weights":
+            assert not {"rgb_0", "semantic_0", "instance_0"} & set(got), what
+        assert ("weights_0" in got) or not Nf, what
+        for head, n in (("fix_semantic", C), ("fix_instance", K)):
+            assert (prior and n) or not [k for k in got if k.startswith(head)], what
+        assert Nf or not [k for k in got if k.endswith("_1")], what
+        # a training render (grad) keeps every coarse map whatever coarse_outputs says, and the empty render is the spec at R = 0
+        full = make_renderer(cfg, net)._output_maps(0, prior, "cpu", grad=True)
+        assert ("rgb_0" in full) and bool(C) == ("semantic_0" in full), what
+        empty = make_renderer(cfg, net)._empty_outputs((2, 0), prior, "cpu")
+        assert {k: tuple(v.shape) for k, v in empty.items()} == {k: (2, 0) + s for k, s in want.items()}, what
+
+
 def test_shard_roundtrip_single_process():
     rays = torch.arange(11 * 8, dtype=torch.float32).reshape(11, 8)
     parts = [shard.shard_rays(rays, r, 3) for r in range(3)]
