@@ -137,7 +137,12 @@ int pnr_mlp_pack(const pnr_mlp_desc* desc, const pnr_mlp_params_host* params, vo
  * packed: device buffer of pnr_mlp_packed_bytes / pnr_mlp_bwd_packed_bytes bytes.  Three small host->device
  * copies (header, chunk table, descriptors) and one kernel are enqueued on `stream`, and `stream` is synchronised
  * once before returning (the copies read call-local host staging memory): the ONE entry point that synchronises;
- * it is set-up work -- never call it inside graph capture, use pnr_mlp_repack_device there. */
+ * it is set-up work -- never call it inside graph capture, use pnr_mlp_repack_device there.
+ * The alignment gap: the data area starts at the next multiple of 1024 behind the chunk table, and the bytes between
+ * the two belong to the image (they count in pnr_mlp_packed_bytes).  pnr_mlp_pack / pnr_mlp_pack_bwd zero them; the
+ * device packer writes the header, the table and the data area and LEAVES THE GAP as the caller handed it in, so a
+ * device image equals the host image byte for byte only in a buffer whose gap was zero (ops.pack_mlp_device allocates
+ * zeros).  Nothing outside [0, packed bytes) and [0, workspace bytes) is written. */
 int64_t pnr_mlp_pack_workspace_bytes(const pnr_mlp_desc* desc, int backward);
 int pnr_mlp_pack_device(const pnr_mlp_desc* desc, const pnr_mlp_params_host* params_dev, int backward,
                         void* workspace, void* packed, void* stream);

@@ -106,7 +106,9 @@ class Network(nn.Module):
     def _pack(self, level, device, precision, backward, fused=False):
         """(desc, packed image on `device`) of level's NeRF, rebuilt when any parameter changed.  When the
         parameters live on that GPU the image is packed there (pnr_mlp_pack_device, buffers reused); otherwise
-        on the host and uploaded."""
+        on the host and uploaded.  Float32, contiguous parameters are re-packed by the kernel alone (graph-capture safe);
+        a network cast with .double() / .bfloat16(), or with a non-contiguous parameter, renders and trains correctly
+        through one full, synchronising pack per image and render -- running it under stream capture is not supported."""
         net = self.nerf(level)                   # raises when a fine level is asked of a coarse-only network
         desc = net.desc(precision)
         if fused and not backward:
@@ -130,11 +132,13 @@ class Network(nn.Module):
         # miss .data writes and HIP-graph replays of the optimiser step
         if hit is not None and hit[0] == ver and not (self.training and on_dev):
             return hit[1], hit[2]
-        ptrs = tuple(p.data_ptr() for p in sd.values())
+        # a parameter that is not float32 and contiguous (net.double(), a transposed view) is packed from a temporary copy:
+        # the descriptors of that pack point at memory that is gone, so no pointers are recorded and every call is a full pack
+        ptrs = tuple(p.data_ptr() for p in sd.values()) if all(p.dtype == torch.float32 and p.is_contiguous() for p in sd.values()) else None
         if on_dev:
             # same parameter storage as last time (an in-place optimiser step): the descriptors already on the device
             # are still right, only the packing kernel has to run again -- no host copies, graph-capture safe
-            same = hit is not None and hit[3] is not None and len(hit) > 4 and hit[4] == ptrs
+            same = hit is not None and hit[3] is not None and len(hit) > 4 and ptrs is not None and hit[4] == ptrs
             img, ws = ops.pack_mlp_device(desc, sd, backward, hit[2] if hit else None, hit[3] if hit else None, repack=same)
         else:
             sd = {k: v.detach().float().cpu() for k, v in sd.items()}

@@ -1082,16 +1082,23 @@ def fused_plan(desc, limit=None):
     return 0
 
 
+def param_in_place(t, device):
+    """Can a kernel read parameter `t` where it lies -- float32, contiguous, on `device`?  Otherwise _param_struct hands it a
+    temporary float32 copy, and nothing that outlives the call (the descriptors of pack_mlp_device) may point at it."""
+    return t.device == torch.device(device) and t.dtype == torch.float32 and t.is_contiguous()
+
+
 def _param_struct(desc, params, device):
     """pnr_mlp_params_host filled with pointers to `params` (dict name -> tensor) moved/kept on `device`.
-    Returns (struct, keep-alive list)."""
+    Returns (struct, keep-alive list): a parameter that is not param_in_place is pointed to through a temporary copy, and that
+    pointer is valid only while the keep-alive list is."""
     keep = []
 
     def fp(name):
         if name not in params:
             return None
         t = params[name].detach()
-        if t.device != torch.device(device) or t.dtype != torch.float32 or not t.is_contiguous():
+        if not param_in_place(t, device):
             t = t.to(device, torch.float32).contiguous()
         keep.append(t)
         return ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float))
@@ -1123,11 +1130,22 @@ def pack_mlp_device(desc, params, backward=False, out=None, workspace=None, repa
     """Pack on the GPU straight from the (CUDA, fp32) parameter tensors: pnr_mlp_pack_device.
     Returns (image uint8 CUDA tensor, workspace) -- pass both back in to reuse the buffers.
     repack=True: `out` / `workspace` come from an earlier call with the SAME parameter tensors (same data pointers) whose
-    values changed in place: only the packing kernel runs (pnr_mlp_repack_device; no host copies, graph-capture safe)."""
+    values changed in place: only the packing kernel runs (pnr_mlp_repack_device; no host copies, graph-capture safe).
+    The descriptors a full pack leaves in `workspace` hold the addresses the kernel reads.  A parameter that is not float32
+    and contiguous (a .double() / .bfloat16() network, a transposed view) is packed from a temporary float32 copy that
+    dies with the call, so such parameters take a full pack every time: repack=True with one of them is a ValueError,
+    raised before anything is launched.  The full pack synchronises, so a network like that cannot run under stream
+    capture."""
     lib = _lib.load()
     dev = next(iter(params.values())).device
     if dev.type != "cuda":
         raise RuntimeError("pack_mlp_device: parameters must be on the GPU")
+    if repack:
+        for name, t in params.items():
+            if not param_in_place(t, dev):
+                raise ValueError("pack_mlp_device(repack=True): parameter %r (%s%s) is packed from a temporary copy; a repack needs "
+                                 "the float32, contiguous tensors the descriptors point at -- make a full pack (repack=False)"
+                                 % (name, t.dtype, "" if t.is_contiguous() else ", not contiguous"))
     nbytes = (lib.pnr_mlp_bwd_packed_bytes if backward else lib.pnr_mlp_packed_bytes)(ctypes.byref(desc))
     if nbytes < 0:
         _lib.check(int(nbytes), "pnr_mlp_packed_bytes")

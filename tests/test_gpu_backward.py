@@ -207,7 +207,8 @@ def test_render_backward_end_to_end(dev):
 
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_device_packer_equals_host_packer(dev, prec):
-    """pnr_mlp_pack_device writes the same image, bit for bit, as the host packers (forward and transposed)."""
+    """pnr_mlp_pack_device writes the same image, bit for bit, as the host packers (forward and transposed).  One geometry;
+    test_gpu_pack_device.py does the same at every geometry, plan and precision, with guards, planted values and the cache."""
     from panopticnerf_amd import make_network
     from types import SimpleNamespace as NS
     torch.manual_seed(1)
