@@ -993,17 +993,128 @@ def _own(out, shape, dtype, dev, what):
     return out
 
 
+# The argument checks of the NeRF core ops, in the vocabulary of the geometry ops above (the caller's name `what` first, plain calls in
+# the order the refusals come).  Below these ops the kernels index flat, so before an op asks for the stream every tensor it hands over
+# has been compared with the sizes passed beside it.  The rule is on ELEMENT COUNT (`_count`: a label as (S,) or (R, N) is the same
+# memory); a shape is tested only where a size is read from it (`_level`: z is (R, N); `_rays`: rays is (R, 8); `_hit_lists`).  A
+# buffer whose size the library computes may be longer than needed, an arena slice (`_at_least`).  One device per call (`_on`).
+def _count(what, name, t, n, why):
+    """`t` (None: absent) holds exactly the n elements the kernel will index; `why`: n in the call's own sizes"""
+    if t is not None and t.numel() != n:
+        raise ValueError("%s: %s holds %d elements, expected %d (%s)" % (what, name, t.numel(), n, why))
+
+
+def _at_least(what, name, t, n, why):
+    if t.numel() < n:
+        raise ValueError("%s: %s holds %d elements, needs at least %d (%s)" % (what, name, t.numel(), n, why))
+
+
+def _rays(what, rays, R=None):
+    """R of the GPU tensor rays (R, 8); with the R that another argument gave (see _level), rays hold R * 8 floats"""
+    _chk(rays, "rays")
+    if R is not None:
+        _count(what, "rays", rays, R * 8, "8 floats per ray")
+    elif rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("%s: rays must be (R, 8), got %s" % (what, tuple(rays.shape)))
+    return rays.shape[0] if R is None else R
+
+
+_IMAGE_BYTES = {}       # (bytes(desc), backward) -> pnr_mlp_[bwd_]packed_bytes: the library builds a plan per query, so an image's size is asked once
+
+
+def _packed(what, desc, packed, name="packed", backward=False):
+    """`packed`: GPU bytes, at least the image the library packs for `desc`.  A descriptor the library has no image for is left
+    to the entry point, which refuses it in its own words before it reads anything."""
+    _chk(packed, name, torch.uint8)
+    key = (bytes(desc), backward)
+    n = _IMAGE_BYTES.get(key)
+    if n is None:
+        lib = _lib.load()
+        n = int((lib.pnr_mlp_bwd_packed_bytes if backward else lib.pnr_mlp_packed_bytes)(ctypes.byref(desc)))
+        if n < 0:
+            return
+        _IMAGE_BYTES[key] = n
+    _at_least(what, name, packed, n, "the image of this descriptor")
+
+
+def _level(what, rays, z, desc=None, packed=None):
+    """(R, N) of a level's samples z (R, N), whose rays hold R * 8 floats and whose `packed` the image of `desc`, all on z's device"""
+    _chk(rays, "rays"), _chk(z, "z")
+    if z.dim() != 2:
+        raise ValueError("%s: z must be (R, N), got %s" % (what, tuple(z.shape)))
+    R, N = z.shape
+    _count(what, "rays", rays, R * 8, "8 floats per ray")
+    if packed is not None:
+        _packed(what, desc, packed)
+    _on(what, z.device, "z", rays=rays, packed=packed)
+    return R, N
+
+
+def _coarse(what, z, weights, u, draw, n_importance):
+    """(R, Nc, device) of sample_pdf's coarse z (R, Nc): weights hold one per sample, u (None: absent) n_importance per ray"""
+    _chk(z, "z"), _chk(weights, "weights")
+    if z.dim() != 2:
+        raise ValueError("%s: z must be (R, Nc), got %s" % (what, tuple(z.shape)))
+    R, Nc = z.shape
+    _count(what, "weights", weights, R * Nc, "one per coarse sample")
+    _count(what, "u", u, R * int(n_importance), "n_importance per ray")
+    _on(what, z.device, "z", weights=weights, u=u, call=draw.call if draw else None)
+    return R, Nc, z.device
+
+
+def _draw_or(x, name):
+    """(tensor or None, Draw or None) of an argument that is explicit values, a Draw in their place, or None"""
+    return (None, x) if _draw(x) else (_chk(x, name), None)
+
+
+def _labels(what, label_sem, label_inst, n, dev, ref_name="z"):
+    """the per-sample labels of a level (None: absent): int32, n = R * N of each, on `dev`"""
+    label_sem, label_inst = _chk(label_sem, "label_sem", torch.int32), _chk(label_inst, "label_inst", torch.int32)
+    _count(what, "label_sem", label_sem, n, "one per sample")
+    _count(what, "label_inst", label_inst, n, "one per sample")
+    _on(what, dev, ref_name, label_sem=label_sem, label_inst=label_inst)
+    return label_sem, label_inst
+
+
+def _hit_lists(what, R, hit_t, hit_box, hit_count, dev, ref_name):
+    """max_hits of the lists bbox_hits / convex_hits / ray_setup made for R rays: hit_t (R, mh, 2), hit_box (R, mh) (None where the op
+    takes none), hit_count (R,), on `dev`"""
+    _chk(hit_t, "hit_t"), _chk(hit_box, "hit_box", torch.int32), _chk(hit_count, "hit_count", torch.int32)
+    if hit_t.dim() != 3 or hit_t.shape[0] != R or hit_t.shape[2] != 2:
+        raise ValueError("%s: hit_t must be (%d, max_hits, 2), got %s" % (what, R, tuple(hit_t.shape)))
+    mh = hit_t.shape[1]
+    for name, t, shape in (("hit_count", hit_count, (R,)), ("hit_box", hit_box, (R, mh))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
+    _on(what, dev, ref_name, hit_t=hit_t, hit_box=hit_box, hit_count=hit_count)
+    return mh
+
+
+def _new_hit_lists(what, R, max_hits, dev, out=None):
+    """(hit_t, hit_box, hit_count) for R rays: fresh, or the caller-owned `out`"""
+    o = out if out is not None else (None, None, None)
+    return (_own(o[0], (R, max_hits, 2), torch.float32, dev, what), _own(o[1], (R, max_hits), torch.int32, dev, what),
+            _own(o[2], (R,), torch.int32, dev, what))
+
+
+def _boxes(what, box, dev, box_ids=None):
+    """M of box (M, 15); box_ids (None: absent) holds its M (semantic id, instance id) pairs"""
+    _chk(box, "box"), _chk(box_ids, "box_ids", torch.int32)
+    if box.dim() != 2 or box.shape[1] != 15:
+        raise ValueError("%s: box must be (M, 15), got %s" % (what, tuple(box.shape)))
+    _count(what, "box_ids", box_ids, 2 * box.shape[0], "a semantic and an instance id per box")
+    _on(what, dev, "rays", box=box, box_ids=box_ids)
+    return box.shape[0]
+
+
 @_on_device
 def stratified(rays, n_samples, lindisp=False, t_rand=None, out=None):
     """rays (R,8) -> z (R,N).  SURVEY 8a row a3.  t_rand: (R,N) uniforms, a Draw (pnr_stratified_rng) or None."""
-    rays = _chk(rays, "rays")
-    R = rays.shape[0]
-    assert rays.shape[-1] == 8
+    R = _rays("stratified", rays)
     z = _own(out, (R, n_samples), torch.float32, rays.device, "stratified")
-    draw = t_rand if _draw(t_rand) else None
-    t_rand = None if draw is not None else _chk(t_rand, "t_rand")
-    if t_rand is not None:
-        assert tuple(t_rand.shape) == (R, n_samples)
+    t_rand, draw = _draw_or(t_rand, "t_rand")
+    _count("stratified", "t_rand", t_rand, R * n_samples, "one per sample")
+    _on("stratified", rays.device, "rays", t_rand=t_rand, call=draw.call if draw else None)
     fn, rand, what = _twin("pnr_stratified", t_rand, draw)
     _lib.check(fn(_p(rays), R, n_samples, int(bool(lindisp)), rand, _p(z), _stream()), what)
     return z
@@ -1011,8 +1122,8 @@ def stratified(rays, n_samples, lindisp=False, t_rand=None, out=None):
 
 @_on_device
 def points(rays, z):
-    rays, z = _chk(rays, "rays"), _chk(z, "z")
-    R, N = z.shape
+    """rays (R,8), z (R,N) -> the sample positions o + z d, (R,N,3)."""
+    R, N = _level("points", rays, z)
     pts = torch.empty((R, N, 3), device=z.device, dtype=torch.float32)
     _lib.check(_lib.load().pnr_points(_p(rays), _p(z), R, N, _p(pts), _stream()), "pnr_points")
     return pts
@@ -1022,6 +1133,8 @@ def points(rays, z):
 def embed(x, L):
     """x (n,3) -> (n, 3+6L).  SURVEY 8a row a4."""
     x = _chk(x, "x")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError("embed: x must be (n, 3), got %s" % (tuple(x.shape),))
     n = x.shape[0]
     out = torch.empty((n, 3 + 6 * L), device=x.device, dtype=torch.float32)
     _lib.check(_lib.load().pnr_embed(_p(x), n, L, _p(out), _stream()), "pnr_embed")
@@ -1088,10 +1201,29 @@ def param_in_place(t, device):
     return t.device == torch.device(device) and t.dtype == torch.float32 and t.is_contiguous()
 
 
-def _param_struct(desc, params, device):
-    """pnr_mlp_params_host filled with pointers to `params` (dict name -> tensor) moved/kept on `device`.
+def param_shapes(desc):
+    """name -> shape of every parameter of the descriptor's network, under the canonical NeRF names (network.py): what the
+    entry points that take a pnr_mlp_params_host read, or write, behind each of its pointers."""
+    W, H, ex, ed = desc.W, desc.W // 2, 3 + 6 * desc.xyz_L, 3 + 6 * desc.dir_L
+    lin = {"pts_linears.%d" % i: (W, ex if i == 0 else W + ex if i - 1 == desc.skip else W) for i in range(desc.D)}
+    lin.update({"alpha_linear": (1, W), "feature_linear": (W, W), "views_linears.0": (H, W + ed), "rgb_linear": (3, H)})
+    for head, n in (("semantic_linears", desc.n_sem), ("instance_linears", desc.n_inst)):
+        if n:
+            lin.update({head + ".0": (H, W), head + ".1": (n, H)} if desc.head_depth == 2 else {head + ".0": (n, W)})
+    shapes = {}
+    for k, (o, i) in lin.items():
+        shapes[k + ".weight"], shapes[k + ".bias"] = (o, i), (o,)
+    return shapes
+
+
+def _param_struct(desc, params, device, what="_param_struct"):
+    """pnr_mlp_params_host filled with pointers to `params` (dict name -> tensor) moved/kept on `device`.  Every parameter of
+    param_shapes(desc) that is present has that shape; an absent one is a null pointer, other names are ignored.
     Returns (struct, keep-alive list): a parameter that is not param_in_place is pointed to through a temporary copy, and that
     pointer is valid only while the keep-alive list is."""
+    for name, shape in param_shapes(desc).items():
+        if name in params and tuple(params[name].shape) != shape:
+            raise ValueError("%s: parameter %s is %s, the descriptor's network has %s" % (what, name, tuple(params[name].shape), shape))
     keep = []
 
     def fp(name):
@@ -1154,37 +1286,35 @@ def pack_mlp_device(desc, params, backward=False, out=None, workspace=None, repa
         out = torch.zeros(int(nbytes), dtype=torch.uint8, device=dev)     # zeros: the table->data alignment gap
     if workspace is None or workspace.numel() < wbytes:
         workspace = torch.empty(int(wbytes), dtype=torch.uint8, device=dev)
-    P, keep = _param_struct(desc, params, dev)
+    _chk(out, "out", torch.uint8), _chk(workspace, "workspace", torch.uint8)
+    _on("pack_mlp_device", dev, "the parameters", out=out, workspace=workspace)
+    P, keep = _param_struct(desc, params, dev, "pack_mlp_device")
     fn = lib.pnr_mlp_repack_device if repack else lib.pnr_mlp_pack_device
     _lib.check(fn(ctypes.byref(desc), ctypes.byref(P), int(backward), _p(workspace), _p(out), _stream()), "pnr_mlp_pack_device")
     return out, workspace
 
 
+def _pack_host(what, desc, params, size, pack):
+    """The body of pack_mlp / pack_mlp_bwd: the entry points `size` and `pack`, by name."""
+    lib = _lib.load()
+    nbytes = getattr(lib, size)(ctypes.byref(desc))
+    if nbytes < 0:
+        _lib.check(int(nbytes), size)
+    P, keep = _param_struct(desc, params, "cpu", what)
+    img = torch.empty(int(nbytes), dtype=torch.uint8)
+    _lib.check(getattr(lib, pack)(ctypes.byref(desc), ctypes.byref(P), ctypes.c_void_p(img.data_ptr())), pack)
+    return img
+
+
 def pack_mlp(desc, params):
     """params: dict name -> float32 tensor (canonical NeRF names, see network.py).
     Returns the packed image as a CPU uint8 tensor (pure host work, no GPU needed)."""
-    lib = _lib.load()
-    nbytes = lib.pnr_mlp_packed_bytes(ctypes.byref(desc))
-    if nbytes < 0:
-        _lib.check(int(nbytes), "pnr_mlp_packed_bytes")
-    P, keep = _param_struct(desc, params, "cpu")
-    img = torch.empty(int(nbytes), dtype=torch.uint8)
-    _lib.check(lib.pnr_mlp_pack(ctypes.byref(desc), ctypes.byref(P), ctypes.c_void_p(img.data_ptr())),
-               "pnr_mlp_pack")
-    return img
+    return _pack_host("pack_mlp", desc, params, "pnr_mlp_packed_bytes", "pnr_mlp_pack")
 
 
 def pack_mlp_bwd(desc, params):
     """Transposed-weight image for pnr_mlp_backward (CPU uint8 tensor).  bf16, n_sem/n_inst <= 64."""
-    lib = _lib.load()
-    nbytes = lib.pnr_mlp_bwd_packed_bytes(ctypes.byref(desc))
-    if nbytes < 0:
-        _lib.check(int(nbytes), "pnr_mlp_bwd_packed_bytes")
-    P, keep = _param_struct(desc, params, "cpu")
-    img = torch.empty(int(nbytes), dtype=torch.uint8)
-    _lib.check(lib.pnr_mlp_pack_bwd(ctypes.byref(desc), ctypes.byref(P), ctypes.c_void_p(img.data_ptr())),
-               "pnr_mlp_pack_bwd")
-    return img
+    return _pack_host("pack_mlp_bwd", desc, params, "pnr_mlp_bwd_packed_bytes", "pnr_mlp_pack_bwd")
 
 
 def train_layout(desc, n_samples):
@@ -1198,9 +1328,7 @@ def train_layout(desc, n_samples):
 @_on_device
 def mlp_forward_train(desc, packed, rays, z):
     """Forward that also saves activations for the backward.  Returns (raw (ch,S) channel-major, acts bf16)."""
-    rays, z = _chk(rays, "rays"), _chk(z, "z")
-    packed = _chk(packed, "packed", torch.uint8)
-    R, N = z.shape
+    R, N = _level("mlp_forward_train", rays, z, desc, packed)
     S = R * N
     acts_off, _ = train_layout(desc, S)
     raw = torch.empty((n_channels(desc), S), device=z.device, dtype=torch.float32)
@@ -1213,10 +1341,13 @@ def mlp_forward_train(desc, packed, rays, z):
 @_on_device
 def mlp_backward(desc, packed_bwd, d_raw, acts, n_rays, n_samples):
     """Data-gradient pass: d_raw (ch,S) + saved activations -> dys (bf16, every layer's pre-activation gradient)."""
-    d_raw = _chk(d_raw, "d_raw")
-    packed_bwd = _chk(packed_bwd, "packed_bwd", torch.uint8)
-    acts = _chk(acts, "acts", torch.bfloat16)
-    _, dys_off = train_layout(desc, n_rays * n_samples)
+    d_raw, acts = _chk(d_raw, "d_raw"), _chk(acts, "acts", torch.bfloat16)
+    S = int(n_rays) * int(n_samples)
+    acts_off, dys_off = train_layout(desc, S)
+    _count("mlp_backward", "d_raw", d_raw, n_channels(desc) * S, "(ch, n_rays * n_samples)")
+    _packed("mlp_backward", desc, packed_bwd, "packed_bwd", backward=True)
+    _at_least("mlp_backward", "acts", acts, acts_off[-1], "train_layout")
+    _on("mlp_backward", d_raw.device, "d_raw", packed_bwd=packed_bwd, acts=acts)
     dys = torch.empty((dys_off[-1],), device=d_raw.device, dtype=torch.bfloat16)
     _lib.check(_lib.load().pnr_mlp_backward(ctypes.byref(desc), _p(packed_bwd), _p(d_raw), _p(acts), _p(dys), n_rays,
                                             n_samples, _stream()), "pnr_mlp_backward")
@@ -1227,16 +1358,25 @@ def mlp_backward(desc, packed_bwd, d_raw, acts, n_rays, n_samples):
 def mlp_wgrad(desc, acts, dys, n_samples, shapes):
     """Weight gradients of every Linear from the training forward's `acts` and the data-gradient pass's `dys`
     (pnr_mlp_wgrad: hand-written MFMA kernel + deterministic slab reduction).  shapes: dict name -> shape of the
-    parameters (state_dict names).  Returns dict name -> fp32 gradient tensor.  SURVEY 8a row a9."""
+    parameters (state_dict names): its keys say which gradients to return, its shapes must be param_shapes(desc)'s.
+    Returns dict name -> fp32 gradient tensor.  SURVEY 8a row a9."""
     acts, dys = _chk(acts, "acts", torch.bfloat16), _chk(dys, "dys", torch.bfloat16)
     lib = _lib.load()
     dev = acts.device
+    acts_off, dys_off = train_layout(desc, n_samples)
+    _at_least("mlp_wgrad", "acts", acts, acts_off[-1], "train_layout")
+    _at_least("mlp_wgrad", "dys", dys, dys_off[-1], "train_layout")
+    _on("mlp_wgrad", dev, "acts", dys=dys)
+    table = param_shapes(desc)
+    for k, shp in shapes.items():
+        if k in table and tuple(shp) != table[k]:
+            raise ValueError("mlp_wgrad: shapes[%r] is %s, the descriptor's network has %s" % (k, tuple(shp), table[k]))
     nbytes = _size_or_raise(lib.pnr_mlp_wgrad_workspace_bytes(ctypes.byref(desc), int(n_samples)), "pnr_mlp_wgrad_workspace_bytes")
     # per call, from torch's caching allocator: stream-ordered and graph-pool aware, so a captured step keeps its own
     # block alive and concurrent streams never share scratch (a process-global buffer did neither)
     ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
     grads = {k: torch.empty(tuple(shp), device=dev, dtype=torch.float32) for k, shp in shapes.items()}
-    G, keep = _param_struct(desc, grads, dev)
+    G, keep = _param_struct(desc, grads, dev, "mlp_wgrad")
     _lib.check(lib.pnr_mlp_wgrad(ctypes.byref(desc), _p(acts), _p(dys), int(n_samples), ctypes.byref(G), _p(ws), _stream()),
                "pnr_mlp_wgrad")
     return grads
@@ -1246,14 +1386,13 @@ def mlp_wgrad(desc, acts, dys, n_samples, shapes):
 def mlp_forward_train_fp32(desc, params, rays, z):
     """fp32 parity mode of the training forward (pnr_mlp_forward_train_fp32): params = dict name -> fp32 GPU parameter
     tensor (read in place, nothing is packed).  Returns (raw (ch,S) channel-major, acts fp32)."""
-    rays, z = _chk(rays, "rays"), _chk(z, "z")
-    R, N = z.shape
+    R, N = _level("mlp_forward_train_fp32", rays, z)
     S = R * N
     lib = _lib.load()
     n = _size_or_raise(lib.pnr_mlp_fp32_acts_floats(ctypes.byref(desc), S), "pnr_mlp_fp32_acts_floats")
     raw = torch.empty((n_channels(desc), S), device=z.device, dtype=torch.float32)
     acts = torch.empty((int(n),), device=z.device, dtype=torch.float32)
-    P, keep = _param_struct(desc, params, z.device)
+    P, keep = _param_struct(desc, params, z.device, "mlp_forward_train_fp32")
     _lib.check(lib.pnr_mlp_forward_train_fp32(ctypes.byref(desc), ctypes.byref(P), _p(rays), _p(z), R, N, _p(raw), 1, S, _p(acts),
                                               _stream()), "pnr_mlp_forward_train_fp32")
     return raw, acts
@@ -1269,11 +1408,14 @@ def mlp_backward_fp32(desc, params, d_raw, acts, n_rays, n_samples):
         raise ValueError(f"d_raw: expected {(n_channels(desc), S)}, got {tuple(d_raw.shape)}")
     lib = _lib.load()
     dev = acts.device
+    n = _size_or_raise(lib.pnr_mlp_fp32_acts_floats(ctypes.byref(desc), S), "pnr_mlp_fp32_acts_floats")
+    _at_least("mlp_backward_fp32", "acts", acts, n, "pnr_mlp_fp32_acts_floats")
+    _on("mlp_backward_fp32", dev, "acts", d_raw=d_raw)
     nbytes = _size_or_raise(lib.pnr_mlp_backward_fp32_workspace_bytes(ctypes.byref(desc), S), "pnr_mlp_backward_fp32_workspace_bytes")
     ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
     grads = {k: torch.empty_like(v, dtype=torch.float32, memory_format=torch.contiguous_format) for k, v in params.items()}
-    P, keep = _param_struct(desc, params, dev)
-    G, keep2 = _param_struct(desc, grads, dev)
+    P, keep = _param_struct(desc, params, dev, "mlp_backward_fp32")
+    G, keep2 = _param_struct(desc, grads, dev, "mlp_backward_fp32")
     _lib.check(lib.pnr_mlp_backward_fp32(ctypes.byref(desc), ctypes.byref(P), _p(d_raw), d_raw.stride(0), _p(acts), int(n_rays),
                                          int(n_samples), ctypes.byref(G), _p(ws), _stream()), "pnr_mlp_backward_fp32")
     return grads
@@ -1307,9 +1449,7 @@ def _chk_raw(raw, ch, S):
 def mlp_forward(desc, packed, rays, z, channel_major=True, out=None):
     """Fused gamma() + NeRF MLP + heads on every sample.  SURVEY 8a rows a4+a5.
     Returns raw as (ch, R*N) when channel_major (fast layout; channel stride padded, see alloc_raw) else (R, N, ch)."""
-    rays, z = _chk(rays, "rays"), _chk(z, "z")
-    packed = _chk(packed, "packed", torch.uint8)
-    R, N = z.shape
+    R, N = _level("mlp_forward", rays, z, desc, packed)
     ch = n_channels(desc)
     S = R * N
     if channel_major:
@@ -1318,7 +1458,8 @@ def mlp_forward(desc, packed, rays, z, channel_major=True, out=None):
     else:
         raw = out if out is not None else torch.empty((R, N, ch), device=z.device, dtype=torch.float32)
         ss, sc = ch, 1
-        _chk(raw, "raw")
+        _count("mlp_forward", "out", _chk(raw, "raw"), S * ch, "(R, N, ch)")
+    _on("mlp_forward", z.device, "z", out=raw)
     _lib.check(_lib.load().pnr_mlp_forward(ctypes.byref(desc), _p(packed), _p(rays), _p(z), R, N, _p(raw), ss, sc,
                                            _stream()), "pnr_mlp_forward")
     return raw
@@ -1329,20 +1470,18 @@ def composite(raw, z, rays, n_sem=0, n_inst=0, channel_major=True, noise=None, l
               sem_mode=0, white_bkgd=False, want_weights=True, out=None):
     """raw2outputs.  SURVEY 8a row a6.  Returns dict of maps (out: optional caller-owned tensors, see _maps).  noise: (R,N) sigma
     noise, a Draw (pnr_composite_rng: noise = draw.scale * the stream's normals, channel-major raw only) or None."""
-    z, rays = _chk(z, "z"), _chk(rays, "rays")
-    draw = noise if _draw(noise) else None
-    noise = None if draw is not None else _chk(noise, "noise")
-    label_sem = _chk(label_sem, "label_sem", torch.int32)
-    label_inst = _chk(label_inst, "label_inst", torch.int32)
-    R, N = z.shape
+    noise, draw = _draw_or(noise, "noise")
+    R, N = _level("composite", rays, z)
     ch = 4 + n_sem + n_inst
     if channel_major:
         ss, sc = 1, _chk_raw(raw, ch, R * N)
     else:
-        _chk(raw, "raw")
-        assert tuple(raw.shape) == (R, N, ch)
+        _count("composite", "raw", _chk(raw, "raw"), R * N * ch, "(R, N, ch)")
         ss, sc = ch, 1
     dev = z.device
+    _count("composite", "noise", noise, R * N, "one per sample")
+    label_sem, label_inst = _labels("composite", label_sem, label_inst, R * N, dev)
+    _on("composite", dev, "z", raw=raw, noise=noise, call=draw.call if draw else None)
     out = _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev)
     g = out.get
     fn, nz, what = _twin("pnr_composite", noise, draw)
@@ -1416,24 +1555,28 @@ def mlp_forward_composite(desc, packed, rays, z, label_sem=None, label_inst=None
     rounding (not bit for bit).  sem_mode as in composite(): 1 composites softmax(logits) of each learned field
     (PNR_MLP_SOFTMAX; an image of a plan with a softmax kernel, see fused_supported / fused_image).  wg_cap: plan 2 only, the MLP launch
     on at most that many workgroups (PNR_MLP_WG_CAP) -- a share of the device, for a launch that runs beside another one."""
-    rays, z, packed = _chk(rays, "rays"), _chk(z, "z"), _chk(packed, "packed", torch.uint8)
-    label_sem = _chk(label_sem, "label_sem", torch.int32)
-    label_inst = _chk(label_inst, "label_inst", torch.int32)
-    R, N = z.shape
-    n_sem, n_inst = desc.n_sem, desc.n_inst
-    dev = z.device
-    lib = _lib.load()
+    image = desc
     desc = desc_for_mode(desc, sem_mode)
     if wg_cap:          # PNR_MLP_WG_CAP: the plan-2 launch on a share of the compute units (Renderer's overlapped levels)
         desc = _desc_with(desc, flags=(desc.flags & 0xFFFF) | ((int(wg_cap) & 0x1FF) << 16))
+    return _fused_level("mlp_forward_composite", desc, image, packed, rays, z, label_sem, label_inst, white_bkgd, want_weights, out)
+
+
+def _fused_level(what, desc, image, packed, rays, z, label_sem, label_inst, white_bkgd, want_weights, out, drop=()):
+    """The body of mlp_forward_composite / mlp_forward_weights: pnr_mlp_forward_composite with the maps of `drop` not asked for.
+    image: the descriptor `packed` was made for (desc: that one with the call's flags)."""
+    R, N = _level(what, rays, z, image, packed)
+    dev = z.device
+    label_sem, label_inst = _labels(what, label_sem, label_inst, R * N, dev)
+    lib = _lib.load()
     nbytes = lib.pnr_mlp_forward_composite_workspace_bytes(ctypes.byref(desc), R, N, int(bool(want_weights)))
     if nbytes < 0:
         raise RuntimeError("pnr_mlp_forward_composite: unsupported geometry (n_samples=%d must be a multiple of 32)" % N)
     ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
-    out = _maps(out, R, N, n_sem, n_inst, label_sem, label_inst, want_weights, dev)
+    out = _maps(out, R, N, desc.n_sem, desc.n_inst, label_sem, label_inst, want_weights, dev, drop=drop)
     g = out.get
     _lib.check(lib.pnr_mlp_forward_composite(ctypes.byref(desc), _p(packed), _p(rays), _p(z), R, N, _p(label_sem), _p(label_inst),
-                                             int(bool(white_bkgd)), _p(out["rgb"]), _p(out["depth"]), _p(out["acc"]),
+                                             int(bool(white_bkgd)), _p(g("rgb")), _p(out["depth"]), _p(out["acc"]),
                                              _p(g("weights")), _p(g("semantic")), _p(g("instance")), _p(g("fix_semantic")),
                                              _p(g("fix_instance")), _p(ws), _stream()), "pnr_mlp_forward_composite")
     return out
@@ -1459,22 +1602,7 @@ def mlp_forward_weights(desc, packed, rays, z, label_sem=None, label_inst=None, 
     for these keys on any other plan of the same network."""
     if desc.plan != 3:
         raise ValueError("mlp_forward_weights: needs the plan-3 image (net.packed(level, device, fused='sigma')), not plan %d" % desc.plan)
-    rays, z, packed = _chk(rays, "rays"), _chk(z, "z"), _chk(packed, "packed", torch.uint8)
-    label_sem = _chk(label_sem, "label_sem", torch.int32)
-    label_inst = _chk(label_inst, "label_inst", torch.int32)
-    R, N = z.shape
-    dev = z.device
-    lib = _lib.load()
-    nbytes = lib.pnr_mlp_forward_composite_workspace_bytes(ctypes.byref(desc), R, N, 1)
-    if nbytes < 0:
-        raise RuntimeError("pnr_mlp_forward_composite: unsupported geometry (n_samples=%d must be a multiple of 32)" % N)
-    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
-    out = _maps(out, R, N, desc.n_sem, desc.n_inst, label_sem, label_inst, True, dev, drop=WEIGHTS_ONLY_DROPS)
-    g = out.get
-    _lib.check(lib.pnr_mlp_forward_composite(ctypes.byref(desc), _p(packed), _p(rays), _p(z), R, N, _p(label_sem), _p(label_inst),
-                                             0, None, _p(out["depth"]), _p(out["acc"]), _p(out["weights"]), None, None,
-                                             _p(g("fix_semantic")), _p(g("fix_instance")), _p(ws), _stream()), "pnr_mlp_forward_composite")
-    return out
+    return _fused_level("mlp_forward_weights", desc, desc, packed, rays, z, label_sem, label_inst, False, True, out, WEIGHTS_ONLY_DROPS)
 
 
 QUERY_WANTS = ("sigma", "labels", "panoptic", "logits")
@@ -1517,13 +1645,15 @@ def mlp_query(desc, packed, points, want=("sigma", "labels"), is_thing=None, out
     if desc.plan != 4:
         raise ValueError("mlp_query: needs the plan-4 image (net.packed(level, device, fused='field')), not plan %d" % desc.plan)
     keys = query_keys(desc, want)
-    points, packed = _chk(points, "points"), _chk(packed, "packed", torch.uint8)
+    points = _chk(points, "points")
     is_thing = _chk(is_thing, "is_thing", torch.int32)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("mlp_query: points must be (P, 3), got %s" % (tuple(points.shape),))
     if is_thing is not None and (not desc.n_sem or is_thing.numel() != desc.n_sem):
         raise ValueError("mlp_query: is_thing must hold n_sem=%d entries of a network with a semantic head" % desc.n_sem)
     P, dev = points.shape[0], points.device
+    _packed("mlp_query", desc, packed)
+    _on("mlp_query", dev, "points", packed=packed, is_thing=is_thing)
     out = dict(out) if out else {}
     res, stride = {}, P
     for k in keys:
@@ -1539,6 +1669,7 @@ def mlp_query(desc, packed, points, want=("sigma", "labels"), is_thing=None, out
         else:
             res[k] = _own(out.get(k), (P,), torch.float32 if k == "sigma" else torch.int32, dev, "mlp_query: out[%r]" % k)
     lg = [res[k] for k in ("sem_logits", "inst_logits") if k in res]
+    _on("mlp_query", dev, "points", **{"out[%r]" % k: res[k] for k in ("sem_logits", "inst_logits") if k in res})
     if lg:
         stride = lg[0].stride(0) if lg[0].shape[0] > 1 else max(P, lg[0].stride(0))
         if any((t.stride(0) if t.shape[0] > 1 else stride) != stride for t in lg):
@@ -1558,15 +1689,22 @@ def composite_backward(raw, z, rays, n_sem, n_inst, grads, noise=None, label_sem
     gradients need the per-sample labels.  ce_sem / ce_inst: 1-element device tensors, the scale of the per-sample
     3D cross-entropy gradient (see ce3d).  sem_mode as in composite().  noise: the forward's tensor, or its Draw (the noise is then
     regenerated in the kernel: pnr_composite_backward_rng).  Returns d_raw (ch, R*N).  SURVEY 8a row a9, 8f-1."""
-    raw, z, rays = _chk(raw, "raw"), _chk(z, "z"), _chk(rays, "rays")
-    draw = noise if _draw(noise) else None
-    noise = None if draw is not None else _chk(noise, "noise")
-    label_sem = _chk(label_sem, "label_sem", torch.int32)
-    label_inst = _chk(label_inst, "label_inst", torch.int32)
-    R, N = z.shape
+    raw = _chk(raw, "raw")
+    noise, draw = _draw_or(noise, "noise")
+    R, N = _level("composite_backward", rays, z)
+    dev, ch = z.device, 4 + n_sem + n_inst
+    _count("composite_backward", "raw", raw, ch * R * N, "(ch, R * N)")
+    _count("composite_backward", "noise", noise, R * N, "one per sample")
+    label_sem, label_inst = _labels("composite_backward", label_sem, label_inst, R * N, dev)
     g = {k: _chk(v.contiguous().float(), "g_" + k) for k, v in grads.items() if v is not None}
+    per_ray = {"rgb": 3, "depth": 1, "acc": 1, "weights": N, "semantic": n_sem, "fix_semantic": n_sem, "instance": n_inst, "fix_instance": n_inst}
+    for k, n in per_ray.items():        # a map of a head the network does not have (n = 0) is not read
+        if n:
+            _count("composite_backward", "g_" + k, g.get(k), R * n, "a gradient of R rows")
     ce_sem = None if ce_sem is None else _chk(ce_sem.reshape(1).float().contiguous(), "ce_sem")
     ce_inst = None if ce_inst is None else _chk(ce_inst.reshape(1).float().contiguous(), "ce_inst")
+    _on("composite_backward", dev, "z", raw=raw, noise=noise, call=draw.call if draw else None, ce_sem=ce_sem, ce_inst=ce_inst,
+        **{"g_" + k: v for k, v in g.items() if k in per_ray})
     d_raw = torch.empty_like(raw)
     fn, nz, what = _twin("pnr_composite_backward3", noise, draw, rng_name="pnr_composite_backward_rng", what="pnr_composite_backward")
     _lib.check(fn(_p(raw), R * N, _p(z), _p(rays), nz, R, N, n_sem, n_inst, int(sem_mode), _p(g.get("rgb")), _p(g.get("depth")),
@@ -1597,6 +1735,12 @@ def losses(weights, maps, targets, n_sem=0, n_inst=0, depth_l2=False, fix_eps=1e
     use = {"rgb": t_rgb is not None, "depth": t_depth is not None, "semantic": t_sem is not None, "fix_semantic": t_sem is not None,
            "instance": t_inst is not None, "fix_instance": t_inst is not None}
     m = {k: v for k, v in m.items() if use[k]}
+    per_ray = {"rgb": 3, "depth": 1, "semantic": int(n_sem), "fix_semantic": int(n_sem), "instance": int(n_inst), "fix_instance": int(n_inst)}
+    named = {k: (v, per_ray[k]) for k, v in m.items()}
+    named.update(rgb_gt=(t_rgb, 3), depth_gt=(t_depth, 1), sem_gt=(t_sem, 1), inst_gt=(t_inst, 1))
+    for name, (t, n) in named.items():
+        _count("losses", name, t, R * n, "R rows")
+    _on("losses", dev, "the first map", **{name: t for name, (t, n) in named.items()})
     grads = {k: torch.empty_like(v) for k, v in m.items()} if want_grads else {}
     out = torch.empty(8, device=dev, dtype=torch.float32)
     ws = torch.empty(int(lib.pnr_losses_workspace_bytes(R)), device=dev, dtype=torch.uint8)
@@ -1617,6 +1761,9 @@ def ce3d(raw, first_channel, n_classes, label):
     label = _chk(label, "label", torch.int32)
     S = label.numel()
     sc = _chk_raw(raw, raw.shape[0], S)
+    if not 0 <= int(first_channel) <= int(first_channel) + int(n_classes) <= raw.shape[0]:
+        raise ValueError("ce3d: channels %d .. %d are not all among raw's %d" % (first_channel, first_channel + n_classes - 1, raw.shape[0]))
+    _on("ce3d", raw.device, "raw", label=label)
     out = torch.empty(2, device=raw.device, dtype=torch.float32)
     ws = torch.empty(int(lib.pnr_ce3d_workspace_bytes(S)), device=raw.device, dtype=torch.uint8)
     _lib.check(lib.pnr_ce3d(_p(raw), sc, int(first_channel), int(n_classes), _p(label), S, _p(out), _p(ws), _stream()), "pnr_ce3d")
@@ -1627,11 +1774,8 @@ def ce3d(raw, first_channel, n_classes, label):
 def sample_pdf(z, weights, n_importance, u=None, want_samples=True, out=None):
     """Coarse z, weights (R,Nc) -> z_fine (R,Nc+Nf) sorted [, z_samples (R,Nf), inds (R,Nf)].
     SURVEY 8a row a7.  u: (R,Nf) uniforms, a Draw (pnr_sample_pdf_rng) or None (deterministic u)."""
-    z, weights = _chk(z, "z"), _chk(weights, "weights")
-    draw = u if _draw(u) else None
-    u = None if draw is not None else _chk(u, "u")
-    R, Nc = z.shape
-    dev = z.device
+    u, draw = _draw_or(u, "u")
+    R, Nc, dev = _coarse("sample_pdf", z, weights, u, draw, n_importance)
     z_fine = _own(out, (R, Nc + n_importance), torch.float32, dev, "sample_pdf")
     zs = inds = None
     if want_samples:
@@ -1645,12 +1789,9 @@ def sample_pdf(z, weights, n_importance, u=None, want_samples=True, out=None):
 @_on_device
 def bbox_hits(rays, box, max_hits=8):
     """rays (R,8), box (M,15) -> hit_t (R,mh,2), hit_box (R,mh) int32, hit_count (R) int32.  Row a8."""
-    rays, box = _chk(rays, "rays"), _chk(box, "box")
-    R, M = rays.shape[0], box.shape[0]
+    R, M = _rays("bbox_hits", rays), _boxes("bbox_hits", box, rays.device)
     dev = rays.device
-    hit_t = torch.empty((R, max_hits, 2), device=dev, dtype=torch.float32)
-    hit_box = torch.empty((R, max_hits), device=dev, dtype=torch.int32)
-    hit_count = torch.empty((R,), device=dev, dtype=torch.int32)
+    hit_t, hit_box, hit_count = _new_hit_lists("bbox_hits", R, max_hits, dev)
     _lib.check(_lib.load().pnr_bbox_hits(_p(rays), R, _p(box), M, max_hits, _p(hit_t), _p(hit_box), _p(hit_count),
                                          _stream()), "pnr_bbox_hits")
     return hit_t, hit_box, hit_count
@@ -1676,10 +1817,7 @@ def convex_hits(rays, planes, offsets, max_hits=8, out=None):
     dev = rays.device
     if planes.shape[0] == 0 and M > 0:          # primitives without planes (each the whole ray): an empty tensor has no address
         planes = planes.new_zeros((1, 4))
-    o = out if out is not None else (None, None, None)
-    hit_t = _own(o[0], (R, max_hits, 2), torch.float32, dev, "convex_hits")
-    hit_box = _own(o[1], (R, max_hits), torch.int32, dev, "convex_hits")
-    hit_count = _own(o[2], (R,), torch.int32, dev, "convex_hits")
+    hit_t, hit_box, hit_count = _new_hit_lists("convex_hits", R, max_hits, dev, out)
     _lib.check(_lib.load().pnr_convex_hits(_p(rays), R, _p(planes), _p(offsets), M, max_hits, _p(hit_t), _p(hit_box), _p(hit_count),
                                            _stream()), "pnr_convex_hits")
     return hit_t, hit_box, hit_count
@@ -1694,17 +1832,12 @@ def ray_setup(rays, box, box_ids=None, n_samples=64, max_hits=8, lindisp=False, 
     stratified -- over the hull of the kept intervals with hull=True, as restrict_rays + stratified --, and (label_sem,
     label_inst) as sample_labels when box_ids is given (else None, None).  Bit for bit the separate ops; max_hits <= 8.  t_rand: (R,N)
     uniforms, a Draw (pnr_ray_setup_rng) or None."""
-    rays, box = _chk(rays, "rays"), _chk(box, "box")
-    draw = t_rand if _draw(t_rand) else None
-    t_rand = None if draw is not None else _chk(t_rand, "t_rand")
-    box_ids = _chk(box_ids, "box_ids", torch.int32)
-    R, M, N = rays.shape[0], box.shape[0], int(n_samples)
-    dev = rays.device
-    if t_rand is not None:
-        assert tuple(t_rand.shape) == (R, N)
-    hit_t = torch.empty((R, max_hits, 2), device=dev, dtype=torch.float32)
-    hit_box = torch.empty((R, max_hits), device=dev, dtype=torch.int32)
-    hit_count = torch.empty((R,), device=dev, dtype=torch.int32)
+    t_rand, draw = _draw_or(t_rand, "t_rand")
+    R, M = _rays("ray_setup", rays), _boxes("ray_setup", box, rays.device, box_ids)
+    dev, N = rays.device, int(n_samples)
+    _count("ray_setup", "t_rand", t_rand, R * N, "one per sample")
+    _on("ray_setup", dev, "rays", t_rand=t_rand, call=draw.call if draw else None)
+    hit_t, hit_box, hit_count = _new_hit_lists("ray_setup", R, max_hits, dev)
     z = _own(out, (R, N), torch.float32, dev, "ray_setup")
     ls = li = None
     if box_ids is not None:
@@ -1720,19 +1853,18 @@ def ray_setup(rays, box, box_ids=None, n_samples=64, max_hits=8, lindisp=False, 
 def sample_pdf_labels(z, weights, n_importance, hits, box_ids, u=None, out=None):
     """sample_pdf + sample_labels of its result in ONE launch (pnr_sample_pdf_labels): (z_fine (R,Nc+Nf), label_sem, label_inst).
     hits = (hit_t, hit_box, hit_count) of bbox_hits / ray_setup.  Bit for bit the separate ops.  u: as in sample_pdf."""
-    z, weights = _chk(z, "z"), _chk(weights, "weights")
-    draw = u if _draw(u) else None
-    u = None if draw is not None else _chk(u, "u")
-    hit_t, hit_box, hit_count = _chk(hits[0], "hit_t"), _chk(hits[1], "hit_box", torch.int32), _chk(hits[2], "hit_count", torch.int32)
+    u, draw = _draw_or(u, "u")
+    R, Nc, dev = _coarse("sample_pdf_labels", z, weights, u, draw, n_importance)
+    hit_t, hit_box, hit_count = hits
+    mh = _hit_lists("sample_pdf_labels", R, hit_t, hit_box, hit_count, dev, "z")
     box_ids = _chk(box_ids, "box_ids", torch.int32)
-    R, Nc = z.shape
-    dev = z.device
+    _on("sample_pdf_labels", dev, "z", box_ids=box_ids)
     Nt = Nc + int(n_importance)
     z_fine = _own(out, (R, Nt), torch.float32, dev, "sample_pdf_labels")
     ls = torch.empty((R, Nt), device=dev, dtype=torch.int32)
     li = torch.empty((R, Nt), device=dev, dtype=torch.int32)
     fn, uu, what = _twin("pnr_sample_pdf_labels", u, draw)
-    _lib.check(fn(_p(z), _p(weights), uu, R, Nc, int(n_importance), _p(z_fine), _p(hit_t), _p(hit_box), _p(hit_count), hit_box.shape[1],
+    _lib.check(fn(_p(z), _p(weights), uu, R, Nc, int(n_importance), _p(z_fine), _p(hit_t), _p(hit_box), _p(hit_count), mh,
                   _p(box_ids), _p(ls), _p(li), _stream()), what)
     return z_fine, ls, li
 
@@ -1740,22 +1872,27 @@ def sample_pdf_labels(z, weights, n_importance, hits, box_ids, u=None, out=None)
 @_on_device
 def restrict_rays(rays, hit_t, hit_count):
     """rays with near / far replaced by the hull of each ray's kept bbox intervals (pnr_restrict_rays); no hit: unchanged."""
-    rays = _chk(rays, "rays")
+    R = _rays("restrict_rays", rays)
+    mh = _hit_lists("restrict_rays", R, hit_t, None, hit_count, rays.device, "rays")
     out = torch.empty_like(rays)
-    _lib.check(_lib.load().pnr_restrict_rays(_p(rays), rays.shape[0], _p(_chk(hit_t, "hit_t")), _p(_chk(hit_count, "hit_count", torch.int32)),
-                                             hit_t.shape[1], _p(out), _stream()), "pnr_restrict_rays")
+    _lib.check(_lib.load().pnr_restrict_rays(_p(rays), R, _p(hit_t), _p(hit_count), mh, _p(out), _stream()), "pnr_restrict_rays")
     return out
 
 
 @_on_device
 def sample_labels(z, hit_t, hit_box, hit_count, box_ids):
-    z, hit_t = _chk(z, "z"), _chk(hit_t, "hit_t")
-    hit_box, hit_count = _chk(hit_box, "hit_box", torch.int32), _chk(hit_count, "hit_count", torch.int32)
-    box_ids = _chk(box_ids, "box_ids", torch.int32)
+    """z (R,N) + the hit lists of its rays + box_ids (M,2) -> (label_sem, label_inst), each (R,N) int32: the ids of the first kept
+    box whose interval holds the sample, -1 outside every box (pnr_sample_labels).  box_ids is indexed by hit_box's values."""
+    z = _chk(z, "z")
+    if z.dim() != 2:
+        raise ValueError("sample_labels: z must be (R, N), got %s" % (tuple(z.shape),))
     R, N = z.shape
+    mh = _hit_lists("sample_labels", R, hit_t, hit_box, hit_count, z.device, "z")
+    box_ids = _chk(box_ids, "box_ids", torch.int32)
+    _on("sample_labels", z.device, "z", box_ids=box_ids)
     ls = torch.empty((R, N), device=z.device, dtype=torch.int32)
     li = torch.empty((R, N), device=z.device, dtype=torch.int32)
-    _lib.check(_lib.load().pnr_sample_labels(_p(z), R, N, _p(hit_t), _p(hit_box), _p(hit_count), hit_box.shape[1],
+    _lib.check(_lib.load().pnr_sample_labels(_p(z), R, N, _p(hit_t), _p(hit_box), _p(hit_count), mh,
                                              _p(box_ids), _p(ls), _p(li), _stream()), "pnr_sample_labels")
     return ls, li
 
@@ -1765,8 +1902,13 @@ def panoptic_labels(sem, inst=None, is_thing=None):
     """Composited maps -> (semantic label, instance label, panoptic id), each (R) int32 (pnr_panoptic_labels)."""
     sem, inst = _chk(sem, "sem"), _chk(inst, "inst")
     is_thing = _chk(is_thing, "is_thing", torch.int32)
+    if sem.dim() != 2 or (inst is not None and (inst.dim() != 2 or inst.shape[0] != sem.shape[0])):
+        raise ValueError("panoptic_labels: sem must be (R, n_sem) and inst (R, n_inst), got %s and %s"
+                         % (tuple(sem.shape), None if inst is None else tuple(inst.shape)))
     R, C = sem.shape
     K = inst.shape[1] if inst is not None else 0
+    _count("panoptic_labels", "is_thing", is_thing, C, "one per class of sem")
+    _on("panoptic_labels", sem.device, "sem", inst=inst, is_thing=is_thing)
     out = [torch.empty(R, device=sem.device, dtype=torch.int32) for _ in range(3)]
     _lib.check(_lib.load().pnr_panoptic_labels(_p(sem), _p(inst), _p(is_thing), R, C, K, _p(out[0]), _p(out[1]), _p(out[2]),
                                                _stream()), "pnr_panoptic_labels")
@@ -1780,5 +1922,8 @@ def confusion(pred, gt, n_classes, conf=None):
     if conf is None:
         conf = torch.zeros((n_classes, n_classes), device=pred.device, dtype=torch.int64)
     _chk(conf, "conf", torch.int64)
+    _count("confusion", "gt", gt, pred.numel(), "one per element of pred")
+    _count("confusion", "conf", conf, int(n_classes) ** 2, "(n_classes, n_classes)")
+    _on("confusion", pred.device, "pred", gt=gt, conf=conf)
     _lib.check(_lib.load().pnr_confusion(_p(pred), _p(gt), pred.numel(), int(n_classes), _p(conf), _stream()), "pnr_confusion")
     return conf

@@ -33,3 +33,19 @@ class _FakeCuda(torch.Tensor):
 
 def _fake(t, device=None):
     return _FakeCuda(t, device)
+
+
+def z(*shape, dtype=torch.float32, device=None):
+    """a contiguous fake GPU tensor of zeros"""
+    return _fake(torch.zeros(*shape, dtype=dtype), device)
+
+
+def zt(*shape, dtype=torch.float32):
+    """a NON-contiguous fake GPU tensor of that shape: the last two axes of its memory are swapped (1-D: every second element)"""
+    if len(shape) == 1:
+        return _fake(torch.zeros(2 * shape[0], dtype=dtype)[::2])
+    return _fake(torch.zeros(*shape[:-2], shape[-1], shape[-2], dtype=dtype).transpose(-1, -2))
+
+
+def cpu(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype)

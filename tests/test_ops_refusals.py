@@ -14,9 +14,9 @@ import torch
 
 from panopticnerf_amd import Pinhole, _lib, ops
 
-from _fake_gpu import _fake
+from _fake_gpu import _fake, cpu, z, zt
 
-H, W = 12, 16                       # the images of test_icp.py
+H, W = 12, 16                      # the images of test_icp.py
 RZ, RY, RX = 3, 4, 5                # a lattice of a few points per axis
 EYE = torch.eye(4)[:3]
 PIN = (50.0, 50.0, 8.0, 6.0)
@@ -24,22 +24,6 @@ CAM = Pinhole(*PIN, W, H)
 REC = ctypes.sizeof(_lib.Frame)
 NO_GPU = " (the HIP path has no CPU fallback)"
 f32, f64, i16, i32, i64, u8 = torch.float32, torch.float64, torch.int16, torch.int32, torch.int64, torch.uint8
-
-
-def z(*shape, dtype=f32, device=None):
-    """a contiguous fake GPU tensor of zeros"""
-    return _fake(torch.zeros(*shape, dtype=dtype), device)
-
-
-def zt(*shape, dtype=f32):
-    """a NON-contiguous fake GPU tensor of that shape: the last two axes of its memory are swapped (1-D: every second element)"""
-    if len(shape) == 1:
-        return _fake(torch.zeros(2 * shape[0], dtype=dtype)[::2])
-    return _fake(torch.zeros(*shape[:-2], shape[-1], shape[-2], dtype=dtype).transpose(-1, -2))
-
-
-def cpu(*shape, dtype=f32):
-    return torch.zeros(*shape, dtype=dtype)
 
 
 @pytest.fixture(autouse=True)
