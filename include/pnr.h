@@ -664,6 +664,115 @@ int pnr_mesh_count(const float* field, int res_x, int res_y, int res_z, float le
 int pnr_mesh_emit(const float* field, int res_x, int res_y, int res_z, float level, const float* lo_host, const float* step_host,
                   const void* workspace, float* vertices, int32_t* faces, int64_t* src, void* stream);
 
+/* ---- nearest neighbours (csrc/pnr_nn.hip; DESIGN.md 8 "Nearest neighbours and geometry metrics"): an exact fixed-radius
+ * nearest-neighbour search between two clouds, the reconstruction metrics accumulated from its answers (accuracy, completeness,
+ * Chamfer distance, precision / recall / F-score), and surface points of a triangle mesh at a given density.  The reference ships
+ * none of this: the rules are this build's and unpinned (tests/_nn_ref.py restates them in numpy, bit for bit).  Float32
+ * throughout unless stated, every operation a single + - * / sqrt in the order given, never an FMA; denormals are not flushed.
+ *
+ * NEAREST NEIGHBOUR.  ref (n, 3) and query (m, 3) float32, a radius D = max_dist with 0 < D < inf.  r2 = D * D.  THE CONTRACT:
+ *   1. the squared distance of a query q to ref[j]: dx = qx - rx, dy = qy - ry, dz = qz - rz, d2 = (dx*dx + dy*dy) + dz*dz.
+ *   2. ref[j] is a CANDIDATE iff its three coordinates are finite and d2 <= r2.
+ *   3. the answer is the candidate with the smallest key = ((uint64) bits(d2) << 32) | (uint32) j: the nearest candidate, a
+ *      distance tie going to the lowest index.  It is the key of point splatting.
+ *   4. index[i] = that j, or -1 where there is no candidate; dist2[i] = that d2, or +inf.  A query with a non-finite coordinate
+ *      gets -1 and +inf and is counted apart.
+ *   5. stats[0..2] += the number of queries that found a neighbour / had none in the radius / were invalid (device int64,
+ *      integer atomics: a block-wide count, then one atomic per block and counter).  stats may be NULL.
+ * The result equals brute force over all n, whatever the acceleration structure.  THE STRUCTURE is a spatial hash, so there are
+ * no bounds to compute and nothing to read back:
+ *   Dp = D * PNR_NN_PAD (1.0009765625f), h = 2 * Dp, inv = 1 / h: three float32 operations on the host.
+ *   The origin o is ref[0], read ON THE DEVICE by every thread (a captured build follows the data); (0, 0, 0) if ref[0] is not
+ *     finite or n == 0.
+ *   The cell of p per axis: c = clamp(floorf((p - o) * inv), -2^20, 2^20), clamped AS A FLOAT and then converted to int
+ *     (PNR_NN_CELL_CLAMP).
+ *   bucket = ((cx * PNR_NN_HASH_X) ^ (cy * PNR_NN_HASH_Y) ^ (cz * PNR_NN_HASH_Z)) & (T - 1) in 32-bit unsigned arithmetic;
+ *     T = table_size is a power of two in 2 .. PNR_NN_MAX_TABLE chosen by the caller (the Python layer: max(1024, the power
+ *     of two at or above 2 n), at most PNR_NN_MAX_TABLE).
+ *   A query visits the buckets of every cell of the box [c(q - Dp), c(q + Dp)] per axis and tests every record in them by
+ *     steps 1 .. 3.  Collisions and a bucket visited twice are harmless under a minimum.
+ *   WHY THIS EQUALS BRUTE FORCE.  A candidate has real |qx - rx| <= D (1 + 2^-21) < Dp.  For floats, r >= x implies r >= fl(x),
+ *     so rx lies in [fl(qx - Dp), fl(qx + Dp)].  The subtraction of o, the multiplication by a positive inv, floorf and the clamp
+ *     are all monotone non-decreasing, so c(q - Dp) <= c(r) <= c(q + Dp) at any coordinate magnitude.  Far from the origin the
+ *     cells only get coarser, or collapse into the clamp cell: that costs time and never a neighbour.
+ *   HOW LARGE THE BOX IS.  In real arithmetic the two corners are exactly one cell apart (h = 2 Dp): 2 cells per axis, 8 buckets.
+ *     The rounding of q -+ Dp moves them apart by up to ulp(q) / (2 Dp) cells more, and the multiplication by up to 2^-23 of the
+ *     cell coordinate, so a box can reach 3 cells on an axis where ulp(q) comes near Dp or the coordinate near the clamp, 4 where
+ *     both happen; once ulp(q) > 2 Dp both corners round to q and the box is one cell.  The kernel loops over whatever the two
+ *     corners give.  Both h and 1 / h must be finite: with a denormal D below about 1.47e-39, 1 / h would be +inf and the corners
+ *     of a query next to the origin the two clamp cells, 2^21 cells apart -- such a D is refused.
+ * pnr_nn_build, three launches and a scan on the one stream behind a launch that zeroes the counts (a kernel, not a memset: a
+ * captured build is a plain chain of kernel nodes), no kernel waiting on another workgroup: (1) every finite reference
+ * point adds 1 to its bucket's count with an int32 atomic (non-finite points are skipped and never appear in the table);
+ * (2) an exclusive int32 scan of the counts into start[0 .. T] (block sums, one block over the sums, add back:
+ * csrc/pnr_scan_dev.h); (3) a returning int32 atomic on the bucket's cursor places the point's 16-byte record
+ * (x, y, z, bits = j) into records (n, 4) float32, in bucket order -- a candidate is then ONE 16-byte load.  The order of the
+ * records inside a bucket depends on arrival and is NOT part of the rule; the outputs of a query do not depend on it.
+ * n == 0 zero-fills start (a NULL start is then left alone).  start: device int32 (T + 1); records: device (n, 4) float32,
+ * 16-byte aligned; workspace: pnr_nn_workspace_bytes(n, T) bytes, 8-byte aligned, free again when the build has run (-1 for
+ * arguments the build refuses).  pnr_nn_query takes the SAME ref, n, max_dist and table_size and the start and records the
+ * build filled; it clamps every start pair into [0, n] before looping, so a damaged table can give wrong answers but never an
+ * out-of-range read.  One thread per query, no host synchronisation in either: both are capture-safe on the one stream.
+ * PNR_EINVAL before any launch, from both: n (or m) outside 0 .. 2^31 - 1; max_dist not positive and finite, so large that
+ * 2 Dp overflows, or so small that 1 / (2 Dp) does; table_size not a power of two in 2 .. 2^28; a null or misaligned pointer (4 bytes; records 16; workspace and
+ * stats 8).  pnr_nn_build with n == 0 and pnr_nn_query with m == 0: PNR_OK before the pointer checks.
+ *
+ * CLOUD METRICS.  pnr_cloud_metrics: index, dist2 (m) as a query wrote them, D = max_dist as above, and n_tau <= PNR_CLOUD_MAX_TAU
+ * (8) thresholds tau_k with 0 < tau_k <= D (HOST floats, copied into the launch).  Query i COUNTS iff dist2[i] is not NaN and --
+ * the choice this build makes of the two possible -- query (m, 3), the coordinates that were asked, is NULL or holds three finite
+ * coordinates at row i: pass the queries and the invalid ones (written as -1 / +inf) are left out; pass NULL and every row counts.
+ * A counted query is FOUND iff index[i] >= 0.  In double: d = sqrt((double) dist2[i]) if found, else (double) D.
+ *   sums[0] += d, sums[1] += d * d                                            (device double[2])
+ *   counts[0] += 1, counts[1] += !found, counts[2 + k] += found and dist2[i] <= tau_k * tau_k (one float32 multiply) for k < n_tau
+ *                                                                             (device int64[2 + PNR_CLOUD_MAX_TAU], integer atomics, exact)
+ * The sums take the fixed order of pnr_depth_metrics: per-thread stride, the wave's butterfly, waves in order, a per-block partial
+ * in workspace, and a one-block second launch that adds the partials in block order and the total once into sums.  No floating
+ * atomics: two calls on the same input and the same box give the same bits.  Both arrays accumulate over calls (the caller
+ * zeroes them once).  workspace: pnr_cloud_metrics_workspace_bytes(m) bytes, 8-byte aligned (-1 for m outside 0 .. 2^31 - 1).
+ * PNR_EINVAL before any launch: a bad m or max_dist; n_tau outside 0 .. 8; a null tau_host with n_tau > 0; a tau_k that is not in
+ * (0, D]; a null index / dist2 / sums / counts / workspace; a misaligned pointer (4 bytes; sums, counts and workspace 8).
+ * m == 0: PNR_OK after the checks of the values.
+ *
+ * MESH SAMPLING.  vertices (V, 3) float32, faces (F, 3) int32, a density rho (points per unit area; finite, >= 0) and a 64-bit
+ * seed = (seed_lo, seed_hi), the Philox key.  With Philox(c) = pnr_philox4x32_10 of the counter c under that key and U(w) =
+ * (w >> 8) * 2^-24 (pnr_uniform of "in-kernel RNG").  Per triangle t with corners p0, p1, p2:
+ *   e1 = p1 - p0, e2 = p2 - p0; n = e1 x e2, each component (a*b) - (c*d) with both products rounded;
+ *   s = (nx*nx + ny*ny) + nz*nz; area = 0.5f * sqrtf(s), correctly rounded.
+ *   u_t = U(word x of Philox({t, 0, 0, 0}));  k_t = min((int) floorf((area * rho) + u_t), PNR_SAMPLE_MAX_PER_FACE): the expected
+ *   count is area * rho, so small triangles are not biased away.  k_t = 0 if area is not finite or a face index is outside 0 .. V - 1.
+ *   Point j < k_t of triangle t draws (x, y, ., .) = Philox({t, 1 + j, 0, 0}): u = U(x), v = U(y); if u + v > 1 both are
+ *   replaced by 1 - u and 1 - v; p = (p0 + u*e1) + v*e2 per component, each operation rounded.
+ * The points come in triangle order, then j order: nothing is atomic, so the output is the same on every call.
+ * pnr_mesh_sample_count writes k_t, scans it in place into start (F + 1) device int32 (the shared scan), and writes the 64-bit
+ * total into total (device int64, 8-byte aligned).  The caller reads total -- the one synchronisation of a sampling, and the
+ * caller's -- refuses a total above 2^31 - 1 (the int32 scan has then wrapped), allocates, and calls pnr_mesh_sample_emit with
+ * the same mesh and seed, start and n_points = total: points (n_points, 3) float32 and face (n_points) int32, the triangle of
+ * each point.  workspace: pnr_mesh_sample_workspace_bytes(F) bytes, 4-byte aligned.  Neither entry point synchronises or
+ * allocates.  PNR_EINVAL before any launch: V outside 0 .. 2^31 - 1 or F outside 0 .. 2^31 - 2; rho negative, NaN or infinite;
+ * a null or misaligned pointer; n_points outside 0 .. 2^31 - 1, or positive with F == 0.  F == 0: start[0] = 0 and total = 0
+ * (a NULL one is left alone).  n_points == 0: PNR_OK, no launch. */
+#define PNR_NN_PAD 1.0009765625f            /* Dp = D * (1 + 2^-10) */
+#define PNR_NN_CELL_CLAMP 1048576.0f        /* 2^20 */
+#define PNR_NN_HASH_X 73856093u
+#define PNR_NN_HASH_Y 19349663u
+#define PNR_NN_HASH_Z 83492791u
+#define PNR_NN_MAX_TABLE 268435456          /* 2^28 buckets */
+#define PNR_CLOUD_MAX_TAU 8
+#define PNR_SAMPLE_MAX_PER_FACE 65535
+int64_t pnr_nn_workspace_bytes(int64_t n, int64_t table_size);
+int pnr_nn_build(const float* ref, int64_t n, float max_dist, int64_t table_size, int32_t* start, float* records, void* workspace,
+                 void* stream);
+int pnr_nn_query(const float* ref, int64_t n, float max_dist, int64_t table_size, const int32_t* start, const float* records,
+                 const float* query, int64_t m, int32_t* index, float* dist2, int64_t* stats, void* stream);
+int64_t pnr_cloud_metrics_workspace_bytes(int64_t m);
+int pnr_cloud_metrics(const int32_t* index, const float* dist2, const float* query, int64_t m, float max_dist,
+                      const float* tau_host, int n_tau, double* sums, int64_t* counts, void* workspace, void* stream);
+int64_t pnr_mesh_sample_workspace_bytes(int64_t n_faces);
+int pnr_mesh_sample_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, float rho, int64_t seed,
+                          int32_t* start, int64_t* total, void* workspace, void* stream);
+int pnr_mesh_sample_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int64_t seed,
+                         const int32_t* start, int64_t n_points, float* points, int32_t* face, void* stream);
+
 /* ---- 8f-4: label-map post-processing and evaluator counters (what follows the path in the reference's evaluate loop;
  * its evaluator is not in the mount, conventions are this build's -- DESIGN.md 8).
  * pnr_panoptic_labels: sem_label = argmax_c sem (lowest index on ties); inst_label = argmax_k inst where is_thing[sem_label]

@@ -1,0 +1,107 @@
+// Exclusive int32 scan of a device array (pnr_nn.hip: the bucket table of the nearest-neighbour index and the per-triangle
+// counts of mesh sampling).  Three launches on one stream, no kernel waits on another workgroup and nothing is atomic:
+//   1. k_scan_tile_sums: workgroup b adds its tile of PNR_SCAN_TILE items into sums[b];
+//   2. k_scan_top:       ONE workgroup turns sums into their exclusive scan, carrying in 64 bits, and writes the 64-bit total;
+//   3. k_scan_apply:     workgroup b scans its tile again and writes out[i] = sums[b] + the items before i in the tile; the
+//                        thread that holds item n - 1 also writes out[n], the int32 total.
+// out has n + 1 entries and MAY BE `in` itself: a workgroup reads its own tile before it writes it, and launch 1 is over.
+// The int32 prefix wraps when the total passes 2^31 - 1; a caller for whom that can happen reads total64 and refuses.
+// (The scan inside pnr_mesh.hip works on its packed info words and is a different one.)
+#pragma once
+#include "pnr_common.h"
+
+#define PNR_SCAN_BLOCK 256
+#define PNR_SCAN_PER_THREAD 4
+#define PNR_SCAN_TILE (PNR_SCAN_BLOCK * PNR_SCAN_PER_THREAD)
+
+static inline int64_t pnr_scan_tiles(int64_t n) { return (n + PNR_SCAN_TILE - 1) / PNR_SCAN_TILE; }
+
+// bytes of `ws` for a scan of n items: one int32 per tile, rounded up to 8 bytes
+static inline int64_t pnr_scan_workspace_bytes(int64_t n) { return (pnr_scan_tiles(n) * 4 + 7) & ~(int64_t)7; }
+
+#ifdef __HIPCC__
+// exclusive scan of v over the 256 threads of the workgroup in thread order; total: the workgroup's sum.  lds: 4 words of T,
+// free again on return.
+template <typename T>
+__device__ __forceinline__ T pnr_block_scan_excl(T v, T* lds, T& total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < PNR_SCAN_BLOCK / 64; ++w) {
+        const T s = lds[w];
+        before += w < wave ? s : (T)0;
+        total += s;
+    }
+    __syncthreads();
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_tile_sums(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums)
+{
+    __shared__ int32_t lds[4];
+    const int64_t base = (int64_t)blockIdx.x * PNR_SCAN_TILE + (int64_t)threadIdx.x * PNR_SCAN_PER_THREAD;
+    int32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < PNR_SCAN_PER_THREAD; ++i) s += base + i < n ? in[base + i] : 0;
+    int32_t total;
+    pnr_block_scan_excl<int32_t>(s, lds, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_top(int32_t* __restrict__ sums, int64_t tiles, long long* __restrict__ total64)
+{
+    __shared__ long long lds[4];
+    long long carry = 0;
+    for (int64_t c = 0; c < tiles; c += PNR_SCAN_BLOCK) {           // (uniform over the workgroup)
+        const int64_t i = c + threadIdx.x;
+        const long long v = i < tiles ? (long long)sums[i] : 0ll;
+        long long total;
+        const long long before = pnr_block_scan_excl<long long>(v, lds, total);
+        if (i < tiles) sums[i] = (int32_t)(carry + before);
+        carry += total;
+    }
+    if (threadIdx.x == 0) total64[0] = carry;
+}
+
+__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_apply(const int32_t* in, int64_t n, const int32_t* __restrict__ sums, int32_t* out)
+{
+    __shared__ int32_t lds[4];
+    const int64_t base = (int64_t)blockIdx.x * PNR_SCAN_TILE + (int64_t)threadIdx.x * PNR_SCAN_PER_THREAD;
+    int32_t v[PNR_SCAN_PER_THREAD], s = 0;
+#pragma unroll
+    for (int i = 0; i < PNR_SCAN_PER_THREAD; ++i) {
+        v[i] = base + i < n ? in[base + i] : 0;
+        s += v[i];
+    }
+    int32_t total;
+    int32_t run = sums[blockIdx.x] + pnr_block_scan_excl<int32_t>(s, lds, total);
+#pragma unroll
+    for (int i = 0; i < PNR_SCAN_PER_THREAD; ++i) {
+        if (base + i < n) out[base + i] = run;
+        run += v[i];
+        if (base + i == n - 1) out[n] = run;
+    }
+}
+
+// out[0 .. n] = the exclusive scan of in[0 .. n) and the total; total64 (device, 8-byte aligned) receives the 64-bit total;
+// ws: pnr_scan_workspace_bytes(n) bytes, 4-byte aligned.  n >= 1.  The caller checks the launches (PNR_CHECK_LAUNCH).
+static inline void pnr_scan_i32(const int32_t* in, int32_t* out, int64_t n, void* ws, int64_t* total, hipStream_t st)
+{
+    const int64_t tiles = pnr_scan_tiles(n);
+    long long* total64 = (long long*)total;
+    int32_t* sums = (int32_t*)ws;
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3((unsigned)tiles), dim3(PNR_SCAN_BLOCK), 0, st, in, n, sums);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(PNR_SCAN_BLOCK), 0, st, sums, tiles, total64);
+    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)tiles), dim3(PNR_SCAN_BLOCK), 0, st, in, n, (const int32_t*)sums, out);
+}
+#endif

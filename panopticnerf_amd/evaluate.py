@@ -35,6 +35,7 @@ class Evaluator:
         self.mc_tol = consistency.DEFAULT_TOL
         self.depth_sums = None      # (5) device float64: sums of |d|, d^2, |d|/gt, d^2/gt, (log pred - log gt)^2 (pnr_depth_metrics)
         self.depth_counts = None    # (5) device int64: compared pixels, ratio < 1.25 / 1.25^2 / 1.25^3, missing predictions
+        self.geom = None            # evaluate_geometry: {"max_dist", "thresholds", "sums": [pred->gt, gt->pred] (2) float64, "counts": likewise (10) int64}
 
     def evaluate(self, output, batch):
         lv = self.level if f"rgb_{self.level}" in output else 0
@@ -133,6 +134,39 @@ class Evaluator:
                                                                self.depth_sums, self.depth_counts)
         return key
 
+    def evaluate_geometry(self, pred_points, gt_points, max_dist, thresholds=()):
+        """Accumulate 3D reconstruction metrics of a predicted cloud (e.g. Mesh.sample of a fused mesh) against a ground-truth
+        cloud (e.g. the accumulated scan), both (n, 3) float32 on the GPU: an index over each (pointcloud.NearestIndex), each
+        queried with the other at radius max_dist, both directions accumulated on the device (ops.cloud_metrics; the rule is
+        in include/pnr.h "nearest neighbours").  Distances are clamped at max_dist, the usual practice: a point with no
+        neighbour within max_dist counts as max_dist.  Points with a non-finite coordinate are left out.  thresholds: at
+        most 8 distances in (0, max_dist] for precision / recall / F-score.  A later call before summarize() must give the same
+        max_dist and thresholds.  Returns the two query results {"pred_to_gt", "gt_to_pred"}."""
+        from . import pointcloud
+        what = "Evaluator.evaluate_geometry"
+        n_p, n_g = ops.nn_cloud(what, "pred_points", pred_points), ops.nn_cloud(what, "gt_points", gt_points)
+        d, _ = ops.nn_params(what, max_dist, max(n_p, n_g))
+        taus = ops.cloud_thresholds(what, thresholds, d)
+        if self.geom is not None and (self.geom["max_dist"] != d or self.geom["thresholds"] != taus):
+            raise ValueError("%s: max_dist and thresholds (%r, %r) differ from those of an earlier call since the last summarize() "
+                             "(%r, %r)" % (what, d, taus, self.geom["max_dist"], self.geom["thresholds"]))
+        if not pred_points.is_cuda or not gt_points.is_cuda:
+            raise RuntimeError("%s: the clouds must be on the GPU (the HIP path has no CPU fallback)" % what)
+        if pred_points.device != gt_points.device:
+            raise ValueError("%s: pred_points is on %s, gt_points on %s" % (what, pred_points.device, gt_points.device))
+        res, terms = {}, []
+        for name, q, ref in (("pred_to_gt", pred_points, gt_points), ("gt_to_pred", gt_points, pred_points)):
+            res[name] = pointcloud.NearestIndex(ref, d).query(q)
+            terms.append(ops.cloud_metrics(res[name]["index"], res[name]["dist2"], d, taus, query=q))
+        # both directions are in hand before either is accumulated: a call that raises half way leaves the accumulators as they were
+        if self.geom is None:
+            self.geom = {"max_dist": d, "thresholds": taus, "sums": [s for s, _ in terms], "counts": [c for _, c in terms]}
+        else:
+            for k, (s, c) in enumerate(terms):
+                self.geom["sums"][k] = self.geom["sums"][k] + s
+                self.geom["counts"][k] = self.geom["counts"][k] + c
+        return res
+
     def _accumulate_pq(self, pred_id, gt_id):
         """Per-frame PQ terms (Kirillov et al.): segments match when same class and IoU > 0.5 (then the match is unique).
         Panoptic ids: class*1000 + instance for things, class for stuff; < 0 = ignore.  Segment ids are re-mapped PER
@@ -184,6 +218,7 @@ class Evaluator:
         finally:
             self.mse, self.conf, self.pq, self._bad_ids, self.mc_agree, self.mc_stats = [], None, None, None, None, None
             self.depth_sums, self.depth_counts = None, None
+            self.geom = None
 
     def _summarize(self):
         out = {}
@@ -226,4 +261,17 @@ class Evaluator:
             out["depth_abs_rel"], out["depth_sq_rel"] = mean(s[2]), mean(s[3])
             out["depth_rmse_log"] = math.sqrt(mean(s[4])) if n else math.nan
             out["depth_d1"], out["depth_d2"], out["depth_d3"] = mean(c[1]), mean(c[2]), mean(c[3])
+        if self.geom is not None:
+            side = []
+            for k in range(2):
+                c, s = [int(v) for v in self.geom["counts"][k].cpu().tolist()], self.geom["sums"][k].cpu().tolist()
+                n = c[0]
+                side.append((n, c[1], s[0] / n if n else math.nan, math.sqrt(s[1] / n) if n else math.nan,
+                             [c[2 + j] / n if n else math.nan for j in range(len(self.geom["thresholds"]))]))
+            (n_p, miss_p, acc, acc_rms, prec), (n_g, miss_g, comp, comp_rms, rec) = side
+            out["geom_accuracy"], out["geom_completeness"], out["geom_chamfer"] = acc, comp, 0.5 * (acc + comp)
+            out["geom_accuracy_rms"], out["geom_completeness_rms"] = acc_rms, comp_rms
+            out["geom_precision"], out["geom_recall"] = prec, rec
+            out["geom_fscore"] = [2.0 * p * r / (p + r) if p + r > 0 else math.nan for p, r in zip(prec, rec)]
+            out["geom_n_pred"], out["geom_n_gt"], out["geom_missing_pred"], out["geom_missing_gt"] = n_p, n_g, miss_p, miss_g
         return out

@@ -5,7 +5,9 @@ GPU (ops.mesh_count / mesh_emit; the rule is written out in include/pnr.h "mesh 
 cases, neighbouring cubes agree on every face diagonal, so the surface is watertight wherever it does not leave the lattice.
 Every vertex lies on a lattice edge and knows the lattice point on the inside end of that edge (`src`): `Mesh.labels(grid)`
 reads any per-point array there.  `from_network` does query_grid + extract + labels.  The numbering of vertices and triangles
-is part of the rule, so the result is the CPU restatement's bit for bit, and the same on every call.
+is part of the rule, so the result is the CPU restatement's bit for bit, and the same on every call.  `Mesh.sample` puts points
+on the surface at a given density (ops.mesh_sample_count / mesh_sample_emit; include/pnr.h "nearest neighbours", MESH SAMPLING):
+what `Evaluator.evaluate_geometry` compares with a ground-truth scan.
 
 Conventions (this build's, unpinned: the reference ships no extractor): inside is field > level (NaN outside); positions are
 query_grid's cell centres lo + (i + 0.5) step; triangles wind so that the normal points from inside to outside; vertices of
@@ -80,6 +82,36 @@ class Mesh:
         """the signed volume sum p0 . (p1 x p2) / 6 in float64 torch: positive for a closed surface, whose normals point outwards"""
         p0, p1, p2 = self._corners()
         return float((p0 * torch.linalg.cross(p1, p2)).sum() / 6.0)
+
+    def sample(self, density=None, n=None, seed=0):
+        """Points on the surface: (points (N, 3) float32, face (N,) int32), face[i] the triangle point i lies on; in triangle
+        order, and the same for the same seed.  Exactly one of density (points per unit area) and n is given; n means
+        density = n / self.area(), so ABOUT n points come back, not exactly n: a triangle of area a gets floor(a density + u)
+        points, u uniform in [0, 1), at most 65535.  Degenerate triangles and triangles with a non-finite corner get none.
+        Per-vertex attributes come through the triangle's first corner: mesh.attributes[name][mesh.faces[face, 0].long()].
+        One host synchronisation, as in extract: the total is read back between the count and the emit launch; with n= there is
+        a second one before it, because self.area() returns a Python float."""
+        if (density is None) == (n is None):
+            raise ValueError("Mesh.sample: give exactly one of density and n")
+        if not self.vertices.is_cuda:
+            raise RuntimeError("Mesh.sample: the mesh must be on the GPU (the HIP path has no CPU fallback)")
+        if n is not None:
+            n, area = int(n), self.area()
+            if n < 0:
+                raise ValueError("Mesh.sample: n must be >= 0 (got %d)" % n)
+            if n and not (0.0 < area < float("inf")):
+                raise ValueError("Mesh.sample: n needs a mesh of positive finite area (it is %r); give density instead" % area)
+            density = n / area if n else 0.0
+        total, start = ops.mesh_sample_count(self.vertices, self.faces, density, seed)
+        N = int(total.item())                                   # the one host synchronisation
+        if N > ops.NN_MAX_POINTS:
+            raise ValueError("Mesh.sample: density %r asks for %d points, more than 2^31 - 1" % (density, N))
+        dev = self.vertices.device
+        points = torch.empty((N, 3), device=dev, dtype=torch.float32)
+        face = torch.empty((N,), device=dev, dtype=torch.int32)
+        if N:
+            ops.mesh_sample_emit(self.vertices, self.faces, seed, start, points, face)
+        return points, face
 
     def save_ply(self, path, colors=None, labels=None):
         """Write a binary little-endian PLY (host code: the arrays are copied off the device).  colors: (V, 3) uint8 as red green

@@ -593,6 +593,195 @@ def mesh_emit(field, level, lo, step, workspace, vertices, faces, src=None):
     return vertices, faces, src
 
 
+NN_MAX_POINTS = 2 ** 31 - 1                     # include/pnr.h "nearest neighbours": n, m and the number of sampled points
+NN_MAX_TABLE_BITS = 28                          # PNR_NN_MAX_TABLE = 2^28 buckets
+CLOUD_MAX_TAU = _lib.CLOUD_MAX_TAU
+CLOUD_COUNTS = 2 + CLOUD_MAX_TAU                # counted, missing, then one per threshold
+_NN_PAD = 1.0009765625                          # PNR_NN_PAD
+
+
+def _f32(v):
+    """the float32 nearest to the Python number v, as a Python float (what ctypes.c_float passes)"""
+    return ctypes.c_float(v).value
+
+
+def nn_params(what, max_dist, n, table_bits=None):
+    """(max_dist, table_size) of an index over n reference points, or the refusal by name: max_dist positive and finite as a
+    float32, with a cell size 2 max_dist that does not overflow and whose inverse does not either (max_dist above about 1.5e-39); table_bits None for the default table of max(1024, the power of
+    two at or above 2 n) buckets, or 1 .. 28 for 2^table_bits buckets"""
+    try:
+        d = _f32(float(max_dist))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: max_dist must be a positive finite number (got %r)" % (what, max_dist)) from None
+    h = _f32(_f32(d * _NN_PAD) * 2.0) if 0.0 < d < _INF else 0.0
+    if not (0.0 < h < _INF) or not (_f32(1.0 / h) < _INF):
+        raise ValueError("%s: max_dist must be positive and finite, with 2 max_dist and 1 / (2 max_dist) finite in float32 (got %r)" % (what, max_dist))
+    n = int(n)
+    if n < 0 or n > NN_MAX_POINTS:
+        raise ValueError("%s: the cloud holds %d points, outside 0 .. 2^31 - 1" % (what, n))
+    if table_bits is None:
+        table_bits = min(max(10, (2 * n - 1).bit_length() if n else 0), NN_MAX_TABLE_BITS)
+    elif isinstance(table_bits, bool) or not isinstance(table_bits, int) or not (1 <= table_bits <= NN_MAX_TABLE_BITS):
+        raise ValueError("%s: table_bits must be an integer in 1 .. %d (got %r)" % (what, NN_MAX_TABLE_BITS, table_bits))
+    return d, 1 << table_bits
+
+
+def nn_cloud(what, name, t):
+    """rows of the point cloud `t`, a float32 (n, 3) tensor on any device, or the refusal by name: the public check the wrappers reuse"""
+    return _cloud(what, name, t)
+
+
+def _cloud(what, name, t, dtype=torch.float32, cols=3):
+    """the (rows, cols) tensor `t` of `dtype` on any device, cols = 0 for (rows,): type, dtype, shape; returns rows"""
+    _tensor(what, name, t)
+    if t.dtype != dtype:
+        raise TypeError("%s: %s must be %s, got %s" % (what, name, dtype, t.dtype))
+    if t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
+        raise ValueError("%s: %s must be %s, got %s" % (what, name, "(n, %d)" % cols if cols else "(n,)", tuple(t.shape)))
+    if t.shape[0] > NN_MAX_POINTS:
+        raise ValueError("%s: %s holds %d rows, more than 2^31 - 1" % (what, name, t.shape[0]))
+    return t.shape[0]
+
+
+def _nn_table(what, start, records, n):
+    """table_size of the (start, records) pair of an index over n points: type, dtype, shape"""
+    _tensor(what, "start", start)
+    if start.dtype != torch.int32:
+        raise TypeError("%s: start must be torch.int32, got %s" % (what, start.dtype))
+    T = start.numel() - 1
+    if start.dim() != 1 or T < 2 or T & (T - 1) or T > 1 << NN_MAX_TABLE_BITS:
+        raise ValueError("%s: start must be (table_size + 1,) with table_size a power of two in 2 .. 2^28, got %s" % (what, tuple(start.shape)))
+    _tensor_table(what, [("records", records, torch.float32, (n, 4))])
+    return T
+
+
+@_on_device
+def nn_build(ref, max_dist, table_bits=None, start=None, records=None):
+    """Build the spatial-hash index of the reference cloud ref (n, 3) float32 for radius max_dist (pnr_nn_build; the rule is in
+    include/pnr.h "nearest neighbours").  Returns (start (table_size + 1,) int32, records (n, 4) float32): per bucket the range
+    of its records, and the records (x, y, z, bits = index) in bucket order.  Both may be caller-owned.  Never synchronises."""
+    n = _cloud("nn_build", "ref", ref)
+    d, T = nn_params("nn_build", max_dist, n, table_bits)
+    _tensor_table("nn_build", (), [("start", start, torch.int32, (T + 1,)), ("records", records, torch.float32, (n, 4))])
+    _same_device("nn_build", ref=ref, start=start, records=records)
+    dev = ref.device
+    start = torch.empty((T + 1,), device=dev, dtype=torch.int32) if start is None else start
+    records = torch.empty((n, 4), device=dev, dtype=torch.float32) if records is None else records
+    ws = torch.empty((_size_or_raise(_lib.load().pnr_nn_workspace_bytes(n, T), "pnr_nn_workspace_bytes") // 8,), device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().pnr_nn_build(_p(ref if n else None), n, d, T, _p(start), _p(records if n else None), _p(ws), _stream()), "pnr_nn_build")
+    return start, records
+
+
+@_on_device
+def nn_query(ref, start, records, query, max_dist, index=None, dist2=None, stats=None):
+    """Nearest reference point within max_dist of every row of query (m, 3) float32 (pnr_nn_query).  ref, start, records and
+    max_dist are nn_build's.  Returns (index (m,) int32, dist2 (m,) float32): -1 and +inf where no reference point is within
+    max_dist or the query is not finite; a tie in distance goes to the lowest index.  stats: (3,) int64, accumulated: queries
+    that found a neighbour / had none in the radius / were invalid.  Never synchronises: the call can be captured."""
+    n = _cloud("nn_query", "ref", ref)
+    T = _nn_table("nn_query", start, records, n)
+    m = _cloud("nn_query", "query", query)
+    d, T = nn_params("nn_query", max_dist, n, T.bit_length() - 1)
+    _tensor_table("nn_query", (), [("index", index, torch.int32, (m,)), ("dist2", dist2, torch.float32, (m,)), ("stats", stats, torch.int64, (3,))])
+    _same_device("nn_query", query=query, ref=ref, start=start, records=records, index=index, dist2=dist2, stats=stats)
+    dev = query.device
+    index = torch.empty((m,), device=dev, dtype=torch.int32) if index is None else index
+    dist2 = torch.empty((m,), device=dev, dtype=torch.float32) if dist2 is None else dist2
+    _lib.check(_lib.load().pnr_nn_query(_p(ref if n else None), n, d, T, _p(start), _p(records if n else None), _p(query if m else None), m,
+                                        _p(index if m else None), _p(dist2 if m else None), _p(stats), _stream()), "pnr_nn_query")
+    return index, dist2
+
+
+def cloud_thresholds(what, thresholds, max_dist):
+    """the thresholds of cloud_metrics as host floats: at most 8, each in (0, max_dist] as float32"""
+    try:
+        taus = [_f32(float(t)) for t in thresholds]
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: thresholds must be a sequence of numbers (got %r)" % (what, thresholds)) from None
+    if len(taus) > CLOUD_MAX_TAU:
+        raise ValueError("%s: at most %d thresholds (got %d)" % (what, CLOUD_MAX_TAU, len(taus)))
+    for t in taus:
+        if not (0.0 < t <= max_dist):
+            raise ValueError("%s: every threshold must satisfy 0 < tau <= max_dist = %r (got %r)" % (what, max_dist, t))
+    return taus
+
+
+@_on_device
+def cloud_metrics(index, dist2, max_dist, thresholds=(), query=None, sums=None, counts=None):
+    """Distance terms of one direction of a cloud comparison from nn_query's answers (pnr_cloud_metrics; the rule is in
+    include/pnr.h "nearest neighbours").  A row counts where dist2 is not NaN and, when `query` (m, 3) -- the coordinates that
+    were asked -- is given, the query was finite.  d = sqrt(dist2) in double where a neighbour was found, else max_dist.
+    Returns (sums (2,) float64, counts (10,) int64), accumulated into when given:
+      sums:   d, d^2;     counts: rows counted, rows without a neighbour, then per threshold tau_k the rows with dist2 <= tau_k^2.
+    Deterministic: no floating atomics."""
+    m = _cloud("cloud_metrics", "index", index, torch.int32, 0)
+    _tensor_table("cloud_metrics", [("dist2", dist2, torch.float32, (m,))],
+                  [("query", query, torch.float32, (m, 3)), ("sums", sums, torch.float64, (2,)), ("counts", counts, torch.int64, (CLOUD_COUNTS,))])
+    d, _ = nn_params("cloud_metrics", max_dist, m)
+    taus = cloud_thresholds("cloud_metrics", thresholds, d)
+    _same_device("cloud_metrics", index=index, dist2=dist2, query=query, sums=sums, counts=counts)
+    dev = index.device
+    sums = torch.zeros((2,), device=dev, dtype=torch.float64) if sums is None else sums
+    counts = torch.zeros((CLOUD_COUNTS,), device=dev, dtype=torch.int64) if counts is None else counts
+    ws = torch.empty((_size_or_raise(_lib.load().pnr_cloud_metrics_workspace_bytes(m), "pnr_cloud_metrics_workspace_bytes") // 8,),
+                     device=dev, dtype=torch.float64)
+    tau_h = (ctypes.c_float * max(len(taus), 1))(*taus)
+    _lib.check(_lib.load().pnr_cloud_metrics(_p(index if m else None), _p(dist2 if m else None), _p(query if m else None), m, d, tau_h, len(taus),
+                                             _p(sums), _p(counts), _p(ws), _stream()), "pnr_cloud_metrics")
+    return sums, counts
+
+
+def _sample_mesh(what, vertices, faces, seed):
+    """(V, F, seed as a signed 64-bit word) of the mesh arguments of the sampling ops: type, dtype, shape"""
+    V = _cloud(what, "vertices", vertices)
+    F = _cloud(what, "faces", faces, torch.int32)
+    if F > NN_MAX_POINTS - 1:
+        raise ValueError("%s: faces holds %d rows, more than 2^31 - 2" % (what, F))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not (-2 ** 63 <= seed < 2 ** 64):
+        raise ValueError("%s: seed must be an integer of at most 64 bits (got %r)" % (what, seed))
+    return V, F, seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+
+@_on_device
+def mesh_sample_count(vertices, faces, density, seed=0, start=None, total=None):
+    """Count the surface points mesh sampling puts on every triangle at `density` points per unit area and scan the counts
+    (pnr_mesh_sample_count; the rule is in include/pnr.h "nearest neighbours", MESH SAMPLING).  vertices (V, 3) float32, faces
+    (F, 3) int32.  Returns (total, start): total (1,) int64 ON THE DEVICE -- reading it is the caller's synchronisation --,
+    start (F + 1,) int32 the exclusive scan mesh_sample_emit needs.  Both may be caller-owned."""
+    V, F, seed = _sample_mesh("mesh_sample_count", vertices, faces, seed)
+    try:
+        rho = _f32(float(density))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("mesh_sample_count: density must be a finite number >= 0 (got %r)" % (density,)) from None
+    if not (0.0 <= rho < _INF):
+        raise ValueError("mesh_sample_count: density must be finite and >= 0 (got %r)" % (density,))
+    _tensor_table("mesh_sample_count", (), [("start", start, torch.int32, (F + 1,)), ("total", total, torch.int64, (1,))])
+    _same_device("mesh_sample_count", vertices=vertices, faces=faces, start=start, total=total)
+    dev = vertices.device
+    start = torch.empty((F + 1,), device=dev, dtype=torch.int32) if start is None else start
+    total = torch.empty((1,), device=dev, dtype=torch.int64) if total is None else total
+    ws = torch.empty((_size_or_raise(_lib.load().pnr_mesh_sample_workspace_bytes(F), "pnr_mesh_sample_workspace_bytes") // 8,), device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().pnr_mesh_sample_count(_p(vertices if V else None), V, _p(faces if F else None), F, rho, seed, _p(start), _p(total), _p(ws),
+                                                 _stream()), "pnr_mesh_sample_count")
+    return total, start
+
+
+@_on_device
+def mesh_sample_emit(vertices, faces, seed, start, points, face):
+    """Write the points mesh_sample_count counted (pnr_mesh_sample_emit): points (N, 3) float32 and face (N,) int32, the triangle
+    of each point, caller-owned and sized by mesh_sample_count's total; in triangle order, then draw order.  vertices, faces,
+    seed and start are mesh_sample_count's."""
+    V, F, seed = _sample_mesh("mesh_sample_emit", vertices, faces, seed)
+    N = _cloud("mesh_sample_emit", "points", points)
+    _tensor_table("mesh_sample_emit", [("start", start, torch.int32, (F + 1,)), ("face", face, torch.int32, (N,))])
+    if N and not F:
+        raise ValueError("mesh_sample_emit: %d points asked of a mesh without faces" % N)
+    _same_device("mesh_sample_emit", vertices=vertices, faces=faces, start=start, points=points, face=face)
+    _lib.check(_lib.load().pnr_mesh_sample_emit(_p(vertices if V else None), V, _p(faces if F else None), F, seed, _p(start), N,
+                                                _p(points if N else None), _p(face if N else None), _stream()), "pnr_mesh_sample_emit")
+    return points, face
+
+
 TSDF_MAX_POINTS = 2 ** 31 - 1                   # include/pnr.h "depth fusion"
 TSDF_BLOCK, TSDF_BLOCKS_PER_CU = 256, 8         # PNR_TSDF_BLOCK, PNR_TSDF_BLOCKS_PER_CU
 
