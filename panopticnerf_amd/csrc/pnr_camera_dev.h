@@ -1,6 +1,6 @@
 // "A camera" in one place (include/pnr.h "ray generation" / "cameras"): the per-pixel ray arithmetic of the three models and
 // pnr_camera_ray, which picks among them by model word; the projection of a world point of any model; the rules a view adds to
-// it (nearest pixel, stored depth); the block reduction of per-thread counters; and the host side of a camera argument (its
+// it (nearest pixel, stored depth); and the host side of a camera argument (its
 // checks, its cam[7] and pose fill).  Callers: k_gen_rays<model> and k_project_points (pnr_camera.hip), k_sample_batch
 // (pnr_batch.hip), k_reproject (pnr_warp.hip) and k_splat_points (pnr_splat.hip), which must write the same bits for the same
 // camera, pose and pixel or point -- no other file branches on the model word.  Every operation is a single + - * / sqrt in one
@@ -203,7 +203,7 @@ __device__ __forceinline__ PnrProj pnr_project_point(int model, const float* cam
         const float lam = pnr_atan2pi(p[0], p[2]);
         const float h = sqrtf(p[0] * p[0] + p[2] * p[2]);
         const float psi = pnr_atan2pi(p[1], h);
-        dom = rng > 0.0f && rng <= FLT_MAX;
+        dom = pnr_pos_finite(rng);
         u = (lam - cam[0]) / cam[1] - 0.5f;
         v = (psi - cam[2]) / cam[3] - 0.5f;
         const float per = 2.0f / __builtin_fabsf(cam[1]);       // the longitude period in pixels: at most one wrap
@@ -239,22 +239,3 @@ __device__ __forceinline__ int pnr_nearest_pixel(float u, int nmax)
 
 // the depth a view of this model stores for a projected point: z-depth in a pinhole view, range otherwise
 __device__ __forceinline__ float pnr_view_depth(int model, const PnrProj& q) { return model == PNR_CAMERA_PINHOLE ? q.z : q.rng; }
-
-// stats[k] += the block's sum of cnt[k], k < K: the wave's butterfly, one LDS atomic per wave, one global atomic per block and
-// non-zero counter.  Called by every thread of the block; h: K words of LDS, free to hold anything before the first barrier.
-template <int K>
-__device__ __forceinline__ void pnr_block_count_add(const unsigned int (&cnt)[K], unsigned int* h, unsigned long long* stats)
-{
-    __syncthreads();
-    if (threadIdx.x < K) h[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        unsigned int c = cnt[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&h[k], c);
-    }
-    __syncthreads();
-    if (threadIdx.x < K && h[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-}

@@ -1,6 +1,8 @@
 // Shared helpers for libpnr.so (gfx950 only).  See include/pnr.h for the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -35,6 +37,11 @@ void pnr_set_error(const char* fmt, ...);
             return PNR_EHIP;                                                       \
         }                                                                          \
     } while (0)
+
+// The two validity tests of the geometry code, host and device: a depth, length or radius that is positive and finite, and a
+// point whose three coordinates are finite.  Comparisons only, so both are false for NaN.
+static __host__ __device__ __forceinline__ bool pnr_pos_finite(float t) { return t > 0.0f && t <= FLT_MAX; }
+static __host__ __device__ __forceinline__ bool pnr_finite3(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }
 
 // Compute units of the CURRENT device (256 on a full MI355X; partitioned / harvested parts report fewer),
 // queried once per device and cached (pnr_api.cpp).

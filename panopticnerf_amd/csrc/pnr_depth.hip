@@ -27,8 +27,6 @@ struct DepthFilterArgs {
     int16_t* support;
 };
 
-__device__ __forceinline__ bool depth_valid(float t) { return t > 0.0f && t <= FLT_MAX; }       // (false for NaN)
-
 __global__ __launch_bounds__(DF_THREADS) void k_depth_filter(const DepthFilterArgs a)
 {
     __shared__ float tile[DF_LH * DF_LW];
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_filter(const DepthFilterAr
     const float c = tile[(ly + r) * DF_LW + lx + r];
     float out = 0.0f;
     int count = 0;
-    if (depth_valid(c)) {
+    if (pnr_pos_finite(c)) {
         const float sigma = a.sigma_a + a.sigma_b * c;
         float acc = 0.0f, ws = 0.0f;
         for (int dy = -r; dy <= r; ++dy) {
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_filter(const DepthFilterAr
                 const float t = row[dx];
                 const float x = (t - c) / sigma;
                 const float u = 1.0f - x * x;
-                if (depth_valid(t) && u > 0.0f) {
+                if (pnr_pos_finite(t) && u > 0.0f) {
                     const float w = (gy * gs[dx < 0 ? -dx : dx]) * (u * u);
                     acc = acc + w * t;
                     ws = ws + w;
@@ -90,7 +88,7 @@ PNR_EXPORT int pnr_depth_filter(int width, int height, const float* depth_in, in
     PNR_REQUIRE(depth_in != depth_out, "pnr_depth_filter: depth_in and depth_out must differ (a pixel reads its neighbours)");
     PNR_REQUIRE(radius >= 0 && radius <= PNR_DEPTH_MAX_RADIUS, "pnr_depth_filter: radius must lie in 0 .. %d", PNR_DEPTH_MAX_RADIUS);
     for (int k = 0; k <= radius; ++k)
-        PNR_REQUIRE(g_host[k] > 0.0f && g_host[k] <= FLT_MAX, "pnr_depth_filter: g[%d] must be positive and finite", k);
+        PNR_REQUIRE(pnr_pos_finite(g_host[k]), "pnr_depth_filter: g[%d] must be positive and finite", k);
     PNR_REQUIRE(sigma_a >= 0.0f && sigma_a <= FLT_MAX && sigma_b >= 0.0f && sigma_b <= FLT_MAX && (sigma_a > 0.0f || sigma_b > 0.0f),
                 "pnr_depth_filter: sigma_a and sigma_b must be non-negative and finite, not both 0");
     PNR_REQUIRE(min_support >= 1, "pnr_depth_filter: min_support must be >= 1");
@@ -131,7 +129,7 @@ __device__ __forceinline__ float4 dn_record(const DepthNormalsArgs& a, int i, in
     const float t = a.depth[(size_t)j * (size_t)a.width + (size_t)i];
     bool ok;
     const PnrRayRec ray = pnr_camera_ray(a.model, a.cam, a.c2w, i, j, 0.0f, 0.0f, ok);
-    if (!(ok && depth_valid(t))) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!(ok && pnr_pos_finite(t))) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return make_float4(t * ray.lo.w, t * ray.hi.x, t * ray.hi.y, t);
 }
 
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_depth_normals(const DepthNormals
             const float cc = (cx * cx + cy * cy) + cz * cz;
             const float len = sqrtf(cc);
             code = PNR_NORMAL_DEGENERATE;
-            if (len > 0.0f && len <= FLT_MAX) {
+            if (pnr_pos_finite(len)) {
                 const float s = (cx * p.x + cy * p.y) + cz * p.z;
                 const float vv = (p.x * p.x + p.y * p.y) + p.z * p.z;
                 code = PNR_NORMAL_GRAZING;

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(PNR_TSDF_BLOCK) void k_tsdf_integrate(const pnr_fra
             const int iu = pnr_nearest_pixel(q.u, fr.width - 1), iv = pnr_nearest_pixel(q.v, fr.height - 1);  // 3
             const int64_t p = (int64_t)iv * fr.width + iu;          // inside the image: 0 <= iu < width, 0 <= iv < height
             const float d = dimg[p];                                                                // 4
-            if (!(d > 0.0f && d <= FLT_MAX && d <= a.max_depth)) continue;
+            if (!(pnr_pos_finite(d) && d <= a.max_depth)) continue;
             const float s = pnr_view_depth(fr.model, q) - d;                                        // 5
             if (s > a.trunc) continue;
             const float phi = s < -a.trunc ? -1.0f : s / a.trunc;                                   // 6
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(PNR_RAYCAST_BLOCK) void k_tsdf_raycast(const Raycas
                         gx = gx / a.step[0]; gy = gy / a.step[1]; gz = gz / a.step[2];
                         const float xx = gx * gx, yy = gy * gy, zz = gz * gz;
                         const float len = sqrtf((xx + yy) + zz);
-                        if (len > 0.0f && len <= FLT_MAX) { nx = -gx / len; ny = -gy / len; nz = -gz / len; }
+                        if (pnr_pos_finite(len)) { nx = -gx / len; ny = -gy / len; nz = -gz / len; }
                     }
                 }
             }

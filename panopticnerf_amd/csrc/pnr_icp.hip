@@ -2,14 +2,15 @@
 // world-space normals, as k_tsdf_raycast writes them.  k_icp_accumulate is one linearisation: per live pixel the projective
 // association (the ray of pnr_camera_ray, the projection of pnr_project_point -- pnr_camera_dev.h, the functions the ray,
 // reprojection and fusion kernels call, so the arithmetic is theirs bit for bit), the gates and the Jacobian row in float32, and
-// the 28 sums of the normal equations in double, reduced in the shape of k_depth_metrics (pnr_splat.hip): fixed stride order per
-// thread, the wave's butterfly, waves through LDS, one row of partials per workgroup, no floating atomics.  k_icp_solve is one
-// workgroup: it adds the rows in block order, factorises, and updates the pose where it lives, in device memory, so K iterations
-// are 2K launches with no host read between them.  tests/_icp_ref.py restates both.
+// the 28 sums of the normal equations in double, reduced in the one stated order (pnr_reduce_dev.h; DESIGN.md section 8 "Ordered
+// reductions"): one row of partials per workgroup, no floating atomics.  k_icp_solve is one workgroup: it adds the rows in block
+// order, factorises, and updates the pose where it lives, in device memory, so K iterations are 2K launches with no host read
+// between them.  tests/_icp_ref.py restates both.
 #include <float.h>
 
 #include "pnr_camera_dev.h"
 #include "pnr_common.h"
+#include "pnr_reduce_dev.h"
 
 struct IcpArgs {
     int model_l, model_m;
@@ -24,7 +25,7 @@ struct IcpArgs {
     unsigned long long* ws;             // slot 0: the rows written; then [blocks][PNR_ICP_ROW]
 };
 
-__global__ __launch_bounds__(256) void k_icp_accumulate(const IcpArgs a)
+__global__ __launch_bounds__(PNR_REDUCE_BLOCK) void k_icp_accumulate(const IcpArgs a)
 {
     __shared__ double red[4][PNR_ICP_SUMS];
     __shared__ unsigned int redc[4];
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const IcpArgs a)
         bool ok;
         const PnrRayRec ray = pnr_camera_ray(a.model_l, a.cam_l, ident, i, j, 0.0f, 0.0f, ok);
         const float t = a.depth_l[q];
-        if (ok && t > 0.0f && t <= FLT_MAX) {
+        if (ok && pnr_pos_finite(t)) {
             const float x = t * ray.lo.w, y = t * ray.hi.x, z = t * ray.hi.y;
             float qv[3], p[3];
 #pragma unroll
@@ -59,9 +60,11 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const IcpArgs a)
                 const int64_t mq = (int64_t)ib * a.width_m + ia;
                 const float dm = a.depth_m[mq];
                 const float nx = a.normal_m[mq * 3 + 0], ny = a.normal_m[mq * 3 + 1], nz = a.normal_m[mq * 3 + 2];
+                // pnr_finite3's test written out: called here, the same test holds four more registers (95 -> 99 VGPRs, a wave
+                // less per SIMD) and the launch measures 1 us (5 %) slower
                 const bool nfin = fabsf(nx) <= FLT_MAX && fabsf(ny) <= FLT_MAX && fabsf(nz) <= FLT_MAX;
                 code = PNR_ICP_NO_MODEL;
-                if (dm > 0.0f && dm <= FLT_MAX && nfin && (nx != 0.0f || ny != 0.0f || nz != 0.0f)) {
+                if (pnr_pos_finite(dm) && nfin && (nx != 0.0f || ny != 0.0f || nz != 0.0f)) {
                     bool okm;
                     const PnrRayRec rm = pnr_camera_ray(a.model_m, a.cam_m, a.c2w_m, ia, ib, 0.0f, 0.0f, okm);
                     if (okm) {
@@ -98,26 +101,14 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const IcpArgs a)
         if (a.code) a.code[q] = (uint8_t)code;
         if (a.residual) a.residual[q] = r;
     }
-    // fixed order: the wave's butterfly, then waves 0..3 of the block
-#pragma unroll
-    for (int k = 0; k < PNR_ICP_SUMS; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
+    // the row: 28 sums, then the count, whose four wave sums go to LDS before the sums' barrier, which covers them
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
     if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    unsigned long long* row = a.ws + 1 + (int64_t)blockIdx.x * PNR_ICP_ROW;
-    if (threadIdx.x < PNR_ICP_SUMS)
-        row[threadIdx.x] = (unsigned long long)__double_as_longlong(((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]);
-    if (threadIdx.x == PNR_ICP_SUMS) row[PNR_ICP_SUMS] = (unsigned long long)redc[0] + redc[1] + redc[2] + redc[3];
+    pnr_block_sum_rows(s, red, (double*)(a.ws + 1), PNR_ICP_ROW);
+    if (threadIdx.x == PNR_ICP_SUMS) a.ws[1 + (int64_t)blockIdx.x * PNR_ICP_ROW + PNR_ICP_SUMS] = (unsigned long long)redc[0] + redc[1] + redc[2] + redc[3];
     if (blockIdx.x == 0 && threadIdx.x == PNR_ICP_SUMS + 1) a.ws[0] = (unsigned long long)gridDim.x;
 }
-
-#define ICP_BATCH 32                    // rows k_icp_solve fetches at once
 
 struct IcpSolveArgs {
     const unsigned long long* ws;
@@ -163,24 +154,11 @@ __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a)
     __shared__ unsigned long long totc;
     const unsigned long long stored = a.ws[0];
     const int rows = stored < (unsigned long long)a.max_rows ? (int)stored : a.max_rows;      // (never past the workspace)
-    // lane s adds slot s of the rows in block order.  The additions are a serial chain, the loads need not be: ICP_BATCH rows are
-    // fetched at once (a row beyond the last counts +0.0, which changes no sum), then added in order.  One load per addition
-    // left the wave waiting a memory latency per row: measured 0.053 against 0.008 ms for 256 rows, results bit-identical.
+    // lane s adds slot s of the rows in block order: the sums' lanes as doubles, the count's lane as integers
     if (threadIdx.x < PNR_ICP_ROW) {
-        double v = 0.0;
-        unsigned long long c = 0;
-        for (int b0 = 0; b0 < rows; b0 += ICP_BATCH) {
-            unsigned long long raw[ICP_BATCH];
-#pragma unroll
-            for (int k = 0; k < ICP_BATCH; ++k) raw[k] = b0 + k < rows ? a.ws[1 + (int64_t)(b0 + k) * PNR_ICP_ROW + threadIdx.x] : 0ull;
-#pragma unroll
-            for (int k = 0; k < ICP_BATCH; ++k) {
-                v += __longlong_as_double((long long)raw[k]);       // (the sums' lanes)
-                c += raw[k];                                        // (the count's lane)
-            }
-        }
-        if (threadIdx.x < PNR_ICP_SUMS) tot[threadIdx.x] = v;
-        else totc = c;
+        const PnrRowsTotal t = pnr_rows_total<PNR_ICP_ROW>(a.ws + 1, rows, threadIdx.x);
+        if (threadIdx.x < PNR_ICP_SUMS) tot[threadIdx.x] = t.sum;
+        else totc = t.words;
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -266,11 +244,7 @@ __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a)
     a.hist[4] = (double)status;
 }
 
-static int64_t icp_blocks(int64_t n_pix)
-{
-    const int64_t b = (n_pix + 255) / 256;
-    return b < 1 ? 1 : b > PNR_ICP_MAX_BLOCKS ? PNR_ICP_MAX_BLOCKS : b;
-}
+static int64_t icp_blocks(int64_t n_pix) { return pnr_reduce_blocks(n_pix, PNR_ICP_MAX_BLOCKS); }
 
 PNR_EXPORT int64_t pnr_icp_workspace_bytes(int64_t n_pix)
 {
@@ -307,7 +281,7 @@ PNR_EXPORT int pnr_icp_accumulate(int model_l, const float* cam_l_host, int widt
     a.depth_l = depth_l; a.pose = pose12; a.depth_m = depth_m; a.normal_m = normal_m;
     a.code = code; a.residual = residual; a.ws = (unsigned long long*)workspace;
     const int grid = pnr_grid_cap(icp_blocks(a.npix), 1);         // (never above icp_blocks: the workspace holds it)
-    hipLaunchKernelGGL(k_icp_accumulate, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_icp_accumulate, dim3(grid), dim3(PNR_REDUCE_BLOCK), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_icp_accumulate");
     return PNR_OK;
 }

@@ -15,8 +15,10 @@
 #include <math.h>
 
 #include "pnr_common.h"
+#include "pnr_reduce_dev.h"
 
 #define PNR_MESH_BLOCK 256
+static_assert(PNR_MESH_BLOCK == PNR_SCAN_BLOCK, "the three scan kernels call pnr_block_scan_excl");
 #define PNR_MESH_ITEMS 4                                    // points a thread handles per chunk
 #define PNR_MESH_CHUNK (PNR_MESH_BLOCK * PNR_MESH_ITEMS)    // 1024 points: one entry of the chunk-sum level
 // -DPNR_MESH_BLOCKS_PER_CU=n (A/B builds): the capped grid of the per-point kernels.  Measured at 256^3 (profiles/README.md "Mesh"):
@@ -137,25 +139,6 @@ __device__ __forceinline__ unsigned mesh_info(unsigned cm, bool ex, bool ey, boo
 
 __device__ __forceinline__ mesh_u64 mesh_counts(unsigned info) { return (mesh_u64)__popc(info & 0x7Fu) | ((mesh_u64)(info >> 8) << 32); }
 
-// exclusive scan of x over the block's 256 threads in thread order; total = the block's sum.  lds: 4 words.
-__device__ __forceinline__ mesh_u64 mesh_block_scan(mesh_u64 x, mesh_u64* lds, mesh_u64& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    mesh_u64 incl = x;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const mesh_u64 y = __shfl_up(incl, dlt);
-        if (lane >= dlt) incl += y;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    const mesh_u64 w0 = lds[0], w1 = lds[1], w2 = lds[2], w3 = lds[3];
-    __syncthreads();                                                // lds may be written again by the caller's next trip
-    total = w0 + w1 + w2 + w3;
-    const mesh_u64 before = wave == 0 ? 0 : wave == 1 ? w0 : wave == 2 ? w0 + w1 : w0 + w1 + w2;
-    return incl - x + before;
-}
-
 // ---- count, step 1: info per point (zeros in the last chunk's padding) and the chunk's sum
 __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_classify(const float* __restrict__ field, MeshDims d, float level,
                                                                   unsigned short* __restrict__ info, mesh_u64* __restrict__ sums)
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_classify(const float* _
             mine += mesh_counts(w);
         }
         mesh_u64 total;
-        mesh_block_scan(mine, lds, total);
+        pnr_block_scan_excl<mesh_u64>(mine, lds, total);
         if (threadIdx.x == 0) sums[chunk] = total;
     }
 }
@@ -198,7 +181,7 @@ __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_scan_sums(mesh_u64* __r
             s += v[j];
         }
         mesh_u64 total;
-        mesh_u64 run = mesh_block_scan(s, lds, total) + carry;
+        mesh_u64 run = pnr_block_scan_excl<mesh_u64>(s, lds, total) + carry;
 #pragma unroll
         for (int j = 0; j < PNR_MESH_SCAN_ITEMS; ++j) {
             if (i0 + j < n_chunks) sums[i0 + j] = run;
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_scan_add(const unsigned
 #pragma unroll
         for (int j = 0; j < PNR_MESH_ITEMS; ++j) s += mesh_counts(w[j]);
         mesh_u64 total;
-        mesh_u64 run = mesh_block_scan(s, lds, total) + sums[chunk];
+        mesh_u64 run = pnr_block_scan_excl<mesh_u64>(s, lds, total) + sums[chunk];
 #pragma unroll
         for (int j = 0; j < PNR_MESH_ITEMS; ++j) {
             rec[n0 + j] = (run & 0xFFFFFFFFull) | ((mesh_u64)w[j] << 32);

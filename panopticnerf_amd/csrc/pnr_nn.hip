@@ -3,13 +3,14 @@
 // triangle mesh at a given density.  The search's answer is brute force's, bit for bit, whatever the table does: the key of
 // pnr_splat_points (distance bits, index) under a minimum, so collisions and a bucket visited twice cost time and nothing else.
 // Small gather-bound kernels in the style of pnr_splat.hip: one thread per point, query or output point, grid-stride; the only
-// LDS is the few words of the block-wide counters.  tests/_nn_ref.py restates every rule in numpy.
+// LDS is the few words of the block-wide counters and sums (pnr_reduce_dev.h; the metric sums take the order of DESIGN.md
+// section 8 "Ordered reductions").  tests/_nn_ref.py restates every rule in numpy.
 #include <float.h>
 #include <math.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
 #include "pnr_philox.h"
+#include "pnr_reduce_dev.h"
 #include "pnr_scan_dev.h"
 
 #define PNR_NN_EMPTY 0xFFFFFFFFFFFFFFFFull
@@ -22,14 +23,12 @@ struct NnGrid {
     unsigned int mask;                    // T - 1
 };
 
-__device__ __forceinline__ bool nn_finite3(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }
-
 __device__ __forceinline__ void nn_origin(const NnGrid& g, float& ox, float& oy, float& oz)
 {
     ox = oy = oz = 0.0f;
     if (g.n > 0) {
         const float x = g.ref[0], y = g.ref[1], z = g.ref[2];
-        if (nn_finite3(x, y, z)) { ox = x; oy = y; oz = z; }
+        if (pnr_finite3(x, y, z)) { ox = x; oy = y; oz = z; }
     }
 }
 
@@ -55,7 +54,7 @@ __device__ __forceinline__ void nn_scatter(const NnGrid& g, int32_t* __restrict_
     nn_origin(g, ox, oy, oz);
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < g.n; j += (int64_t)gridDim.x * blockDim.x) {
         const float x = g.ref[3 * j], y = g.ref[3 * j + 1], z = g.ref[3 * j + 2];
-        if (!nn_finite3(x, y, z)) continue;
+        if (!pnr_finite3(x, y, z)) continue;
         const unsigned int b = nn_bucket(nn_cell(x, ox, g.inv), nn_cell(y, oy, g.inv), nn_cell(z, oz, g.inv), g.mask);
         if (!FILL) {
             atomicAdd(&cursor[b], 1);
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(256) void k_nn_query(const NnQueryArgs a)
         const float qx = a.q[3 * i], qy = a.q[3 * i + 1], qz = a.q[3 * i + 2];
         unsigned long long best = PNR_NN_EMPTY;
         int slot = 2;
-        if (nn_finite3(qx, qy, qz)) {
+        if (pnr_finite3(qx, qy, qz)) {
             const int x0 = nn_cell(qx - a.dp, ox, a.g.inv), x1 = nn_cell(qx + a.dp, ox, a.g.inv);
             const int y0 = nn_cell(qy - a.dp, oy, a.g.inv), y1 = nn_cell(qy + a.dp, oy, a.g.inv);
             const int z0 = nn_cell(qz - a.dp, oz, a.g.inv), z1 = nn_cell(qz + a.dp, oz, a.g.inv);
@@ -144,7 +143,7 @@ struct CloudMetricArgs {
     int n_blocks;
 };
 
-__global__ __launch_bounds__(256) void k_cloud_metrics(const CloudMetricArgs a)
+__global__ __launch_bounds__(PNR_REDUCE_BLOCK) void k_cloud_metrics(const CloudMetricArgs a)
 {
     __shared__ double red[4][2];
     __shared__ unsigned int hc[PNR_CM_COUNTS];
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(256) void k_cloud_metrics(const CloudMetricArgs a)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.m; i += (int64_t)gridDim.x * blockDim.x) {
         const float d2 = a.dist2[i];
         if (d2 != d2) continue;
-        if (a.query && !nn_finite3(a.query[3 * i], a.query[3 * i + 1], a.query[3 * i + 2])) continue;
+        if (a.query && !pnr_finite3(a.query[3 * i], a.query[3 * i + 1], a.query[3 * i + 2])) continue;
         const bool found = a.index[i] >= 0;
         const double d = found ? sqrt((double)d2) : a.dmax;
         cnt[0] += 1u;
@@ -165,35 +164,15 @@ __global__ __launch_bounds__(256) void k_cloud_metrics(const CloudMetricArgs a)
         s[0] += d;
         s[1] += d * d;
     }
-    if (threadIdx.x < PNR_CM_COUNTS) hc[threadIdx.x] = 0;
-    __syncthreads();
-    // fixed order: the wave's butterfly, then waves 0..3 of the block (k_depth_metrics' order)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < PNR_CM_COUNTS; ++k) {
-        unsigned int c = cnt[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&hc[k], c);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        a.partial[(int64_t)blockIdx.x * 2 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    if (threadIdx.x < PNR_CM_COUNTS && hc[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)hc[threadIdx.x]);
+    pnr_block_sum_rows(s, red, a.partial, 2);
+    pnr_block_count_add(cnt, hc, a.counts);
 }
 
 // one block: term t adds the partials of blocks 0, 1, ... in that order, then once into sums[t] (no floating atomics anywhere)
 __global__ __launch_bounds__(64) void k_cloud_metrics_final(const CloudMetricArgs a)
 {
     if (threadIdx.x >= 2) return;
-    double v = 0.0;
-    for (int b = 0; b < a.n_blocks; ++b) v += a.partial[(int64_t)b * 2 + threadIdx.x];
+    const double v = pnr_rows_total<2>((const unsigned long long*)a.partial, a.n_blocks, threadIdx.x).sum;
     a.sums[threadIdx.x] = a.sums[threadIdx.x] + v;
 }
 
@@ -265,10 +244,9 @@ __global__ __launch_bounds__(256) void k_mesh_sample_emit(const SampleArgs a)
 
 // ---- entry points
 
-static bool nn_radius_ok(float d) { return d > 0.0f && d <= FLT_MAX; }
 // the cell size h = 2 Dp and its inverse are both finite: a denormal max_dist whose 1 / h is +inf would send the two corners of
 // a query's box to the two clamp cells, 2^21 cells per axis
-static bool nn_cell_ok(float d) { return nn_radius_ok(d * PNR_NN_PAD * 2.0f) && nn_radius_ok(1.0f / (d * PNR_NN_PAD * 2.0f)); }
+static bool nn_cell_ok(float d) { return pnr_pos_finite(d * PNR_NN_PAD * 2.0f) && pnr_pos_finite(1.0f / (d * PNR_NN_PAD * 2.0f)); }
 static bool nn_table_ok(int64_t T) { return T >= 2 && T <= PNR_NN_MAX_TABLE && (T & (T - 1)) == 0; }
 
 static NnGrid nn_grid(const float* ref, int64_t n, float max_dist, int64_t T, float* dp_out)
@@ -290,9 +268,9 @@ PNR_EXPORT int pnr_nn_build(const float* ref, int64_t n, float max_dist, int64_t
                             void* workspace, void* stream)
 {
     PNR_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, "pnr_nn_build: n must be within 0 .. 2^31 - 1");
-    PNR_REQUIRE(nn_radius_ok(max_dist), "pnr_nn_build: max_dist must be positive and finite (got %g)", (double)max_dist);
+    PNR_REQUIRE(pnr_pos_finite(max_dist), "pnr_nn_build: max_dist must be positive and finite (got %g)", (double)max_dist);
     PNR_REQUIRE(nn_table_ok(table_size), "pnr_nn_build: table_size must be a power of two in 2 .. 2^28 (got %lld)", (long long)table_size);
-    PNR_REQUIRE(nn_radius_ok(max_dist * PNR_NN_PAD * 2.0f), "pnr_nn_build: max_dist is too large: the cell size 2 max_dist overflows");
+    PNR_REQUIRE(pnr_pos_finite(max_dist * PNR_NN_PAD * 2.0f), "pnr_nn_build: max_dist is too large: the cell size 2 max_dist overflows");
     PNR_REQUIRE(nn_cell_ok(max_dist), "pnr_nn_build: max_dist is too small: 1 / (2 max_dist) overflows (got %g)", (double)max_dist);
     PNR_REQUIRE(((uintptr_t)start & 3) == 0, "pnr_nn_build: start must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -324,9 +302,9 @@ PNR_EXPORT int pnr_nn_query(const float* ref, int64_t n, float max_dist, int64_t
 {
     PNR_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, "pnr_nn_query: n must be within 0 .. 2^31 - 1");
     PNR_REQUIRE(m >= 0 && m <= (int64_t)INT32_MAX, "pnr_nn_query: m must be within 0 .. 2^31 - 1");
-    PNR_REQUIRE(nn_radius_ok(max_dist), "pnr_nn_query: max_dist must be positive and finite (got %g)", (double)max_dist);
+    PNR_REQUIRE(pnr_pos_finite(max_dist), "pnr_nn_query: max_dist must be positive and finite (got %g)", (double)max_dist);
     PNR_REQUIRE(nn_table_ok(table_size), "pnr_nn_query: table_size must be a power of two in 2 .. 2^28 (got %lld)", (long long)table_size);
-    PNR_REQUIRE(nn_radius_ok(max_dist * PNR_NN_PAD * 2.0f), "pnr_nn_query: max_dist is too large: the cell size 2 max_dist overflows");
+    PNR_REQUIRE(pnr_pos_finite(max_dist * PNR_NN_PAD * 2.0f), "pnr_nn_query: max_dist is too large: the cell size 2 max_dist overflows");
     PNR_REQUIRE(nn_cell_ok(max_dist), "pnr_nn_query: max_dist is too small: 1 / (2 max_dist) overflows (got %g)", (double)max_dist);
     if (m == 0) return PNR_OK;
     PNR_REQUIRE(start && query && index && dist2, "pnr_nn_query: null start, query, index or dist2");
@@ -346,23 +324,17 @@ PNR_EXPORT int pnr_nn_query(const float* ref, int64_t n, float max_dist, int64_t
     return PNR_OK;
 }
 
-static int64_t cloud_metric_blocks(int64_t m)
-{
-    const int64_t b = (m + 255) / 256;
-    return b < 1 ? 1 : b > PNR_CM_MAX_BLOCKS ? PNR_CM_MAX_BLOCKS : b;
-}
-
 PNR_EXPORT int64_t pnr_cloud_metrics_workspace_bytes(int64_t m)
 {
     if (m < 0 || m > (int64_t)INT32_MAX) return -1;
-    return cloud_metric_blocks(m) * 2 * (int64_t)sizeof(double);
+    return pnr_reduce_blocks(m, PNR_CM_MAX_BLOCKS) * 2 * (int64_t)sizeof(double);
 }
 
 PNR_EXPORT int pnr_cloud_metrics(const int32_t* index, const float* dist2, const float* query, int64_t m, float max_dist,
                                  const float* tau_host, int n_tau, double* sums, int64_t* counts, void* workspace, void* stream)
 {
     PNR_REQUIRE(m >= 0 && m <= (int64_t)INT32_MAX, "pnr_cloud_metrics: m must be within 0 .. 2^31 - 1");
-    PNR_REQUIRE(nn_radius_ok(max_dist), "pnr_cloud_metrics: max_dist must be positive and finite (got %g)", (double)max_dist);
+    PNR_REQUIRE(pnr_pos_finite(max_dist), "pnr_cloud_metrics: max_dist must be positive and finite (got %g)", (double)max_dist);
     PNR_REQUIRE(n_tau >= 0 && n_tau <= PNR_CLOUD_MAX_TAU, "pnr_cloud_metrics: n_tau must be within 0 .. %d thresholds (got %d)", PNR_CLOUD_MAX_TAU, n_tau);
     PNR_REQUIRE(n_tau == 0 || tau_host, "pnr_cloud_metrics: null tau_host");
     CloudMetricArgs a;
@@ -378,8 +350,8 @@ PNR_EXPORT int pnr_cloud_metrics(const int32_t* index, const float* dist2, const
     PNR_REQUIRE((((uintptr_t)sums | (uintptr_t)counts | (uintptr_t)workspace) & 7) == 0, "pnr_cloud_metrics: sums, counts and workspace must be 8-byte aligned");
     a.index = index; a.dist2 = dist2; a.query = query; a.m = m; a.dmax = (double)max_dist; a.n_tau = n_tau;
     a.partial = (double*)workspace; a.sums = sums; a.counts = (unsigned long long*)counts;
-    a.n_blocks = pnr_grid_cap(cloud_metric_blocks(m), 4);       // (never above cloud_metric_blocks: the workspace holds it)
-    hipLaunchKernelGGL(k_cloud_metrics, dim3(a.n_blocks), dim3(256), 0, (hipStream_t)stream, a);
+    a.n_blocks = pnr_grid_cap(pnr_reduce_blocks(m, PNR_CM_MAX_BLOCKS), 4);       // (never above that: the workspace holds it)
+    hipLaunchKernelGGL(k_cloud_metrics, dim3(a.n_blocks), dim3(PNR_REDUCE_BLOCK), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(k_cloud_metrics_final, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_cloud_metrics");
     return PNR_OK;

@@ -6,11 +6,12 @@
 //                        thread that holds item n - 1 also writes out[n], the int32 total.
 // out has n + 1 entries and MAY BE `in` itself: a workgroup reads its own tile before it writes it, and launch 1 is over.
 // The int32 prefix wraps when the total passes 2^31 - 1; a caller for whom that can happen reads total64 and refuses.
-// (The scan inside pnr_mesh.hip works on its packed info words and is a different one.)
+// The block primitive is pnr_block_scan_excl (pnr_reduce_dev.h), the one pnr_mesh.hip scans its packed 64-bit counts with; that
+// file's multi-launch scan around it (chunk sums out of the classify kernel, 64-bit words) is a different one.
 #pragma once
 #include "pnr_common.h"
+#include "pnr_reduce_dev.h"
 
-#define PNR_SCAN_BLOCK 256
 #define PNR_SCAN_PER_THREAD 4
 #define PNR_SCAN_TILE (PNR_SCAN_BLOCK * PNR_SCAN_PER_THREAD)
 
@@ -20,32 +21,6 @@ static inline int64_t pnr_scan_tiles(int64_t n) { return (n + PNR_SCAN_TILE - 1)
 static inline int64_t pnr_scan_workspace_bytes(int64_t n) { return (pnr_scan_tiles(n) * 4 + 7) & ~(int64_t)7; }
 
 #ifdef __HIPCC__
-// exclusive scan of v over the 256 threads of the workgroup in thread order; total: the workgroup's sum.  lds: 4 words of T,
-// free again on return.
-template <typename T>
-__device__ __forceinline__ T pnr_block_scan_excl(T v, T* lds, T& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < PNR_SCAN_BLOCK / 64; ++w) {
-        const T s = lds[w];
-        before += w < wave ? s : (T)0;
-        total += s;
-    }
-    __syncthreads();
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_tile_sums(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums)
 {
     __shared__ int32_t lds[4];

@@ -2,13 +2,15 @@
 // into a z-buffer of packed 64-bit keys (depth bits, point index) with one native unsigned 64-bit atomic minimum per covered
 // pixel, so the nearest point wins, a depth tie goes to the lowest index and the result does not depend on arrival order; a
 // second kernel unpacks the buffer into a depth and an index image; a third accumulates depth-error metrics of a predicted
-// depth image against such a ground truth.  Small scatter- / gather-bound kernels in the style of pnr_warp.hip: one thread per
+// depth image against such a ground truth (its double sums in the order of DESIGN.md section 8 "Ordered reductions",
+// pnr_reduce_dev.h).  Small scatter- / gather-bound kernels in the style of pnr_warp.hip: one thread per
 // point or pixel, grid-stride, camera and pose in the kernel arguments.  The projection is pnr_project_point (pnr_camera_dev.h)
 // and nothing else, so the arithmetic is k_project_points' bit for bit (the nearest pixel and the stored depth are k_reproject's); tests/_splat_ref.py restates the whole rule in numpy.
 #include <float.h>
 
 #include "pnr_camera_dev.h"
 #include "pnr_common.h"
+#include "pnr_reduce_dev.h"
 
 // -DPNR_SPLAT_PREREAD=1 (A/B builds): a plain read of the cell skips the atomic when the key cannot lower it.  A cell only ever
 // decreases, so a stale read errs towards issuing the atomic.  Off by default; tools/splat_time.py is its A/B (profiles/README.md
@@ -93,7 +95,7 @@ struct DepthMetricArgs {
     int n_blocks;
 };
 
-__global__ __launch_bounds__(256) void k_depth_metrics(const DepthMetricArgs a)
+__global__ __launch_bounds__(PNR_REDUCE_BLOCK) void k_depth_metrics(const DepthMetricArgs a)
 {
     __shared__ double red[4][5];
     __shared__ unsigned int hc[5];
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void k_depth_metrics(const DepthMetricArgs a)
         const float g = a.gt[i];
         if (!(fabsf(g) <= FLT_MAX && g >= a.d_min && g <= a.d_max)) continue;
         const float p = a.pred[i];
-        if (!(p > 0.0f && p <= FLT_MAX)) {
+        if (!pnr_pos_finite(p)) {
             cnt[4] += 1u;
             continue;
         }
@@ -123,36 +125,15 @@ __global__ __launch_bounds__(256) void k_depth_metrics(const DepthMetricArgs a)
         s[3] += d2 / gd;
         s[4] += l * l;
     }
-    if (threadIdx.x < 5) hc[threadIdx.x] = 0;
-    __syncthreads();
-    // fixed order: the wave's butterfly, then waves 0..3 of the block
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        double v = s[k];
-        unsigned int c = cnt[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            v += __shfl_xor(v, m, 64);
-            c += __shfl_xor(c, m, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            red[threadIdx.x >> 6][k] = v;
-            if (c) atomicAdd(&hc[k], c);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        a.partial[(int64_t)blockIdx.x * 5 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-        if (hc[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)hc[threadIdx.x]);
-    }
+    pnr_block_sum_rows(s, red, a.partial, 5);
+    pnr_block_count_add(cnt, hc, a.counts);
 }
 
 // one block: term t adds the partials of blocks 0, 1, ... in that order, then once into sums[t] (no floating atomics anywhere)
 __global__ __launch_bounds__(64) void k_depth_metrics_final(const DepthMetricArgs a)
 {
     if (threadIdx.x >= 5) return;
-    double v = 0.0;
-    for (int b = 0; b < a.n_blocks; ++b) v += a.partial[(int64_t)b * 5 + threadIdx.x];
+    const double v = pnr_rows_total<5>((const unsigned long long*)a.partial, a.n_blocks, threadIdx.x).sum;
     a.sums[threadIdx.x] = a.sums[threadIdx.x] + v;
 }
 
@@ -198,16 +179,10 @@ PNR_EXPORT int pnr_splat_resolve(const int64_t* zbuf, int64_t n_pix, float* dept
     return PNR_OK;
 }
 
-static int64_t depth_metric_blocks(int64_t n)
-{
-    const int64_t b = (n + 255) / 256;
-    return b < 1 ? 1 : b > PNR_DM_MAX_BLOCKS ? PNR_DM_MAX_BLOCKS : b;
-}
-
 PNR_EXPORT int64_t pnr_depth_metrics_workspace_bytes(int64_t n)
 {
     if (n < 0) return -1;
-    return depth_metric_blocks(n) * 5 * (int64_t)sizeof(double);
+    return pnr_reduce_blocks(n, PNR_DM_MAX_BLOCKS) * 5 * (int64_t)sizeof(double);
 }
 
 PNR_EXPORT int pnr_depth_metrics(const float* pred, const float* gt, const uint8_t* mask, int64_t n, float d_min, float d_max,
@@ -221,9 +196,9 @@ PNR_EXPORT int pnr_depth_metrics(const float* pred, const float* gt, const uint8
     DepthMetricArgs a;
     a.pred = pred; a.gt = gt; a.mask = mask; a.n = n; a.d_min = d_min; a.d_max = d_max;
     a.partial = (double*)workspace; a.sums = sums; a.counts = (unsigned long long*)counts;
-    const int64_t blocks = depth_metric_blocks(n);
+    const int64_t blocks = pnr_reduce_blocks(n, PNR_DM_MAX_BLOCKS);
     a.n_blocks = pnr_grid_cap(blocks, 4);               // (never above `blocks`: the workspace holds it)
-    hipLaunchKernelGGL(k_depth_metrics, dim3(a.n_blocks), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_depth_metrics, dim3(a.n_blocks), dim3(PNR_REDUCE_BLOCK), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(k_depth_metrics_final, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_depth_metrics");
     return PNR_OK;

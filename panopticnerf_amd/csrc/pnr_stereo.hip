@@ -466,7 +466,7 @@ PNR_EXPORT int pnr_sgm_select(const uint16_t* S, int width, int height, int max_
 PNR_EXPORT int pnr_disparity_depth(const int16_t* d16, int64_t n, float fb, float d_min, float d_max, float* depth, void* stream)
 {
     PNR_REQUIRE(n >= 0, "pnr_disparity_depth: bad size");
-    PNR_REQUIRE(fb > 0.0f && fb <= FLT_MAX, "pnr_disparity_depth: fb = fx * baseline must be positive and finite");
+    PNR_REQUIRE(pnr_pos_finite(fb), "pnr_disparity_depth: fb = fx * baseline must be positive and finite");
     PNR_REQUIRE(d_min > 0.0f && d_min <= d_max, "pnr_disparity_depth: the range must satisfy 0 < d_min <= d_max (d_max may be +inf)");
     if (n == 0) return PNR_OK;
     PNR_REQUIRE(d16 && depth, "pnr_disparity_depth: null d16 or depth");

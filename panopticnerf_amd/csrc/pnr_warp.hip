@@ -3,13 +3,14 @@
 // images on both sides the visible pairs are counted into the cross-view confusion matrix of the multi-view consistency metric.
 // A small gather-bound kernel in the style of pnr_camera.hip: one thread per source pixel, grid-stride, cameras and poses in
 // the kernel arguments.  The ray is pnr_camera_ray and the projection pnr_project_point (pnr_camera_dev.h), the same functions
-// the ray and projection kernels call, so the arithmetic is theirs bit for bit; the nearest pixel, the depth a view stores and
-// the reduction of the stats are that header's too (shared with pnr_splat.hip).  tests/_warp_ref.py restates the whole rule in
-// float32 (tests/_pano_ref.py with a panoramic view on either side).
+// the ray and projection kernels call, so the arithmetic is theirs bit for bit; the nearest pixel and the depth a view stores
+// are that header's too (shared with pnr_splat.hip), the reduction of the stats is pnr_reduce_dev.h's.  tests/_warp_ref.py
+// restates the whole rule in float32 (tests/_pano_ref.py with a panoramic view on either side).
 #include <float.h>
 
 #include "pnr_camera_dev.h"
 #include "pnr_common.h"
+#include "pnr_reduce_dev.h"
 
 #define PNR_WARP_LDS_CLASSES 128        // up to here `agree` is a per-block LDS histogram (k_confusion's limit: 64 KiB)
 
@@ -51,7 +52,8 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
             bool ok;
             const PnrRayRec ray = pnr_camera_ray(a.model_src, a.cam_src, a.c2w, i, j, 0.0f, 0.0f, ok);
             const float t = a.depth_src[p];
-            if (ok && t > 0.0f && t <= FLT_MAX) {
+            const bool have = pnr_pos_finite(t);     // (named first: called inside the chain below, the compiler lays the kernel out anew)
+            if (ok && have) {
                 const float X = ray.lo.x + t * ray.lo.w, Y = ray.lo.y + t * ray.hi.x, Z = ray.lo.z + t * ray.hi.y;
                 const PnrProj q = pnr_project_point(a.model_tgt, a.cam_tgt, a.w2c, a.umax, X, Y, Z);
                 u = q.u;
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
                     if (a.depth_tgt) {
                         const float e = pnr_view_depth(a.model_tgt, q);
                         const float dt = a.depth_tgt[tq];
-                        if (!(dt > 0.0f && dt <= FLT_MAX)) code = -3;
+                        if (!pnr_pos_finite(dt)) code = -3;
                         else if (!(fabsf(e - dt) <= a.tol_abs + a.tol_rel * e)) code = -4;
                     }
                     if (code >= 0 && count) {

@@ -8,8 +8,9 @@
     (test_icp_ref.py: its checks can fail).
 (c) accumulate64: the same decisions in float64, and `excluded`: the pixels where float32 may legitimately decide differently,
     from a running first-order error bound (_warp_ref.E) carried through this rule's own operations.
-(d) the sums: `terms` (the exact per-pixel products, in float64), `rows_device` (the kernel's summation order: a thread's
-    stride order, the wave's butterfly, the four waves, one row per workgroup) and `combine` (the rows in block order).
+(d) the sums: `terms` (the exact per-pixel products, in float64), `rows_device` and `combine` (the kernel's summation order,
+    restated once for every ordered sum of the library in _reduce_ref.py: a thread's stride order, the wave's butterfly, the
+    four waves, one row per workgroup, the rows in block order).
 (e) solve: the Cholesky factorisation, the series and the pose update in Python floats (IEEE double), in the header's order.
 
 A live frame is (model, cam, width, height); a model view is (model, cam, c2w (3, 4), width, height) with depth (height, width)
@@ -21,6 +22,7 @@ import numpy as np
 
 import _camera_ref as cr
 import _pano_ref as pr
+import _reduce_ref as rr
 import _tsdf_ref as tr
 import _warp_ref as wr
 
@@ -271,41 +273,23 @@ def terms(out):
 
 def blocks_for(n_pix, compute_units=256):
     """the grid of k_icp_accumulate on a device of that many compute units"""
-    return max(1, min((n_pix + 255) // 256, MAX_BLOCKS, compute_units))
+    return rr.blocks_for(n_pix, MAX_BLOCKS, compute_units, 1)
 
 
 def rows_device(out, n_pix, grid):
-    """(grid, 28) float64 and (grid) int64: the rows a launch of `grid` workgroups writes, in the kernel's order of additions"""
+    """(grid, 28) float64 and (grid) int64: the rows a launch of `grid` workgroups writes, in the kernel's order of additions
+    (_reduce_ref.rows_device; a pixel that is no MATCH adds nothing)"""
     T, idx = terms(out)
     full = np.zeros((n_pix, SUMS))
     full[idx] = T
-    hit = np.zeros(n_pix, np.int64)
-    hit[idx] = 1
-    threads = grid * 256
-    trips = (n_pix + threads - 1) // threads
-    pad = np.zeros((trips * threads, SUMS))
-    pad[:n_pix] = full
-    padc = np.zeros(trips * threads, np.int64)
-    padc[:n_pix] = hit
-    acc = np.zeros((threads, SUMS))
-    for k in range(trips):                      # a thread's pixels in stride order; a pixel that is no MATCH adds nothing
-        chunk = pad[k * threads:(k + 1) * threads]
-        acc = np.where(padc[k * threads:(k + 1) * threads, None] != 0, acc + chunk, acc)
-    v = acc.reshape(grid, 4, 64, SUMS)
-    lane = np.arange(64)
-    for m in (32, 16, 8, 4, 2, 1):              # the butterfly: every lane adds its partner's value
-        v = v + v[:, :, lane ^ m]
-    w = v[:, :, 0]
-    rows = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
-    return rows, padc.reshape(trips, grid, 256).sum((0, 2))
+    hit = np.zeros(n_pix, bool)
+    hit[idx] = True
+    return rr.rows_device(full, hit, grid)
 
 
 def combine(rows, counts):
     """the 28 sums and the count of rows added in block order from 0.0"""
-    tot = [0.0] * SUMS
-    for row in np.asarray(rows, np.float64).reshape(-1, SUMS):
-        tot = [tot[k] + float(row[k]) for k in range(SUMS)]
-    return tot, int(np.sum(np.asarray(counts, np.int64)))
+    return rr.combine(np.asarray(rows, np.float64).reshape(-1, SUMS)), int(np.sum(np.asarray(counts, np.int64)))
 
 
 # ------------------------------------------------------------------------------------------------ (e) the solve

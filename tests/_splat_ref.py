@@ -221,6 +221,24 @@ def metrics32_64(pred, gt, mask=None, d_range=(1e-3, 80.0), variant=None):
     return sums, counts, bound
 
 
+def metric_terms(pred, gt, mask=None, d_range=(1e-3, 80.0)):
+    """((n, 5) float64, (n) bool): every pixel's five terms in the kernel's operation order (zeros where the pixel adds nothing)
+    and the pixels that add.  Terms 0 .. 3 are single IEEE + - * / on doubles made from float32 inputs: the kernel's bits.
+    Term 4 goes through the logarithm and is the kernel's only to the bound of metrics32_64."""
+    f = np.float32
+    p, g = np.asarray(pred, f).reshape(-1), np.asarray(gt, f).reshape(-1)
+    with np.errstate(all="ignore"):
+        ok = (np.abs(g) <= FMAX) & (g >= f(d_range[0])) & (g <= f(d_range[1])) & (p > 0) & (np.abs(p) <= FMAX)
+        if mask is not None:
+            ok &= np.asarray(mask).reshape(-1) != 0
+        pd, gd = np.where(ok, p, f(1.0)).astype(np.float64), np.where(ok, g, f(1.0)).astype(np.float64)
+        d = pd - gd
+        ad, d2 = np.abs(d), d * d
+        l = np.log(pd) - np.log(gd)
+        terms = np.stack([ad, d2, ad / gd, d2 / gd, l * l], -1)
+    return np.where(ok[:, None], terms, 0.0), ok
+
+
 def summary(sums, counts):
     """what Evaluator.summarize() reports of the depth accumulators"""
     n = int(counts[0])

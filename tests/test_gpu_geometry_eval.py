@@ -3,7 +3,8 @@
 non-negative float64 terms added in another order than math.fsum: every partial sum is at most the total S and each of the
 m - 1 additions rounds by at most 2^-53 of it, so |sum - fsum| <= m 2^-53 S -- for m <= 10^4 a relative 1.2e-12, asserted as
 1e-12 (the issue's bound; the tests print the share of it used).  The terms themselves are equal on both sides: the square root of
-a float32 in double is correctly rounded in numpy and in the kernel."""
+a float32 in double is correctly rounded in numpy and in the kernel.  On inputs whose roots are exact the sums also equal
+_reduce_ref's restatement of the kernel's order of additions bit for bit."""
 import math
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 import _nn_ref as nr
+import _reduce_ref as rr
 from panopticnerf_amd import ops, pointcloud
 from panopticnerf_amd.evaluate import Evaluator
 
@@ -74,6 +76,49 @@ def test_cloud_metrics_counts_and_sums(dev):
     first_s = nr.cloud_metrics(index, dist2, D, TAUS, query=q)[0]
     close(float(sums[0]), math.fsum([want_s[0], first_s[0]]), "sum d, accumulated")
     close(float(sums[1]), math.fsum([want_s[1], first_s[1]]), "sum d^2, accumulated")
+
+
+# 1 .. 1000: one lane, a wave less one, a wave, two waves, a block less one, a block, two blocks, four; then a second trip
+ORDER_SIZES = (1, 63, 64, 65, 255, 256, 257, 1000, "second trip")
+
+
+@pytest.mark.parametrize("m", ORDER_SIZES)
+def test_cloud_metrics_sums_in_the_stated_order_to_the_bit(dev, m):
+    """both sums equal _reduce_ref's restatement of the order (a thread's stride order, the butterfly, the four waves, the rows
+    in block order) bit for bit, for the grid the entry point derives from the device; "second trip": just past 256 x the full
+    grid + 1, so threads add a second item.  dist2 holds squares of k 2^e, k < 2^12: exact in float32 with an exact root, so any
+    faithful sqrt returns k 2^e and the test pins the order, not the libm; e spans 44 binades, so the additions round and
+    another order gives other bits (asserted on the reference side).  Rows without a neighbour add max_dist, rows with a NaN
+    dist2 or a non-finite query add nothing.  Accumulating into given sums is old + new to the bit."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if m == "second trip":
+        m = 256 * min(1024, 4 * cus) + 77
+    grid = rr.blocks_for(m, 1024, cus, 4)
+    rng = np.random.default_rng(m)
+    root = np.ldexp(rng.integers(1, 4096, m).astype(np.float32), rng.integers(-50, -6, m)).astype(np.float32)
+    dist2 = root * root
+    assert np.array_equal(dist2.astype(np.float64), root.astype(np.float64) ** 2) and np.array_equal(np.sqrt(dist2.astype(np.float64)), root.astype(np.float64))
+    index = rng.integers(0, 1000, m).astype(np.int32)
+    q = rng.uniform(-4, 4, size=(m, 3)).astype(np.float32)
+    if m > 1:
+        lost, nan, bad = (rng.choice(m, max(m // 7, 1), replace=False) for _ in range(3))
+        index[lost], dist2[lost] = -1, np.inf
+        dist2[nan] = np.nan
+        q[bad, rng.integers(0, 3, bad.size)] = np.resize(np.float32([np.nan, np.inf, -np.inf]), bad.size)
+    max_dist = 1.7
+    active = ~np.isnan(dist2) & nr.finite_rows(q)
+    d = np.where(index >= 0, root.astype(np.float64), np.float64(np.float32(max_dist)))
+    terms = np.where(active[:, None], np.stack([d, d * d], -1), 0.0)
+    want = rr.total(terms, active, grid)
+    if m > 1000:
+        assert (want != rr.total(terms[::-1], active[::-1], grid)).all(), "the data do not tell two orders apart"
+    i_d, d_d, q_d = G(index, dev), G(dist2, dev), G(q, dev)
+    sums, counts = ops.cloud_metrics(i_d, d_d, max_dist, query=q_d)
+    assert counts.tolist()[:2] == [int(active.sum()), int((active & (index < 0)).sum())] and active.any()
+    assert np.array_equal(N_(sums).view(np.uint64), want.view(np.uint64)), (m, grid, N_(sums), want)
+    old = torch.tensor([1e6 / 3.0, 0.1], dtype=torch.float64, device=dev)
+    acc, acc_c = ops.cloud_metrics(i_d, d_d, max_dist, query=q_d, sums=old.clone(), counts=counts.clone())
+    assert np.array_equal(N_(acc).view(np.uint64), (N_(old) + want).view(np.uint64)) and torch.equal(acc_c, 2 * counts)
 
 
 def test_sqrt_of_a_float32_in_double_is_the_same_on_both_sides(dev):

@@ -2,7 +2,8 @@
 against tests/_splat_ref.py's restatement of the rule (include/pnr.h "point splatting").  The z-buffer, the two resolved images
 and every counter are integers or float32 words that must be EQUAL; only the metric sums (float64, another summation order
 than math.fsum) carry a bound, the one _splat_ref.metrics32_64 derives per term (test_depth_metrics prints the largest share of
-it that each case uses).  tests/test_splat_ref.py pins the restatement on the CPU."""
+it that each case uses), and the four sums without a logarithm also equal _reduce_ref's restatement of the kernel's order of
+additions bit for bit.  tests/test_splat_ref.py pins the restatement on the CPU."""
 import itertools
 from types import SimpleNamespace as NS
 
@@ -12,6 +13,7 @@ import torch
 
 import _camera_ref as cr
 import _pano_ref as pr
+import _reduce_ref as rr
 import _splat_ref as sr
 from panopticnerf_amd import Equirect, Fisheye, Pinhole, camera, make_network, make_renderer, ops, pointcloud, synthetic
 from panopticnerf_amd.evaluate import Evaluator
@@ -423,6 +425,40 @@ def test_depth_metrics(dev):
     s, c = ops.depth_metrics(T(pred.reshape(48, 64), dev), T(gt.reshape(48, 64), dev), d_range=(2.0, 30.0))
     ws, wc, wb = sr.metrics32_64(pred, gt, None, (2.0, 30.0))
     assert np.array_equal(N_(c), wc) and (np.abs(N_(s) - ws) <= wb).all()
+
+
+# 1 .. 1000: one lane, a wave less one, a wave, two waves, a block less one, a block, two blocks, four; then a second trip
+ORDER_SIZES = (1, 63, 64, 65, 255, 256, 257, 1000, "second trip")
+
+
+@pytest.mark.parametrize("n", ORDER_SIZES)
+def test_depth_metrics_sums_in_the_stated_order_to_the_bit(dev, n):
+    """sums 0 .. 3 (|d|, d^2, |d| / gt, d^2 / gt) equal _reduce_ref's restatement of the order (a thread's stride order, the
+    butterfly, the four waves, the rows in block order) bit for bit, for the grid the entry point derives from the device;
+    "second trip": just past 256 x the full grid + 1, so threads add a second item.  Their terms are single IEEE + - * / on
+    doubles made from float32 inputs, which numpy float64 reproduces exactly.  Sum 4 goes through the device's double log,
+    which nobody has shown to be correctly rounded: it stays under the derived bound of _splat_ref.metrics32_64 only.
+    Accumulating into given sums is old + new to the bit."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if n == "second trip":
+        n = 256 * min(1024, 4 * cus) + 77
+    grid = rr.blocks_for(n, 1024, cus, 4)
+    pred, gt, mask = _depth_pair(n, 1000 + n)
+    if n == 1:
+        pred[:], gt[:], mask[:] = 12.5, 10.0, 1
+    terms, active = sr.metric_terms(pred, gt, mask)
+    assert active.any() and (n < 63 or not active.all())
+    want = rr.total(terms[:, :4], active, grid)
+    P, G, M = T(pred, dev), T(gt, dev), T(mask, dev)
+    s, c = ops.depth_metrics(P, G, M)
+    assert int(c[0]) == int(active.sum())
+    assert np.array_equal(N_(s)[:4].view(np.uint64), want.view(np.uint64)), (n, grid, N_(s)[:4], want)
+    ws, _, wb = sr.metrics32_64(pred, gt, mask)
+    assert abs(float(s[4]) - ws[4]) <= wb[4]
+    old = torch.tensor([0.1, 1e6 / 3.0, 7.0, 1e-9, 2.5], dtype=torch.float64, device=dev)
+    acc_s, acc_c = ops.depth_metrics(P, G, M, sums=old.clone(), counts=c.clone())
+    assert np.array_equal(N_(acc_s)[:4].view(np.uint64), (N_(old)[:4] + want).view(np.uint64)) and torch.equal(acc_c, 2 * c)
+    assert torch.equal(acc_s[4:], old[4:] + s[4:])
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,7 @@
 """pnr_nn_build and pnr_nn_query on a room-sized cloud, hip events (torch.cuda.Event) around a captured graph of 20 launches, in
 one process (profiles/README.md "Nearest neighbours"): the surface points of synthetic.room_depth seen through an equirect
 camera, lifted; n of them are the reference cloud, n others, moved by a few centimetres, the queries, at D = 0.05 m.  Reports the
-build and the query time, the records tested per query (counted with torch from the table the build made), the bytes the query
+build and the query time, the cloud metrics of the answers (both kernels), the records tested per query (counted with torch from the table the build made), the bytes the query
 moves per second, the device's clocks, and -- for scale, not a pass mark -- a chunked torch.cdist brute force on a subset.
    python tools/nn_time.py [n] [rounds] [brute force subset]          (PNR_LIB_PATH selects an A/B build of the library)"""
 import os, subprocess, sys
@@ -107,6 +107,9 @@ print("    %-40s %s" % ("build (zero, count, scan, fill)", line))
 us_q, line = timed(lambda: ops.nn_query(ref, start, records, query, D, index=index, dist2=dist2))
 moved = n * (12 + 8 + 8 * per_bucket + 16 * per_query)          # query, outputs, a start pair per bucket, 16 bytes per record
 print("    %-40s %s   (%.1f GB/s asked of the memory system, %.1f Mqueries/s)" % ("query", line, moved / us_q / 1e3, n / us_q))
+cm_sums, cm_counts = torch.zeros(2, dtype=torch.float64, device=dev), torch.zeros(10, dtype=torch.int64, device=dev)
+_, line = timed(lambda: ops.cloud_metrics(index, dist2, D, (0.01, 0.02, 0.05), query=query, sums=cm_sums, counts=cm_counts))
+print("    %-40s %s" % ("cloud_metrics (both kernels)", line))
 lines, busy = clocks_while(lambda: ops.nn_query(ref, start, records, query, D, index=index, dist2=dist2))
 print("    clocks read %s:" % ("while the query ran" if busy else "AFTER the queued queries had finished"))
 for l in lines:
