@@ -27,35 +27,10 @@ import struct
 import sys
 from contextlib import contextmanager
 
-import os
-# Cache policy of the LDS-DMA weight pieces: the DEFAULT one.  With " nt" (what k_mlp_pp uses, -1 % there) this kernel's weight stream
-# missed the L2 for 20 % of its 69 GB per fine-level launch -- 13.8 GB of fabric traffic per launch (rocprofv3 FETCH_SIZE; k_mlp_pp: 2.1 GB,
-# the default policy: 0.09 GB) -- and the part paid for it in clock: 11.5 ms at 1773-1793 MHz with nt, 10.66 ms at 1863-1877 MHz without
-# (same box, profiles/r05/r05p).  tools/build_tt_variant.sh builds A/B variants (PNR_TT_DMA_POLICY=" nt" | " sc0" | " sc1").
-DMA_POLICY = os.environ.get("PNR_TT_DMA_POLICY", "")
-STORE_NT = ""           # cache policy of the record / quadruple stores (" nt": measured +-0, round 5)
-PIECE_FRAC = 1.0        # the pieces of a chunk go out in this first fraction of its gaps (0.5: measured slower)
-WAIT2 = os.environ.get("PNR_TT_WAIT2", "0") != "0"             # (A/B builds) one s_waitcnt lgkmcnt per two fragments instead of one per fragment
-# (A/B builds, tools/build_tt_variant.sh) the TRAINING-FORWARD PROTOTYPE: every packed activation block (trunk, feature, views, head hidden layers:
-# 5.4 KB per sample, what k_mlp_fused<TRAIN> saves for the backward pass) is also stored to a scratch region -- 1 KiB per store, fully
-# coalesced, layout arbitrary: the kernel's results stay valid, the stores are what is being timed (profiles/r06/r06p).  The library must be
-# told too: PNR_TT_SAVE_PROTO=1 in the environment makes the launcher allocate and pass the region.
-SAVE_PROTO = os.environ.get("PNR_TT_SAVE", "0") != "0"
-ABL_ALL = int(os.environ.get("PNR_TT_ABL", "0"))        # (A/B builds; results INVALID) the timing-only ablations in every kernel: 1 = no weight pieces
-SAVE_REGION = 352 * 1024                # bytes per wave and group: 2 tiles x 32 samples x 5.5 KiB
-# The pack / ReLU / v_accvgpr_write triples as a three-stage software pipeline over the packed registers of a unit (closure j: write of pair
-# j - 2, ReLU of pair j - 1, convert of pair j; three rotating temporaries): no instruction of a closure depends on another one of the same
-# closure, where the plain form is three DEPENDENT instructions back to back (A/B builds: PNR_TT_PACK_PIPE=0)
-PACK_PIPE = os.environ.get("PNR_TT_PACK_PIPE", "1") != "0"
-V_T2 = 15                               # third pack temporary (V_TRACE's register: trace / save-prototype builds keep the plain form)
-SHARE_BIAS = os.environ.get("PNR_TT_SHARE_BIAS", "1") != "0"     # one armed accumulator per block: tile 1's first MFMA reads tile 0's (A/B builds)
-NSLOT, SLOT = 4, int(os.environ.get("PNR_TT_SLOT_KIB", "33")) * 1024      # (A/B builds: the slot stride, tools/build_tt_variant.sh)
-ACC_PERM = [int(x) for x in os.environ.get("PNR_TT_ACC_PERM", "0,1,2,3,4,5,6,7").split(",")]     # register block of accumulator i (A/B builds)
-SLOT_POS = [int(x) for x in os.environ.get("PNR_TT_SLOT_ORDER", "0,1,2,3").split(",")]      # physical position of logical slot c % 4
-
-
-def slot_base(sl):
-    return SLOT_POS[sl] * SLOT
+# The training-forward prototype of this kernel (every packed activation block also stored, what k_mlp_fused<TRAIN> saves for the
+# backward pass) was measured and is gone: its 2 x 2 against the shipped kernel is recorded in profiles/r06/r06p and DESIGN.md 7.
+V_T2 = 15                               # third pack temporary (V_TRACE's register: trace builds keep the plain pack form)
+NSLOT, SLOT = 4, 33 * 1024              # chunk c in LDS slot c % 4 at (c % 4) * SLOT: other strides / slot orders +-0 (profiles/r05/r05t, r05v)
 P = 4                                   # fragment ring (quads)
 D, SKIP = 8, 4
 
@@ -86,8 +61,6 @@ S_SAVE, S_REC_T = 58, 60                # saved exec; the two tiles' record poin
 S_MSK = 64                              # store masks of the (up to) three logit blocks: s[64:69] = lanes with hi == 0 and channel < n_out
 S_REC_I = 70                            # the two tiles' record pointers + 4 n_sem (the instance columns): s[70:73]
 S_AUX = 82                              # s[82:83]: the per-ray table k_ray_aux wrote (gamma(d) of both half-waves and |d|: 128 B per ray)
-S_SV, S_SVBASE, S_SVT = 84, 88, 86      # save prototype: running store address s[84:85], the region's base s[88:89], a temporary
-V_SV = 15                               # save prototype: lane * 16 (V_TRACE's register: the trace builds have no save prototype)
 S_VMSK = 76                             # softmax kernels: s[76:77] / s[78:79] = ALL lanes whose channel of the semantic / instance head's last block exists
 S_LWW, S_LWR = 74, 75                   # LDS addresses of this wave's local-weight table: + 4 (lane & 31) to write, + (V_BIAS[0] = slot 0 + 16 hi) to read
 LW_BASE = NSLOT * SLOT                  # [4 waves][2 tiles][32 floats] behind the weight slots (1 KiB)
@@ -166,7 +139,7 @@ class Gen:
         # the tail normalises each head's transposed logit blocks per sample before the weighted sums (tail_softmax), operation for
         # operation fuse_softmax_t of the ping-pong kernel (pnr_mlp_fuse.h): k_mlp_tt_sm_s<n>i<m>
         self.softmax = softmax
-        self.nbs, self.nbi, self.name, self.trace, self.abl = nbs, nbi, name, trace, abl or ABL_ALL
+        self.nbs, self.nbi, self.name, self.trace, self.abl = nbs, nbi, name, trace, abl
         self.nstamp = 0
         self.o = []
         self.nlabel = 0
@@ -373,12 +346,13 @@ class Gen:
             self.e("s_cbranch_scc1 %s" % skip)
         # the instruction's immediate offset moves BOTH addresses (memory and LDS): M0 carries the run's base only -- and stays
         # what it is for the four pieces of a run (nothing else in the loop writes M0; trace builds do)
-        m0 = slot_base(slot) + 16 * m * 1024
+        m0 = slot * SLOT + 16 * m * 1024
         if self.m0 != m0 or skip or self.trace:
             self.e("s_add_u32 m0, s%d, 0x%x" % (S_W4K, m0))
             self.e("s_nop 0")                   # SALU write of M0 -> LDS-DMA: one wait state
         self.m0 = None if skip else m0          # (a guarded piece: the waves that skipped it did not write M0)
-        tag = self.vm_op("global_load_lds_dwordx4 v%d, s[%d:%d] offset:%d%s" % (V_DMA + m, S_PIECE, S_PIECE + 1, i * 1024, DMA_POLICY), certain)
+        # default cache policy: " nt" missed the L2 for 20 % of the weight stream and cost 7 % in clock (profiles/r05/r05p, r05q)
+        tag = self.vm_op("global_load_lds_dwordx4 v%d, s[%d:%d] offset:%d" % (V_DMA + m, S_PIECE, S_PIECE + 1, i * 1024), certain)
         if skip:
             self.o.append(skip + ":")
         return tag
@@ -806,17 +780,18 @@ class Gen:
             e("v_mov_b32 v%d, v%d" % (T[7], acc + 2))
             e("s_and_b64 s[%d:%d], s[%d:%d], s[%d:%d]" % (S_SAVE, S_SAVE + 1, VAL, VAL + 1, S_HI0, S_HI0 + 1))
             e("s_mov_b64 exec, s[%d:%d]" % (S_SAVE, S_SAVE + 1))
-            self.vm_op("global_store_dwordx4 v%d, %s, s[%d:%d]%s" % (d, vr(T[4], 4), S_PS, S_PS + 1, STORE_NT))
+            # default cache policy of the record / quadruple stores: " nt" measured +-0 (profiles/README.md, round 5 ablation table)
+            self.vm_op("global_store_dwordx4 v%d, %s, s[%d:%d]" % (d, vr(T[4], 4), S_PS, S_PS + 1))
             e("s_mov_b64 exec, 1")                                                   # lane 0: rec[0] = q
             e("v_mov_b32 v%d, s%d" % (x, S_Q))
             e("v_mov_b32 v%d, 0" % d)
-            self.vm_op("global_store_dword v%d, v%d, s[%d:%d]%s" % (d, x, S_REC_T + 2 * t, S_REC_T + 2 * t + 1, STORE_NT))
+            self.vm_op("global_store_dword v%d, v%d, s[%d:%d]" % (d, x, S_REC_T + 2 * t, S_REC_T + 2 * t + 1))
             e("s_mov_b64 exec, -1")
         self.q(28, stores)
 
     # ------------------------------------------------------------------ accumulators
     def acc_reg(self, i):
-        return V_ACC + 16 * ACC_PERM[i]
+        return V_ACC + 16 * i           # in order: swapped / interleaved register blocks measured +-0 (profiles/r05/r05v)
 
     def acc_take(self, n):
         assert len(self.acc_free) >= n, ("accumulators exhausted", self.acc_free)
@@ -846,16 +821,16 @@ class Gen:
                     while not self.acc_free and self.side_busy():       # a queued epilogue still holds accumulators: run it now
                         self.drain_side(8)
                     u["accs"][key] = self.acc_take(1)[0]
-                if t == 1 and SHARE_BIAS:
+                if t == 1:
                     # the two tiles of a block start from the SAME bias: tile 1's first MFMA takes tile 0's armed accumulator as its
                     # C operand (emit_unit issues it in front of tile 0's) -- its own accumulator is only taken, never armed: half the
-                    # arming reads (408 of the 816 LDS reads per group), same values
+                    # arming reads (408 of the 816 LDS reads per group), same values: -1.9 % (profiles/r06/r06m)
                     plans.append([take])
                     continue
                 if l["mode"] == "logits":       # transposed product: every register = bias of channel lane & 31
                     def first(key=key, slot=slot, take=take):           # the address lives in the accumulator's first register, read last
                         take()
-                        self.e("v_add_u32 v%d, 0x%x, v%d" % (self.acc_reg(u["accs"][key]), slot_base(slot), V_LB4))
+                        self.e("v_add_u32 v%d, 0x%x, v%d" % (self.acc_reg(u["accs"][key]), slot * SLOT, V_LB4))
                     ops.append(first)
                     for r in list(range(1, 16)) + [0]:
                         ops.append(lambda key=key, r=r, off=bias_off + b_in_chunk * 128: u["arm_tags"].append(
@@ -874,7 +849,7 @@ class Gen:
     # ------------------------------------------------------------------ pack / ReLU of a unit's accumulators -> list of (dst, closure)
     def pack_ops(self, u):
         l = self.layers[u["layer"]]
-        if PACK_PIPE and not self.trace and not SAVE_PROTO:
+        if not self.trace:
             return self.pack_ops_pipelined(u)
         out = []
         for bi, blk in enumerate(u["blocks"]):
@@ -898,7 +873,10 @@ class Gen:
         return out
 
     def pack_ops_pipelined(self, u):
-        """-> [([destinations final after this closure], closure, accumulator)]: see PACK_PIPE"""
+        """-> [([destinations final after this closure], closure, accumulator)]: the pack / ReLU / v_accvgpr_write triples as a
+        three-stage software pipeline over the packed registers of a unit (closure j: write of pair j - 2, ReLU of pair j - 1,
+        convert of pair j; three rotating temporaries) -- no instruction of a closure depends on another one of the same closure,
+        where the plain form is three DEPENDENT instructions back to back: -0.35 % (profiles/r06/r06s)"""
         l = self.layers[u["layer"]]
         relu = l["mode"] == "relu"
         pairs = []
@@ -944,8 +922,8 @@ class Gen:
     # ------------------------------------------------------------------ one unit of MFMAs with its fillers
     @staticmethod
     def tile_at(ks, t):
-        """the tile of the t-th MFMA of a fragment: (0, 1), except at a block's first k-step with SHARE_BIAS: (1, 0)"""
-        return 1 - t if (SHARE_BIAS and ks == 0) else t
+        """the tile of the t-th MFMA of a fragment: (0, 1), except at a block's first k-step (the shared bias, arm_plan): (1, 0)"""
+        return 1 - t if ks == 0 else t
 
     def b_operand(self, u, ks, t):
         l = self.layers[u["layer"]]
@@ -1048,7 +1026,7 @@ class Gen:
         cost = [3 * sum(1 for j in must_at.get(g, []) if j < n and dls[j] is not None or (j < n and musts[j] in pack_fns)) +
                 sum(1 for j in must_at.get(g, [])) for g in range(nm)]
         for idx, j in enumerate(mine):
-            span = max(len(mine) + 1, int(PIECE_FRAC * (nm - 3)))
+            span = max(len(mine) + 1, nm - 3)       # over all of the unit's gaps (the first half only: measured slower, round 5)
             lo = 1 + (idx * span) // max(1, len(mine))
             hi = max(lo + 1, 1 + ((idx + 1) * span) // max(1, len(mine)))
             g = min(range(lo, min(hi, nm - 1)), key=lambda x: (cost[x], x))
@@ -1065,15 +1043,11 @@ class Gen:
                     for tg in u["arm_tags"][-1:]:
                         self.wait_lgkm(tg)                          # the unit's bias has landed (in-order: the last read covers all)
                     first_wait_done = True
-                if WAIT2 and f + 1 < len(frags):
-                    if f % 2 == 0:                                  # one counted wait per TWO fragments: the younger of the pair covers both
-                        self.wait_lgkm(self.ring_tags[(gi + 1) % P])
-                else:
-                    self.wait_lgkm(self.ring_tags[gi % P])
+                self.wait_lgkm(self.ring_tags[gi % P])          # one counted wait per fragment (per TWO: +-0, profiles/r06/r06m)
             tile = self.tile_at(ks, t)
             a = self.acc_reg(u["accs"][(bi, tile)])
-            # a block's first k-step (SHARE_BIAS): tile 1 first, reading the bias out of tile 0's accumulator, then tile 0 in place
-            c_in = self.acc_reg(u["accs"][(bi, 0)]) if (SHARE_BIAS and ks == 0) else a
+            # a block's first k-step: tile 1 first, reading the bias out of tile 0's accumulator, then tile 0 in place
+            c_in = self.acc_reg(u["accs"][(bi, 0)]) if ks == 0 else a
             bloc = self.b_operand(u, ks, tile)
             ring = vr(V_RING + 4 * (gi % P), 4)
             if swap:
@@ -1096,8 +1070,6 @@ class Gen:
             self.drain_side(1 if l["name"].startswith("L") or l["name"] in ("feature", "views") else 3 if late else 2)
         for g in sorted(must_at):                       # (positions beyond the last gap: none by construction)
             assert g < nm, (g, nm)
-        if SAVE_PROTO and packs:
-            self.queue_saves([dst for dst, _, _ in packs])
         # ---- this unit's own results: packed during the next unit, or reduced by the side queue
         if l["mode"] in ("relu", "linear"):
             self.pending_pack = dict(ops=self.pack_ops(u), accs=list(u["accs"].values()))
@@ -1319,7 +1291,7 @@ class Gen:
             for k, (u, bi, blk, inst) in enumerate(blocks):
                 e("s_mov_b64 exec, s[%d:%d]" % (S_MSK + 2 * k, S_MSK + 2 * k + 1))
                 base = (S_REC_I if inst else S_REC_T) + 2 * t
-                self.vm_op("global_store_dword v%d, v%d, s[%d:%d] offset:%d%s" % (V_LB4, oth[t][k], base, base + 1, 4 + 128 * blk, STORE_NT))
+                self.vm_op("global_store_dword v%d, v%d, s[%d:%d] offset:%d" % (V_LB4, oth[t][k], base, base + 1, 4 + 128 * blk))
             e("s_mov_b64 exec, -1")
         self.stamp(len(self.units) + 4)
         if self.softmax:
@@ -1426,40 +1398,8 @@ class Gen:
             e("s_mov_b64 s[%d:%d], s[%d:%d]" % (S_VALID + 2 * t, S_VALID + 2 * t + 1, S_NVALID + 2 * t, S_NVALID + 2 * t + 1))
             e("s_mov_b64 s[%d:%d], s[%d:%d]" % (S_LAST + 2 * t, S_LAST + 2 * t + 1, S_NLAST + 2 * t, S_NLAST + 2 * t + 1))
 
-    def save_base(self):
-        """s[S_SV : S_SV + 1] = region base + (4 group + wave) * SAVE_REGION"""
-        e = self.e
-        e("s_lshl_b32 s%d, s%d, 2" % (S_SVT, S_GRP))
-        e("s_add_u32 s%d, s%d, s%d" % (S_SVT, S_SVT, S_WAVE))
-        self.lit(S_K, SAVE_REGION)
-        e("s_mul_hi_u32 s%d, s%d, s%d" % (S_SV + 1, S_SVT, S_K))
-        e("s_mul_i32 s%d, s%d, s%d" % (S_SV, S_SVT, S_K))
-        e("s_add_u32 s%d, s%d, s%d" % (S_SV, S_SV, S_SVBASE))
-        e("s_addc_u32 s%d, s%d, s%d" % (S_SV + 1, S_SV + 1, S_SVBASE + 1))
-        self.save_n = 0
-
-    def queue_saves(self, regs):
-        """side work: 16-byte-per-lane stores of the packed registers `regs` [(kind, index)] -- quads of consecutive registers"""
-        regs = sorted(regs)
-        assert len(regs) % 4 == 0
-        for i in range(0, len(regs), 4):
-            k, r = regs[i]
-            assert [x for x in regs[i:i + 4]] == [(k, r + j) for j in range(4)], regs[i:i + 4]
-
-            def fn(k=k, r=r):
-                self.vm_op("global_store_dwordx4 v%d, %s, s[%d:%d] offset:%d" % (V_SV, (ar if k == "a" else vr)(r, 4), S_SV, S_SV + 1,
-                                                                                   1024 * (self.save_n % 4)))
-                self.save_n += 1
-                if self.save_n % 4 == 0:
-                    with self.atomic():         # (the carry: no other scalar instruction between the two)
-                        self.e("s_add_u32 s%d, s%d, 0x1000" % (S_SV, S_SV))
-                        self.e("s_addc_u32 s%d, s%d, 0" % (S_SV + 1, S_SV + 1))
-            self.q(1, fn)
-
     def group_body(self):
         self.m0 = None
-        if SAVE_PROTO:
-            self.save_base()
         assert self.acc_free == [i for i in range(8) if i not in self.units[0]["accs"].values()], self.acc_free
         self.last_stamp = None
         for ui in range(len(self.units)):
@@ -1482,7 +1422,7 @@ class Gen:
         e, name = self.e, self.name
         self.o += ["\t.text", "\t.globl\t%s" % name, "\t.p2align\t8", "\t.type\t%s,@function" % name, "%s:" % name]
         for dst, off, n in ((S_IMG, 0x0, 2), (S_RAYS, 0x8, 2), (S_Z, 0x10, 2), (S_S, 0x18, 2), (S_MAGIC, 0x20, 2), (S_NGRP, 0x28, 2),
-                            (S_REC, 0x30, 2), (S_RECF, 0x38, 1), (S_PS, 0x40, 2), (S_NSEM, 0x48, 2), (S_CLK, 0x50, 2), (S_AUX, 0x58, 2)) + (((S_SVBASE, 0x60, 2),) if SAVE_PROTO else ()):
+                            (S_REC, 0x30, 2), (S_RECF, 0x38, 1), (S_PS, 0x40, 2), (S_NSEM, 0x48, 2), (S_CLK, 0x50, 2), (S_AUX, 0x58, 2)):
             e("s_load_dword%s %s, s[0:1], 0x%x" % ("x2" if n == 2 else "", sr(dst, n), off))
         # wave id from v0 itself (never written): a v_readfirstlane of a register that is re-used a few instructions later was
         # observed to return the LATER value while scalar-load data was returning (tools/probe/gen_two_tile_asm.py)
@@ -1496,7 +1436,7 @@ class Gen:
         e("v_and_b32 v%d, 1, v%d" % (V_LB4, V_LB4))
         e("v_lshlrev_b32 v%d, 4, v%d" % (V_LB4, V_LB4))                  # hi * 16
         for sl in range(NSLOT):
-            self.lit(S_T0, slot_base(sl))
+            self.lit(S_T0, sl * SLOT)
             e("v_add_u32 v%d, s%d, v%d" % (V_FRAG + sl, S_T0, V_LANE16))
             e("v_add_u32 v%d, s%d, v%d" % (V_BIAS + sl, S_T0, V_LB4))
         for k in range(3):
@@ -1505,10 +1445,6 @@ class Gen:
                 e("v_add_u32 v%d, 0x%x, v%d" % (V_DMA + k, 16384 * k, V_DMA + k))
         e("v_and_b32 v%d, 31, v0" % V_LB4)
         e("v_lshlrev_b32 v%d, 2, v%d" % (V_LB4, V_LB4))
-        if SAVE_PROTO:
-            assert not self.trace
-            e("v_and_b32 v%d, 63, v0" % V_SV)
-            e("v_lshlrev_b32 v%d, 4, v%d" % (V_SV, V_SV))
         e("s_mov_b32 s%d, -1" % S_LO32)
         e("s_mov_b32 s%d, 0" % (S_LO32 + 1))
         e("s_mov_b32 s%d, 1" % S_N0)
@@ -1517,7 +1453,7 @@ class Gen:
         e("s_mov_b32 s%d, 0" % (S_HI0 + 1))
         e("s_lshr_b32 s%d, s%d, 4" % (S_LWW, S_W4K))                      # wave * 256: this wave's [2 tiles][32] local-weight table
         e("s_add_u32 s%d, s%d, 0x%x" % (S_LWW, S_LWW, LW_BASE))
-        e("s_sub_u32 s%d, s%d, 0x%x" % (S_LWR, S_LWW, slot_base(0)))      # + V_BIAS[0] (= slot 0's base + 16 hi) = table + 16 hi
+        e("s_sub_u32 s%d, s%d, 0x%x" % (S_LWR, S_LWW, 0 * SLOT))          # + V_BIAS[0] (= slot 0's base + 16 hi) = table + 16 hi
         e("s_waitcnt lgkmcnt(0)")
         # store masks of the logit blocks (constant): channel = 32 blk + (lane & 31) < n_out, lanes 0..31 only
         for k, (blk, inst) in enumerate(self.logit_blocks()):

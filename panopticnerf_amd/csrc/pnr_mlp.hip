@@ -38,15 +38,9 @@ int pnr_mlp_validate(const pnr_mlp_desc* d);
 
 #include "pnr_mlp_core.h"
 #include "pnr_mlp_pp.h"
-#ifndef PNR_FUSE_TRANSPOSED
-#define PNR_FUSE_TRANSPOSED 1      /* fused epilogue: logit blocks computed transposed (operands swapped), see PPChunk::mma<SWAP> */
-#endif
 #include "pnr_mlp_fuse.h"
 #include "pnr_mlp_tt.h"
 #define PNR_QUERY_MAX_POINTS (((int64_t)1 << 31) - 4096)
-#ifndef PNR_TRAIN_TILES_EXPERIMENT
-#define PNR_TRAIN_TILES_EXPERIMENT 0
-#endif
 // Hidden layer: inputs = up to two register segments, output -> registers (next B operand).
 // save != nullptr (training, bf16): the output block is also stored slot-ordered for the backward.
 template <int PREC, int TILES, class CTX, int KIND, int NA, int NB, int NFB_OUT, int MODE, int NOUT>
@@ -411,7 +405,7 @@ __device__ __forceinline__ void pp_layer_regs(CTX& c, u32x4 (&A)[CTX::P], const 
     for (int cb = 0; cb < NFB_OUT / FBC; ++cb) {
         // L of chunk cb, last part.  For the layer's 2nd, 3rd, ... chunk the first fragments were already requested (below)
         // in the shadow of the previous chunk's refill / epilogue; the bias reads and the drain are left.
-        if (cb == 0 || !PNR_PP_EARLY) CH::first_frags(c.frag_addr(), A);
+        if (cb == 0) CH::first_frags(c.frag_addr(), A);
         CH::bias_issue(c.bias_addr(), q);
         f32x16 acc[FBC];
         CH::bias_finish(q, acc);                                // waits for every LDS read of the phase
@@ -428,7 +422,7 @@ __device__ __forceinline__ void pp_layer_regs(CTX& c, u32x4 (&A)[CTX::P], const 
         };
         c.m_done();                                             // M -> L of the next chunk; own refill pieces landed
         const bool nxt_same = cb + 1 < NFB_OUT / FBC;           // the next chunk has this chunk's shape
-        if (PNR_PP_EARLY && nxt_same) CH::first_frags(c.next_frag_addr(), A);
+        if (nxt_same) CH::first_frags(c.next_frag_addr(), A);
         c.refill_begin();
 #pragma unroll
         for (int b = 0; b < FBC; ++b) {
@@ -454,7 +448,7 @@ __device__ __forceinline__ void pp_layer_out(CTX& c, u32x4 (&A)[CTX::P], const u
 #pragma unroll 1
     for (int fb = 0; fb < nfb; ++fb) {
         f32x16 acc[1];
-        const bool logits_t = FUSE && PNR_FUSE_TRANSPOSED && ch_base != 0;      // wave-uniform
+        const bool logits_t = FUSE && ch_base != 0;      // wave-uniform: fused logit blocks are computed transposed (PPChunk::mma<SWAP>)
         if (logits_t) {
             CH::prologue_swapped(c.frag_addr(), c.bias_addr() - c.hi * 16, c.lane, A, acc);
             CH::template mma<true>(c.frag_addr(), A, inA, inB, acc, [&](auto... k) { if constexpr (sizeof...(k) == 0) { c.stamp(6); c.barrier(); c.stamp(2); } else c.stamp(k...); });
@@ -467,8 +461,7 @@ __device__ __forceinline__ void pp_layer_out(CTX& c, u32x4 (&A)[CTX::P], const u
         c.refill_one();
         if constexpr (FUSE) {
             if (ch_base == 0) fuse_rgbs(c.a, *st, c.hi, c.lane & 31, acc[0]);
-            else if (PNR_FUSE_TRANSPOSED) fuse_logits_t(*st, c.hi, c.lane, fb, n_out, PNR_FUSE_REC_LOGITS + (ch_base - 4), acc[0]);
-            else fuse_logits(*st, c.hi, c.lane & 31, fb, n_out, PNR_FUSE_REC_LOGITS + (ch_base - 4), acc[0]);
+            else fuse_logits_t(*st, c.hi, c.lane, fb, n_out, PNR_FUSE_REC_LOGITS + (ch_base - 4), acc[0]);
         } else if (!(PNR_PP_ABL & 4)) store_raw_block(c.a, samp, c.hi, fb, n_out, ch_base, acc[0]);
         c.refill_rest();
         c.advance();
@@ -524,9 +517,7 @@ __device__ __forceinline__ void pp_logits_merged(CTX& c, u32x4 (&A)[CTX::P], con
     c.stamp(6);
     c.barrier();                                                    // L -> M
     c.stamp(2);
-#if PNR_PP_PRIO
-    __builtin_amdgcn_s_setprio(PNR_PP_PRIO);
-#endif
+    __builtin_amdgcn_s_setprio(1);
     pp_static_for<NF>([&](auto I) {
         constexpr int i = I;
         constexpr int ks = i / FB, b = i % FB;
@@ -543,9 +534,7 @@ __device__ __forceinline__ void pp_logits_merged(CTX& c, u32x4 (&A)[CTX::P], con
             __builtin_amdgcn_sched_barrier(0);
         }
     });
-#if PNR_PP_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     c.m_done();
     c.refill_begin();
     if constexpr (SOFTMAX) {            // a head's blocks together: the softmax runs over all of its channels
@@ -927,15 +916,6 @@ static int mlp_forward_impl(const pnr_mlp_desc* desc, const void* packed, const 
             return desc->W == 256 ? launch_mlp_pp<256, false>(a, st) : launch_mlp_pp<128, false>(a, st);
         if (desc->schedule == 2 && acts)
             return desc->W == 256 ? launch_mlp_pp<256, true>(a, st) : launch_mlp_pp<128, true>(a, st);
-#if PNR_TRAIN_TILES_EXPERIMENT
-        // round-6 experiment (tools/build_ab.sh tt:"-DPNR_TRAIN_TILES_EXPERIMENT=1"; profiles/r06b): the training forward with ONE wave per
-        // SIMD and 2 / 3 sample tiles per wave.  3: a weight pass feeds 384 samples instead of 256 (timing only: S % 384 == 0)
-        if (acts && desc->schedule == 3 && desc->W == 256) return launch_mlp<PNR_PREC_BF16, 256, 2, 4, 1, true>(a, st);
-        if (acts && desc->schedule == 4 && desc->W == 256) {
-            PNR_REQUIRE(a.S % 384 == 0, "schedule 4 (experiment): S must be a multiple of 384");
-            return launch_mlp<PNR_PREC_BF16, 256, 3, 4, 1, true>(a, st);
-        }
-#endif
         if (acts)
             return desc->W == 256 ? launch_mlp<PNR_PREC_BF16, 256, 1, 8, 2, true>(a, st)
                                   : launch_mlp<PNR_PREC_BF16, 128, 1, 8, 2, true>(a, st);
@@ -952,10 +932,6 @@ PNR_EXPORT int pnr_mlp_forward(const pnr_mlp_desc* desc, const void* packed, con
 }
 
 #define PNR_RAY_AUX_BYTES 128
-// A/B builds only (tools/build_tt_variant.sh save PNR_TT_SAVE=1, run with PNR_TT_SAVE_PROTO=1): the training-forward prototype of the
-// two-tile kernel stores every packed activation block to a scratch region behind the per-ray table (profiles/r06/r06p)
-#define PNR_TT_SAVE_REGION (352 * 1024)
-static bool pnr_tt_save_proto() { static const bool on = getenv("PNR_TT_SAVE_PROTO") != nullptr; return on; }
 int pnr_composite_combine_launch(const float* rec, int rec_floats, bool logit_sums, const float4* ps, const float* z,
                                  const int32_t* label_sem, const int32_t* label_inst, int64_t R, int N, int C, int K, int white_bkgd,
                                  float* rgb, float* depth, float* acc, float* weights, float* sem, float* inst, float* fix_sem,
@@ -976,8 +952,7 @@ PNR_EXPORT int64_t pnr_mlp_forward_composite_workspace_bytes(const pnr_mlp_desc*
     if (pnr_mlp_validate(desc) != PNR_OK || n_rays < 0 || n_samples < 32 || (n_samples & 31)) return -1;
     const int64_t S = n_rays * n_samples, tiles = (S + 255) / 256 * 8;
     if (desc->plan == 3) return tiles * record_floats(*desc) * 4 + S * 16 + 256;
-    return tiles * pnr_fuse_record_floats(desc->n_sem, desc->n_inst) * 4 + S * 16 + 256 + PNR_RAY_AUX_BYTES + n_rays * PNR_RAY_AUX_BYTES +
-           (pnr_tt_save_proto() ? tiles / 8 * 4 * PNR_TT_SAVE_REGION + 4096 : 0);
+    return tiles * pnr_fuse_record_floats(desc->n_sem, desc->n_inst) * 4 + S * 16 + 256 + PNR_RAY_AUX_BYTES + n_rays * PNR_RAY_AUX_BYTES;
 }
 
 // What the two-tile kernel needs of a RAY rather than of a sample: |d| and gamma(d / |d|), in the registers embed_lane hands a lane
@@ -1041,7 +1016,6 @@ static int fused_mlp_launch(const pnr_mlp_desc* desc, const void* packed, const 
         k_ray_aux<<<dim3((unsigned)((2 * n_rays + 255) / 256)), dim3(256), 0, st>>>(rays, n_rays, aux);
         t.aux = aux;
         t.n_wg = (desc->flags >> 16) & 0x1FF;
-        if (pnr_tt_save_proto()) t.save = (void*)(((uintptr_t)((uint8_t*)aux + n_rays * PNR_RAY_AUX_BYTES) + 4095) & ~(uintptr_t)4095);
         const bool trace = (desc->flags & 0xFF00) == PNR_MLP_TRACE;     // + (a << 4), a in 1..7: the timing-only ablation a
         return pnr_mlp_tt_launch(t, (desc->n_sem + 31) / 32, (desc->n_inst + 31) / 32, a.head_depth, a.head_tap, softmax, st, trace,
                                  trace ? ((desc->flags >> 4) & 7) : 0);

@@ -25,7 +25,6 @@ struct FuseState {
     float lwr[16];     // lane (n, hi), register r: the local weight of sample row(r, hi) -- what a TRANSPOSED logit accumulator (lane =
                        // channel, register r = sample row(r, hi)) is multiplied by.  16 VGPRs; round 2 kept the 32 weights wave-uniform in
                        // SGPRs, which lived across five chunks, spilled to VGPR lanes and cost each logit block 64 FMAs + the reloads
-    float lw;          // this lane's own sample weight (lane n of either half)
     float zz, zn, dn;  // z of the sample, z of the ray's next sample, |d|
     int samp;          // sample index or -1
     bool last;         // the sample is its ray's last one (interval 1e10), from the input prefetch
@@ -61,11 +60,6 @@ __device__ __forceinline__ void fuse_rgbs(const MlpArgs& a, FuseState& st, int h
     float excl, q;
     tile_scan(f, n, excl, q);
     const float lw = alpha * excl;
-#if defined(PNR_FUSE_TRANSPOSED) && !PNR_FUSE_TRANSPOSED
-    st.lw = __shfl(lw, n, 64);                   // butterfly form of the logit blocks: both halves need the weight of sample n
-#else
-    st.lw = lw;
-#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float w0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lw), pnr_row_of(r, 0)));
@@ -76,23 +70,6 @@ __device__ __forceinline__ void fuse_rgbs(const MlpArgs& a, FuseState& st, int h
         if (valid) a.ps[st.samp] = make_float4(lw, acc[0], acc[1], acc[2]);
         if (n == 0) st.rec[0] = q;
     }
-}
-
-// a 32-row logit block (rows fb*32 + row(r, hi), valid below n_out) -> record floats at rec_base + row
-__device__ __forceinline__ void fuse_logits(FuseState& st, int hi, int n, int fb, int n_out, int rec_base, const f32x16& acc)
-{
-    const float wn = st.lw;                              // this lane's sample weight
-    (void)n;
-    float r[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r[k] = wn * acc[k];
-    group_sum_batch<32, 16>(r);
-    // every lane of a half-wave now holds the 16 sums of its half: lane n = k keeps sum k, one store instruction writes them
-    float v = r[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) v = (n == k) ? r[k] : v;
-    const int row = fb * 32 + pnr_row_of(n & 15, hi);
-    if (n < 16 && row < n_out) st.rec[rec_base + row] = v;
 }
 
 // a 32-channel logit block computed TRANSPOSED (PPChunk::mma<SWAP>: lane = channel fb*32 + (lane & 31), register r = sample

@@ -29,10 +29,7 @@ int pnr_mlp_validate(const pnr_mlp_desc* d)
                 d->precision);
     PNR_REQUIRE(d->head_tap == 0 || d->head_tap == 1, "pnr_mlp: head_tap=%d must be 0 (trunk output) or 1 (feature)", d->head_tap);
     PNR_REQUIRE(d->head_depth >= 0 && d->head_depth <= 2, "pnr_mlp: head_depth=%d must be 1 or 2", d->head_depth);
-#ifndef PNR_TRAIN_TILES_EXPERIMENT
-#define PNR_TRAIN_TILES_EXPERIMENT 0
-#endif
-    PNR_REQUIRE(d->schedule >= 0 && d->schedule <= (PNR_TRAIN_TILES_EXPERIMENT ? 6 : 2), "pnr_mlp: schedule=%d must be 0 (default), 1 (lock-step) or 2 (ping-pong)", d->schedule);
+    PNR_REQUIRE(d->schedule >= 0 && d->schedule <= 2, "pnr_mlp: schedule=%d must be 0 (default), 1 (lock-step) or 2 (ping-pong)", d->schedule);
     PNR_REQUIRE(d->plan == 0 || (d->plan == 1 && pnr_plan1_supported(*d)) || (d->plan == 2 && pnr_plan2_supported(*d)) ||
                 (d->plan == 3 && pnr_plan3_supported(*d)) || (d->plan == 4 && pnr_plan4_supported(*d)),
                 "pnr_mlp: plan=%d is not available for this geometry (ask pnr_mlp_fused_plan; plans 3 and 4: bf16 only)", d->plan);
@@ -54,8 +51,7 @@ PNR_EXPORT int pnr_mlp_fused_plan(const pnr_mlp_desc* desc)
     pnr_mlp_desc d = *desc;
     d.plan = 0;
     if (pnr_mlp_validate(&d) != PNR_OK) return 0;
-    if ((d.flags & PNR_MLP_SOFTMAX) && d.n_sem + d.n_inst > 0)      // softmax compositing: the best plan that HAS a softmax kernel
-        return pnr_plan2_supported(d) ? 2 : pnr_plan1_supported(d) ? 1 : 0;       // (k_mlp_tt_sm_* / _d1sm_*: both head depths)
+    // logits and softmax compositing alike: plans 1 and 2 have a softmax kernel wherever they exist (k_mlp_tt_sm_* / _d1sm_*: both head depths)
     return pnr_plan2_supported(d) ? 2 : pnr_plan1_supported(d) ? 1 : 0;
 }
 

@@ -78,9 +78,6 @@ __device__ __forceinline__ void pp_wait(u32x4& a)
 #ifndef PNR_PP_RING
 #define PNR_PP_RING 4        /* measured: 4 = 5 > 6 > 8 > 10 (3 fragments = ~100 cycles in flight cover the LDS latency; fewer registers) */
 #endif
-#ifndef PNR_PP_PRIO
-#define PNR_PP_PRIO 1        /* s_setprio of the M phase: +1 % measured */
-#endif
 // cache policy of the refill's LDS-DMA pieces (0 = default, 1 = sc0, 2 = nt).  Round 3, on the scalar-base pieces, same box,
 // two passes: default 11.079 / 11.065 ms @1795-1805 MHz, sc0 11.071 / 11.072, nt 10.985 / 10.992 @1818-1840 (-0.75 %, and
 // at a higher clock: less power) -> nt.  (Rounds 1-2, per-lane-pointer pieces: nt was +1 % -- re-measured, not assumed.)
@@ -89,10 +86,6 @@ __device__ __forceinline__ void pp_wait(u32x4& a)
 #define PNR_PP_DMA_AUX 2
 #endif
 // timing-only ablations (A/B builds; results are wrong): 1 = no refill pieces, 2 = no fragment reads inside the MFMA loop
-// 1: the first fragments of a layer's 2nd, 3rd, ... chunk are read right after the previous chunk's M -> L barrier
-#ifndef PNR_PP_EARLY
-#define PNR_PP_EARLY 1
-#endif
 #ifndef PNR_PP_ABL
 #define PNR_PP_ABL 0
 #endif
@@ -455,9 +448,7 @@ struct PPChunk {
                                                const uint32_t (&inB)[NB > 0 ? NB : 1], f32x16 (&acc)[FBC], BARRIER&& barrier)
     {
         barrier();
-#if PNR_PP_PRIO
-        __builtin_amdgcn_s_setprio(PNR_PP_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(1);          // the M phase above the partner group's L phase: +1 % measured
         pp_static_for<NF>([&](auto I) {
             constexpr int i = I;
             constexpr int ks = i / FBC, b = i % FBC;
@@ -486,8 +477,6 @@ struct PPChunk {
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
-#if PNR_PP_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     }
 };

@@ -17,7 +17,7 @@ namespace {
 struct DevTable {
     hipModule_t mod = nullptr;
     hipFunction_t fn[8][4][2] = {};     // [variant = 4 head_tap + 2 softmax + (head_depth == 1)][nbs][nbi]; without heads: variant 0
-    hipFunction_t fn_trace[8] = {};     // [ablation]: 0 = the trace build; 1, 2, 3, 4, 7 exist only in PNR_TT_ABL=1 builds of the library
+    hipFunction_t fn_trace[8] = {};     // [ablation]: 0 = the trace build; 1, 2, 3, 4, 7 exist only in EXTRA_TT=abl builds of the library
     bool tried = false, ok = false;
 };
 DevTable g_tab[64];

@@ -17,7 +17,7 @@ struct PnrTTArgs {
     int32_t n_sem, n_inst;      // 72
     unsigned long long* clk;    // 80  optional {shader cycles, 100 MHz ticks} of workgroup 0's first wave
     const void* aux;            // 88  per-ray table of k_ray_aux (pnr_mlp.hip): [ray][half-wave]{8 packed gamma(d) registers, |d|, 7 pad}
-    void* save;                 // 96  null; A/B builds of the training-forward prototype (PNR_TT_SAVE=1 kernels): 352 KiB per (group, wave)
+    uint64_t reserved;          // 96  zero: no kernel reads it (the kernel argument segment stays 104 bytes)
 };
 static_assert(sizeof(PnrTTArgs) == 104, "k_mlp_tt reads its arguments at fixed offsets");
 

@@ -51,9 +51,6 @@ typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
 #ifndef WG_SLAB
 #define WG_SLAB 8192
 #endif
-#ifndef WG_SLAB_MAJOR
-#define WG_SLAB_MAJOR 0           /* 1: the jobs of one slab side by side (re-reads of shared regions from cache): measured +12 % time */
-#endif
 #ifndef WG_ISSUE_SPLIT
 #define WG_ISSUE_SPLIT 0            /* 1: the next tile's LDS-DMA pieces are issued between the k-steps instead of en bloc */
 #endif
@@ -355,13 +352,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad(const WgArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [2][A tile | B tile]
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#if WG_SLAB_MAJOR
-    // slab-major: the jobs of one slab run side by side, so the regions several jobs read (h = X_D: feature, alpha, sem0,
-    // inst0; gamma(x): layers 0 and skip+1; dY_views, d[rgb, sigma]: twice each) are re-read while still cached
-    const int slab = blockIdx.x / a.n_jobs, jb = blockIdx.x - slab * a.n_jobs;
-#else
+    // job-major (slab-major, the jobs of one slab side by side to re-read shared regions from cache: measured +12 % time)
     const int jb = blockIdx.x / a.n_slabs, slab = blockIdx.x - jb * a.n_slabs;
-#endif
     // region widths are 32, 64, 128 or 256 slots: one straight-line instance of the loop per shape
     const int shape = (31 - __builtin_clz(a.job[jb].ma >> 5)) * 4 + (31 - __builtin_clz(a.job[jb].nb >> 5));
     if (a.job[jb].a2_off >= 0) {       // two stacked 128-slot dY regions against one 256-slot X (wg_plan makes no other stack)

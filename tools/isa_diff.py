@@ -1,13 +1,16 @@
-"""Compare the gfx950 code of every kernel between two builds' saved assembly (the Makefile's -save-temps=obj output,
+r"""Compare the gfx950 code of every kernel between two builds' saved assembly (the Makefile's -save-temps=obj output,
 build/obj/*-hip-amdgcn-amd-amdhsa-gfx950.s).  Used to show that a change leaves the existing kernel instantiations' ISA
 untouched: e.g. build the parent commit, copy build/obj/*.s aside, build this tree, then
 
-    python3 tools/isa_diff.py OLD_DIR build/obj
+    python3 tools/isa_diff.py [--rename REGEX=REPL ...] OLD_DIR build/obj
 
 Each kernel is compared from its entry label to its .Lfunc_end marker, with label names, the kernel's own symbol, section
 directives and comments normalised away; kernels
 are matched by demangled name, an empty template parameter pack ignored (a kernel that gained a trailing `class... Rng` pack, e.g.
-k_stratified -> k_stratified<>, is the same kernel when its plain instance's code is).
+k_stratified -> k_stratified<>, is the same kernel when its plain instance's code is).  --rename REGEX=REPL (repeatable) rewrites the
+OLD build's demangled names with re.sub before matching, for a kernel whose template parameter list changed: e.g. after a
+constant third parameter was dropped, --rename 'k_mlp_fused<(\d+), (\d+), 1, =k_mlp_fused<\1, \2, ' pairs the old
+k_mlp_fused<1, 256, 1, 8, 2, true> with the new k_mlp_fused<1, 256, 8, 2, true>.
 Prints one line per kernel of the OLD build (same / DIFFERENT / missing) and the kernels only the new build has; exit status
 1 if any old kernel differs or is missing."""
 import glob
@@ -39,8 +42,15 @@ def kernels(path):
     return {names[k]: v for k, v in out.items()}
 
 
-def main(old_dir, new_dir):
+def renamed(name, renames):
+    for pat, repl in renames:
+        name = re.sub(pat, repl, name)
+    return name
+
+
+def main(old_dir, new_dir, renames=()):
     old, new = kernels(old_dir), kernels(new_dir)
+    old = {renamed(k, renames): v for k, v in old.items()}
     bad = 0
     for name in sorted(old):
         if name not in new:
@@ -58,4 +68,11 @@ def main(old_dir, new_dir):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="re.sub applied to the OLD build's demangled kernel names before matching (repeatable)")
+    ap.add_argument("old_dir")
+    ap.add_argument("new_dir")
+    args = ap.parse_args()
+    sys.exit(main(args.old_dir, args.new_dir, [tuple(r.split("=", 1)) for r in args.rename]))
