@@ -22,56 +22,22 @@ Time structure per 256-sample group (one workgroup; tile = (wave, t), record ind
   accumulators are packed / reduced while the NEXT unit's MFMAs run, the unit after that finds its bias already in its
   accumulators.  Weight fragments pass through a ring of 4 register quads, 3 fragments ahead, counted lgkmcnt.
   Side work (input fetch and gamma(x) of the NEXT group, the compositing epilogue) is a queue of instructions drained a few
-  per MFMA gap; what depends on the RAY alone (|d|, gamma(d / |d|)) is loaded from the table k_ray_aux (pnr_mlp.hip) wrote."""
-import struct
+  per MFMA gap; what depends on the RAY alone (|d|, gamma(d / |d|)) is loaded from the table k_ray_aux (pnr_mlp.hip) wrote.
+
+This file is the kernel itself.  Beside it: tt_regs.py (the register map, checked at import), tt_emit.py (text, wait counters, side
+queue), tt_plan.py (chunks, units, pieces), tt_math.py (the transcribed arithmetic)."""
+import os
 import sys
-from contextlib import contextmanager
+
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:      # (loaded by path: tests/test_pack.py)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tt_math  # noqa: E402
+import tt_plan  # noqa: E402
+from tt_emit import Emitter  # noqa: E402
+from tt_regs import *  # noqa: E402,F401,F403
 
 # The training-forward prototype of this kernel (every packed activation block also stored, what k_mlp_fused<TRAIN> saves for the
 # backward pass) was measured and is gone: its 2 x 2 against the shipped kernel is recorded in profiles/r06/r06p and DESIGN.md 7.
-V_T2 = 15                               # third pack temporary (V_TRACE's register: trace builds keep the plain pack form)
-NSLOT, SLOT = 4, 33 * 1024              # chunk c in LDS slot c % 4 at (c % 4) * SLOT: other strides / slot orders +-0 (profiles/r05/r05t, r05v)
-P = 4                                   # fragment ring (quads)
-D, SKIP = 8, 4
-
-# ---- VGPR map
-V_TID, V_LANE16, V_FRAG, V_BIAS, V_T0, V_DMA, V_LB4, V_TRACE = 0, 1, 2, 6, 10, 11, 14, 15
-# V_DMA + m: lane * 16 + wave * 4 KiB + m * 16 KiB: the LDS-DMA pieces' address offsets.  A wave copies the fragments
-# 16 m + 4 wave + i (i < 4: the instruction's immediate offset i KiB) of a chunk -- runs of four, round-robin over the waves.
-V_T1 = 1    # second pack temporary (lane * 16 is only needed to build the bases): one temporary for consecutive packs let the
-            # v_accvgpr_write of a pack see the NEXT pack's value (measured: records differed)
-V_RING, V_ACC = 16, 32                  # ring: v[16:31]; accumulators 0..7: v[32 + 16 i : +16]
-V_EX, V_ED = 160, 192                   # gamma(x) [2 tiles][16], gamma(d) [2][8]
-V_G = 208                               # g blocks 0, 1 of both tiles [2][16]  (views' first two blocks; the other two live in A0)
-V_ZZ, V_ZN, V_DN, V_LW = 240, 242, 244, 246      # [2] each: per-tile compositing state of the CURRENT group
-V_IN = 224                              # next group's inputs [2][8]: ox oy oz dx dy dz zz zn   (v[224:239])
-V_TMP = 208                             # encoder / epilogue temporaries share the g area once g is dead: v[208:223]
-V_PTMP = 248                            # 8 more temporaries v[248:255]
-V_AUXA = V_PTMP + 6                     # [2 tiles]: the lane's address in the per-ray table between the fetch of a tile and its point (v[254:255])
-V_LWA = V_IN + 2                        # address of the local-weight table reads in a group's last unit (the next group's o_z: dead since its point)
-# ---- AGPR map: two activation arrays of [2 tiles][64]
-A0, A1 = 0, 128
-# ---- SGPR map
-S_IMG, S_RAYS, S_Z, S_S, S_N, S_MAGIC, S_SHIFT, S_NGRP, S_NWG, S_REC, S_RECF, S_PS, S_NSEM, S_NINST, S_CLK = 4, 6, 8, 10, 11, 12, 13, 14, 15, 16, 18, 20, 22, 23, 24
-S_WAVE, S_W4K, S_GRP, S_PIECE, S_T0, S_T1 = 26, 27, 28, 30, 34, 35
-S_VALID, S_LAST = 36, 40                # [2 tiles] x 64-bit masks of the CURRENT group: s[36:39], s[40:43]
-S_NVALID, S_NLAST = 44, 48              # the same of the NEXT group (filled at fetch time): s[44:47], s[48:51]
-S_LO32, S_N0, S_HI0 = 52, 54, 56        # constants: lanes 0..31, lanes {0, 32}, lanes with hi == 0 (= lanes 0..31)
-S_SAVE, S_REC_T = 58, 60                # saved exec; the two tiles' record pointers s[60:61], s[62:63]
-S_MSK = 64                              # store masks of the (up to) three logit blocks: s[64:69] = lanes with hi == 0 and channel < n_out
-S_REC_I = 70                            # the two tiles' record pointers + 4 n_sem (the instance columns): s[70:73]
-S_AUX = 82                              # s[82:83]: the per-ray table k_ray_aux wrote (gamma(d) of both half-waves and |d|: 128 B per ray)
-S_VMSK = 76                             # softmax kernels: s[76:77] / s[78:79] = ALL lanes whose channel of the semantic / instance head's last block exists
-S_LWW, S_LWR = 74, 75                   # LDS addresses of this wave's local-weight table: + 4 (lane & 31) to write, + (V_BIAS[0] = slot 0 + 16 hi) to read
-LW_BASE = NSLOT * SLOT                  # [4 waves][2 tiles][32 floats] behind the weight slots (1 KiB)
-S_CLK0 = 96                             # s[96:99] clocks at start
-S_K = 100                               # s100: literal constants that VOP3 cannot carry
-S_Q = 19                                # the tile's Q (v_readlane) between the scan and its store
-S_GRP2 = 29                             # the group whose inputs are being prefetched
-
-
-def f32(x):
-    return struct.unpack("<I", struct.pack("<f", x))[0]
 
 
 def vr(lo, n):
@@ -95,37 +61,9 @@ class Loc:
         return (ar if self.kind == "a" else vr)(self.base + i, n)
 
 
-class Sim:
-    """in-order counters: every issued operation is appended; wait(tag) = "at most N outstanding" with N = the CERTAIN operations
-    issued after `tag` (operations some waves skip do not count: conservative)."""
-    def __init__(self, name, cap):
-        self.name, self.cap, self.q, self.n = name, cap, [], 0
-
-    def push(self, certain=True):
-        self.n += 1
-        self.q.append((self.n, certain))
-        return self.n
-
-    def wait_count(self, tag):
-        if tag is None or not any(t == tag for t, _ in self.q):
-            return None                         # already covered by an earlier wait
-        idx = [t for t, _ in self.q].index(tag)
-        n = sum(1 for _, c in self.q[idx + 1:] if c)
-        n = min(n, self.cap)
-        # everything up to tag is known complete once the wait passes -- but only if counts were exact; drop them anyway: a later
-        # wait on an older tag returns None (covered)
-        self.q = self.q[idx + 1:]
-        return n
-
-    def drain(self):
-        self.q = []
-
-    def state(self):
-        return [c for _, c in self.q]
-
-
-class Gen:
+class Gen(Emitter):
     def __init__(self, nbs, nbi, name, trace=False, abl=0, depth=2, softmax=False, tap=0):
+        Emitter.__init__(self, name)
         # abl (trace builds only; results invalid): 1 = no LDS-DMA pieces in the loop, 2 = no chunk hand-over (vmcnt + barrier),
         # 4 = no pack / ReLU of the hidden layers
         # depth: pnr_mlp_desc.head_depth -- 2: heads W -> W/2 -> n (sem0 | inst0 | sem1 | inst1); 1: one Linear W -> n per head, straight from
@@ -139,13 +77,8 @@ class Gen:
         # the tail normalises each head's transposed logit blocks per sample before the weighted sums (tail_softmax), operation for
         # operation fuse_softmax_t of the ping-pong kernel (pnr_mlp_fuse.h): k_mlp_tt_sm_s<n>i<m>
         self.softmax = softmax
-        self.nbs, self.nbi, self.name, self.trace, self.abl = nbs, nbi, name, trace, abl
-        self.nstamp = 0
-        self.o = []
-        self.nlabel = 0
-        self.lgkm = Sim("lgkm", 15)
-        self.vm = Sim("vm", 63)
-        self.side, self.side_lo, self.outbox, self.capture = [], [], [], None
+        self.nbs, self.nbi, self.trace, self.abl = nbs, nbi, trace, abl
+        self.nstamp, self.last_stamp = 0, None
         self.ring_tags = [None] * P
         self.piece_tag = {}
         self.pending_pack = None
@@ -155,166 +88,16 @@ class Gen:
         self.acc_free = list(range(8))
         self.lwr_acc = self.lwr_tag = None
         self.aux_tags = {}
-        self.build_plan()
-        self.build_units()
+        self.layers, self.chunks = tt_plan.build_plan(nbs, nbi, depth)
+        self.NC = len(self.chunks)
+        self.units = tt_plan.build_units(self.layers, self.chunks)
         self.stream = []
         for u in self.units:
             u["frag0"] = len(self.stream)
             self.stream += [(sl, of) for sl, of, _, _ in self.unit_frags(u)]
 
-    # ------------------------------------------------------------------ plan (mirrors pnr_build_plan, plan 2)
-    def build_plan(self):
-        L = []
-
-        def add(name, nblk, segs, fbc, mode):
-            nks = sum(n for _, n in segs)
-            if fbc * nks + 1 > 33:
-                fbc = 1
-            L.append(dict(name=name, nblk=nblk, segs=segs, nks=nks, fbc=fbc, mode=mode))
-        for i in range(D):
-            if i == 0:
-                add("L0", 8, [("ex", 4)], 8, "relu")
-            elif i - 1 == SKIP:
-                add("L%d" % i, 8, [("ex", 4), ("h", 16)], 2, "relu")
-            else:
-                add("L%d" % i, 8, [("h", 16)], 2, "relu")
-        add("feature", 8, [("h", 16)], 2, "linear")
-        add("views", 4, [("F", 16), ("ed", 2)], 2, "relu")
-        add("rgbs", 1, [("g", 8), ("hh", 16)], 1, "rgbs")
-        # heads: sem0 | inst0 | sem1 | inst1 -- a logit layer never follows its own hidden layer directly (the hidden layer's last
-        # blocks would have to be packed inside the logit unit's first MFMA gaps), sem1's reduction runs beside inst1
-        if self.depth == 1:             # one Linear per head: the logit layers read h itself (16 k-steps)
-            if self.nbs:
-                add("sem1", self.nbs, [("tap", 16)], self.nbs, "logits")
-            if self.nbi:
-                add("inst1", 1, [("tap", 16)], 1, "logits")
-        else:
-            if self.nbs:
-                add("sem0", 4, [("tap", 16)], 2, "relu")
-            if self.nbi:
-                add("inst0", 4, [("tap", 16)], 2, "relu")
-            if self.nbs:
-                add("sem1", self.nbs, [("shs", 8)], self.nbs, "logits")
-            if self.nbi:
-                add("inst1", 1, [("shi", 8)], 1, "logits")
-        self.layers = L
-        self.chunks = []
-        off = 0
-        for li, l in enumerate(L):
-            for fb in range(0, l["nblk"], l["fbc"]):
-                nfrag = l["fbc"] * l["nks"] + 1
-                self.chunks.append(dict(layer=li, fb=fb, nfb=l["fbc"], off=off, nfrag=nfrag))
-                off += nfrag
-        self.total_frags = off
-        # slot = chunk % 4 is static, so a group is a multiple of four chunks: geometries whose image has 42 (no heads) or 45 (no
-        # instance head) chunks get DUMMY chunks at the group's end -- one piece of image fragment 0 into the slot, a hand-over,
-        # no unit.  The image itself is unchanged (pnr_build_plan knows nothing of them)
-        while len(self.chunks) % NSLOT:
-            self.chunks.append(dict(layer=None, fb=0, nfb=0, off=0, nfrag=1, dummy=True))
-        self.NC = len(self.chunks)
-        assert self.NC % NSLOT == 0, self.NC
-        assert max(c["nfrag"] for c in self.chunks) <= 33
-
-    # ------------------------------------------------------------------ emission helpers
-    # Side work is written as closures; when one is taken off the queue it runs in CAPTURE mode: plain instructions become strings
-    # in the outbox, operations the counters must see (LDS reads, vector-memory operations, waits, accumulator releases) become
-    # deferred calls that run when the outbox entry is actually emitted -- so the counters see every operation in PROGRAM order.
-    class Holder:
-        def __init__(self, v=None):
-            self.v = v
-
-    def e(self, s):
-        if self.capture is not None:
-            self.capture.append("\t" + s)
-        else:
-            self.o.append("\t" + s)
-
-    def defer(self, fn):
-        if self.capture is not None:
-            self.capture.append(fn)
-        else:
-            fn()
-
-    @contextmanager
-    def atomic(self):
-        """side-work instructions that must not be separated by main-stream instructions: a changed EXEC mask (the MFMA stream's
-        LDS reads, packs and LDS-DMA pieces must run on all lanes) or a dependence on SCC (the pieces' s_add_u32 clobbers it)"""
-        if self.capture is None:
-            yield
-            return
-        outer, self.capture = self.capture, []
-        try:
-            yield
-        finally:
-            grp, self.capture = self.capture, outer
-            outer.append(grp)
-
-    def label(self):
-        self.nlabel += 1
-        return ".L%s_%d" % (self.name, self.nlabel)
-
-    def lds_read(self, instr):
-        h = Gen.Holder()
-
-        def now():
-            self.o.append("\t" + instr)
-            h.v = self.lgkm.push()
-        self.defer(now)
-        return h
-
-    def vm_op(self, instr, certain=True):
-        h = Gen.Holder()
-
-        def now():
-            self.o.append("\t" + instr)
-            h.v = self.vm.push(certain)
-        self.defer(now)
-        return h
-
-    def wait_lgkm(self, h):
-        def now():
-            n = self.lgkm.wait_count(h.v if isinstance(h, Gen.Holder) else h)
-            if n is not None:
-                self.o.append("\ts_waitcnt lgkmcnt(%d)" % n)
-        if h is not None:
-            self.defer(now)
-
-    def wait_vm(self, h):
-        def now():
-            n = self.vm.wait_count(h.v if isinstance(h, Gen.Holder) else h)
-            if n is not None:
-                self.o.append("\ts_waitcnt vmcnt(%d)" % n)
-        if h is not None:
-            self.defer(now)
-
-    def lit(self, sreg, val):
-        """s_mov of a 32-bit literal (VOP3 instructions cannot carry one on gfx9)"""
-        self.e("s_mov_b32 s%d, 0x%x" % (sreg, val & 0xffffffff))
-
-    def q(self, cost, fn, low=False):
-        """queue side work; low: work that holds no accumulator (the encoders) -- it waits for everything else"""
-        (self.side_lo if low else self.side).append(fn)
-
-    def side_busy(self):
-        return bool(self.side or self.side_lo or self.outbox)
-
-    def drain_side(self, budget=None):
-        """emit queued side work: all of it (budget None) or `budget` instructions"""
-        spent = 0
-        while self.side_busy() and (budget is None or spent < budget):
-            if not self.outbox:
-                fn = self.side.pop(0) if self.side else self.side_lo.pop(0)
-                self.capture = []
-                fn()
-                self.outbox, self.capture = self.capture, None
-                continue
-            x = self.outbox.pop(0)
-            for y in (x if isinstance(x, list) else [x]):
-                if callable(y):
-                    y()
-                else:
-                    self.o.append(y)
-                spent += 1
+    def unit_frags(self, u):
+        return tt_plan.unit_frags(self.layers, self.chunks, u)
 
     # ------------------------------------------------------------------ LDS-DMA
     def chunk_base(self, chunk):
@@ -322,21 +105,10 @@ class Gen:
         self.e("s_add_u32 s%d, s%d, 0x%x" % (S_PIECE, S_IMG, self.chunks[chunk]["off"] * 1024))
         self.e("s_addc_u32 s%d, s%d, 0" % (S_PIECE + 1, S_IMG + 1))
 
-    def piece_list(self, chunk):
-        """(m, i, waves) of the LDS-DMA pieces of a chunk: fragment 16 m + 4 wave + i, issued by waves 0 .. waves - 1"""
-        n = self.chunks[chunk]["nfrag"]
-        out = []
-        for m in range((n + 15) // 16):
-            for i in range(4):
-                nw = max(0, min(4, -(-(n - 16 * m - i) // 4)))
-                if nw:
-                    out.append((m, i, nw))
-        return out
-
     def piece(self, chunk, j):
         """piece j of image chunk `chunk` -> its LDS slot: M0 and the load (the address is the chunk's base + this lane's constant
         offset register + an immediate; the first version's per-piece 64-bit SALU add cost a third of a piece)"""
-        m, i, nw = self.piece_list(chunk)[j]
+        m, i, nw = tt_plan.piece_list(self.chunks, chunk)[j]
         slot = chunk % NSLOT
         skip = None
         certain = nw >= 4
@@ -357,8 +129,17 @@ class Gen:
             self.o.append(skip + ":")
         return tag
 
-    def pieces_of(self, chunk):
-        return len(self.piece_list(chunk))
+    def issue_piece(self, chunk, j):
+        """piece j of `chunk` with what goes in front of the first one; its tag is what the chunk's hand-over waits for"""
+        if j == 0:
+            self.chunk_base(chunk)
+        self.piece_tag[chunk] = self.piece(chunk, j)
+
+    def hand_over(self, chunk):
+        """end of `chunk`: this wave's pieces of chunk + 2 have landed, and after ONE barrier everybody's have"""
+        if not self.abl & 2:
+            self.wait_vm(self.piece_tag.get((chunk + 2) % self.NC))
+            self.e("s_barrier")
 
     # ------------------------------------------------------------------ operand locations of the layer inputs
     def loc_of(self, seg, layer_index, t, ks):
@@ -435,142 +216,7 @@ class Gen:
             return self.shi_block(blk, t)
         raise KeyError(n)
 
-    # ------------------------------------------------------------------ units
-    def build_units(self):
-        """the MFMA stream of one group: list of units, each = (chunk, layer, blocks, ...)"""
-        U = []
-        for ci, c in enumerate(self.chunks):
-            if c.get("dummy"):
-                continue
-            l = self.layers[c["layer"]]
-            step = 2 if l["mode"] != "logits" else min(c["nfb"], 2)        # (a third semantic block, nbs = 3: units [0, 1] and [2])
-            if l["name"] == "rgbs":
-                step = 1
-            blocks = list(range(c["fb"], c["fb"] + c["nfb"]))
-            first = True
-            for i in range(0, len(blocks), step):
-                U.append(dict(chunk=ci, layer=c["layer"], blocks=blocks[i:i + step], first_of_chunk=first,
-                              last_of_chunk=(i + step >= len(blocks))))
-                first = False
-        self.units = U
-
-    def unit_frags(self, u):
-        """fragments of a unit in consumption order: (lds slot, byte offset in slot, ks, b index in unit)"""
-        c = self.chunks[u["chunk"]]
-        l = self.layers[u["layer"]]
-        out = []
-        for ks in range(l["nks"]):
-            for bi, blk in enumerate(u["blocks"]):
-                out.append((u["chunk"] % NSLOT, ((blk - c["fb"]) * l["nks"] + ks) * 1024, ks, bi))
-        return out
-
-    def seg_of_ks(self, layer, ks):
-        for seg, n in layer["segs"]:
-            if ks < n:
-                return seg, ks
-            ks -= n
-        raise IndexError
-
     # ------------------------------------------------------------------ the pieces of side work
-    # ---- arithmetic building blocks (all scalar fp32, one value per lane; temporaries named by register number)
-    def div(self, res, num, den, t):
-        """res = num / den, correctly rounded (the sequence hipcc emits for -fhip-fp32-correctly-rounded-divide-sqrt); t: 5 temps"""
-        a, r, b, q_, x = t[:5]
-        e = self.e
-        e("v_div_scale_f32 v%d, s[%d:%d], v%d, v%d, v%d" % (a, S_T0 + 0, S_T0 + 1, den, den, num))
-        e("v_rcp_f32 v%d, v%d" % (r, a))
-        e("v_div_scale_f32 v%d, vcc, v%d, v%d, v%d" % (b, num, den, num))
-        e("v_fma_f32 v%d, -v%d, v%d, 1.0" % (x, a, r))
-        e("v_fmac_f32 v%d, v%d, v%d" % (r, x, r))
-        e("v_mul_f32 v%d, v%d, v%d" % (q_, b, r))
-        e("v_fma_f32 v%d, -v%d, v%d, v%d" % (x, a, q_, b))
-        e("v_fmac_f32 v%d, v%d, v%d" % (q_, x, r))
-        e("v_fma_f32 v%d, -v%d, v%d, v%d" % (a, a, q_, b))
-        e("v_div_fmas_f32 v%d, v%d, v%d, v%d" % (a, a, r, q_))
-        e("v_div_fixup_f32 v%d, v%d, v%d, v%d" % (res, a, den, num))
-
-    def sqrt(self, res, x, t):
-        """res = sqrtf(x), correctly rounded (hipcc's sequence); x is clobbered; t: 3 temps"""
-        y, ym, tt = t[:3]
-        e = self.e
-        self.lit(S_K, 0x0f800000)
-        e("v_mul_f32 v%d, 0x4f800000, v%d" % (tt, x))
-        e("v_cmp_gt_f32 vcc, s%d, v%d" % (S_K, x))
-        e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (x, x, tt))
-        e("v_sqrt_f32 v%d, v%d" % (y, x))
-        e("s_nop 0")
-        e("v_add_u32 v%d, -1, v%d" % (ym, y))
-        e("v_fma_f32 v%d, -v%d, v%d, v%d" % (tt, ym, y, x))
-        e("v_cmp_ge_f32 s[%d:%d], 0, v%d" % (S_T0, S_T0 + 1, tt))
-        e("v_cndmask_b32 v%d, v%d, v%d, s[%d:%d]" % (ym, y, ym, S_T0, S_T0 + 1))
-        e("v_add_u32 v%d, 1, v%d" % (tt, y))
-        e("v_fma_f32 v%d, -v%d, v%d, v%d" % (y, tt, y, x))
-        e("v_cmp_lt_f32 s[%d:%d], 0, v%d" % (S_T0, S_T0 + 1, y))
-        e("v_cndmask_b32 v%d, v%d, v%d, s[%d:%d]" % (ym, ym, tt, S_T0, S_T0 + 1))
-        e("v_mul_f32 v%d, 0x37800000, v%d" % (tt, ym))
-        e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (ym, ym, tt))
-        e("v_mov_b32 v%d, 0x260" % tt)
-        e("v_cmp_class_f32 vcc, v%d, v%d" % (x, tt))
-        e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (res, ym, x))
-
-    def sincos(self, s_out, c_out, x, t):
-        """sincos_cw (pnr_mlp.hip): s_out, c_out = sin, cos of v[x]; t: 6 temps"""
-        kf, r, r2, a, b, ki = t[:6]
-        e = self.e
-        C = dict(twoopi=f32(0.636619772367581343), c1=f32(1.57079637050628662109375), c2=f32(-4.371139000186241e-08),
-                 s3=f32(-1.9515295891e-4), s2=f32(8.3321608736e-3), s1=f32(-1.6666654611e-1),
-                 c4=f32(2.443315711809948e-5), c3=f32(-1.388731625493765e-3), c2b=f32(4.166664568298827e-2))
-        assert C["twoopi"] == 0x3f22f983 and C["c1"] == 0x3fc90fdb and C["c2"] == 0xb33bbd2e and C["s3"] == 0xb94ca1f9
-        assert C["s2"] == 0x3c08839e and C["s1"] == 0xbe2aaaa3 and C["c4"] == 0x37ccf5ce and C["c3"] == 0xbab6061a and C["c2b"] == 0x3d2aaaa5
-        e("v_mul_f32 v%d, 0x%x, v%d" % (kf, C["twoopi"], x))
-        e("v_rndne_f32 v%d, v%d" % (kf, kf))
-        e("v_mov_b32 v%d, v%d" % (r, x))
-        e("v_fmac_f32 v%d, 0x%x, v%d" % (r, C["c1"] ^ 0x80000000, kf))              # r = fma(kf, -C1, x) = fma(-kf, C1, x)
-        e("v_fmac_f32 v%d, 0x%x, v%d" % (r, C["c2"] ^ 0x80000000, kf))              # r = fma(-kf, C2, r)
-        e("v_cvt_i32_f32 v%d, v%d" % (ki, kf))
-        e("v_mul_f32 v%d, v%d, v%d" % (r2, r, r))
-        # sine polynomial
-        e("v_mov_b32 v%d, 0x%x" % (a, C["s2"]))
-        e("v_fmac_f32 v%d, 0x%x, v%d" % (a, C["s3"], r2))                           # sp = fma(r2, s3, s2)
-        e("v_fmaak_f32 v%d, v%d, v%d, 0x%x" % (a, r2, a, C["s1"]))                  # sp = fma(r2, sp, s1)
-        e("v_mul_f32 v%d, v%d, v%d" % (b, r, r2))                                   # r * r2
-        e("v_fma_f32 v%d, v%d, v%d, v%d" % (a, b, a, r))                            # sn = fma(r * r2, sp, r)
-        # cosine polynomial
-        e("v_mov_b32 v%d, 0x%x" % (b, C["c3"]))
-        e("v_fmac_f32 v%d, 0x%x, v%d" % (b, C["c4"], r2))                           # cp = fma(r2, c4, c3)
-        e("v_fmaak_f32 v%d, v%d, v%d, 0x%x" % (b, r2, b, C["c2b"]))                 # cp = fma(r2, cp, c2)
-        e("v_fma_f32 v%d, v%d, v%d, -0.5" % (b, r2, b))                             # cp = fma(r2, cp, -0.5)
-        e("v_fma_f32 v%d, v%d, v%d, 1.0" % (b, r2, b))                              # cs = fma(r2, cp, 1)
-        # quadrant
-        e("v_and_b32 v%d, 1, v%d" % (r, ki))
-        e("v_cmp_eq_u32 vcc, 0, v%d" % r)
-        e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (r2, b, a))                          # so = (k & 1) ? cs : sn
-        e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (kf, a, b))                          # co = (k & 1) ? sn : cs
-        e("v_and_b32 v%d, 2, v%d" % (a, ki))
-        e("v_lshlrev_b32 v%d, 30, v%d" % (a, a))
-        e("v_xor_b32 v%d, v%d, v%d" % (s_out, r2, a))                               # s = so ^ ((k & 2) << 30)
-        e("v_add_u32 v%d, 1, v%d" % (a, ki))
-        e("v_and_b32 v%d, 2, v%d" % (a, a))
-        e("v_lshlrev_b32 v%d, 30, v%d" % (a, a))
-        e("v_xor_b32 v%d, v%d, v%d" % (c_out, kf, a))                               # c = co ^ (((k + 1) & 2) << 30)
-
-    def band_pack(self, dst3, s, c):
-        """three packed registers of one band: (s_x s_y) (s_z c_x) (c_y c_z)"""
-        e = self.e
-        e("v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (dst3, s[0], s[1]))
-        e("v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (dst3 + 1, s[2], c[0]))
-        e("v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (dst3 + 2, c[1], c[2]))
-
-    def band_next(self, s, c, t):
-        """double-angle step, in place: s2 = (2 s) c, c2 = fma(-2 s, s, 1)"""
-        e = self.e
-        for a in range(3):
-            e("v_add_f32 v%d, v%d, v%d" % (t, s[a], s[a]))                          # 2 s (exact)
-            e("v_mul_f32 v%d, v%d, v%d" % (t, t, c[a]))                             # s2 = (2 s) * c
-            e("v_mul_f32 v%d, -2.0, v%d" % (c[a], s[a]))                            # -2 s
-            e("v_fma_f32 v%d, v%d, v%d, 1.0" % (c[a], c[a], s[a]))                  # c2 = fma(-2 s, s, 1)
-            e("v_mov_b32 v%d, v%d" % (s[a], t))
-
     # ---- next group's inputs: address, loads (tile t), masks
     def fetch_tile(self, t, grp_sreg):
         """issue the loads of tile t of group s[grp_sreg]: ox oy oz dx | dy dz | zz | zn -> V_IN + 8 t; masks -> S_NVALID / S_NLAST"""
@@ -638,7 +284,7 @@ class Gen:
                 e("v_mul_f32 v%d, v%d, v%d" % (q[a], vi + 3 + a, vi + 6))
                 e("v_add_f32 v%d, v%d, v%d" % (q[a], vi + a, q[a]))
         if part == "x":
-            out.append((6, points))
+            out.append(points)
 
         def aux_x():
             # |d| = sqrt((dx dx + dy dy) + dz dz) and gamma(d / |d|) are PER-RAY values: k_ray_aux (pnr_mlp.hip) computed them once per
@@ -648,7 +294,7 @@ class Gen:
             self.aux_tags[t] = self.vm_op("global_load_dword v%d, v%d, s[%d:%d] offset:32" % (vi + 0, V_AUXA + t, S_AUX, S_AUX + 1))
             e("v_mov_b32 v%d, v%d" % (vi + 3, V_AUXA + t))
         if part == "x":
-            out.append((2, aux_x))
+            out.append(aux_x)
 
         def xyz_reg():
             # reg 0 of gamma(x): pack(hi ? pz : px, hi ? 0 : py)
@@ -663,24 +309,24 @@ class Gen:
             for a in range(3):
                 e("v_mul_f32 v%d, v%d, v%d" % (q[a], q[a], tt))         # p * base
         if part == "x":
-            out.append((12, xyz_reg))
+            out.append(xyz_reg)
             for a in range(3):
-                out.append((30, (lambda a=a: self.sincos(s[a], c[a], q[a], w))))
+                out.append(lambda a=a: tt_math.sincos(self, s[a], c[a], q[a], w))
             for fp in range(5):
-                out.append((3, (lambda fp=fp: self.band_pack(ex + 1 + 3 * fp, s, c))))
+                out.append(lambda fp=fp: tt_math.band_pack(self, ex + 1 + 3 * fp, s, c))
                 if fp < 4:
-                    out.append((15, (lambda: self.band_next(s, c, tt))))
+                    out.append(lambda: tt_math.band_next(self, s, c, tt))
 
         if part == "x":
-            out.append((1, (lambda: self.wait_vm(self.aux_tags[t]))))       # |d| has landed before anything (park) copies it
+            out.append(lambda: self.wait_vm(self.aux_tags[t]))       # |d| has landed before anything (park) copies it
             return out
 
         def d_load():
             # this lane's eight packed registers of gamma(d): [x|y or z|0] [band 0 triple] [band 1 triple] [0], as embed_lane writes them
             self.vm_op("global_load_dwordx4 %s, v%d, s[%d:%d]" % (vr(ed, 4), vi + 3, S_AUX, S_AUX + 1))
             self.aux_tags[2 + t] = self.vm_op("global_load_dwordx4 %s, v%d, s[%d:%d] offset:16" % (vr(ed + 4, 4), vi + 3, S_AUX, S_AUX + 1))
-        out.append((2, d_load))
-        out.append((1, (lambda: self.wait_vm(self.aux_tags[2 + t]))))
+        out.append(d_load)
+        out.append(lambda: self.wait_vm(self.aux_tags[2 + t]))
         return out
 
     # ---- the compositing epilogue of the rgb / sigma block (fuse_rgbs) of tile t; acc = VGPR base of its accumulator
@@ -725,7 +371,7 @@ class Gen:
             e("v_add_f32 v%d, 0x2edbe6ff, v%d" % (f, f))
             e("v_mov_b32 v%d, 1.0" % n)
             e("v_cndmask_b32 v%d, v%d, v%d, s[%d:%d]" % (f, n, f, VAL, VAL + 1))
-        self.q(36, alpha)
+        self.q(alpha)
 
         def scan():
             # inclusive product over lanes 0..31 of each half (tile_scan): row_shr 1, 2, 4, 8, row_bcast15 into rows 1 and 3
@@ -750,9 +396,9 @@ class Gen:
                 with self.atomic():
                     e("v_add_u32 v%d, s%d, v%d" % (n, S_LWW, V_LB4))
                     e("s_mov_b64 exec, s[%d:%d]" % (S_HI0, S_HI0 + 1))
-                    self.lds_read("ds_write_b32 v%d, v%d offset:%d" % (n, V_LW + t, 128 * t))
+                    self.lgkm_op("ds_write_b32 v%d, v%d offset:%d" % (n, V_LW + t, 128 * t))
                     e("s_mov_b64 exec, -1")
-        self.q(26 + (4 if self.nbs else 0), scan)
+        self.q(scan)
 
         def stores():
           with self.atomic():
@@ -787,7 +433,7 @@ class Gen:
             e("v_mov_b32 v%d, 0" % d)
             self.vm_op("global_store_dword v%d, v%d, s[%d:%d]" % (d, x, S_REC_T + 2 * t, S_REC_T + 2 * t + 1))
             e("s_mov_b64 exec, -1")
-        self.q(28, stores)
+        self.q(stores)
 
     # ------------------------------------------------------------------ accumulators
     def acc_reg(self, i):
@@ -834,14 +480,14 @@ class Gen:
                     ops.append(first)
                     for r in list(range(1, 16)) + [0]:
                         ops.append(lambda key=key, r=r, off=bias_off + b_in_chunk * 128: u["arm_tags"].append(
-                            self.lds_read("ds_read_b32 v%d, v%d offset:%d" % (self.acc_reg(u["accs"][key]) + r, self.acc_reg(u["accs"][key]), off))))
+                            self.lgkm_op("ds_read_b32 v%d, v%d offset:%d" % (self.acc_reg(u["accs"][key]) + r, self.acc_reg(u["accs"][key]), off))))
                 else:
                     for m in range(4):
                         def rd(key=key, m=m, off=bias_off + b_in_chunk * 128 + m * 32, take=take):
                             if m == 0:
                                 take()
                             a = self.acc_reg(u["accs"][key])
-                            u["arm_tags"].append(self.lds_read("ds_read_b128 %s, v%d offset:%d" % (vr(a + 4 * m, 4), V_BIAS + slot, off)))
+                            u["arm_tags"].append(self.lgkm_op("ds_read_b128 %s, v%d offset:%d" % (vr(a + 4 * m, 4), V_BIAS + slot, off)))
                         ops.append(rd)
                 plans.append(ops)
         return plans
@@ -926,39 +572,53 @@ class Gen:
         return 1 - t if ks == 0 else t
 
     def b_operand(self, u, ks, t):
-        l = self.layers[u["layer"]]
-        seg, k = self.seg_of_ks(l, ks)
-        li = u["layer"]
-        return self.loc_of(seg, li, t, k)
+        seg, k = tt_plan.seg_of_ks(self.layers[u["layer"]], ks)
+        return self.loc_of(seg, u["layer"], t, k)
 
-    def emit_unit(self, ui, side_budget=3):
-        U = self.units
-        u = U[ui]
+    def emit_unit(self, ui):
+        u = self.units[ui]
         l = self.layers[u["layer"]]
-        c = self.chunks[u["chunk"]]
-        frags = self.unit_frags(u)
-        nm = 2 * len(frags)
-        swap = l["mode"] == "logits"
-        e = self.e
-        e("; ==== unit %d: %s blocks %s (chunk %d, slot %d), %d MFMAs" % (ui, l["name"], u["blocks"], u["chunk"], u["chunk"] % NSLOT, nm))
+        nm = 2 * len(self.unit_frags(u))
+        self.e("; ==== unit %d: %s blocks %s (chunk %d, slot %d), %d MFMAs" % (ui, l["name"], u["blocks"], u["chunk"], u["chunk"] % NSLOT, nm))
         self.stamp(ui)
-        if l["name"] == "L%d" % (SKIP + 2) and u["blocks"][0] == 0:
-            self.queue_inputs_early()
-        if l["name"] == "views" and u["blocks"] == [0]:
-            self.drain_side()                       # (nothing left normally) the early side work uses the g area
-        if l["name"] == "views" and u["blocks"] == [1]:
-            self.park()
-        if l["name"] == (("sem0" if self.nbs else "inst0") if self.depth == 2 else "sem1") and u["blocks"][0] == 0:
-            self.unpark()
-        if l["name"] == "views" and u["blocks"] == [2]:
-            self.g2_acc = self.acc_take(1)[0]       # home of g block 2 (packed during the next unit) until the rgb / sigma unit is issued
-        # ---- what has to happen inside this unit
+        hook = self.group_hooks().get((l["name"], u["blocks"][0]))
+        if hook:
+            hook()
+        musts, lwr_from = self.unit_musts(ui)
+        # nothing to pack (the previous unit's results go through the side queue and hold their accumulators until then): arm in
+        # the unit's last third
+        late = bool(musts) and ui + 1 < len(self.units) and not any(is_pack for _, _, is_pack in musts)
+        must_at = self.place_musts(musts, nm, lwr_from, late)
+        piece_at = self.place_pieces(ui, nm, musts, must_at)
+        self.mfma_loop(u, [fn for fn, _, _ in musts], must_at, piece_at,
+                       1 if l["name"].startswith("L") or l["name"] in ("feature", "views") else 3 if late else 2)
+        self.unit_results(u)
+        if u["last_of_chunk"]:
+            self.end_chunk(u["chunk"])
+
+    def group_hooks(self):
+        """(layer, first block) of the unit in front of which something happens once per group -> what"""
+        first_head = ("sem0" if self.nbs else "inst0") if self.depth == 2 else "sem1"
+        return {("L%d" % (SKIP + 2), 0): self.queue_inputs_early,
+                ("views", 0): self.drain_side,          # (nothing left normally) the early side work uses the g area
+                ("views", 1): self.park,
+                ("views", 2): self.take_g2,
+                (first_head, 0): self.unpark}
+
+    def take_g2(self):
+        self.g2_acc = self.acc_take(1)[0]           # home of g block 2 (packed during the next unit) until the rgb / sigma unit is issued
+
+    def unit_musts(self, ui):
+        """what has to happen inside unit ui, in program order -> ([(closure, deadline, is_pack)], index of the first local-weight
+        read or None); deadline: the MFMA (index in the unit) that must find the closure done, or None"""
+        u = self.units[ui]
+        frags = self.unit_frags(u)
         # (1) the previous unit's pack / ReLU, each before the first MFMA of THIS unit that reads its destination
         prev = self.pending_pack
         self.pending_pack = None
         packs = prev["ops"] if prev else []
         reads = {}
-        for i in range(nm):
+        for i in range(2 * len(frags)):
             f, t = i // 2, i % 2
             loc = self.b_operand(u, frags[f][2], self.tile_at(frags[f][2], t))
             for r in range(4):
@@ -966,47 +626,43 @@ class Gen:
         # ... and, pipelined with it, the NEXT unit's bias: as soon as an accumulator is packed it is released and re-armed.  One list
         # of "musts" in program order, spread evenly over the unit's gaps (the first version packed in the first 60 % of the gaps
         # and armed in the last 25 %: up to seven fillers per gap where five hide, and nothing to do in between)
-        nxt = U[ui + 1] if ui + 1 < len(U) else None
+        nxt = self.units[ui + 1] if ui + 1 < len(self.units) else None
         plans = self.arm_plan(nxt) if nxt is not None else []
-        musts, dls, pack_fns = [], [], set()
+        musts = []
         by_acc = {}
         for dst, fn, a in packs:
             by_acc.setdefault(a, []).append((dst, fn))
         k = 0
         for a, lst in by_acc.items():
             for dst, fn in lst:
-                musts.append(fn if not self.abl & 4 else (lambda: None))
-                pack_fns.add(musts[-1])
                 if isinstance(dst, list):           # pipelined packs: every destination that becomes final in this closure
                     dd = [reads[d] for d in dst if d in reads]
-                    dls.append(min(dd) if dd else None)
+                    dl = min(dd) if dd else None
                 else:
-                    dls.append(reads.get(dst))
-            musts.append(lambda a=a: self.acc_release([a]))
-            dls.append(None)
+                    dl = reads.get(dst)
+                musts.append((fn if not self.abl & 4 else (lambda: None), dl, True))
+            musts.append((lambda a=a: self.acc_release([a]), None, False))
             if k < len(plans):
-                for op in plans[k]:
-                    musts.append(op)
-                    dls.append(None)
+                musts += [(op, None, False) for op in plans[k]]
                 k += 1
         for kk in range(k, len(plans)):
-            for op in plans[kk]:
-                musts.append(op)
-                dls.append(None)
+            musts += [(op, None, False) for op in plans[kk]]
         lwr_from = None
-        if nxt is None and (self.logit_units or l["mode"] == "logits"):
+        if nxt is None and (self.logit_units or self.layers[u["layer"]]["mode"] == "logits"):
             # the group's last unit: the logit tail's per-register weights lwr[r] = lw[row(r, hi)] of both tiles come back from the LDS
             # table (rgbs_epilogue: scan) into the two accumulators nobody holds any more -- behind the packs that release them
             lwr_from = len(musts)
-            for op in self.lwr_ops():
-                musts.append(op)
-                dls.append(None)
+            musts += [(op, None, False) for op in self.lwr_ops()]
+        return musts, lwr_from
+
+    @staticmethod
+    def place_musts(musts, nm, lwr_from, late):
+        """-> {gap: [indices into musts]}: the musts spread over the unit's nm gaps, none behind its deadline"""
         n = len(musts)
         pos = []
-        late = not packs and n > 0 and nxt is not None  # nothing to pack (the previous unit's results go through the side queue and hold
-        for j in range(n):                              # their accumulators until then): arm in the unit's last third
+        for j, (_, dl, _) in enumerate(musts):
             spread = 1 + (j * max(1, nm - 6)) // max(1, n) if not late else (2 * nm) // 3 + (j * max(1, nm // 3 - 5)) // max(1, n)
-            pos.append(spread if dls[j] is None else min(spread, max(0, dls[j] - 2)))
+            pos.append(spread if dl is None else min(spread, max(0, dl - 2)))
         if lwr_from is not None:                        # the local-weight reads: in the unit's second half (the side queue drains first)
             nl = n - lwr_from
             for j in range(lwr_from, n):
@@ -1015,16 +671,21 @@ class Gen:
             pos[j] = min(pos[j], pos[j + 1])
         must_at = {}
         for j, g in enumerate(pos):
+            assert g < nm, (g, nm)                      # (positions beyond the last gap: none by construction)
             must_at.setdefault(g, []).append(j)
-        # (2) LDS-DMA pieces of chunk + 3, spread over the chunk's units
+        return must_at
+
+    def place_pieces(self, ui, nm, musts, must_at):
+        """-> {gap: [piece indices]}: this unit's share of the LDS-DMA pieces of chunk + 3 (they are spread over the chunk's units),
+        each in the cheapest gap of its stretch"""
+        U = self.units
         piece_at = {}
-        cu = [k for k, x in enumerate(U) if x["chunk"] == u["chunk"]]
-        c3 = (u["chunk"] + 3) % self.NC
-        npieces = self.pieces_of(c3)
+        cu = [k for k, x in enumerate(U) if x["chunk"] == U[ui]["chunk"]]
+        npieces = tt_plan.pieces_of(self.chunks, (U[ui]["chunk"] + 3) % self.NC)
         k_in = cu.index(ui)
         mine = [j for j in range(npieces) if (j * len(cu)) // npieces == k_in]
-        cost = [3 * sum(1 for j in must_at.get(g, []) if j < n and dls[j] is not None or (j < n and musts[j] in pack_fns)) +
-                sum(1 for j in must_at.get(g, [])) for g in range(nm)]
+        # what a gap already holds: a pack or a must with a deadline weighs 4, any other must 1, a piece 2
+        cost = [sum(4 if musts[j][1] is not None or musts[j][2] else 1 for j in must_at.get(g, [])) for g in range(nm)]
         for idx, j in enumerate(mine):
             span = max(len(mine) + 1, nm - 3)       # over all of the unit's gaps (the first half only: measured slower, round 5)
             lo = 1 + (idx * span) // max(1, len(mine))
@@ -1032,9 +693,17 @@ class Gen:
             g = min(range(lo, min(hi, nm - 1)), key=lambda x: (cost[x], x))
             cost[g] += 2
             piece_at.setdefault(g, []).append(j)
-        # ---- the MFMAs
+        return piece_at
+
+    def mfma_loop(self, u, fillers, must_at, piece_at, side_budget):
+        """the unit's MFMAs; in the gap behind each: the ring's next fragment, the gap's musts (fillers[j] for j in must_at), its
+        pieces of chunk + 3 and side_budget instructions of side work"""
+        e = self.e
+        frags = self.unit_frags(u)
+        swap = self.layers[u["layer"]]["mode"] == "logits"
+        c3 = (u["chunk"] + 3) % self.NC
         first_wait_done = False
-        for i in range(nm):
+        for i in range(2 * len(frags)):
             f, t = i // 2, i % 2
             slot, off, ks, bi = frags[f]
             gi = u["frag0"] + f                                    # index in the group's fragment stream
@@ -1059,25 +728,23 @@ class Gen:
                 gn = gi + P - 1
                 if gn < len(self.stream):
                     sl, of = self.stream[gn]
-                    self.ring_tags[gn % P] = self.lds_read("ds_read_b128 %s, v%d offset:%d" % (vr(V_RING + 4 * (gn % P), 4), V_FRAG + sl, of))
+                    self.ring_tags[gn % P] = self.lgkm_op("ds_read_b128 %s, v%d offset:%d" % (vr(V_RING + 4 * (gn % P), 4), V_FRAG + sl, of))
             for j in must_at.get(i, []):
-                musts[j]()
+                fillers[j]()
             for j in ([] if self.abl & 1 else piece_at.get(i, [])):
-                if j == 0:
-                    self.chunk_base(c3)
-                tg = self.piece(c3, j)
-                self.piece_tag[c3] = tg
-            self.drain_side(1 if l["name"].startswith("L") or l["name"] in ("feature", "views") else 3 if late else 2)
-        for g in sorted(must_at):                       # (positions beyond the last gap: none by construction)
-            assert g < nm, (g, nm)
-        # ---- this unit's own results: packed during the next unit, or reduced by the side queue
+                self.issue_piece(c3, j)
+            self.drain_side(side_budget)
+
+    def unit_results(self, u):
+        """what becomes of the unit's accumulators: packed during the next unit, or reduced by the side queue, or kept for the tail"""
+        l = self.layers[u["layer"]]
         if l["mode"] in ("relu", "linear"):
             self.pending_pack = dict(ops=self.pack_ops(u), accs=list(u["accs"].values()))
         elif l["mode"] == "rgbs":
             for t in range(2):
                 self.rgbs_epilogue(t, self.acc_reg(u["accs"][(0, t)]))
             ids = list(u["accs"].values())
-            self.q(0, lambda: self.defer(lambda: self.acc_release(ids)))
+            self.q(lambda: self.defer(lambda: self.acc_release(ids)))
             self.queue_inputs_late()
             self.acc_release([self.g2_acc])         # g is dead: every MFMA of the rgb / sigma unit has been issued
             self.g2_acc = None
@@ -1088,27 +755,19 @@ class Gen:
             # three independent FMA chains beside each other -- one block at a time is a chain of 16 dependent FMAs and two LDS
             # round trips with nothing to overlap them (the first version's tail: 2650 cycles)
             self.logit_units.append(u)
-        # ---- chunk hand-over
-        if u["last_of_chunk"]:
-            c2 = (u["chunk"] + 2) % self.NC
-            if not self.abl & 2:
-                self.wait_vm(self.piece_tag.get(c2))
-                e("s_barrier")
-            # dummy chunks behind the group's last real chunk: their share of the weight stream (the pieces of chunk + 3) and their
-            # hand-over, with whatever side work is queued between the pieces
-            d = u["chunk"] + 1
-            while d < self.NC and self.chunks[d].get("dummy"):
-                e("; ==== dummy chunk %d (slot %d)" % (d, d % NSLOT))
-                c3 = (d + 3) % self.NC
-                for j in ([] if self.abl & 1 else range(self.pieces_of(c3))):
-                    if j == 0:
-                        self.chunk_base(c3)
-                    self.piece_tag[c3] = self.piece(c3, j)
-                    self.drain_side(2)
-                if not self.abl & 2:
-                    self.wait_vm(self.piece_tag.get((d + 2) % self.NC))
-                    e("s_barrier")
-                d += 1
+
+    def end_chunk(self, chunk):
+        """the hand-over behind a chunk's last unit, and the dummy chunks behind the group's last real chunk: their share of the
+        weight stream (the pieces of chunk + 3) and their hand-over, with whatever side work is queued between the pieces"""
+        self.hand_over(chunk)
+        d = chunk + 1
+        while d < self.NC and self.chunks[d].get("dummy"):
+            self.e("; ==== dummy chunk %d (slot %d)" % (d, d % NSLOT))
+            for j in ([] if self.abl & 1 else range(tt_plan.pieces_of(self.chunks, (d + 3) % self.NC))):
+                self.issue_piece((d + 3) % self.NC, j)
+                self.drain_side(2)
+            self.hand_over(d)
+            d += 1
 
     def tail_softmax(self, blocks, lwr_reg, tag_lwr):
         """semantic_activation = softmax: per head and tile, IN PLACE -- the head's logit accumulators become e = exp(x - max) and the
@@ -1122,8 +781,7 @@ class Gen:
         semantic head's FMA chains are issued before the instance head rescales them."""
         e = self.e
         M = (V_TMP, V_RING)                         # m / d of the tile: 16 registers each (g area; the fragment ring is idle at a group's end)
-        TMP = [V_IN + 10, V_IN + 11, V_IN + 12, V_IN + 13]  # temporaries of the xor-16 steps: the next group's o_z and q of tile 1 (dead: its
-                                                            # gamma(d) is encoded) -- NOT the logits tail's sums / oth registers (V_IN + 1..5, 9)
+        TMP = [V_SMX + i for i in range(4)]         # temporaries of the xor-16 steps
         ninf = V_PTMP + 6
         heads = []
         for inst in (False, True):
@@ -1232,7 +890,7 @@ class Gen:
                 for h2 in range(2):
                     def rd(t=t, q=q, h2=h2):
                         dst = self.acc_reg(self.lwr_acc[t]) + 4 * q + ((2 * h2 + 2) & 3)
-                        self.lwr_tag = self.lds_read("ds_read_b64 %s, v%d offset:%d" % (vr(dst, 2), V_LWA, 128 * t + 32 * q + 8 * h2))
+                        self.lwr_tag = self.lgkm_op("ds_read_b64 %s, v%d offset:%d" % (vr(dst, 2), V_LWA, 128 * t + 32 * q + 8 * h2))
                     ops.append(rd)
         return ops
 
@@ -1282,7 +940,7 @@ class Gen:
                         else:
                             e("v_fmac_f32 v%d, v%d, v%d" % (sums[t][k], lwr_reg(t, r), a + r))
             for t in ts:
-                tags[t] = [self.lds_read("ds_bpermute_b32 v%d, v%d, v%d" % (oth[t][k], adr, sums[t][k])) for k in range(nb)]
+                tags[t] = [self.lgkm_op("ds_bpermute_b32 v%d, v%d, v%d" % (oth[t][k], adr, sums[t][k])) for k in range(nb)]
 
         def stores(t):
             for k in range(nb):                     # the sums under the FULL exec mask, then the masked stores
@@ -1315,14 +973,14 @@ class Gen:
                 self.e("s_add_u32 s%d, s%d, s%d" % (S_GRP2, S_GRP, S_NWG))
                 self.e("s_cmp_lt_i32 s%d, s%d" % (S_GRP2, S_NGRP))
                 self.e("s_cselect_b32 s%d, s%d, s%d" % (S_GRP2, S_GRP2, S_GRP))
-        self.q(3, which)
+        self.q(which)
         tags = {}
         for t in range(2):
-            self.q(34, (lambda t=t: tags.__setitem__(t, self.fetch_tile(t, S_GRP2))))
+            self.q(lambda t=t: tags.__setitem__(t, self.fetch_tile(t, S_GRP2)))
         for t in range(2):
-            self.q(1, (lambda t=t: self.wait_vm(tags[t])))      # (deferred: the holder is filled when the load is emitted)
-            for cost, fn in self.encode_tile(t, "x"):
-                self.q(cost, fn)
+            self.q(lambda t=t: self.wait_vm(tags[t]))      # (deferred: the holder is filled when the load is emitted)
+            for fn in self.encode_tile(t, "x"):
+                self.q(fn)
 
     PARK = (3, 6, 7, 0)             # what of V_IN outlives gamma(x): the per-ray table address, z, z_next, |d|
 
@@ -1347,12 +1005,12 @@ class Gen:
         grew by what the head units shrank, profiles/r06/r06f.  What the kernel pays for is the NUMBER of non-MFMA instructions, not
         where they stand.)"""
         for t in range(2):
-            for cost, fn in self.encode_tile(t, "d"):
-                self.q(cost, fn, low=True)
+            for fn in self.encode_tile(t, "d"):
+                self.q(fn, low=True)
 
     # ------------------------------------------------------------------ trace builds (k_mlp_tt_*_trace): s_memtime per unit
     def stamp(self, idx):
-        """lane idx of v13 := low word of s_memtime here (written one stamp later: the scalar load has returned by then); the
+        """lane idx of V_TRACE := low word of s_memtime here (written one stamp later: the scalar load has returned by then); the
         clock output of a trace build is the 64 stamps of workgroup 0's first wave in its LAST group"""
         if not self.trace:
             return
@@ -1366,14 +1024,14 @@ class Gen:
         if idx == len(self.units) + 3:
             # the group's end also goes to lane 56 + (group counter & 7): the durations of the last eight groups
             skip = self.label()
-            self.o += ["\ts_waitcnt lgkmcnt(0)", "\ts_and_b32 s%d, s101, 7" % S_T0, "\ts_add_u32 s%d, s%d, 56" % (S_T0, S_T0),
+            self.o += ["\ts_waitcnt lgkmcnt(0)", "\ts_and_b32 s%d, s%d, 7" % (S_T0, S_NDONE), "\ts_add_u32 s%d, s%d, 56" % (S_T0, S_T0),
                        "\ts_mov_b32 m0, s%d" % S_T0, "\ts_nop 1",
                        "\tv_writelane_b32 v%d, s%d, m0" % (V_TRACE, pair),
                        # every 32nd group's end (groups 0, 32, .., 160) to lanes 48..53: the average group time per window
-                       "\ts_and_b32 s%d, s101, 31" % S_T0, "\ts_cmp_eq_u32 s%d, 0" % S_T0, "\ts_cbranch_scc0 %s" % skip,
-                       "\ts_lshr_b32 s%d, s101, 5" % S_T0, "\ts_add_u32 s%d, s%d, 48" % (S_T0, S_T0), "\ts_mov_b32 m0, s%d" % S_T0,
+                       "\ts_and_b32 s%d, s%d, 31" % (S_T0, S_NDONE), "\ts_cmp_eq_u32 s%d, 0" % S_T0, "\ts_cbranch_scc0 %s" % skip,
+                       "\ts_lshr_b32 s%d, s%d, 5" % (S_T0, S_NDONE), "\ts_add_u32 s%d, s%d, 48" % (S_T0, S_T0), "\ts_mov_b32 m0, s%d" % S_T0,
                        "\ts_nop 1", "\tv_writelane_b32 v%d, s%d, m0" % (V_TRACE, pair), skip + ":",
-                       "\ts_add_u32 s101, s101, 1"]
+                       "\ts_add_u32 s%d, s%d, 1" % (S_NDONE, S_NDONE)]
 
     # ------------------------------------------------------------------ group boundary
     def prefetch_first_unit(self):
@@ -1385,7 +1043,7 @@ class Gen:
                 op()
         for g in range(P - 1):
             sl, of = self.stream[g]
-            self.ring_tags[g % P] = self.lds_read("ds_read_b128 %s, v%d offset:%d" % (vr(V_RING + 4 * (g % P), 4), V_FRAG + sl, of))
+            self.ring_tags[g % P] = self.lgkm_op("ds_read_b128 %s, v%d offset:%d" % (vr(V_RING + 4 * (g % P), 4), V_FRAG + sl, of))
 
     def advance_group_state(self):
         """the prefetched group becomes the current one: z, z_next, |d| and the masks"""
@@ -1423,7 +1081,7 @@ class Gen:
         self.o += ["\t.text", "\t.globl\t%s" % name, "\t.p2align\t8", "\t.type\t%s,@function" % name, "%s:" % name]
         for dst, off, n in ((S_IMG, 0x0, 2), (S_RAYS, 0x8, 2), (S_Z, 0x10, 2), (S_S, 0x18, 2), (S_MAGIC, 0x20, 2), (S_NGRP, 0x28, 2),
                             (S_REC, 0x30, 2), (S_RECF, 0x38, 1), (S_PS, 0x40, 2), (S_NSEM, 0x48, 2), (S_CLK, 0x50, 2), (S_AUX, 0x58, 2)):
-            e("s_load_dword%s %s, s[0:1], 0x%x" % ("x2" if n == 2 else "", sr(dst, n), off))
+            e("s_load_dword%s %s, %s, 0x%x" % ("x2" if n == 2 else "", sr(dst, n), sr(S_KARG), off))
         # wave id from v0 itself (never written): a v_readfirstlane of a register that is re-used a few instructions later was
         # observed to return the LATER value while scalar-load data was returning (tools/probe/gen_two_tile_asm.py)
         e("v_readfirstlane_b32 s%d, v0" % S_WAVE)
@@ -1453,7 +1111,7 @@ class Gen:
         e("s_mov_b32 s%d, 0" % (S_HI0 + 1))
         e("s_lshr_b32 s%d, s%d, 4" % (S_LWW, S_W4K))                      # wave * 256: this wave's [2 tiles][32] local-weight table
         e("s_add_u32 s%d, s%d, 0x%x" % (S_LWW, S_LWW, LW_BASE))
-        e("s_sub_u32 s%d, s%d, 0x%x" % (S_LWR, S_LWW, 0 * SLOT))          # + V_BIAS[0] (= slot 0's base + 16 hi) = table + 16 hi
+        e("s_sub_u32 s%d, s%d, 0x%x" % (S_LWR, S_LWW, 0))          # + V_BIAS[0] (= slot 0's base + 16 hi) = table + 16 hi
         e("s_waitcnt lgkmcnt(0)")
         # store masks of the logit blocks (constant): channel = 32 blk + (lane & 31) < n_out, lanes 0..31 only
         for k, (blk, inst) in enumerate(self.logit_blocks()):
@@ -1471,14 +1129,13 @@ class Gen:
                         e("v_add_u32 v%d, %d, v%d" % (V_T0, 32 * (nblk - 1), V_T0))
                     e("v_cmp_gt_i32 s[%d:%d], s%d, v%d" % (S_VMSK + 2 * k, S_VMSK + 2 * k + 1, sreg, V_T0))
         lend, lloop, lfin = self.label(), self.label(), self.label()
-        e("s_mov_b32 s%d, s2" % S_GRP)
+        e("s_mov_b32 s%d, s%d" % (S_GRP, S_WG))
         e("s_cmp_ge_i32 s%d, s%d" % (S_GRP, S_NGRP))
         e("s_cbranch_scc1 %s" % lend)
         # chunks 0, 1, 2 -> slots 0, 1, 2
         for c in range(3):
-            self.chunk_base(c)
-            for j in range(self.pieces_of(c)):
-                self.piece_tag[c] = self.piece(c, j)
+            for j in range(tt_plan.pieces_of(self.chunks, c)):
+                self.issue_piece(c, j)
         e("s_waitcnt vmcnt(0)")
         self.vm.drain()
         e("s_barrier")
@@ -1488,7 +1145,7 @@ class Gen:
         for t in range(2):
             self.wait_vm(tags[t])
             for part in ("x", "d"):
-                for _, fn in self.encode_tile(t, part):
+                for fn in self.encode_tile(t, part):
                     fn()
         self.advance_group_state()
         if not self.trace:
@@ -1496,8 +1153,8 @@ class Gen:
             e("s_memrealtime s[%d:%d]" % (S_CLK0 + 2, S_CLK0 + 3))
         else:
             e("v_mov_b32 v%d, 0" % V_TRACE)
-            e("s_mov_b32 s101, 0")
-            e("s_memtime s[90:91]")                                  # the workgroup's start
+            e("s_mov_b32 s%d, 0" % S_NDONE)
+            e("s_memtime %s" % sr(S_WGCLK))                                  # the workgroup's start
             e("s_waitcnt lgkmcnt(0)")
         e("s_waitcnt lgkmcnt(0)")
         self.lgkm.drain()
@@ -1526,8 +1183,8 @@ class Gen:
             e("s_cbranch_scc1 %s" % lw)
             e("s_memtime s[%d:%d]" % (S_CLK0, S_CLK0 + 1))
             e("s_waitcnt lgkmcnt(0)")
-            e("s_sub_u32 s%d, s%d, s90" % (S_CLK0, S_CLK0))
-            e("s_lshl_b32 s%d, s2, 2" % S_T0)
+            e("s_sub_u32 s%d, s%d, s%d" % (S_CLK0, S_CLK0, S_WGCLK))
+            e("s_lshl_b32 s%d, s%d, 2" % (S_T0, S_WG))
             e("s_add_u32 s%d, s%d, 256" % (S_T0, S_T0))
             e("v_mov_b32 v%d, s%d" % (V_T0, S_T0))
             e("v_mov_b32 v%d, s%d" % (V_T1, S_CLK0))
@@ -1536,7 +1193,7 @@ class Gen:
             e("s_mov_b64 exec, -1")
             e("s_waitcnt vmcnt(0)")
             self.o.append(lw + ":")
-        e("s_cmp_lg_u32 s2, 0")
+        e("s_cmp_lg_u32 s%d, 0" % S_WG)
         e("s_cbranch_scc1 %s" % lfin)
         if self.trace:
             e("s_cmp_lg_u32 s%d, 0" % S_WAVE)
@@ -1546,7 +1203,7 @@ class Gen:
             e("global_store_dword v%d, v%d, s[%d:%d]" % (V_T0, V_TRACE, S_CLK, S_CLK + 1))
             e("s_waitcnt vmcnt(0)")
             e("s_branch %s" % lfin)
-        e("s_memtime s[%d:%d]" % (S_T0 - 0, S_T0 + 1))
+        e("s_memtime s[%d:%d]" % (S_T0, S_T0 + 1))
         e("s_memrealtime s[%d:%d]" % (S_SAVE, S_SAVE + 1))
         e("s_waitcnt lgkmcnt(0)")
         e("s_sub_u32 s%d, s%d, s%d" % (S_T0, S_T0, S_CLK0))
@@ -1556,12 +1213,12 @@ class Gen:
         e("v_cmp_eq_u32 vcc, 0, v0")
         e("s_and_saveexec_b64 s[%d:%d], vcc" % (S_VALID, S_VALID + 1))
         e("s_cbranch_execz %s" % lfin)
-        e("v_mov_b32 v20, s%d" % S_T0)
-        e("v_mov_b32 v21, s%d" % S_T1)
-        e("v_mov_b32 v22, s%d" % S_SAVE)
-        e("v_mov_b32 v23, s%d" % (S_SAVE + 1))
+        e("v_mov_b32 v%d, s%d" % (V_CLKOUT, S_T0))
+        e("v_mov_b32 v%d, s%d" % (V_CLKOUT + 1, S_T1))
+        e("v_mov_b32 v%d, s%d" % (V_CLKOUT + 2, S_SAVE))
+        e("v_mov_b32 v%d, s%d" % (V_CLKOUT + 3, S_SAVE + 1))
         e("v_mov_b32 v%d, 0" % V_T0)
-        e("global_store_dwordx4 v%d, v[20:23], s[%d:%d]" % (V_T0, S_CLK, S_CLK + 1))
+        e("global_store_dwordx4 v%d, %s, s[%d:%d]" % (V_T0, vr(V_CLKOUT, 4), S_CLK, S_CLK + 1))
         e("s_waitcnt vmcnt(0)")
         self.o.append(lfin + ":")
         e("s_endpgm")
@@ -1570,7 +1227,7 @@ class Gen:
                    "\t\t.amdhsa_group_segment_fixed_size %d" % (NSLOT * SLOT + 1024),
                    "\t\t.amdhsa_private_segment_fixed_size 0", "\t\t.amdhsa_kernarg_size %d" % KERNARG_BYTES, "\t\t.amdhsa_user_sgpr_count 2",
                    "\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1", "\t\t.amdhsa_system_sgpr_workgroup_id_x 1",
-                   "\t\t.amdhsa_system_vgpr_workitem_id 0", "\t\t.amdhsa_next_free_vgpr 512", "\t\t.amdhsa_next_free_sgpr 102",
+                   "\t\t.amdhsa_system_vgpr_workitem_id 0", "\t\t.amdhsa_next_free_vgpr 512", "\t\t.amdhsa_next_free_sgpr %d" % NEXT_FREE_SGPR,
                    "\t\t.amdhsa_accum_offset 256", "\t\t.amdhsa_reserve_vcc 1", "\t\t.amdhsa_float_denorm_mode_32 3",
                    "\t\t.amdhsa_float_denorm_mode_16_64 3", "\t\t.amdhsa_dx10_clamp 1", "\t\t.amdhsa_ieee_mode 1",
                    "\t.end_amdhsa_kernel", ""]
