@@ -1096,6 +1096,112 @@ int pnr_tsdf_raycast(int model, const float* cam_host, const float* c2w12_host, 
                      const float* weight, float min_weight, float dt, int max_steps, float* depth, float* normal, int32_t* src,
                      uint8_t* code, void* stream);
 
+/* ---- mesh ray casting (csrc/pnr_meshcast.hip; DESIGN.md 8 "Mesh ray casting"): a triangle mesh seen from any camera, or along a
+ * list of rays -- the first hit per ray: depth, face, barycentric weights, nearest corner, flat normal and side.  The reference
+ * ships none of this: the rule is this build's and unpinned (tests/_meshcast_ref.py restates it in numpy, bit for bit).  Float32
+ * throughout unless stated, every operation a single + - * / sqrt in the order given, never an FMA; divide and sqrt correctly
+ * rounded; denormals are not flushed.  THE ANSWER IS DEFINED BY BRUTE FORCE OVER ALL FACES; the index below only prunes.
+ *
+ * INPUTS.  vertices (V, 3) float32, faces (F, 3) int32.  The ray of element q is
+ *   pnr_mesh_raycast:   o, d, near, far = pnr_camera_ray(model, cam, c2w, i, j, near_, far_, ok) unchanged, q = j width + i;
+ *   pnr_mesh_cast_rays: the record rays[q] = (o, d, near, far) of an (n, 8) array, ok = true.
+ *   NO_RAY if !ok, if a component of o or d is not finite, if d = 0, or if !(0 <= near <= far) (a NaN fails; far may be +inf).
+ *   depth is the ray parameter t of the hit: z-depth in a pinhole frame, range in a fisheye or equirect frame (render_view's
+ *   and pnr_tsdf_raycast's convention).
+ * RAY-TRIANGLE TEST: the watertight test of Woop, Benthin and Wald (JCGT 2013), two-sided.  Once per ray:
+ *   kz = the axis of largest |d_k|, the lowest axis on a tie; kx = kz + 1, ky = kx + 1 (mod 3), swapped if d[kz] < 0;
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ *  Per face with corners v0, v1, v2:
+ *   A = v0 - o, B = v1 - o, C = v2 - o;   Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz]; B and C alike.
+ *   U = Cx * By - Cy * Bx,  V = Ax * Cy - Ay * Cx,  W = Bx * Ay - By * Ax.
+ *   If any of the three is exactly 0, all three are recomputed in double -- both products exact, one subtraction -- and rounded
+ *   to float32 once.
+ *   MISS if one of U, V, W is < 0 and one is > 0.   det = (U + V) + W;  MISS if det == 0.
+ *   t = ((U * Az + V * Bz) + W * Cz) / det + 0.0f (the addition turns -0 into +0).  MISS unless near <= t <= far: a NaN misses.
+ *   BOX TEST.  M = the largest of the nine |A_k|, |B_k|, |C_k| (max, in any order: exact), e = PNR_MESHCAST_BOX_TOL * M (2^-17,
+ *   one multiply).  Per world axis k: q_k = t * d_k (the hit point relative to the origin), lo_k = min(min(A_k, B_k), C_k),
+ *   hi_k = max(max(A_k, B_k), C_k);  MISS unless lo_k - e <= q_k <= hi_k + e on all three axes.  t is a mean of the corners'
+ *   depths Az, Bz, Cz along the ray's dominant axis with weights U, V, W; for a ray that crosses the face its error is a few
+ *   2^-24 of the largest |depth|, so that of every q_k = t d_k is a few 2^-24 of max |A[kz]| <= M (|d_k| <= |d[kz]|): inside
+ *   e with a factor of some thirty to spare, at any distance from the face and any incidence -- along the face's normal the
+ *   error of t d shrinks with the sine of the incidence as the error of t grows with its inverse.  For a ray nearly IN the
+ *   plane of a face U, V, W are cancellation noise and t an arbitrary mean of Az, Bz, Cz: such a "hit" far from the face is
+ *   none.  The test also ties every hit to the box the index files the face under, which is what makes the index exact
+ *   (DESIGN.md).  Watertightness is that of the edge functions: a ray through a shared edge passes the sign test of both
+ *   faces; it hits unless the noise of t carries the hit point out of the widened boxes of both, which takes a ray within
+ *   about 2^-17 of the planes of both AND a crossing that close to the rim of both boxes.
+ * WINNER: the hit with the smallest key ((uint64) bits(t) << 32) | (uint32) face -- the key of pnr_splat_points and pnr_nn_query:
+ *   the nearest face, a tie in t going to the lowest face index (t >= +0, so the bits order as the values do).
+ * OUTPUTS, caller-owned device arrays, one element per ray; the optional ones may be NULL:
+ *     depth   float32          t                                                          0 off a hit
+ *     face    int32            the winning face                                           -1
+ *     code    uint8            PNR_RAYCAST_HIT, _NO_RAY or _MISSED
+ *     bary    float32 (., 3)   U / det, V / det, W / det: the weights of v0, v1, v2       0        optional
+ *     vertex  int32            the index of the corner with the largest weight, the       -1       optional
+ *                              first on a tie: what per-vertex labels are read through
+ *     normal  float32 (., 3)   below                                                      0        optional
+ *     side    int8             +1 / -1                                                    0        optional
+ *   n = (v1 - v0) x (v2 - v0), each component (a * b) - (c * d);  dot = (nx * dx + ny * dy) + nz * dz;  side = +1 if dot < 0 -- the
+ *   ray met the side the winding normal points to --, else -1.  len = sqrt((nx nx + ny ny) + nz nz); normal = n / len, negated
+ *   if side = -1, so it faces the ray's origin: the convention of pnr_tsdf_raycast and pnr_depth_normals that pnr_icp_accumulate
+ *   expects.  len not positive and finite: normal = 0 and the element is still a HIT.
+ * THE INDEX: a uniform grid res_x x res_y x res_z over the box from lo with cells of size cell (HOST values; inv_k = 1 / cell_k, one
+ *   float32 division).  Grid coordinates g_k(p) = (p_k - lo_k) * inv_k.  PAD = PNR_MESHCAST_PAD = 1/16 cell.
+ *   pnr_mesh_grid_bounds: bounds[0..2] / [3..5] = the smallest / largest coordinate per axis over the corners of USABLE faces (every
+ *     index in range, every coordinate finite), +inf / -inf if there is none; bounds[6] = the bits of their number (uint32),
+ *     bounds[7] = 0.  Integer atomics on order-preserving keys: exact in any order.  The caller widens the box and picks res.
+ *   pnr_mesh_grid_count: every usable face adds 1 (int32 atomic) to every cell of [floor(min g_k - PAD), floor(max g_k + PAD)] per
+ *     axis over its corners, clamped to the grid as floats; then the shared scan (csrc/pnr_scan_dev.h) into start[0 .. cells] and
+ *     the 64-bit entry total into total.  The caller reads total -- its synchronisation --, refuses one above 2^31 - 1, allocates
+ *     records (total, 12) float32 and calls pnr_mesh_grid_fill with the same mesh, grid, start and workspace: a returning atomic on
+ *     the cell's cursor places the 48-byte record (v0, v1, v2, bits = face, 0, 0): a candidate is three 16-byte loads, no gather.
+ *     The fill CONSUMES the cursors its count left in the workspace: one fill per count, nothing else using the workspace in
+ *     between; a second fill needs a second count (it would place records below their cells' ranges, inside the array).
+ *     The order of the records in a cell depends on arrival and is not part of the rule.  cell index = (cz res_y + cy) res_x + cx.
+ *   A CAST computes og = (o - lo) * inv, dg = d * inv per axis, and its REACH = max_k (|og_k| + (float)(res_k + 1)) * cell_k: a
+ *     bound in world units on every |component| of a corner of the grid's faces relative to the origin.  It takes THE PLAIN LOOP
+ *     over all faces unless reach <= PNR_MESHCAST_MAX_REACH (4096) * the smallest cell_k -- then the box test's tolerance is at
+ *     most 2^-5 of any cell, half a PAD --, or if some og_k or dg_k is not finite, the dominant dg_k is 0, or the clip below
+ *     overflows: a camera very far from a small mesh, or a grid of very unequal cells, is slow and right.  Otherwise the ray is
+ *     clipped to [near, far] and to the grid box widened by PAD; no overlap: MISSED.  It walks the layers of the axis of largest
+ *     |dg_k| in order from the one it enters in; per layer the parameters at which it enters and leaves the slab, clamped to the
+ *     clip, give the other two coordinates at both, and every cell of [floor(min - PAD), floor(max + PAD)] on those two axes is
+ *     visited, every record in it tested by the rule above and the smallest key kept, wherever that hit lies.  After a layer
+ *     the walk stops once the best hit lies more than PAD short of the layer's far face.  Start pairs are clamped into
+ *     [0, n_entries]: a damaged table can give wrong answers, never an out-of-range read.  DESIGN.md argues why the outputs equal
+ *     the plain loop's whatever res is.
+ * The casts read the mesh and the index when the kernel runs, never synchronise and are capture-safe; the camera, the pose and
+ * the grid's res, lo and cell are host values baked into the launch.  workspace: pnr_mesh_grid_workspace_bytes(res) bytes, 8-byte
+ * aligned, the same block for bounds, count and fill (-1 for a res outside 1 .. PNR_MESHCAST_MAX_RES).
+ * PNR_EINVAL before any launch: V or F outside 0 .. 2^31 - 1; null vertices or faces of a non-empty mesh; a misaligned array (4
+ * bytes; records and rays 16; workspace and total 8); a res outside 1 .. 1024; null or non-finite lo; a cell that is not positive and
+ * finite with a finite inverse; n_entries outside 0 .. 2^31 - 1; a null start, or null records with n_entries > 0; null depth, face
+ * or code; pnr_mesh_raycast: an unknown model, null camera or pose, a bad image size, a camera the model's checks refuse,
+ * !(near_ >= 0), !(far_ > near_); pnr_mesh_cast_rays: n_rays outside 0 .. 2^31 - 1, null rays (n_rays == 0: PNR_OK before the other
+ * checks).  F == 0 is no error: every ray that is one is MISSED. */
+#define PNR_MESHCAST_PAD 0.0625f
+#define PNR_MESHCAST_BOX_TOL 0x1p-17f
+#define PNR_MESHCAST_MAX_RES 1024
+#define PNR_MESHCAST_MAX_REACH 4096.0f
+int64_t pnr_mesh_grid_workspace_bytes(int res_x, int res_y, int res_z);
+int pnr_mesh_grid_bounds(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, float* bounds,
+                         void* workspace, void* stream);
+int pnr_mesh_grid_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int res_x, int res_y,
+                        int res_z, const float* lo_host, const float* cell_host, int32_t* start, int64_t* total, void* workspace,
+                        void* stream);
+int pnr_mesh_grid_fill(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int res_x, int res_y,
+                       int res_z, const float* lo_host, const float* cell_host, const int32_t* start, int64_t n_entries,
+                       float* records, void* workspace, void* stream);
+int pnr_mesh_raycast(int model, const float* cam_host, const float* c2w12_host, int width, int height, float near_, float far_,
+                     const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int res_x, int res_y,
+                     int res_z, const float* lo_host, const float* cell_host, const int32_t* start, const float* records,
+                     int64_t n_entries, float* depth, int32_t* face, uint8_t* code, float* bary, int32_t* vertex, float* normal,
+                     int8_t* side, void* stream);
+int pnr_mesh_cast_rays(const float* rays, int64_t n_rays, const float* vertices, int64_t n_vertices, const int32_t* faces,
+                       int64_t n_faces, int res_x, int res_y, int res_z, const float* lo_host, const float* cell_host,
+                       const int32_t* start, const float* records, int64_t n_entries, float* depth, int32_t* face, uint8_t* code,
+                       float* bary, int32_t* vertex, float* normal, int8_t* side, void* stream);
+
 /* ---- pose tracking (csrc/pnr_icp.hip; DESIGN.md 8 "Pose tracking"): the pose of a live depth frame refined against a model view
  * -- a view (camera M, c2w_M, depth, world-space normal) as pnr_tsdf_raycast writes it -- by projective association and a
  * point-to-plane Gauss-Newton iteration.  The reference ships no tracker: the rule is this build's and unpinned.  The pose lives

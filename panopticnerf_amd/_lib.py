@@ -17,6 +17,7 @@ CAMERA_PINHOLE, CAMERA_FISHEYE, CAMERA_EQUIRECT = 0, 1, 3     # the model word o
 TAG_PIXEL, TAG_FRAME = 16, 17             # pnr_sample_batch's stream tags (include/pnr.h PNR_TAG_*)
 SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr.h PNR_SAMPLE_*)
 NORMAL_OK, NORMAL_NO_DEPTH, NORMAL_NO_NEIGHBOUR, NORMAL_DEGENERATE, NORMAL_GRAZING = 0, 1, 2, 3, 4    # pnr_depth_normals' codes (PNR_NORMAL_*)
+MESHCAST_MAX_RES, MESHCAST_MAX_REACH, MESHCAST_PAD = 1024, 4096.0, 0.0625    # include/pnr.h "mesh ray casting" (PNR_MESHCAST_*)
 DEPTH_MAX_RADIUS = 8                      # pnr_depth_filter's largest radius (PNR_DEPTH_MAX_RADIUS)
 NN_MAX_TABLE, CLOUD_MAX_TAU, SAMPLE_MAX_PER_FACE = 1 << 28, 8, 65535      # include/pnr.h "nearest neighbours" (PNR_NN_MAX_TABLE, PNR_CLOUD_MAX_TAU, PNR_SAMPLE_MAX_PER_FACE)
 
@@ -139,6 +140,17 @@ SIGNATURES = {
     "pnr_mesh_sample_workspace_bytes": (c_i64, [c_i64]),
     "pnr_mesh_sample_count": (c_int, [c_f, c_i64, c_f, c_i64, ctypes.c_float, c_i64, c_f, c_f, c_f, c_f]),
     "pnr_mesh_sample_emit": (c_int, [c_f, c_i64, c_f, c_i64, c_i64, c_f, c_i64, c_f, c_f, c_f]),
+    "pnr_mesh_grid_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "pnr_mesh_grid_bounds": (c_int, [c_f, c_i64, c_f, c_i64, c_f, c_f, c_f]),
+    "pnr_mesh_grid_count": (c_int, [c_f, c_i64, c_f, c_i64, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                    c_f, c_f, c_f, c_f]),
+    "pnr_mesh_grid_fill": (c_int, [c_f, c_i64, c_f, c_i64, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                   c_f, c_i64, c_f, c_f, c_f]),
+    "pnr_mesh_raycast": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,
+                                 ctypes.c_float, c_f, c_i64, c_f, c_i64, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float),
+                                 ctypes.POINTER(ctypes.c_float), c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_mesh_cast_rays": (c_int, [c_f, c_i64, c_f, c_i64, c_f, c_i64, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_float), c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_tsdf_integrate": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "pnr_tsdf_raycast": (c_int, [c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int, c_int, ctypes.c_float,

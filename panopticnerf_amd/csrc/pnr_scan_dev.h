@@ -1,5 +1,6 @@
 // Exclusive int32 scan of a device array (pnr_nn.hip: the bucket table of the nearest-neighbour index and the per-triangle
-// counts of mesh sampling).  Three launches on one stream, no kernel waits on another workgroup and nothing is atomic:
+// counts of mesh sampling; pnr_meshcast.hip: the cell table of the ray-casting grid -- the kernels are `static`, each file that
+// includes this header carries its own copy).  Three launches on one stream, no kernel waits on another workgroup and nothing is atomic:
 //   1. k_scan_tile_sums: workgroup b adds its tile of PNR_SCAN_TILE items into sums[b];
 //   2. k_scan_top:       ONE workgroup turns sums into their exclusive scan, carrying in 64 bits, and writes the 64-bit total;
 //   3. k_scan_apply:     workgroup b scans its tile again and writes out[i] = sums[b] + the items before i in the tile; the
@@ -21,7 +22,7 @@ static inline int64_t pnr_scan_tiles(int64_t n) { return (n + PNR_SCAN_TILE - 1)
 static inline int64_t pnr_scan_workspace_bytes(int64_t n) { return (pnr_scan_tiles(n) * 4 + 7) & ~(int64_t)7; }
 
 #ifdef __HIPCC__
-__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_tile_sums(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums)
+static __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_tile_sums(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums)
 {
     __shared__ int32_t lds[4];
     const int64_t base = (int64_t)blockIdx.x * PNR_SCAN_TILE + (int64_t)threadIdx.x * PNR_SCAN_PER_THREAD;
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_tile_sums(const int32_t
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_top(int32_t* __restrict__ sums, int64_t tiles, long long* __restrict__ total64)
+static __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_top(int32_t* __restrict__ sums, int64_t tiles, long long* __restrict__ total64)
 {
     __shared__ long long lds[4];
     long long carry = 0;
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_top(int32_t* __restrict
     if (threadIdx.x == 0) total64[0] = carry;
 }
 
-__global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_apply(const int32_t* in, int64_t n, const int32_t* __restrict__ sums, int32_t* out)
+static __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_apply(const int32_t* in, int64_t n, const int32_t* __restrict__ sums, int32_t* out)
 {
     __shared__ int32_t lds[4];
     const int64_t base = (int64_t)blockIdx.x * PNR_SCAN_TILE + (int64_t)threadIdx.x * PNR_SCAN_PER_THREAD;

@@ -7,7 +7,9 @@ Every vertex lies on a lattice edge and knows the lattice point on the inside en
 reads any per-point array there.  `from_network` does query_grid + extract + labels.  The numbering of vertices and triangles
 is part of the rule, so the result is the CPU restatement's bit for bit, and the same on every call.  `Mesh.sample` puts points
 on the surface at a given density (ops.mesh_sample_count / mesh_sample_emit; include/pnr.h "nearest neighbours", MESH SAMPLING):
-what `Evaluator.evaluate_geometry` compares with a ground-truth scan.
+what `Evaluator.evaluate_geometry` compares with a ground-truth scan.  `raycast` and `cast_rays` look at a mesh: the first hit of
+every pixel's ray of any camera, or of a list of rays, with depth, face, nearest vertex, flat normal and the per-vertex
+attributes carried into the image (ops.mesh_raycast / mesh_cast_rays through a `RayIndex`; include/pnr.h "mesh ray casting").
 
 Conventions (this build's, unpinned: the reference ships no extractor): inside is field > level (NaN outside); positions are
 query_grid's cell centres lo + (i + 0.5) step; triangles wind so that the normal points from inside to outside; vertices of
@@ -18,6 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .camera import is_camera
 
 
 def _vec3(v, what):
@@ -47,19 +50,49 @@ def lattice(lo, hi, res):
 class Mesh:
     """vertices (V, 3) float32, faces (T, 3) int32, src (V,) int64 -- all on the GPU.  src[v] is the flat index
     (iz * res_y + iy) * res_x + ix of the lattice point on the inside end of vertex v's edge.  res = (res_x, res_y, res_z).
-    attributes: per-vertex arrays attached by from_network; grid: the query_grid outputs from_network extracted from, else None."""
+    attributes: per-vertex arrays attached by from_network; grid: the query_grid outputs from_network extracted from, else None.
+    A mesh that did not come from a lattice (`from_arrays`) has src, res, lo, step and level None."""
 
     def __init__(self, vertices, faces, src, res, lo, step, level):
         self.vertices, self.faces, self.src = vertices, faces, src
-        self.res, self.lo, self.step, self.level = tuple(res), lo, step, level
+        self.res, self.lo, self.step, self.level = None if res is None else tuple(res), lo, step, level
         self.attributes = {}
         self.grid = None
 
+    @classmethod
+    def from_arrays(cls, vertices, faces, attributes=None, device=None):
+        """A mesh from plain arrays: vertices (V, 3) float32 and faces (F, 3) int32, torch tensors or numpy arrays, kept where they
+        are or moved to `device`; attributes: a dict of per-vertex arrays (V, ...), moved with them.  No lattice stands behind
+        such a mesh: src, res, lo, step and level are None, and labels() refuses it."""
+        def tensor(name, a, dtype=None, cols=None):
+            t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("Mesh.from_arrays: %s must be a tensor or a numpy array, got %s" % (name, type(a).__name__))
+            if dtype is not None and t.dtype != dtype:
+                raise TypeError("Mesh.from_arrays: %s must be %s, got %s" % (name, dtype, t.dtype))
+            if cols is not None and (t.dim() != 2 or t.shape[1] != cols):
+                raise ValueError("Mesh.from_arrays: %s must be (n, %d), got %s" % (name, cols, tuple(t.shape)))
+            return (t if device is None else t.to(device)).contiguous()
+        v, f = tensor("vertices", vertices, torch.float32, 3), tensor("faces", faces, torch.int32, 3)
+        if v.device != f.device:
+            raise ValueError("Mesh.from_arrays: faces is on %s, vertices on %s" % (f.device, v.device))
+        m = cls(v, f, None, None, None, None, None)
+        for name, a in (attributes or {}).items():
+            t = tensor("attributes[%r]" % (name,), a)
+            if t.dim() < 1 or t.shape[0] != v.shape[0] or t.device != v.device:
+                raise ValueError("Mesh.from_arrays: attributes[%r] must hold one row per vertex (%d) on %s, got %s on %s"
+                                 % (name, v.shape[0], v.device, tuple(t.shape), t.device))
+            m.attributes[name] = t
+        return m
+
     def __repr__(self):
-        return "Mesh(%d vertices, %d faces, lattice %d x %d x %d)" % ((self.vertices.shape[0], self.faces.shape[0]) + self.res)
+        head = "Mesh(%d vertices, %d faces" % (self.vertices.shape[0], self.faces.shape[0])
+        return head + (")" if self.res is None else ", lattice %d x %d x %d)" % self.res)
 
     def labels(self, grid):
         """grid[src]: any (res_z, res_y, res_x) tensor (labels, sigma, ...) read at the lattice point behind each vertex"""
+        if self.res is None or self.src is None:
+            raise ValueError("Mesh.labels: this mesh did not come from a lattice (Mesh.from_arrays): it has no src to read a grid at")
         rx, ry, rz = self.res
         if not isinstance(grid, torch.Tensor) or tuple(grid.shape) != (rz, ry, rx):
             raise ValueError("Mesh.labels: grid must be a (%d, %d, %d) tensor (res_z, res_y, res_x), got %s"
@@ -191,3 +224,171 @@ def from_network(net, lo, hi, res, level, want=("labels",), **query_kw):
             mesh.attributes[name] = mesh.labels(g)
     mesh.grid = grid
     return mesh
+
+
+HIT, NO_RAY, MISSED = ops.RAYCAST_HIT, ops.RAYCAST_NO_RAY, ops.RAYCAST_MISSED
+_TWO_FACES_A_CELL = 2.0
+
+
+class RayIndex:
+    """The uniform grid `raycast` and `cast_rays` prune with (include/pnr.h "mesh ray casting", THE INDEX): per cell the 48-byte
+    records -- three corners and the face index -- of the faces whose padded box touches it.  It never changes an answer: a cast
+    equals brute force over all faces bit for bit, whatever `res` is.
+
+    The build SYNCHRONISES twice, as mesh.extract and Mesh.sample read their totals: the bounds of the usable faces (every index
+    in range, every corner finite) are read back to choose the resolution, and the entry total to size the records.  The box is
+    the bounds widened per side by max(extent / 1024, largest |coordinate| / 2^20, 1e-30), so a flat mesh still has cells of
+    positive size.  res=None: about two faces a cell -- (volume / (usable faces / 2))^(1/3) over the axes that are not flat gives the
+    number of cells per axis, at most 1024, one cell on a flat axis; res=(res_x, res_y, res_z) overrides it.  The cells are cubes: one
+    size, the smallest with which res cells cover the box on every axis (grid_box).
+    Memory: 48 bytes per entry (a face is entered in every cell it touches: two to three times on a mesh whose triangles are
+    about the size of a cell, and (cells it spans) times when they are much larger) plus 4 bytes per cell; an entry total above
+    2^31 - 1 is refused.  The index is for the mesh as it was: after vertices move, build a new one."""
+
+    def __init__(self, mesh, res=None):
+        if not isinstance(mesh, Mesh):
+            raise TypeError("mesh.RayIndex: mesh must be a mesh.Mesh")
+        if res is not None:
+            res = ops.meshcast_res("mesh.RayIndex", res)
+        V, F = ops.meshcast_mesh("mesh.RayIndex", mesh.vertices, mesh.faces)
+        if not mesh.vertices.is_cuda:
+            raise RuntimeError("mesh.RayIndex: the mesh must be on the GPU (the HIP path has no CPU fallback)")
+        self.n_vertices, self.n_faces = V, F
+        b = ops.mesh_grid_bounds(mesh.vertices, mesh.faces).cpu()   # the first host synchronisation: all eight words at once
+        usable = int(b.view(torch.int32)[6])
+        self.lo, self.cell, auto = grid_box(b[:6].numpy(), usable, res)
+        self.res = auto if res is None else res
+        total, self.start, ws = ops.mesh_grid_count(mesh.vertices, mesh.faces, self.res, self.lo, self.cell)
+        n = int(total.item())                                     # the second
+        if n > ops.MESHCAST_MAX_ENTRIES:
+            raise ValueError("mesh.RayIndex: a grid of %d x %d x %d holds %d entries, more than 2^31 - 1; pass a coarser res" % (self.res + (n,)))
+        self.records = torch.empty((n, 12), device=mesh.vertices.device, dtype=torch.float32)
+        ops.mesh_grid_fill(mesh.vertices, mesh.faces, self.res, self.lo, self.cell, self.start, self.records, ws)
+
+    def __repr__(self):
+        return "RayIndex(%d x %d x %d cells, %d entries of %d faces)" % (self.res + (self.records.shape[0], self.n_faces))
+
+
+def grid_box(bounds, usable, res=None):
+    """(lo, cell, res) of a RayIndex from the six bounds (float32 numpy) of `usable` faces: float32 numpy lo and cell size per
+    axis and the resolution (the default, or `res` as given).  The cells are CUBES -- one size on all three axes, the smallest
+    with which `res` cells cover the widened box on every axis, the box centred in the grid: a cast walks the grid only while
+    its reach is within 4096 of the SMALLEST cell (include/pnr.h), so unequal cells would send rays to the plain loop.  Host
+    arithmetic; the rule is RayIndex's docstring."""
+    f = np.float32
+    if not usable or not np.isfinite(bounds).all():
+        return np.zeros(3, f), np.ones(3, f), (1, 1, 1)
+    lo, hi = bounds[:3].astype(f), bounds[3:6].astype(f)
+    with np.errstate(all="ignore"):
+        ext = (hi - lo).astype(np.float64)
+    if not np.isfinite(ext).all():
+        raise ValueError("mesh.RayIndex: the mesh's bounds %r leave no finite float32 grid" % (bounds[:6].tolist(),))
+    if res is None:
+        live = ext > 0
+        k = int(live.sum())
+        r = [1, 1, 1]
+        if k:
+            side = (float(np.prod(ext[live])) / max(usable / _TWO_FACES_A_CELL, 1.0)) ** (1.0 / k)
+            r = [min(max(int(np.ceil(e / side)), 1), ops.MESHCAST_MAX_RES) if l and side > 0 else 1 for e, l in zip(ext, live)]
+        res = tuple(r)
+    with np.errstate(all="ignore"):
+        m = f(max(float(ext.max()) / 1024.0, float(np.abs(bounds[:6]).max()) / 2.0 ** 20, 1e-30))
+        lo, hi = (lo - m).astype(f), (hi + m).astype(f)
+        r32 = np.asarray(res, f)
+        side = ((hi - lo) / r32).astype(f).max()
+        lo = (lo - (r32 * side - (hi - lo)) * f(0.5)).astype(f)
+        cell = np.full(3, side, f)
+    if not (np.isfinite(lo).all() and np.isfinite(side) and side > 0 and (lo + r32 * side >= hi - m).all() and (lo <= bounds[:3]).all()):
+        raise ValueError("mesh.RayIndex: the mesh's bounds %r leave no finite float32 grid" % (bounds[:6].tolist(),))
+    return lo, cell, res
+
+
+def _index_for(what, mesh, index):
+    if not isinstance(mesh, Mesh):
+        raise TypeError("%s: mesh must be a mesh.Mesh" % what)
+    if index is None:
+        return RayIndex(mesh)
+    if not isinstance(index, RayIndex):
+        raise TypeError("%s: index must be a mesh.RayIndex" % what)
+    if (index.n_vertices, index.n_faces) != (mesh.vertices.shape[0], mesh.faces.shape[0]):
+        raise ValueError("%s: index was built for a mesh of %d vertices and %d faces, this one has %d and %d"
+                         % (what, index.n_vertices, index.n_faces, mesh.vertices.shape[0], mesh.faces.shape[0]))
+    return index
+
+
+def _attribute_names(what, mesh, attributes):
+    taken = [n for n, _, _ in ops.MESHCAST_OUTPUTS] + ["valid"]
+    for name in mesh.attributes if attributes else ():
+        if name in taken:
+            raise ValueError("%s: the attribute %r has the name of one of the maps (%s); rename it or pass attributes=False"
+                             % (what, name, ", ".join(taken)))
+
+
+def _cast_maps(mesh, lead, normals):
+    dev = mesh.vertices.device
+    return {n: torch.empty(lead + tail, dtype=dt, device=dev) for n, dt, tail in ops.MESHCAST_OUTPUTS if normals or n != "normal"}
+
+
+def _finish(mesh, maps, attributes):
+    maps["valid"] = maps["code"] == HIT
+    if attributes:
+        at = maps["vertex"].clamp(min=0).long()
+        for name, a in mesh.attributes.items():
+            if not mesh.vertices.shape[0]:
+                continue
+            v = maps["valid"].reshape(maps["valid"].shape + (1,) * (a.dim() - 1))
+            off = torch.zeros((), dtype=a.dtype, device=a.device) if a.dtype == torch.uint8 or a.dtype.is_floating_point or a.dtype == torch.bool \
+                else torch.full((), -1, dtype=a.dtype, device=a.device)
+            maps[name] = torch.where(v, a[at], off)
+    return maps
+
+
+def raycast(mesh, camera, c2w, near, far, index=None, normals=True, attributes=True):
+    """Render `mesh` into (camera, c2w): the first hit of every pixel's ray, in ONE launch (ops.mesh_raycast; the rule is in
+    include/pnr.h "mesh ray casting"): a watertight ray-triangle test, two-sided, the nearest face winning and a tie going to the
+    lowest face index -- a ray through a shared edge or vertex of a closed mesh hits (a hit must lie within its face's box:
+    a ray in the plane of a face does not hit that face somewhere else).  camera: camera.Pinhole / Fisheye /
+    Equirect; c2w: 3x4 camera-to-world; index: a RayIndex of this mesh (None: one is built here, which synchronises twice -- keep
+    one to cast again).  Returns a maps dict of (height, width, ...) images on the mesh's device, which (camera, c2w, maps)
+    makes a view for consistency.reproject, pointcloud.lift, Evaluator.evaluate_depth and fusion.track:
+        depth   float32   the ray parameter of the hit, render_view's convention (z-depth in a pinhole, range in a fisheye /
+                          equirect frame); 0 off the surface
+        code    uint8     HIT, NO_RAY or MISSED;  valid  bool = code == HIT
+        face    int32     the face hit;  vertex  int32  its corner nearest the hit;  both -1 off the surface
+        bary    float32 (., 3)  the weights of the face's three corners at the hit, 0 off the surface
+        normal  float32 (., 3)  with normals: the face's unit normal turned towards the camera, 0 off the surface
+        side    int8      +1 where the ray met the side the winding normal points to, -1 the other, 0 off the surface
+        with attributes: every per-vertex array of mesh.attributes gathered at vertex with torch indexing -- integer arrays -1
+        off the surface, uint8 colours and floats 0.  An attribute named like one of the maps above is refused by name.
+    The cast never synchronises and can be captured in a graph."""
+    what = "mesh.raycast"
+    index = _index_for(what, mesh, index)
+    _attribute_names(what, mesh, attributes)
+    if not is_camera(camera):
+        raise TypeError("%s: camera must be a camera.Pinhole, camera.Fisheye or camera.Equirect, not %r" % (what, camera))
+    near, far = ops.meshcast_range(what, near, far)
+    if not mesh.vertices.is_cuda:
+        raise RuntimeError("%s: the mesh must be on the GPU (the HIP path has no CPU fallback)" % what)
+    h, w = int(camera.height), int(camera.width)
+    maps = _cast_maps(mesh, (h, w), normals)
+    ops.mesh_raycast(camera.model, camera.params, c2w, w, h, near, far, mesh.vertices, mesh.faces, index.res, index.lo, index.cell,
+                     index.start, index.records, maps)
+    return _finish(mesh, maps, attributes)
+
+
+def cast_rays(mesh, rays, index=None, normals=True, attributes=True):
+    """`raycast` along rays (n, 8) float32 = (o, d, near, far) on the mesh's device (ops.mesh_cast_rays): the same maps as (n, ...)
+    arrays; depth is in units of each ray's own d.  A ray with a non-finite o or d, d = 0 or !(0 <= near <= far) is NO_RAY.
+    Consecutive rays share a wave: callers who want coherence sort them.  The rays are read when the kernel runs, so a captured
+    cast follows a ray tensor edited in place."""
+    what = "mesh.cast_rays"
+    index = _index_for(what, mesh, index)
+    _attribute_names(what, mesh, attributes)
+    if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("%s: rays must be an (n, 8) float32 tensor, got %s"
+                         % (what, "%s %s" % (rays.dtype, tuple(rays.shape)) if isinstance(rays, torch.Tensor) else type(rays).__name__))
+    if not mesh.vertices.is_cuda:
+        raise RuntimeError("%s: the mesh must be on the GPU (the HIP path has no CPU fallback)" % what)
+    maps = _cast_maps(mesh, (rays.shape[0],), normals)
+    ops.mesh_cast_rays(rays, mesh.vertices, mesh.faces, index.res, index.lo, index.cell, index.start, index.records, maps)
+    return _finish(mesh, maps, attributes)

@@ -890,6 +890,173 @@ def raycast_default_max_steps(res, step, dt):
     return min(int(diag / float(dt)) + 2, 2 ** 31 - 1)
 
 
+MESHCAST_MAX_RES = _lib.MESHCAST_MAX_RES        # PNR_MESHCAST_MAX_RES (include/pnr.h "mesh ray casting")
+MESHCAST_MAX_ENTRIES = 2 ** 31 - 1
+MESHCAST_OUTPUTS = (("depth", torch.float32, ()), ("face", torch.int32, ()), ("code", torch.uint8, ()), ("bary", torch.float32, (3,)),
+                    ("vertex", torch.int32, ()), ("normal", torch.float32, (3,)), ("side", torch.int8, ()))
+
+
+def meshcast_mesh(what, vertices, faces):
+    """(V, F) of the mesh arguments of the ray-casting ops: vertices (V, 3) float32, faces (F, 3) int32 on any device"""
+    return _cloud(what, "vertices", vertices), _cloud(what, "faces", faces, torch.int32)
+
+
+def meshcast_res(what, res):
+    """res = (res_x, res_y, res_z) of a ray-casting grid as ints, each within 1 .. 1024, or the refusal by name"""
+    try:
+        r = tuple(int(v) for v in res)
+    except (TypeError, ValueError):
+        raise ValueError("%s: res must be three integers (res_x, res_y, res_z), got %r" % (what, res)) from None
+    if len(r) != 3 or any(isinstance(v, bool) for v in res) or not all(1 <= v <= MESHCAST_MAX_RES for v in r):
+        raise ValueError("%s: res must be three integers within 1 .. %d, got %r" % (what, MESHCAST_MAX_RES, res))
+    return r
+
+
+def meshcast_grid(what, res, lo, cell):
+    """(res, lo, cell) of a ray-casting grid with lo and cell as host floats: lo finite, cell positive and finite with a finite
+    float32 inverse"""
+    res = meshcast_res(what, res)
+    lo_h, cell_h = _host_floats(lo, 3, what + ": lo"), _host_floats(cell, 3, what + ": cell")
+    if not all(abs(v) < _INF for v in lo_h):
+        raise ValueError("%s: lo must be finite (got %r)" % (what, list(lo_h)))
+    if not all(0.0 < v < _INF and _f32(1.0 / v) < _INF for v in cell_h):
+        raise ValueError("%s: cell must be positive and finite, with a finite inverse (got %r)" % (what, list(cell_h)))
+    return res, lo_h, cell_h
+
+
+def meshcast_range(what, near, far):
+    near, far = float(near), float(far)
+    if not (near >= 0.0 and far > near):
+        raise ValueError("%s: need 0 <= near < far (got %r, %r)" % (what, near, far))
+    return near, far
+
+
+def _meshcast_table(what, res, start, records):
+    """n_entries of the (start, records) pair of a grid of `res`: type, dtype, shape"""
+    cells = res[0] * res[1] * res[2]
+    _tensor_table(what, [("start", start, torch.int32, (cells + 1,))])
+    _tensor(what, "records", records)
+    if records.dtype != torch.float32:
+        raise TypeError("%s: records must be torch.float32, got %s" % (what, records.dtype))
+    if records.dim() != 2 or records.shape[1] != 12 or records.shape[0] > MESHCAST_MAX_ENTRIES:
+        raise ValueError("%s: records must be (n_entries, 12) with at most 2^31 - 1 entries, got %s" % (what, tuple(records.shape)))
+    return records.shape[0]
+
+
+def mesh_grid_workspace(res, device):
+    """the block that mesh_grid_bounds, mesh_grid_count and mesh_grid_fill share for a grid of `res`"""
+    res = meshcast_res("mesh_grid_workspace", res)
+    return torch.empty((_size_or_raise(_lib.load().pnr_mesh_grid_workspace_bytes(*res), "pnr_mesh_grid_workspace_bytes") // 8,), device=device, dtype=torch.int64)
+
+
+@_on_device
+def mesh_grid_bounds(vertices, faces, bounds=None):
+    """The box of a mesh's usable faces (pnr_mesh_grid_bounds; include/pnr.h "mesh ray casting", THE INDEX).  Returns bounds (8,)
+    float32 ON THE DEVICE -- reading it is the caller's synchronisation: lo (3), hi (3), the bits of the number of usable faces
+    (bounds.view(torch.int32)[6]), 0.  +inf / -inf without a usable face."""
+    what = "mesh_grid_bounds"
+    V, F = meshcast_mesh(what, vertices, faces)
+    _tensor_table(what, (), [("bounds", bounds, torch.float32, (8,))])
+    _same_device(what, vertices=vertices, faces=faces, bounds=bounds)
+    dev = vertices.device
+    bounds = torch.empty((8,), device=dev, dtype=torch.float32) if bounds is None else bounds
+    ws = mesh_grid_workspace((1, 1, 1), dev)
+    _lib.check(_lib.load().pnr_mesh_grid_bounds(_p(vertices if V else None), V, _p(faces if F else None), F, _p(bounds), _p(ws), _stream()),
+               "pnr_mesh_grid_bounds")
+    return bounds
+
+
+@_on_device
+def mesh_grid_count(vertices, faces, res, lo, cell, start=None, total=None, workspace=None):
+    """Count the entries of every cell of a ray-casting grid and scan them (pnr_mesh_grid_count).  res = (res_x, res_y, res_z); lo,
+    cell: the grid's float32 origin and cell size per axis, host values.  Returns (total, start, workspace): total (1,) int64 ON
+    THE DEVICE -- reading it is the caller's synchronisation --, start (cells + 1,) int32, and the workspace mesh_grid_fill needs."""
+    what = "mesh_grid_count"
+    V, F = meshcast_mesh(what, vertices, faces)
+    res, lo_h, cell_h = meshcast_grid(what, res, lo, cell)
+    cells = res[0] * res[1] * res[2]
+    _tensor_table(what, (), [("start", start, torch.int32, (cells + 1,)), ("total", total, torch.int64, (1,))])
+    _same_device(what, vertices=vertices, faces=faces, start=start, total=total, workspace=workspace)
+    dev = vertices.device
+    start = torch.empty((cells + 1,), device=dev, dtype=torch.int32) if start is None else start
+    total = torch.empty((1,), device=dev, dtype=torch.int64) if total is None else total
+    workspace = mesh_grid_workspace(res, dev) if workspace is None else workspace
+    _lib.check(_lib.load().pnr_mesh_grid_count(_p(vertices if V else None), V, _p(faces if F else None), F, res[0], res[1], res[2], lo_h, cell_h,
+                                               _p(start), _p(total), _p(workspace), _stream()), "pnr_mesh_grid_count")
+    return total, start, workspace
+
+
+@_on_device
+def mesh_grid_fill(vertices, faces, res, lo, cell, start, records, workspace):
+    """Write the 48-byte records mesh_grid_count counted (pnr_mesh_grid_fill): records (n_entries, 12) float32, caller-owned and
+    sized by mesh_grid_count's total; mesh, grid, start and workspace are mesh_grid_count's."""
+    what = "mesh_grid_fill"
+    V, F = meshcast_mesh(what, vertices, faces)
+    res, lo_h, cell_h = meshcast_grid(what, res, lo, cell)
+    n = _meshcast_table(what, res, start, records)
+    _tensor(what, "workspace", workspace)
+    _same_device(what, vertices=vertices, faces=faces, start=start, records=records, workspace=workspace)
+    _lib.check(_lib.load().pnr_mesh_grid_fill(_p(vertices if V else None), V, _p(faces if F else None), F, res[0], res[1], res[2], lo_h, cell_h,
+                                              _p(start), n, _p(records if n else None), _p(workspace), _stream()), "pnr_mesh_grid_fill")
+    return records
+
+
+def _meshcast_outputs(what, lead, out):
+    """the output arrays of a cast as pnr_mesh_* takes them: `out` maps names of MESHCAST_OUTPUTS to caller-owned tensors of shape
+    lead + the output's own; depth, face and code are needed"""
+    if not isinstance(out, dict):
+        raise ValueError("%s: out must be a dict of output tensors, got %s" % (what, type(out).__name__))
+    _names(what, out, [n for n, _, _ in MESHCAST_OUTPUTS], "unknown output %(key)s (known: %(known)s)")
+    _tensor_table(what, [(n, out.get(n), dt, lead + tail) for n, dt, tail in MESHCAST_OUTPUTS[:3]],
+                  [(n, out.get(n), dt, lead + tail) for n, dt, tail in MESHCAST_OUTPUTS[3:]])
+    return [out.get(n) for n, _, _ in MESHCAST_OUTPUTS]
+
+
+@_on_device
+def mesh_raycast(camera_model, cam, c2w, width, height, near, far, vertices, faces, res, lo, cell, start, records, out):
+    """First hit of every pixel's ray with a triangle mesh (pnr_mesh_raycast; the rule is in include/pnr.h "mesh ray casting").
+    camera_model, cam, c2w, width, height: as tsdf_raycast takes them.  vertices, faces: the mesh; res, lo, cell, start, records:
+    the grid mesh_grid_count / mesh_grid_fill built for it.  out: dict of caller-owned (height, width, ...) images -- depth float32,
+    face int32, code uint8, and optionally bary (., 3) float32, vertex int32, normal (., 3) float32, side int8.  Never
+    synchronises; returns None."""
+    what = "mesh_raycast"
+    word, cam_h = _camera_model(what, "camera_model", camera_model, cam)
+    c2w_h = _host_floats(c2w, 12, what + ": c2w")
+    width, height = _image_size(what, width, height)
+    near, far = meshcast_range(what, near, far)
+    V, F = meshcast_mesh(what, vertices, faces)
+    res, lo_h, cell_h = meshcast_grid(what, res, lo, cell)
+    n = _meshcast_table(what, res, start, records)
+    outs = _meshcast_outputs(what, (height, width), out)
+    _same_device(what, vertices=vertices, faces=faces, start=start, records=records, **out)
+    _lib.check(_lib.load().pnr_mesh_raycast(word, cam_h, c2w_h, width, height, near, far, _p(vertices if V else None), V, _p(faces if F else None), F,
+                                            res[0], res[1], res[2], lo_h, cell_h, _p(start), _p(records if n else None), n, *[_p(t) for t in outs],
+                                            _stream()), "pnr_mesh_raycast")
+
+
+@_on_device
+def mesh_cast_rays(rays, vertices, faces, res, lo, cell, start, records, out):
+    """First hit of every ray of rays (n, 8) float32 = (o, d, near, far) with a triangle mesh (pnr_mesh_cast_rays): mesh_raycast
+    with the rays given; out: (n, ...) arrays.  The rays are read when the kernel runs.  Never synchronises; returns None."""
+    what = "mesh_cast_rays"
+    _tensor(what, "rays", rays)
+    if rays.dtype != torch.float32:
+        raise TypeError("%s: rays must be torch.float32, got %s" % (what, rays.dtype))
+    R = _rays(what, rays)
+    if R > NN_MAX_POINTS:
+        raise ValueError("%s: rays holds %d rows, more than 2^31 - 1" % (what, R))
+    V, F = meshcast_mesh(what, vertices, faces)
+    res, lo_h, cell_h = meshcast_grid(what, res, lo, cell)
+    n = _meshcast_table(what, res, start, records)
+    outs = _meshcast_outputs(what, (R,), out)
+    _same_device(what, rays=rays, vertices=vertices, faces=faces, start=start, records=records, **out)
+    if R == 0:
+        return
+    _lib.check(_lib.load().pnr_mesh_cast_rays(_p(rays), R, _p(vertices if V else None), V, _p(faces if F else None), F, res[0], res[1], res[2],
+                                              lo_h, cell_h, _p(start), _p(records if n else None), n, *[_p(t) for t in outs], _stream()),
+               "pnr_mesh_cast_rays")
+
+
 # PNR_ICP_* (include/pnr.h "pose tracking"): the per-pixel codes and the solve's status
 ICP_MATCH, ICP_NO_DEPTH, ICP_OUTSIDE, ICP_NO_MODEL, ICP_TOO_FAR, ICP_BACK_FACING = 0, 1, 2, 3, 4, 5
 ICP_OK, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = 0, 1, 2, 3

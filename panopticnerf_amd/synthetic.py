@@ -310,3 +310,56 @@ def room_depth(camera, c2w, lo, hi, normals=False):
     n = torch.zeros_like(d)
     n.scatter_(-1, axis[..., None], -torch.sign(torch.gather(d, -1, axis[..., None])))
     return depth, torch.where(ok[..., None], n, torch.zeros_like(n)).to(torch.float32)
+
+
+def icosphere(subdiv=2, radius=1.0, center=(0.0, 0.0, 0.0), device=None):
+    """A closed triangle mesh of the sphere, for tests and examples of `mesh.raycast`: the icosahedron, every face split in
+    four `subdiv` times with the new vertices pushed out to the sphere -- 20 * 4^subdiv faces wound so that the normals point
+    outwards, every edge shared by exactly two faces.  Float64 on the host, then center + radius * v rounded to float32 once.
+    Returns a mesh.Mesh.from_arrays mesh, on the CPU or on `device`."""
+    import numpy as np
+    from .mesh import Mesh
+    subdiv = int(subdiv)
+    if not 0 <= subdiv <= 7:
+        raise ValueError("icosphere: subdiv must be within 0 .. 7 (got %d)" % subdiv)
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    v = [np.asarray(x, np.float64) / np.linalg.norm(x) for x in v]
+    for _ in range(subdiv):
+        mid, nf = {}, []
+
+        def middle(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                m = v[a] + v[b]
+                v.append(m / np.linalg.norm(m))
+                mid[k] = len(v) - 1
+            return mid[k]
+        for a, b, c in f:
+            ab, bc, ca = middle(a, b), middle(b, c), middle(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    verts = (np.asarray(center, np.float64).reshape(1, 3) + float(radius) * np.asarray(v)).astype(np.float32)
+    return Mesh.from_arrays(verts, np.asarray(f, np.int32), device=device)
+
+
+def box_mesh(lo, hi, device=None):
+    """The axis-aligned box [lo, hi] as 8 vertices and 12 faces wound so that the normals point INTO the room: the mesh of the
+    scene `room_depth` renders in closed form.  Vertex i has the hi coordinate on axis k where bit k of i is set.  Returns a
+    mesh.Mesh.from_arrays mesh, on the CPU or on `device`."""
+    import numpy as np
+    from .mesh import Mesh
+    lo32, hi32 = np.asarray(lo, np.float32).reshape(-1), np.asarray(hi, np.float32).reshape(-1)
+    if lo32.shape != (3,) or hi32.shape != (3,) or not (np.isfinite(lo32).all() and np.isfinite(hi32).all() and (lo32 < hi32).all()):
+        raise ValueError("box_mesh: lo and hi must be finite 3-vectors with lo < hi on every axis")
+    verts = np.asarray([[(hi32 if (i >> k) & 1 else lo32)[k] for k in range(3)] for i in range(8)], np.float32)
+    faces = []
+    for k in range(3):
+        u, w = (k + 1) % 3, (k + 2) % 3                  # e_u x e_w = e_k: this order winds a wall's normal along +k
+        for top in (0, 1):
+            q = [(top << k) | (a << u) | (b << w) for a, b in ((0, 0), (1, 0), (1, 1), (0, 1))]
+            q = q[::-1] if top else q
+            faces += [(q[0], q[1], q[2]), (q[0], q[2], q[3])]
+    return Mesh.from_arrays(verts, np.asarray(faces, np.int32), device=device)
