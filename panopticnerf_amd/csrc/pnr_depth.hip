@@ -3,12 +3,13 @@
 // through LDS, every pixel walks its window row-major and weighs a neighbour by the host's spatial weights and a compact biweight
 // of the depth difference -- no transcendental, so tests/_depth_ref.py restates it bit for bit.  k_depth_normals gives every pixel
 // its camera-relative vector v = t d (the ray of pnr_camera_ray, pnr_camera_dev.h: the arithmetic of the ray, fusion and tracking
-// kernels), shares the tile's vectors through LDS, and crosses the differences along the two image axes.  Float32, one rounding
+// kernels; the view is a PnrView, pnr_geom_dev.h), shares the tile's vectors through LDS (2-D tiles with a halo, this file's
+// own), and crosses the differences along the two image axes.  Float32, one rounding
 // per operation (-ffp-contract=off), no atomics: two runs give the same bits.
 #include <float.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
+#include "pnr_geom_dev.h"
 
 #define DF_R PNR_DEPTH_MAX_RADIUS
 #define DF_TX PNR_DEPTH_TILE_X
@@ -111,10 +112,7 @@ PNR_EXPORT int pnr_depth_filter(int width, int height, const float* depth_in, in
 #define DN_THREADS (DN_TX * DN_TY)
 
 struct DepthNormalsArgs {
-    int model;
-    float cam[7];
-    float c2w[12];
-    int width, height;
+    PnrView view;                       // pose = c2w
     unsigned int tiles_x;
     float jump_a, jump_b, mc2;
     const float* depth;
@@ -126,9 +124,9 @@ struct DepthNormalsArgs {
 // step 1 of a pixel inside the image: (v, t), or all 0 where its NO_DEPTH test fails
 __device__ __forceinline__ float4 dn_record(const DepthNormalsArgs& a, int i, int j)
 {
-    const float t = a.depth[(size_t)j * (size_t)a.width + (size_t)i];
+    const float t = a.depth[(size_t)j * (size_t)a.view.width + (size_t)i];
     bool ok;
-    const PnrRayRec ray = pnr_camera_ray(a.model, a.cam, a.c2w, i, j, 0.0f, 0.0f, ok);
+    const PnrRayRec ray = pnr_camera_ray(a.view.model, a.view.cam, a.view.pose, i, j, 0.0f, 0.0f, ok);
     if (!(ok && pnr_pos_finite(t))) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return make_float4(t * ray.lo.w, t * ray.hi.x, t * ray.hi.y, t);
 }
@@ -142,19 +140,19 @@ __global__ __launch_bounds__(DN_THREADS) void k_depth_normals(const DepthNormals
         const int ly = e / DN_LW, lx = e - ly * DN_LW;
         const int64_t i = i0 + lx, j = j0 + ly;
         float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (i >= 0 && i < a.width && j >= 0 && j < a.height) rec = dn_record(a, (int)i, (int)j);
+        if (i >= 0 && i < a.view.width && j >= 0 && j < a.view.height) rec = dn_record(a, (int)i, (int)j);
         tile[e] = rec;
     }
     __syncthreads();
     const int lx = threadIdx.x % DN_TX + 1, ly = threadIdx.x / DN_TX + 1;
     const int64_t i = i0 + lx, j = j0 + ly;
-    if (i >= a.width || j >= a.height) return;
+    if (i >= a.view.width || j >= a.view.height) return;
     const float4 p = tile[ly * DN_LW + lx];
     const float t = p.w;
     int code = PNR_NORMAL_NO_DEPTH;
     float n[3] = {0.0f, 0.0f, 0.0f}, vtx[3] = {0.0f, 0.0f, 0.0f};
     if (t != 0.0f) {
-        vtx[0] = a.c2w[3] + p.x; vtx[1] = a.c2w[7] + p.y; vtx[2] = a.c2w[11] + p.z;
+        vtx[0] = a.view.pose[3] + p.x; vtx[1] = a.view.pose[7] + p.y; vtx[2] = a.view.pose[11] + p.z;
         const float thr = a.jump_a + a.jump_b * t;
         const float4 nb[4] = {tile[ly * DN_LW + lx - 1], tile[ly * DN_LW + lx + 1], tile[(ly - 1) * DN_LW + lx], tile[(ly + 1) * DN_LW + lx]};
         bool use[4];
@@ -168,10 +166,10 @@ __global__ __launch_bounds__(DN_THREADS) void k_depth_normals(const DepthNormals
         }
         code = PNR_NORMAL_NO_NEIGHBOUR;
         if ((use[0] || use[1]) && (use[2] || use[3])) {
-            const float cx = D[0][1] * D[1][2] - D[0][2] * D[1][1];
-            const float cy = D[0][2] * D[1][0] - D[0][0] * D[1][2];
-            const float cz = D[0][0] * D[1][1] - D[0][1] * D[1][0];
-            const float cc = (cx * cx + cy * cy) + cz * cz;
+            float c[3];
+            pnr_cross3(D[0], D[1], c);
+            const float cx = c[0], cy = c[1], cz = c[2];
+            const float cc = (cx * cx + cy * cy) + cz * cz;         // (the grazing test needs the squared length too)
             const float len = sqrtf(cc);
             code = PNR_NORMAL_DEGENERATE;
             if (pnr_pos_finite(len)) {
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_depth_normals(const DepthNormals
             }
         }
     }
-    const size_t q = (size_t)j * (size_t)a.width + (size_t)i;
+    const size_t q = (size_t)j * (size_t)a.view.width + (size_t)i;
     a.normal[q * 3 + 0] = n[0]; a.normal[q * 3 + 1] = n[1]; a.normal[q * 3 + 2] = n[2];
     if (a.vertex) { a.vertex[q * 3 + 0] = vtx[0]; a.vertex[q * 3 + 1] = vtx[1]; a.vertex[q * 3 + 2] = vtx[2]; }
     if (a.code) a.code[q] = (uint8_t)code;
@@ -195,20 +193,14 @@ __global__ __launch_bounds__(DN_THREADS) void k_depth_normals(const DepthNormals
 PNR_EXPORT int pnr_depth_normals(int model, const float* cam_host, const float* c2w12_host, int width, int height, const float* depth,
                                  float jump_a, float jump_b, float mc2, float* normal, float* vertex, uint8_t* code, void* stream)
 {
-    PNR_REQUIRE(pnr_camera_model_ok(model), "pnr_depth_normals: unknown camera model %d", model);
-    PNR_REQUIRE(cam_host && c2w12_host, "pnr_depth_normals: null camera or pose");
-    PNR_REQUIRE(width >= 1 && height >= 1 && (int64_t)width * height <= INT32_MAX, "pnr_depth_normals: bad size (the image holds 1 .. 2^31 - 1 pixels)");
-    const int rc = pnr_camera_check(model, cam_host, width, height, "pnr_depth_normals");
+    DepthNormalsArgs a;
+    const int rc = pnr_view_check("pnr_depth_normals", nullptr, model, cam_host, c2w12_host, width, height, true, a.view);
     if (rc) return rc;
+    PNR_REQUIRE((int64_t)width * height <= INT32_MAX, "pnr_depth_normals: bad size (the image holds 1 .. 2^31 - 1 pixels)");
     PNR_REQUIRE(depth && normal, "pnr_depth_normals: null depth or normal");
     PNR_REQUIRE((((uintptr_t)depth | (uintptr_t)normal | (uintptr_t)vertex) & 3) == 0, "pnr_depth_normals: depth, normal and vertex must be 4-byte aligned");
     PNR_REQUIRE(jump_a >= 0.0f && jump_b >= 0.0f, "pnr_depth_normals: jump_a and jump_b must be non-negative (they may be inf)");
     PNR_REQUIRE(mc2 >= 0.0f && mc2 <= 1.0f, "pnr_depth_normals: mc2 (the squared cosine) must lie in [0, 1]");
-    DepthNormalsArgs a;
-    a.model = model;
-    pnr_camera_fill(model, cam_host, a.cam);
-    pnr_pose_fill(c2w12_host, a.c2w);
-    a.width = width; a.height = height;
     a.jump_a = jump_a; a.jump_b = jump_b; a.mc2 = mc2;
     a.depth = depth; a.normal = normal; a.vertex = vertex; a.code = code;
     const int64_t tiles_x = ((int64_t)width + DN_TX - 1) / DN_TX, tiles_y = ((int64_t)height + DN_TY - 1) / DN_TY;

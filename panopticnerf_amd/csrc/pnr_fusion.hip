@@ -13,8 +13,8 @@
 #include <float.h>
 #include <math.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
+#include "pnr_geom_dev.h"
 
 // the launch constants PNR_TSDF_BLOCK and PNR_TSDF_BLOCKS_PER_CU are include/pnr.h's (a test sizes a lattice from them)
 #define PNR_TSDF_CONF_MAX (1 << 30)
@@ -31,12 +31,6 @@ struct TsdfArgs {
     int32_t *label, *conf;
 };
 
-__device__ __forceinline__ float tsdf_coord(unsigned int i, float lo, float step)
-{
-    const float m = ((float)i + 0.5f) * step;                       // a multiply, then an add: never an FMA (-ffp-contract=off)
-    return m + lo;
-}
-
 template <bool RGB, bool LABEL>
 __global__ __launch_bounds__(PNR_TSDF_BLOCK) void k_tsdf_integrate(const pnr_frame* __restrict__ frames, const float* __restrict__ w2c,
                                                                    const TsdfArgs a)
@@ -45,7 +39,8 @@ __global__ __launch_bounds__(PNR_TSDF_BLOCK) void k_tsdf_integrate(const pnr_fra
         const unsigned int n = (unsigned int)n64;
         const unsigned int iz = n / a.sz, r = n - iz * a.sz;
         const unsigned int iy = r / a.rx, ix = r - iy * a.rx;
-        const float X = tsdf_coord(ix, a.lo[0], a.step[0]), Y = tsdf_coord(iy, a.lo[1], a.step[1]), Z = tsdf_coord(iz, a.lo[2], a.step[2]);
+        const float X = pnr_lattice_coord((float)ix, a.lo[0], a.step[0]), Y = pnr_lattice_coord((float)iy, a.lo[1], a.step[1]),
+                    Z = pnr_lattice_coord((float)iz, a.lo[2], a.step[2]);
         const size_t at = (size_t)n;
         float t = a.tsdf[at], w = a.weight[at];
         float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, cw = 0.0f;
@@ -113,12 +108,8 @@ PNR_EXPORT int pnr_tsdf_integrate(const pnr_frame* frames, const float* w2c, int
     PNR_REQUIRE(((((uintptr_t)tsdf) | ((uintptr_t)weight) | ((uintptr_t)rgb) | ((uintptr_t)rgb_weight) | ((uintptr_t)label) | ((uintptr_t)conf)) & 3) == 0,
                 "pnr_tsdf_integrate: misaligned volume array (4 bytes)");
     PNR_REQUIRE(f0 >= 0 && f1 >= f0, "pnr_tsdf_integrate: bad frame range [%d, %d) (0 <= f0 <= f1)", f0, f1);
-    PNR_REQUIRE(res_x >= 1 && res_y >= 1 && res_z >= 1 && (int64_t)res_x * res_y <= INT32_MAX && (int64_t)res_x * res_y * res_z <= INT32_MAX,
-                "pnr_tsdf_integrate: bad lattice %d x %d x %d (every res >= 1, at most 2^31 - 1 points)", res_x, res_y, res_z);
-    PNR_REQUIRE(lo_host && step_host, "pnr_tsdf_integrate: null lo or step");
-    for (int k = 0; k < 3; ++k)
-        PNR_REQUIRE(isfinite(lo_host[k]) && isfinite(step_host[k]) && step_host[k] != 0.0f,
-                    "pnr_tsdf_integrate: lo and step must be finite and step non-zero (axis %d)", k);
+    const int rc = pnr_lattice_check("pnr_tsdf_integrate", res_x, res_y, res_z, lo_host, step_host, 1, INT32_MAX, true);
+    if (rc) return rc;
     PNR_REQUIRE(trunc > 0.0f && isfinite(trunc), "pnr_tsdf_integrate: trunc must be positive and finite");
     PNR_REQUIRE(max_depth > 0.0f, "pnr_tsdf_integrate: max_depth must be positive (it may be +inf)");
     PNR_REQUIRE(w_max >= 1.0f, "pnr_tsdf_integrate: w_max must be >= 1 (it may be +inf)");
@@ -144,7 +135,7 @@ PNR_EXPORT int pnr_tsdf_integrate(const pnr_frame* frames, const float* w2c, int
 // Volume ray casting (include/pnr.h "volume ray casting"): the volume seen from any camera.  tests/_raycast_ref.py restates the
 // rule in numpy; everything here equals it bit for bit.
 //
-// One thread per pixel; a wave is an 8 x 8 pixel TILE, not 64 pixels of a row, so the rays of a wave walk neighbouring cells and
+// One thread per pixel; a wave is an 8 x 8 pixel TILE (pnr_tile_grid, pnr_geom_dev.h), not 64 pixels of a row, so the rays of a wave walk neighbouring cells and
 // its gathers fall into few cache lines; a block is four tiles side by side, one block per four tiles (no cap: a ray's work runs
 // from nothing to max_steps samples, and the hardware's dispatcher balances what a tile-stride loop would fix).  Partial tiles at
 // the right and bottom edges are masked.  The ray is pnr_camera_ray's, the bits of the ray kernels.  Inside the march the eight
@@ -321,14 +312,9 @@ PNR_EXPORT int pnr_tsdf_raycast(int model, const float* cam_host, const float* c
                 "pnr_tsdf_raycast: misaligned array (tsdf, weight, depth, normal, src: 4 bytes)");
     PNR_REQUIRE(width >= 1 && height >= 1 && (int64_t)width * height <= INT32_MAX,
                 "pnr_tsdf_raycast: bad image %d x %d (width, height >= 1, at most 2^31 - 1 pixels)", width, height);
-    const int rc = pnr_camera_check(model, cam_host, width, height, "pnr_tsdf_raycast");
+    int rc = pnr_camera_check(model, cam_host, width, height, "pnr_tsdf_raycast");
+    if (!rc) rc = pnr_lattice_check("pnr_tsdf_raycast", res_x, res_y, res_z, lo_host, step_host, 2, INT32_MAX, true);
     if (rc) return rc;
-    PNR_REQUIRE(res_x >= 2 && res_y >= 2 && res_z >= 2 && (int64_t)res_x * res_y <= INT32_MAX && (int64_t)res_x * res_y * res_z <= INT32_MAX,
-                "pnr_tsdf_raycast: bad lattice %d x %d x %d (every res >= 2, at most 2^31 - 1 points)", res_x, res_y, res_z);
-    PNR_REQUIRE(lo_host && step_host, "pnr_tsdf_raycast: null lo or step");
-    for (int k = 0; k < 3; ++k)
-        PNR_REQUIRE(isfinite(lo_host[k]) && isfinite(step_host[k]) && step_host[k] != 0.0f,
-                    "pnr_tsdf_raycast: lo and step must be finite and step non-zero (axis %d)", k);
     PNR_REQUIRE(dt > 0.0f && isfinite(dt), "pnr_tsdf_raycast: dt must be positive and finite");
     PNR_REQUIRE(max_steps >= 0, "pnr_tsdf_raycast: max_steps must be >= 0 (got %d)", max_steps);
     PNR_REQUIRE(min_weight > 0.0f, "pnr_tsdf_raycast: min_weight must be positive");
@@ -340,11 +326,9 @@ PNR_EXPORT int pnr_tsdf_raycast(int model, const float* cam_host, const float* c
     a.near_ = near_; a.far_ = far_; a.min_weight = min_weight; a.dt = dt;
     a.res[0] = res_x; a.res[1] = res_y; a.res[2] = res_z;
     for (int k = 0; k < 3; ++k) { a.lo[k] = lo_host[k]; a.step[k] = step_host[k]; }
-    const int64_t tiles_x = ((int64_t)width + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE, tiles_y = ((int64_t)height + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE;
-    a.tiles_x = (unsigned int)tiles_x;
-    a.n_tiles = tiles_x * tiles_y;                                  // at most 2^28 + 2^25: the grid below fits a launch
+    int64_t blocks;
+    pnr_tile_grid(width, height, &a.tiles_x, &a.n_tiles, &blocks);
     a.tsdf = tsdf; a.weight = weight; a.depth = depth; a.normal = normal; a.src = src; a.code = code;
-    const int64_t blocks = (a.n_tiles + PNR_RAYCAST_BLOCK / 64 - 1) / (PNR_RAYCAST_BLOCK / 64);
     hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned int)blocks), dim3(PNR_RAYCAST_BLOCK), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_tsdf_raycast");
     return PNR_OK;

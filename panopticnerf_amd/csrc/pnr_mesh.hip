@@ -12,10 +12,11 @@
 //
 // All four are memory bound.  A point's x neighbour is the next lane's point (coalesced); its y and z neighbours are other
 // rows of the same launch, read again from L2.  A chunk is PNR_MESH_CHUNK consecutive points; a block walks chunks grid-stride.
+// The lattice's check and points are pnr_geom_dev.h's; the 64-bit scan over chunk sums is this file's own, not pnr_scan_dev.h's.
 #include <math.h>
 
 #include "pnr_common.h"
-#include "pnr_reduce_dev.h"
+#include "pnr_geom_dev.h"
 
 #define PNR_MESH_BLOCK 256
 static_assert(PNR_MESH_BLOCK == PNR_SCAN_BLOCK, "the three scan kernels call pnr_block_scan_excl");
@@ -232,12 +233,6 @@ struct MeshEmitArgs {
     float lo[3], step[3];
 };
 
-__device__ __forceinline__ float mesh_coord(int i, float lo, float step)
-{
-    const float m = ((float)i + 0.5f) * step;                       // a multiply, then an add: never an FMA (-ffp-contract=off)
-    return m + lo;
-}
-
 __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_emit(MeshEmitArgs a)
 {
     // a thread's copy of the records of its cube's corners 0 .. 6 (corner 7 owns no edge of the cube): the triangle table
@@ -257,9 +252,10 @@ __global__ __launch_bounds__(PNR_MESH_BLOCK) void k_mesh_emit(MeshEmitArgs a)
             float v[8];
             mesh_load8(a.field, d, n, ix, iy, iz, ex, ey, ez, v);
             if (mask != 0 && a.vertices) {
-                const float pa[3] = {mesh_coord(ix, a.lo[0], a.step[0]), mesh_coord(iy, a.lo[1], a.step[1]), mesh_coord(iz, a.lo[2], a.step[2])};
-                const float pb[3] = {mesh_coord(ix + 1, a.lo[0], a.step[0]), mesh_coord(iy + 1, a.lo[1], a.step[1]),
-                                     mesh_coord(iz + 1, a.lo[2], a.step[2])};
+                const float pa[3] = {pnr_lattice_coord((float)ix, a.lo[0], a.step[0]), pnr_lattice_coord((float)iy, a.lo[1], a.step[1]),
+                                     pnr_lattice_coord((float)iz, a.lo[2], a.step[2])};
+                const float pb[3] = {pnr_lattice_coord((float)(ix + 1), a.lo[0], a.step[0]), pnr_lattice_coord((float)(iy + 1), a.lo[1], a.step[1]),
+                                     pnr_lattice_coord((float)(iz + 1), a.lo[2], a.step[2])};
                 const bool in0 = v[0] > a.level;
                 size_t vi = (size_t)(unsigned)own;
 #pragma unroll
@@ -376,12 +372,9 @@ PNR_EXPORT int pnr_mesh_count(const float* field, int res_x, int res_y, int res_
 PNR_EXPORT int pnr_mesh_emit(const float* field, int res_x, int res_y, int res_z, float level, const float* lo_host, const float* step_host,
                              const void* workspace, float* vertices, int32_t* faces, int64_t* src, void* stream)
 {
-    PNR_REQUIRE(mesh_res_ok(res_x, res_y, res_z), "pnr_mesh_emit: bad lattice %d x %d x %d (every res >= 1, at most (2^31 - 1) / 12 points)",
-                res_x, res_y, res_z);
+    const int rc = pnr_lattice_check("pnr_mesh_emit", res_x, res_y, res_z, lo_host, step_host, 1, PNR_MESH_MAX_POINTS, false);
+    if (rc) return rc;
     PNR_REQUIRE(isfinite(level), "pnr_mesh_emit: level must be finite");
-    PNR_REQUIRE(lo_host && step_host, "pnr_mesh_emit: null lo or step");
-    for (int k = 0; k < 3; ++k)
-        PNR_REQUIRE(isfinite(lo_host[k]) && isfinite(step_host[k]), "pnr_mesh_emit: lo and step must be finite (axis %d)", k);
     PNR_REQUIRE(field && workspace, "pnr_mesh_emit: null field or workspace");
     PNR_REQUIRE(((uintptr_t)field & 3) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)vertices & 3) == 0 &&
                     ((uintptr_t)faces & 3) == 0 && ((uintptr_t)src & 7) == 0,

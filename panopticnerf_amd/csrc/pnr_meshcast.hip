@@ -1,27 +1,19 @@
 // Mesh ray casting (include/pnr.h "mesh ray casting"): the first hit of a ray with a triangle mesh, for the pixels of any camera
 // or a list of rays -- the way back from a Mesh to an image.  The answer is DEFINED by brute force over all faces: the watertight
-// ray-triangle test of Woop, Benthin and Wald in float32, two-sided, under the key of pnr_splat_points and pnr_nn_query
-// (bits(t), face) and a minimum.  The uniform grid built here only prunes: whatever its resolution, the outputs are brute
-// force's bit for bit (DESIGN.md section 8 "Mesh ray casting" has the argument; tests/_meshcast_ref.py restates rule and walk).
-// Build: bounds (integer atomics on order-preserving keys), per-face cell counts, the shared scan, fill -- pnr_nn.hip's pattern.
-// Cast: one thread per ray, a wave an 8 x 8 pixel tile (k_tsdf_raycast's shape) or 64 consecutive rays; one device body for
-// both.  A cell entry is a 48-byte record of the three corners and the face index: a candidate is three 16-byte loads and no
-// dependent gather.  No LDS, no floating atomics, nothing waits on anything.
+// ray-triangle test of Woop, Benthin and Wald in float32, two-sided, under pnr_key(t, face) and a minimum (pnr_geom_dev.h, as
+// everything shared below).  The uniform grid built here only prunes: whatever its resolution, the outputs are brute force's
+// bit for bit (DESIGN.md section 8 "Mesh ray casting" has the argument; tests/_meshcast_ref.py restates rule and walk).
+// Build: bounds (integer atomics on order-preserving keys), per-face cell counts, the shared scan, fill (pnr_table_carve,
+// pnr_table_range).  Cast: one thread per ray, a wave an 8 x 8 pixel tile (pnr_tile_grid) or 64 consecutive rays; one device
+// body for both.  The mesh is a PnrMesh.  A cell entry is a 48-byte record of the three corners and the face index: a candidate
+// is three 16-byte loads and no dependent gather.  No LDS, no floating atomics, nothing waits on anything.
 #include <float.h>
 #include <math.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
-#include "pnr_reduce_dev.h"
-#include "pnr_scan_dev.h"
+#include "pnr_geom_dev.h"
 
-#define MC_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define MC_BOUNDS_WORDS 8                   // workspace words of the bounds: 3 min keys, 3 max keys, the usable faces, one spare
-
-struct McMesh {
-    const float* vertices; int64_t n_vertices;
-    const int32_t* faces; int64_t n_faces;
-};
 
 struct McGrid {
     int res[3];
@@ -34,7 +26,7 @@ struct McGrid {
 struct McTri { float v[3][3]; bool ok; };
 
 // the corners of face t; ok = every index in range and every coordinate finite (a face that is not ok never hits)
-__device__ __forceinline__ McTri mc_tri(const McMesh& m, int64_t t)
+__device__ __forceinline__ McTri mc_tri(const PnrMesh& m, int64_t t)
 {
     McTri r;
     const int32_t i[3] = {m.faces[3 * t], m.faces[3 * t + 1], m.faces[3 * t + 2]};
@@ -63,7 +55,7 @@ __global__ __launch_bounds__(64) void k_meshcast_bounds_init(unsigned int* __res
     if (threadIdx.x < MC_BOUNDS_WORDS) w[threadIdx.x] = threadIdx.x < 3 ? 0xFFFFFFFFu : 0u;
 }
 
-__global__ __launch_bounds__(256) void k_meshcast_bounds(const McMesh m, unsigned int* __restrict__ w)
+__global__ __launch_bounds__(256) void k_meshcast_bounds(const PnrMesh m, unsigned int* __restrict__ w)
 {
     unsigned int lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, n = 0u;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m.n_faces; t += (int64_t)gridDim.x * blockDim.x) {
@@ -112,7 +104,7 @@ __device__ __forceinline__ int mc_cell(float g, int res) { return (int)fminf(fma
 // FILL = false: cursor[cell] += 1 for every cell of the face's padded box.  FILL = true: the face's record goes to
 // start[cell] + (the value the cell's cursor had) - 1, the cursor counting down from the cell's count.
 template <bool FILL>
-__device__ __forceinline__ void mc_scatter(const McMesh& m, const McGrid& g, int32_t* __restrict__ cursor, float4* __restrict__ records)
+__device__ __forceinline__ void mc_scatter(const PnrMesh& m, const McGrid& g, int32_t* __restrict__ cursor, float4* __restrict__ records)
 {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m.n_faces; t += (int64_t)gridDim.x * blockDim.x) {
         const McTri r = mc_tri(m, t);
@@ -142,14 +134,9 @@ __device__ __forceinline__ void mc_scatter(const McMesh& m, const McGrid& g, int
     }
 }
 
-__global__ __launch_bounds__(256) void k_meshcast_zero(int32_t* __restrict__ p, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
-}
+__global__ __launch_bounds__(256) void k_meshcast_count(const PnrMesh m, const McGrid g, int32_t* __restrict__ cursor) { mc_scatter<false>(m, g, cursor, nullptr); }
 
-__global__ __launch_bounds__(256) void k_meshcast_count(const McMesh m, const McGrid g, int32_t* __restrict__ cursor) { mc_scatter<false>(m, g, cursor, nullptr); }
-
-__global__ __launch_bounds__(256) void k_meshcast_fill(const McMesh m, const McGrid g, int32_t* __restrict__ cursor, float4* __restrict__ records)
+__global__ __launch_bounds__(256) void k_meshcast_fill(const PnrMesh m, const McGrid g, int32_t* __restrict__ cursor, float4* __restrict__ records)
 {
     mc_scatter<true>(m, g, cursor, records);
 }
@@ -208,15 +195,15 @@ __device__ __forceinline__ McHit mc_test(const McRay& r, const float (&v0)[3], c
 __device__ __forceinline__ void mc_keep(const McHit& h, int face, unsigned long long& best)
 {
     if (h.hit) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint(h.t) << 32) | (unsigned int)face;
+        const unsigned long long key = pnr_key(h.t, (unsigned int)face);
         best = key < best ? key : best;
     }
 }
 
 // the plain loop over all faces: what the rule says, and the path of a ray whose grid coordinates are too large for the walk
-__device__ __forceinline__ unsigned long long mc_brute(const McMesh& m, const McRay& r)
+__device__ __forceinline__ unsigned long long mc_brute(const PnrMesh& m, const McRay& r)
 {
-    unsigned long long best = MC_EMPTY;
+    unsigned long long best = PNR_KEY_EMPTY;
     for (int64_t t = 0; t < m.n_faces; ++t) {
         const McTri tri = mc_tri(m, t);
         if (tri.ok) mc_keep(mc_test(r, tri.v[0], tri.v[1], tri.v[2]), (int)t, best);
@@ -247,7 +234,7 @@ __device__ __forceinline__ bool mc_walk(const McGrid& g, const McRay& r, unsigne
     const float dz = mc_pick(dg, kz), oz = mc_pick(og, kz);
     if (dz == 0.0f) return false;                                   // (d != 0 but d * inv underflowed)
     float t_in = r.near_, t_out = r.far_;
-    best = MC_EMPTY;
+    best = PNR_KEY_EMPTY;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float a = -PNR_MESHCAST_PAD, b = (float)g.res[k] + PNR_MESHCAST_PAD;
@@ -284,16 +271,15 @@ __device__ __forceinline__ bool mc_walk(const McGrid& g, const McRay& r, unsigne
             for (int cx = x0; cx <= x1; ++cx) {
                 const int64_t cell = (int64_t)L * sz + (int64_t)cy * sy + (int64_t)cx * sx;
                 if (cell < 0 || cell >= n_cells) continue;
-                const int s = min(max(g.start[cell], 0), n32);      // clamped: a damaged table reads inside
-                const int e = min(max(g.start[cell + 1], s), n32);
-                for (int q = s; q < e; ++q) {
+                const PnrRange rg = pnr_table_range(g.start, cell, n32);
+                for (int q = rg.s; q < rg.e; ++q) {
                     const float4 p0 = g.records[3 * (int64_t)q], p1 = g.records[3 * (int64_t)q + 1], p2 = g.records[3 * (int64_t)q + 2];
                     const float v0[3] = {p0.x, p0.y, p0.z}, v1[3] = {p0.w, p1.x, p1.y}, v2[3] = {p1.z, p1.w, p2.x};
                     mc_keep(mc_test(r, v0, v1, v2), __float_as_int(p2.y), best);
                 }
             }
-        if (best != MC_EMPTY) {                                     // the best hit lies more than PAD short of this layer's far face
-            const float tb_ = __uint_as_float((unsigned int)(best >> 32));
+        if (best != PNR_KEY_EMPTY) {                                     // the best hit lies more than PAD short of this layer's far face
+            const float tb_ = pnr_key_value(best);
             const float gzb = oz + tb_ * dz;
             if ((up ? zb - gzb : gzb - zb) > PNR_MESHCAST_PAD) break;
         }
@@ -304,7 +290,7 @@ __device__ __forceinline__ bool mc_walk(const McGrid& g, const McRay& r, unsigne
 }
 
 struct McArgs {
-    McMesh m;
+    PnrMesh m;
     McGrid g;
     int model, width, height;
     float cam[7], c2w[12], near_, far_;
@@ -339,13 +325,13 @@ __device__ __forceinline__ void mc_cast(const McArgs& a, size_t q, const PnrRayR
         if (dz < 0.0f) { const int s = kx; kx = ky; ky = s; }
         r.kx = kx; r.ky = ky; r.kz = kz;
         r.Sx = mc_pick(r.d, kx) / dz; r.Sy = mc_pick(r.d, ky) / dz; r.Sz = 1.0f / dz;
-        unsigned long long best = MC_EMPTY;
+        unsigned long long best = PNR_KEY_EMPTY;
         if (!mc_walk(a.g, r, best)) best = mc_brute(a.m, r);
         code = PNR_RAYCAST_MISSED;
-        if (best != MC_EMPTY && (int64_t)(unsigned int)best < a.m.n_faces) {       // (a damaged table never reads outside)
+        if (best != PNR_KEY_EMPTY && (int64_t)pnr_key_index(best) < a.m.n_faces) {       // (a damaged table never reads outside)
             code = PNR_RAYCAST_HIT;
-            face = (int32_t)(unsigned int)best;
-            depth = __uint_as_float((unsigned int)(best >> 32));
+            face = (int32_t)pnr_key_index(best);
+            depth = pnr_key_value(best);
             const McTri tri = mc_tri(a.m, face);                    // (the winner is a usable face: its record was made from these)
             const McHit h = mc_test(r, tri.v[0], tri.v[1], tri.v[2]);
             b[0] = h.U / h.det; b[1] = h.V / h.det; b[2] = h.W / h.det;
@@ -400,17 +386,6 @@ __global__ __launch_bounds__(PNR_RAYCAST_BLOCK) void k_mesh_cast(const McArgs a)
 
 // ---- entry points
 
-static int mc_mesh_check(const char* who, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, McMesh& m)
-{
-    PNR_REQUIRE(n_vertices >= 0 && n_vertices <= (int64_t)INT32_MAX, "%s: n_vertices must be within 0 .. 2^31 - 1", who);
-    PNR_REQUIRE(n_faces >= 0 && n_faces <= (int64_t)INT32_MAX, "%s: n_faces must be within 0 .. 2^31 - 1", who);
-    PNR_REQUIRE(n_faces == 0 || faces, "%s: null faces", who);
-    PNR_REQUIRE(n_faces == 0 || n_vertices == 0 || vertices, "%s: null vertices", who);
-    PNR_REQUIRE((((uintptr_t)vertices | (uintptr_t)faces) & 3) == 0, "%s: vertices and faces must be 4-byte aligned", who);
-    m.vertices = vertices; m.n_vertices = n_vertices; m.faces = faces; m.n_faces = n_faces;
-    return PNR_OK;
-}
-
 static bool mc_res_ok(int rx, int ry, int rz)
 {
     return rx >= 1 && ry >= 1 && rz >= 1 && rx <= PNR_MESHCAST_MAX_RES && ry <= PNR_MESHCAST_MAX_RES && rz <= PNR_MESHCAST_MAX_RES;
@@ -439,14 +414,14 @@ PNR_EXPORT int64_t pnr_mesh_grid_workspace_bytes(int res_x, int res_y, int res_z
 {
     if (!mc_res_ok(res_x, res_y, res_z)) return -1;
     const int64_t cells = (int64_t)res_x * res_y * res_z;
-    return (MC_BOUNDS_WORDS * 4 + pnr_scan_workspace_bytes(cells) + cells * 4 + 7) & ~(int64_t)7;      // the bounds' keys, the scan's tile sums, the cursors
+    return pnr_table_carve(MC_BOUNDS_WORDS * 4, cells, true).bytes;      // the bounds' keys, the scan's tile sums, the cursors
 }
 
 PNR_EXPORT int pnr_mesh_grid_bounds(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, float* bounds,
                                     void* workspace, void* stream)
 {
-    McMesh m;
-    const int rc = mc_mesh_check("pnr_mesh_grid_bounds", vertices, n_vertices, faces, n_faces, m);
+    PnrMesh m;
+    const int rc = pnr_mesh_check("pnr_mesh_grid_bounds", vertices, n_vertices, faces, n_faces, INT32_MAX, m);
     if (rc) return rc;
     PNR_REQUIRE(bounds && workspace, "pnr_mesh_grid_bounds: null bounds or workspace");
     PNR_REQUIRE(((uintptr_t)bounds & 3) == 0 && ((uintptr_t)workspace & 7) == 0, "pnr_mesh_grid_bounds: bounds must be 4-byte and workspace 8-byte aligned");
@@ -463,9 +438,9 @@ PNR_EXPORT int pnr_mesh_grid_count(const float* vertices, int64_t n_vertices, co
                                    int res_z, const float* lo_host, const float* cell_host, int32_t* start, int64_t* total, void* workspace,
                                    void* stream)
 {
-    McMesh m;
+    PnrMesh m;
     McGrid g;
-    int rc = mc_mesh_check("pnr_mesh_grid_count", vertices, n_vertices, faces, n_faces, m);
+    int rc = pnr_mesh_check("pnr_mesh_grid_count", vertices, n_vertices, faces, n_faces, INT32_MAX, m);
     if (rc) return rc;
     rc = mc_grid_check("pnr_mesh_grid_count", res_x, res_y, res_z, lo_host, cell_host, g);
     if (rc) return rc;
@@ -474,11 +449,11 @@ PNR_EXPORT int pnr_mesh_grid_count(const float* vertices, int64_t n_vertices, co
                 "pnr_mesh_grid_count: start must be 4-byte, total and workspace 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int64_t cells = mc_cells(g);
-    char* ws = (char*)workspace + MC_BOUNDS_WORDS * 4;
-    int32_t* cursor = (int32_t*)(ws + pnr_scan_workspace_bytes(cells));
-    hipLaunchKernelGGL(k_meshcast_zero, dim3(pnr_grid_cap((cells + 255) / 256)), dim3(256), 0, st, cursor, cells);
+    const PnrTableWs w = pnr_table_carve(MC_BOUNDS_WORDS * 4, cells, true);
+    int32_t* cursor = (int32_t*)((char*)workspace + w.cursor);
+    pnr_zero_i32(cursor, cells, st);
     if (n_faces > 0) hipLaunchKernelGGL(k_meshcast_count, dim3(pnr_grid_cap((n_faces + 255) / 256)), dim3(256), 0, st, m, g, cursor);
-    pnr_scan_i32(cursor, start, cells, ws, total, st);
+    pnr_scan_i32(cursor, start, cells, (char*)workspace + w.sums, total, st);
     PNR_CHECK_LAUNCH("pnr_mesh_grid_count");
     return PNR_OK;
 }
@@ -487,9 +462,9 @@ PNR_EXPORT int pnr_mesh_grid_fill(const float* vertices, int64_t n_vertices, con
                                   int res_z, const float* lo_host, const float* cell_host, const int32_t* start, int64_t n_entries,
                                   float* records, void* workspace, void* stream)
 {
-    McMesh m;
+    PnrMesh m;
     McGrid g;
-    int rc = mc_mesh_check("pnr_mesh_grid_fill", vertices, n_vertices, faces, n_faces, m);
+    int rc = pnr_mesh_check("pnr_mesh_grid_fill", vertices, n_vertices, faces, n_faces, INT32_MAX, m);
     if (rc) return rc;
     rc = mc_grid_check("pnr_mesh_grid_fill", res_x, res_y, res_z, lo_host, cell_host, g);
     if (rc) return rc;
@@ -499,7 +474,7 @@ PNR_EXPORT int pnr_mesh_grid_fill(const float* vertices, int64_t n_vertices, con
     PNR_REQUIRE(((uintptr_t)start & 3) == 0 && ((uintptr_t)records & 15) == 0 && ((uintptr_t)workspace & 7) == 0,
                 "pnr_mesh_grid_fill: start must be 4-byte, records 16-byte and workspace 8-byte aligned");
     g.start = start; g.n_entries = n_entries;
-    int32_t* cursor = (int32_t*)((char*)workspace + MC_BOUNDS_WORDS * 4 + pnr_scan_workspace_bytes(mc_cells(g)));
+    int32_t* cursor = (int32_t*)((char*)workspace + pnr_table_carve(MC_BOUNDS_WORDS * 4, mc_cells(g), true).cursor);
     hipLaunchKernelGGL(k_meshcast_fill, dim3(pnr_grid_cap((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, g, cursor, (float4*)records);
     PNR_CHECK_LAUNCH("pnr_mesh_grid_fill");
     return PNR_OK;
@@ -510,7 +485,7 @@ static int mc_cast_check(const char* who, const float* vertices, int64_t n_verti
                          int res_z, const float* lo_host, const float* cell_host, const int32_t* start, const float* records, int64_t n_entries,
                          float* depth, int32_t* face, uint8_t* code, float* bary, int32_t* vertex, float* normal, int8_t* side, McArgs& a)
 {
-    int rc = mc_mesh_check(who, vertices, n_vertices, faces, n_faces, a.m);
+    int rc = pnr_mesh_check(who, vertices, n_vertices, faces, n_faces, INT32_MAX, a.m);
     if (rc) return rc;
     rc = mc_grid_check(who, res_x, res_y, res_z, lo_host, cell_host, a.g);
     if (rc) return rc;
@@ -549,10 +524,8 @@ PNR_EXPORT int pnr_mesh_raycast(int model, const float* cam_host, const float* c
     a.model = model; a.width = width; a.height = height; a.near_ = near_; a.far_ = far_;
     pnr_camera_fill(model, cam_host, a.cam);
     pnr_pose_fill(c2w12_host, a.c2w);
-    const int64_t tiles_x = ((int64_t)width + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE, tiles_y = ((int64_t)height + PNR_RAYCAST_TILE - 1) / PNR_RAYCAST_TILE;
-    a.tiles_x = (unsigned int)tiles_x;
-    a.n_tiles = tiles_x * tiles_y;                                  // at most 2^28 + 2^25: the grid below fits a launch
-    const int64_t blocks = (a.n_tiles + PNR_RAYCAST_BLOCK / 64 - 1) / (PNR_RAYCAST_BLOCK / 64);
+    int64_t blocks;
+    pnr_tile_grid(width, height, &a.tiles_x, &a.n_tiles, &blocks);
     hipLaunchKernelGGL(k_mesh_cast<true>, dim3((unsigned int)blocks), dim3(PNR_RAYCAST_BLOCK), 0, (hipStream_t)stream, a);
     PNR_CHECK_LAUNCH("pnr_mesh_raycast");
     return PNR_OK;

@@ -1,19 +1,17 @@
 // Nearest neighbours and geometry metrics (include/pnr.h "nearest neighbours"): an exact fixed-radius nearest-neighbour search
 // between two clouds through a spatial hash, the reconstruction metrics accumulated from its answers, and surface points of a
-// triangle mesh at a given density.  The search's answer is brute force's, bit for bit, whatever the table does: the key of
-// pnr_splat_points (distance bits, index) under a minimum, so collisions and a bucket visited twice cost time and nothing else.
-// Small gather-bound kernels in the style of pnr_splat.hip: one thread per point, query or output point, grid-stride; the only
+// triangle mesh at a given density.  The search's answer is brute force's, bit for bit, whatever the table does: pnr_key
+// (distance bits, index; pnr_geom_dev.h) under a minimum, so collisions and a bucket visited twice cost time and nothing else.
+// Small gather-bound kernels: one thread per point, query or output point, grid-stride; the only
 // LDS is the few words of the block-wide counters and sums (pnr_reduce_dev.h; the metric sums take the order of DESIGN.md
 // section 8 "Ordered reductions").  tests/_nn_ref.py restates every rule in numpy.
 #include <float.h>
 #include <math.h>
 
 #include "pnr_common.h"
+#include "pnr_geom_dev.h"
 #include "pnr_philox.h"
-#include "pnr_reduce_dev.h"
-#include "pnr_scan_dev.h"
 
-#define PNR_NN_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define PNR_CM_MAX_BLOCKS 1024            // k_cloud_metrics' grid limit: what pnr_cloud_metrics_workspace_bytes sizes for
 #define PNR_CM_COUNTS (2 + PNR_CLOUD_MAX_TAU)
 
@@ -60,15 +58,9 @@ __device__ __forceinline__ void nn_scatter(const NnGrid& g, int32_t* __restrict_
             atomicAdd(&cursor[b], 1);
         } else {
             const int64_t at = (int64_t)start[b] + (int64_t)atomicSub(&cursor[b], 1) - 1;
-            if (at >= 0 && at < g.n) records[at] = make_float4(x, y, z, __int_as_float((int)j));     // (a damaged table never writes outside)
+            if (at >= 0 && at < g.n) records[at] = make_float4(x, y, z, __int_as_float((int)j));
         }
     }
-}
-
-// p[0 .. n) = 0: a kernel and not a memset, so that a captured build is a plain chain of kernel nodes
-__global__ __launch_bounds__(256) void k_nn_zero(int32_t* __restrict__ p, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
 }
 
 __global__ __launch_bounds__(256) void k_nn_count(const NnGrid g, int32_t* __restrict__ cursor) { nn_scatter<false>(g, cursor, nullptr, nullptr); }
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(256) void k_nn_query(const NnQueryArgs a)
     const int n32 = (int)a.g.n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.m; i += (int64_t)gridDim.x * blockDim.x) {
         const float qx = a.q[3 * i], qy = a.q[3 * i + 1], qz = a.q[3 * i + 2];
-        unsigned long long best = PNR_NN_EMPTY;
+        unsigned long long best = PNR_KEY_EMPTY;
         int slot = 2;
         if (pnr_finite3(qx, qy, qz)) {
             const int x0 = nn_cell(qx - a.dp, ox, a.g.inv), x1 = nn_cell(qx + a.dp, ox, a.g.inv);
@@ -107,22 +99,21 @@ __global__ __launch_bounds__(256) void k_nn_query(const NnQueryArgs a)
                 for (int cy = y0; cy <= y1; ++cy)
                     for (int cx = x0; cx <= x1; ++cx) {
                         const unsigned int b = nn_bucket(cx, cy, cz, a.g.mask);
-                        const int s = min(max(a.start[b], 0), n32);                 // clamped: a damaged table reads inside
-                        const int e = min(max(a.start[b + 1], s), n32);
-                        for (int r = s; r < e; ++r) {
+                        const PnrRange rg = pnr_table_range(a.start, b, n32);
+                        for (int r = rg.s; r < rg.e; ++r) {
                             const float4 p = a.records[r];
                             const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
                             const float d2 = (dx * dx + dy * dy) + dz * dz;
                             if (d2 <= a.r2) {
-                                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)__float_as_int(p.w);
+                                const unsigned long long key = pnr_key(d2, __float_as_uint(p.w));
                                 best = key < best ? key : best;
                             }
                         }
                     }
-            slot = best == PNR_NN_EMPTY ? 1 : 0;
+            slot = best == PNR_KEY_EMPTY ? 1 : 0;
         }
-        a.index[i] = best == PNR_NN_EMPTY ? -1 : (int32_t)(unsigned int)best;
-        a.dist2[i] = best == PNR_NN_EMPTY ? INFINITY : __uint_as_float((unsigned int)(best >> 32));
+        a.index[i] = best == PNR_KEY_EMPTY ? -1 : (int32_t)pnr_key_index(best);
+        a.dist2[i] = best == PNR_KEY_EMPTY ? INFINITY : pnr_key_value(best);
 #pragma unroll
         for (int k = 0; k < 3; ++k) cnt[k] += slot == k ? 1u : 0u;
     }
@@ -177,8 +168,7 @@ __global__ __launch_bounds__(64) void k_cloud_metrics_final(const CloudMetricArg
 }
 
 struct SampleArgs {
-    const float* vertices; int64_t n_vertices;
-    const int32_t* faces; int64_t n_faces;
+    PnrMesh m;
     float rho;
     uint32_t seed_lo, seed_hi;
     int32_t* start;                     // count: the counts, in place of their scan; emit: the scan
@@ -188,28 +178,27 @@ struct SampleArgs {
 
 struct SampleTri { float p0[3], e1[3], e2[3]; bool ok; };
 
-__device__ __forceinline__ SampleTri sample_tri(const SampleArgs& a, int64_t t)
+__device__ __forceinline__ SampleTri sample_tri(const PnrMesh& m, int64_t t)
 {
     SampleTri r;
-    const int32_t i0 = a.faces[3 * t], i1 = a.faces[3 * t + 1], i2 = a.faces[3 * t + 2];
-    r.ok = i0 >= 0 && i0 < a.n_vertices && i1 >= 0 && i1 < a.n_vertices && i2 >= 0 && i2 < a.n_vertices;
+    const int32_t i0 = m.faces[3 * t], i1 = m.faces[3 * t + 1], i2 = m.faces[3 * t + 2];
+    r.ok = i0 >= 0 && i0 < m.n_vertices && i1 >= 0 && i1 < m.n_vertices && i2 >= 0 && i2 < m.n_vertices;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        r.p0[c] = r.ok ? a.vertices[3 * (int64_t)i0 + c] : 0.0f;
-        r.e1[c] = r.ok ? a.vertices[3 * (int64_t)i1 + c] - r.p0[c] : 0.0f;
-        r.e2[c] = r.ok ? a.vertices[3 * (int64_t)i2 + c] - r.p0[c] : 0.0f;
+        r.p0[c] = r.ok ? m.vertices[3 * (int64_t)i0 + c] : 0.0f;
+        r.e1[c] = r.ok ? m.vertices[3 * (int64_t)i1 + c] - r.p0[c] : 0.0f;
+        r.e2[c] = r.ok ? m.vertices[3 * (int64_t)i2 + c] - r.p0[c] : 0.0f;
     }
     return r;
 }
 
 __global__ __launch_bounds__(256) void k_mesh_sample_count(const SampleArgs a)
 {
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.n_faces; t += (int64_t)gridDim.x * blockDim.x) {
-        const SampleTri r = sample_tri(a, t);
-        const float nx = r.e1[1] * r.e2[2] - r.e1[2] * r.e2[1];
-        const float ny = r.e1[2] * r.e2[0] - r.e1[0] * r.e2[2];
-        const float nz = r.e1[0] * r.e2[1] - r.e1[1] * r.e2[0];
-        const float s = (nx * nx + ny * ny) + nz * nz;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.m.n_faces; t += (int64_t)gridDim.x * blockDim.x) {
+        const SampleTri r = sample_tri(a.m, t);
+        float n[3];
+        pnr_cross3(r.e1, r.e2, n);
+        const float s = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
         int k = 0;
         if (r.ok && s <= FLT_MAX) {                     // (a NaN or infinite s: the area is not finite)
             const float area = 0.5f * sqrtf(s);
@@ -225,14 +214,14 @@ __global__ __launch_bounds__(256) void k_mesh_sample_emit(const SampleArgs a)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_points; i += (int64_t)gridDim.x * blockDim.x) {
         // the triangle t with start[t] <= i < start[t + 1]: the last t whose start is <= i
-        int64_t lo = 0, hi = a.n_faces - 1;
+        int64_t lo = 0, hi = a.m.n_faces - 1;
         while (lo < hi) {
             const int64_t mid = (lo + hi + 1) >> 1;
             if ((int64_t)a.start[mid] <= i) lo = mid; else hi = mid - 1;
         }
         const int64_t t = lo;
         const uint32_t j = (uint32_t)(i - (int64_t)a.start[t]);
-        const SampleTri r = sample_tri(a, t);
+        const SampleTri r = sample_tri(a.m, t);
         const pnr_u4 w = pnr_philox4x32_10(pnr_u4{(uint32_t)t, 1u + j, 0u, 0u}, a.seed_lo, a.seed_hi);
         float u = pnr_uniform(w.x), v = pnr_uniform(w.y);
         if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
@@ -261,7 +250,7 @@ static NnGrid nn_grid(const float* ref, int64_t n, float max_dist, int64_t T, fl
 PNR_EXPORT int64_t pnr_nn_workspace_bytes(int64_t n, int64_t table_size)
 {
     if (n < 0 || n > (int64_t)INT32_MAX || !nn_table_ok(table_size)) return -1;
-    return 8 + pnr_scan_workspace_bytes(table_size) + table_size * 4;      // the scan's total, its tile sums, the cursors
+    return pnr_table_carve(8, table_size, true).bytes;      // the scan's total, its tile sums, the cursors
 }
 
 PNR_EXPORT int pnr_nn_build(const float* ref, int64_t n, float max_dist, int64_t table_size, int32_t* start, float* records,
@@ -276,7 +265,7 @@ PNR_EXPORT int pnr_nn_build(const float* ref, int64_t n, float max_dist, int64_t
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {                               // an empty cloud: an all-zero table (a null start: nothing to fill)
         if (start) {
-            hipLaunchKernelGGL(k_nn_zero, dim3(pnr_grid_cap((table_size + 256) / 256)), dim3(256), 0, st, start, table_size + 1);
+            pnr_zero_i32(start, table_size + 1, st);
             PNR_CHECK_LAUNCH("pnr_nn_build");
         }
         return PNR_OK;
@@ -287,11 +276,12 @@ PNR_EXPORT int pnr_nn_build(const float* ref, int64_t n, float max_dist, int64_t
     PNR_REQUIRE(((uintptr_t)records & 15) == 0, "pnr_nn_build: records must be 16-byte aligned");
     PNR_REQUIRE(((uintptr_t)workspace & 7) == 0, "pnr_nn_build: workspace must be 8-byte aligned");
     const NnGrid g = nn_grid(ref, n, max_dist, table_size, nullptr);
-    int32_t* cursor = (int32_t*)((char*)workspace + 8 + pnr_scan_workspace_bytes(table_size));
+    const PnrTableWs w = pnr_table_carve(8, table_size, true);
+    int32_t* cursor = (int32_t*)((char*)workspace + w.cursor);
     const int grid = pnr_grid_cap((n + 255) / 256);
-    hipLaunchKernelGGL(k_nn_zero, dim3(pnr_grid_cap((table_size + 255) / 256)), dim3(256), 0, st, cursor, table_size);
+    pnr_zero_i32(cursor, table_size, st);
     hipLaunchKernelGGL(k_nn_count, dim3(grid), dim3(256), 0, st, g, cursor);
-    pnr_scan_i32(cursor, start, table_size, (char*)workspace + 8, (int64_t*)workspace, st);
+    pnr_scan_i32(cursor, start, table_size, (char*)workspace + w.sums, (int64_t*)workspace, st);
     hipLaunchKernelGGL(k_nn_fill, dim3(grid), dim3(256), 0, st, g, cursor, (const int32_t*)start, (float4*)records);
     PNR_CHECK_LAUNCH("pnr_nn_build");
     return PNR_OK;
@@ -357,40 +347,31 @@ PNR_EXPORT int pnr_cloud_metrics(const int32_t* index, const float* dist2, const
     return PNR_OK;
 }
 
-static int sample_check(const char* who, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces)
-{
-    PNR_REQUIRE(n_vertices >= 0 && n_vertices <= (int64_t)INT32_MAX, "%s: n_vertices must be within 0 .. 2^31 - 1", who);
-    PNR_REQUIRE(n_faces >= 0 && n_faces <= (int64_t)INT32_MAX - 1, "%s: n_faces must be within 0 .. 2^31 - 2", who);
-    PNR_REQUIRE(n_faces == 0 || faces, "%s: null faces", who);
-    PNR_REQUIRE(n_faces == 0 || n_vertices == 0 || vertices, "%s: null vertices", who);
-    PNR_REQUIRE((((uintptr_t)vertices | (uintptr_t)faces) & 3) == 0, "%s: vertices and faces must be 4-byte aligned", who);
-    return PNR_OK;
-}
-
+#define SAMPLE_MAX_FACES ((int64_t)INT32_MAX - 1)             // the scan writes n_faces + 1 int32 entries
 PNR_EXPORT int64_t pnr_mesh_sample_workspace_bytes(int64_t n_faces)
 {
-    if (n_faces < 0 || n_faces > (int64_t)INT32_MAX - 1) return -1;
-    return pnr_scan_workspace_bytes(n_faces);
+    if (n_faces < 0 || n_faces > SAMPLE_MAX_FACES) return -1;
+    return pnr_table_carve(0, n_faces, false).bytes;
 }
 
 PNR_EXPORT int pnr_mesh_sample_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, float rho, int64_t seed,
                                      int32_t* start, int64_t* total, void* workspace, void* stream)
 {
-    const int rc = sample_check("pnr_mesh_sample_count", vertices, n_vertices, faces, n_faces);
+    SampleArgs a;
+    const int rc = pnr_mesh_check("pnr_mesh_sample_count", vertices, n_vertices, faces, n_faces, SAMPLE_MAX_FACES, a.m);
     if (rc) return rc;
     PNR_REQUIRE(rho >= 0.0f && rho <= FLT_MAX, "pnr_mesh_sample_count: rho must be finite and >= 0 (got %g)", (double)rho);
     PNR_REQUIRE(((uintptr_t)start & 3) == 0 && ((uintptr_t)total & 7) == 0, "pnr_mesh_sample_count: start must be 4-byte and total 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (n_faces == 0) {                         // no faces: start[0] = 0 and total = 0 (a null one: nothing to fill)
-        if (start) hipLaunchKernelGGL(k_nn_zero, dim3(1), dim3(256), 0, st, start, (int64_t)1);
-        if (total) hipLaunchKernelGGL(k_nn_zero, dim3(1), dim3(256), 0, st, (int32_t*)total, (int64_t)2);
+        if (start) pnr_zero_i32(start, 1, st);
+        if (total) pnr_zero_i32((int32_t*)total, 2, st);
         if (start || total) PNR_CHECK_LAUNCH("pnr_mesh_sample_count");
         return PNR_OK;
     }
     PNR_REQUIRE(start && total, "pnr_mesh_sample_count: null start or total");
     PNR_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "pnr_mesh_sample_count: workspace must be non-null and 4-byte aligned");
-    SampleArgs a;
-    a.vertices = vertices; a.n_vertices = n_vertices; a.faces = faces; a.n_faces = n_faces; a.rho = rho;
+    a.rho = rho;
     a.seed_lo = (uint32_t)(uint64_t)seed; a.seed_hi = (uint32_t)((uint64_t)seed >> 32);
     a.start = start; a.n_points = 0; a.points = nullptr; a.face = nullptr;
     hipLaunchKernelGGL(k_mesh_sample_count, dim3(pnr_grid_cap((n_faces + 255) / 256)), dim3(256), 0, st, a);
@@ -402,15 +383,15 @@ PNR_EXPORT int pnr_mesh_sample_count(const float* vertices, int64_t n_vertices, 
 PNR_EXPORT int pnr_mesh_sample_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int64_t seed,
                                     const int32_t* start, int64_t n_points, float* points, int32_t* face, void* stream)
 {
-    const int rc = sample_check("pnr_mesh_sample_emit", vertices, n_vertices, faces, n_faces);
+    SampleArgs a;
+    const int rc = pnr_mesh_check("pnr_mesh_sample_emit", vertices, n_vertices, faces, n_faces, SAMPLE_MAX_FACES, a.m);
     if (rc) return rc;
     PNR_REQUIRE(n_points >= 0 && n_points <= (int64_t)INT32_MAX, "pnr_mesh_sample_emit: n_points must be within 0 .. 2^31 - 1");
     if (n_points == 0) return PNR_OK;
     PNR_REQUIRE(n_faces >= 1, "pnr_mesh_sample_emit: n_points > 0 on a mesh without faces");
     PNR_REQUIRE(start && points && face, "pnr_mesh_sample_emit: null start, points or face");
     PNR_REQUIRE((((uintptr_t)start | (uintptr_t)points | (uintptr_t)face) & 3) == 0, "pnr_mesh_sample_emit: start, points and face must be 4-byte aligned");
-    SampleArgs a;
-    a.vertices = vertices; a.n_vertices = n_vertices; a.faces = faces; a.n_faces = n_faces; a.rho = 0.0f;
+    a.rho = 0.0f;
     a.seed_lo = (uint32_t)(uint64_t)seed; a.seed_hi = (uint32_t)((uint64_t)seed >> 32);
     a.start = (int32_t*)start; a.n_points = n_points; a.points = points; a.face = face;
     hipLaunchKernelGGL(k_mesh_sample_emit, dim3(pnr_grid_cap((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);

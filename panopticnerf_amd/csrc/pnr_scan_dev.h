@@ -1,6 +1,7 @@
-// Exclusive int32 scan of a device array (pnr_nn.hip: the bucket table of the nearest-neighbour index and the per-triangle
-// counts of mesh sampling; pnr_meshcast.hip: the cell table of the ray-casting grid -- the kernels are `static`, each file that
-// includes this header carries its own copy).  Three launches on one stream, no kernel waits on another workgroup and nothing is atomic:
+// Exclusive int32 scan of a device array, and the kernel that zeroes one (pnr_nn.hip: the bucket table of the nearest-neighbour
+// index and the per-triangle counts of mesh sampling; pnr_meshcast.hip: the cell table of the ray-casting grid -- the kernels
+// are `static`, each file that includes this header carries its own copy).  Three launches on one stream, no kernel waits on
+// another workgroup and nothing is atomic:
 //   1. k_scan_tile_sums: workgroup b adds its tile of PNR_SCAN_TILE items into sums[b];
 //   2. k_scan_top:       ONE workgroup turns sums into their exclusive scan, carrying in 64 bits, and writes the 64-bit total;
 //   3. k_scan_apply:     workgroup b scans its tile again and writes out[i] = sums[b] + the items before i in the tile; the
@@ -68,6 +69,14 @@ static __global__ __launch_bounds__(PNR_SCAN_BLOCK) void k_scan_apply(const int3
         if (base + i == n - 1) out[n] = run;
     }
 }
+
+// p[0 .. n) = 0: a kernel and not a memset, so that a captured build is a plain chain of kernel nodes
+static __global__ __launch_bounds__(256) void k_zero_i32(int32_t* __restrict__ p, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
+}
+
+static inline void pnr_zero_i32(int32_t* p, int64_t n, hipStream_t st) { hipLaunchKernelGGL(k_zero_i32, dim3(pnr_grid_cap((n + 255) / 256)), dim3(256), 0, st, p, n); }
 
 // out[0 .. n] = the exclusive scan of in[0 .. n) and the total; total64 (device, 8-byte aligned) receives the 64-bit total;
 // ws: pnr_scan_workspace_bytes(n) bytes, 4-byte aligned.  n >= 1.  The caller checks the launches (PNR_CHECK_LAUNCH).

@@ -3,14 +3,13 @@
 // pixel, so the nearest point wins, a depth tie goes to the lowest index and the result does not depend on arrival order; a
 // second kernel unpacks the buffer into a depth and an index image; a third accumulates depth-error metrics of a predicted
 // depth image against such a ground truth (its double sums in the order of DESIGN.md section 8 "Ordered reductions",
-// pnr_reduce_dev.h).  Small scatter- / gather-bound kernels in the style of pnr_warp.hip: one thread per
-// point or pixel, grid-stride, camera and pose in the kernel arguments.  The projection is pnr_project_point (pnr_camera_dev.h)
+// pnr_reduce_dev.h).  Small scatter- / gather-bound kernels: one thread per point or pixel, grid-stride, the view
+// (PnrView) in the kernel arguments; the key is pnr_key (both pnr_geom_dev.h).  The projection is pnr_project_point (pnr_camera_dev.h)
 // and nothing else, so the arithmetic is k_project_points' bit for bit (the nearest pixel and the stored depth are k_reproject's); tests/_splat_ref.py restates the whole rule in numpy.
 #include <float.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
-#include "pnr_reduce_dev.h"
+#include "pnr_geom_dev.h"
 
 // -DPNR_SPLAT_PREREAD=1 (A/B builds): a plain read of the cell skips the atomic when the key cannot lower it.  A cell only ever
 // decreases, so a stale read errs towards issuing the atomic.  Off by default; tools/splat_time.py is its A/B (profiles/README.md
@@ -19,14 +18,10 @@
 #define PNR_SPLAT_PREREAD 0
 #endif
 
-#define PNR_SPLAT_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define PNR_DM_MAX_BLOCKS 1024            // k_depth_metrics' grid limit: what pnr_depth_metrics_workspace_bytes sizes for
 
 struct SplatArgs {
-    int model;
-    float cam[7];
-    float w2c[12];
-    int width, height;
+    PnrView view;                       // pose = w2c
     float umax, vmax, near_, far_;
     const float* points; int64_t n;
     unsigned int index_base;
@@ -40,23 +35,23 @@ __global__ __launch_bounds__(256) void k_splat_points(const SplatArgs a)
     unsigned int cnt[3] = {0, 0, 0};                    // landed / left the view / clipped
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
         const float X = a.points[3 * i], Y = a.points[3 * i + 1], Z = a.points[3 * i + 2];
-        const PnrProj q = pnr_project_point(a.model, a.cam, a.w2c, a.umax, X, Y, Z);
+        const PnrProj q = pnr_project_point(a.view.model, a.view.cam, a.view.pose, a.umax, X, Y, Z);
         int slot = 1;
         if (q.dom && pnr_uv_inside(q.u, q.v, a.umax, a.vmax)) {
-            const int wmax = a.width - 1, hmax = a.height - 1;
+            const int wmax = a.view.width - 1, hmax = a.view.height - 1;
             const int iu = pnr_nearest_pixel(q.u, wmax), iv = pnr_nearest_pixel(q.v, hmax);
-            const float e = pnr_view_depth(a.model, q);
+            const float e = pnr_view_depth(a.view.model, q);
             slot = 2;
             if (e >= a.near_ && e <= a.far_) {
                 slot = 0;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(e) << 32) | (unsigned int)(a.index_base + (unsigned int)i);
+                const unsigned long long key = pnr_key(e, a.index_base + (unsigned int)i);
 #pragma unroll
                 for (int dy = -RADIUS; dy <= RADIUS; ++dy) {
 #pragma unroll
                     for (int dx = -RADIUS; dx <= RADIUS; ++dx) {
                         const int x = iu + dx, y = iv + dy;
                         if (x >= 0 && x <= wmax && y >= 0 && y <= hmax) {       // clipped at the border, never wrapped
-                            unsigned long long* cell = a.zbuf + ((int64_t)y * a.width + x);
+                            unsigned long long* cell = a.zbuf + ((int64_t)y * a.view.width + x);
 #if PNR_SPLAT_PREREAD
                             if (key < *(volatile unsigned long long*)cell) atomicMin(cell, key);
 #else
@@ -78,9 +73,9 @@ __global__ __launch_bounds__(256) void k_splat_resolve(const unsigned long long*
 {
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_pix; q += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long c = zbuf[q];
-        const bool empty = c == PNR_SPLAT_EMPTY;
-        if (depth) depth[q] = empty ? 0.0f : __uint_as_float((unsigned int)(c >> 32));
-        if (index) index[q] = empty ? -1 : (int32_t)(unsigned int)c;
+        const bool empty = c == PNR_KEY_EMPTY;
+        if (depth) depth[q] = empty ? 0.0f : pnr_key_value(c);
+        if (index) index[q] = empty ? -1 : (int32_t)pnr_key_index(c);
     }
 }
 
@@ -141,23 +136,16 @@ PNR_EXPORT int pnr_splat_points(int model, const float* cam_host, const float* w
                                 int64_t n, int64_t index_base, float near_, float far_, int radius, int64_t* zbuf, int64_t* stats,
                                 void* stream)
 {
-    PNR_REQUIRE(pnr_camera_model_ok(model), "pnr_splat_points: unknown camera model %d", model);
-    PNR_REQUIRE(cam_host && w2c12_host, "pnr_splat_points: null camera or pose");
-    PNR_REQUIRE(width >= 1 && height >= 1 && n >= 0 && (int64_t)width * height <= INT32_MAX,
-                "pnr_splat_points: bad size (the image holds at most 2^31 - 1 pixels)");
-    const int rc = pnr_camera_check(model, cam_host, width, height, "pnr_splat_points");
+    SplatArgs a;
+    const int rc = pnr_view_check("pnr_splat_points", nullptr, model, cam_host, w2c12_host, width, height, true, a.view);
     if (rc) return rc;
+    PNR_REQUIRE(n >= 0 && (int64_t)width * height <= INT32_MAX, "pnr_splat_points: bad size (n >= 0, the image holds at most 2^31 - 1 pixels)");
     PNR_REQUIRE(radius >= 0 && radius <= 2, "pnr_splat_points: radius must be 0, 1 or 2 (got %d)", radius);
     PNR_REQUIRE(near_ >= 0.0f && far_ >= near_, "pnr_splat_points: near and far must satisfy 0 <= near <= far (far may be +inf)");
     PNR_REQUIRE(index_base >= 0 && index_base + n <= (int64_t)INT32_MAX, "pnr_splat_points: index_base + n must stay within 0 .. 2^31 - 1");
     if (n == 0) return PNR_OK;                  // before the pointer checks: an empty cloud has a null pointer
     PNR_REQUIRE(points && zbuf, "pnr_splat_points: null points or zbuf");
-    SplatArgs a;
-    a.model = model;
-    pnr_camera_fill(model, cam_host, a.cam);
-    pnr_pose_fill(w2c12_host, a.w2c);
-    a.width = width; a.height = height;
-    a.umax = (float)width - 0.5f; a.vmax = (float)height - 0.5f; a.near_ = near_; a.far_ = far_;
+    a.umax = pnr_view_umax(a.view); a.vmax = pnr_view_vmax(a.view); a.near_ = near_; a.far_ = far_;
     a.points = points; a.n = n; a.index_base = (unsigned int)index_base;
     a.zbuf = (unsigned long long*)zbuf; a.stats = (unsigned long long*)stats;
     const int grid = pnr_grid_cap((n + 255) / 256);

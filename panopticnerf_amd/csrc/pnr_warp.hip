@@ -1,26 +1,22 @@
 // Cross-view reprojection (include/pnr.h "cross-view reprojection"): a source pixel is lifted with the source depth image,
 // projected into the target view, matched to the nearest target pixel and tested against the target depth image; with label
 // images on both sides the visible pairs are counted into the cross-view confusion matrix of the multi-view consistency metric.
-// A small gather-bound kernel in the style of pnr_camera.hip: one thread per source pixel, grid-stride, cameras and poses in
-// the kernel arguments.  The ray is pnr_camera_ray and the projection pnr_project_point (pnr_camera_dev.h), the same functions
+// A small gather-bound kernel: one thread per source pixel, grid-stride, the two views (PnrView, pnr_geom_dev.h) in the kernel
+// arguments.  The ray is pnr_camera_ray and the projection pnr_project_point (pnr_camera_dev.h), the same functions
 // the ray and projection kernels call, so the arithmetic is theirs bit for bit; the nearest pixel and the depth a view stores
-// are that header's too (shared with pnr_splat.hip), the reduction of the stats is pnr_reduce_dev.h's.  tests/_warp_ref.py
+// are that header's too, the reduction of the stats is pnr_reduce_dev.h's.  tests/_warp_ref.py
 // restates the whole rule in float32 (tests/_pano_ref.py with a panoramic view on either side).
 #include <float.h>
 
-#include "pnr_camera_dev.h"
 #include "pnr_common.h"
-#include "pnr_reduce_dev.h"
+#include "pnr_geom_dev.h"
 
 #define PNR_WARP_LDS_CLASSES 128        // up to here `agree` is a per-block LDS histogram (k_confusion's limit: 64 KiB)
 
 struct ReprojectArgs {
-    int model_src, model_tgt;
-    float cam_src[7], cam_tgt[7];
-    float c2w[12], w2c[12];
-    int width_src, width_tgt, height_tgt;
+    PnrView src, tgt;                   // src.pose = c2w of the source, tgt.pose = w2c of the target
     int64_t npix_src;
-    float umax, vmax, tol_abs, tol_rel;
+    float umax, vmax, tol_abs, tol_rel; // the bounds of tgt
     const int32_t* pix; int64_t R;
     const float *depth_src, *depth_tgt;
     const int32_t *label_src, *label_tgt;
@@ -48,22 +44,22 @@ __global__ __launch_bounds__(256) void k_reproject(const ReprojectArgs a)
         int code = -1;
         float u = 0.0f, v = 0.0f;
         if (p >= 0 && p < a.npix_src) {                 // an index outside the source image has nothing to reproject
-            const int j = (int)(p / a.width_src), i = (int)(p - (int64_t)j * a.width_src);
+            const int j = (int)(p / a.src.width), i = (int)(p - (int64_t)j * a.src.width);
             bool ok;
-            const PnrRayRec ray = pnr_camera_ray(a.model_src, a.cam_src, a.c2w, i, j, 0.0f, 0.0f, ok);
+            const PnrRayRec ray = pnr_camera_ray(a.src.model, a.src.cam, a.src.pose, i, j, 0.0f, 0.0f, ok);
             const float t = a.depth_src[p];
             const bool have = pnr_pos_finite(t);     // (named first: called inside the chain below, the compiler lays the kernel out anew)
             if (ok && have) {
                 const float X = ray.lo.x + t * ray.lo.w, Y = ray.lo.y + t * ray.hi.x, Z = ray.lo.z + t * ray.hi.y;
-                const PnrProj q = pnr_project_point(a.model_tgt, a.cam_tgt, a.w2c, a.umax, X, Y, Z);
+                const PnrProj q = pnr_project_point(a.tgt.model, a.tgt.cam, a.tgt.pose, a.umax, X, Y, Z);
                 u = q.u;
                 v = q.v;
                 code = -2;
                 if (q.dom && pnr_uv_inside(u, v, a.umax, a.vmax)) {
-                    const int tq = pnr_nearest_pixel(v, a.height_tgt - 1) * a.width_tgt + pnr_nearest_pixel(u, a.width_tgt - 1);
+                    const int tq = pnr_nearest_pixel(v, a.tgt.height - 1) * a.tgt.width + pnr_nearest_pixel(u, a.tgt.width - 1);
                     code = tq;
                     if (a.depth_tgt) {
-                        const float e = pnr_view_depth(a.model_tgt, q);
+                        const float e = pnr_view_depth(a.tgt.model, q);
                         const float dt = a.depth_tgt[tq];
                         if (!pnr_pos_finite(dt)) code = -3;
                         else if (!(fabsf(e - dt) <= a.tol_abs + a.tol_rel * e)) code = -4;
@@ -106,8 +102,9 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
                 "pnr_reproject: bad size (each image holds at most 2^31 - 1 pixels)");
     if (n == 0) return PNR_OK;                  // before the pointer checks: an empty pixel list has a null pointer
     PNR_REQUIRE(pix || n == (int64_t)width_src * height_src, "pnr_reproject: without pixel indices n must be width_src*height_src");
-    int rc = pnr_camera_check(model_src, cam_src_host, width_src, height_src, "pnr_reproject: src");
-    if (!rc) rc = pnr_camera_check(model_tgt, cam_tgt_host, width_tgt, height_tgt, "pnr_reproject: tgt");
+    ReprojectArgs a;                            // (the cameras are checked once there is work, as ever)
+    int rc = pnr_view_check("pnr_reproject", "src", model_src, cam_src_host, c2w_src12_host, width_src, height_src, true, a.src);
+    if (!rc) rc = pnr_view_check("pnr_reproject", "tgt", model_tgt, cam_tgt_host, w2c_tgt12_host, width_tgt, height_tgt, true, a.tgt);
     if (rc) return rc;
     PNR_REQUIRE(depth_src, "pnr_reproject: null source depth image");
     PNR_REQUIRE(tol_abs >= 0.0f && tol_abs <= FLT_MAX && tol_rel >= 0.0f && tol_rel <= FLT_MAX,
@@ -117,14 +114,7 @@ PNR_EXPORT int pnr_reproject(int model_src, const float* cam_src_host, const flo
     PNR_REQUIRE(labels || !agree, "pnr_reproject: agree needs label images on both sides");
     PNR_REQUIRE(!labels || (n_classes >= 1 && n_classes <= 8192), "pnr_reproject: n_classes must be in 1 .. 8192 (got %d)", n_classes);
     PNR_REQUIRE((((uintptr_t)uv) & 7) == 0, "pnr_reproject: uv must be an 8-byte aligned device buffer");
-    ReprojectArgs a;
-    a.model_src = model_src; a.model_tgt = model_tgt;
-    pnr_camera_fill(model_src, cam_src_host, a.cam_src);
-    pnr_camera_fill(model_tgt, cam_tgt_host, a.cam_tgt);
-    pnr_pose_fill(c2w_src12_host, a.c2w);
-    pnr_pose_fill(w2c_tgt12_host, a.w2c);
-    a.width_src = width_src; a.width_tgt = width_tgt; a.height_tgt = height_tgt; a.npix_src = (int64_t)width_src * height_src;
-    a.umax = (float)width_tgt - 0.5f; a.vmax = (float)height_tgt - 0.5f; a.tol_abs = tol_abs; a.tol_rel = tol_rel;
+    a.npix_src = (int64_t)width_src * height_src; a.umax = pnr_view_umax(a.tgt); a.vmax = pnr_view_vmax(a.tgt); a.tol_abs = tol_abs; a.tol_rel = tol_rel;
     a.pix = pix; a.R = n; a.depth_src = depth_src; a.depth_tgt = depth_tgt;
     a.label_src = labels ? label_src : nullptr; a.label_tgt = labels ? label_tgt : nullptr; a.n_classes = labels ? n_classes : 0;
     a.match = match; a.uv = reinterpret_cast<float2*>(uv);
