@@ -1341,6 +1341,64 @@ int pnr_depth_filter(int width, int height, const float* depth_in, int radius, c
 int pnr_depth_normals(int model, const float* cam_host, const float* c2w12_host, int width, int height, const float* depth,
                       float jump_a, float jump_b, float mc2, float* normal, float* vertex, uint8_t* code, void* stream);
 
+/* ---- connected components (csrc/pnr_components.hip; tests/_cc_ref.py restates the rule in numpy): the components of an image, a
+ * lattice or a triangle mesh, numbered in a fixed order, with the size of each.  The reference ships none of this: the rule is this
+ * build's and unpinned.  The result is exact and the same on every call, whatever the schedule.
+ *
+ * ELEMENTS AND LINKS.  A lattice (res_z, res_y, res_x) is indexed flat, i = (iz * res_y + iy) * res_x + ix; an image is the
+ *   lattice with res_z = 1.  Two neighbouring elements are LINKED iff both are foreground and the mode's test holds.
+ *   full = 0: neighbours differ by +-1 on exactly one axis (6 in a volume, 4 in an image).
+ *   full = 1: neighbours differ by at most 1 on every axis and are not the element itself (26 in a volume, 8 in an image).
+ *   Nothing wraps and nothing links across the lattice border.
+ * MODES.  PNR_CC_KEYS, int32 data: an element is foreground iff key >= 0; two neighbours are linked iff their keys are equal.  A
+ *   mask is keys {-1, 0}; a panoptic lattice is its ids.
+ *   PNR_CC_VALUES, float32 data with tol >= 0 (+inf allowed, NaN refused): an element is foreground iff the value is finite and
+ *   > 0 (the "0 = no depth" convention); two neighbours are linked iff fabsf(a - b) <= tol, one float32 subtraction.  A component
+ *   is the transitive closure of the links: a ~ b ~ c joins a and c even where |a - c| > tol.
+ * OUTPUTS.  labels (int32, the data's shape): -1 on background, on foreground the component's number in 0 .. count - 1.  The
+ *   components are numbered by their lowest flat index: raster order of the first element.  count: (1) int64 on the device.
+ *   size (int32, the data's shape; NULL: not wanted): the number of elements of the element's own component, 0 on background.
+ * MESHES.  The elements are the vertices 0 .. n_vertices - 1; a face links its three vertices.  A face with an index outside that
+ *   range links nothing and gets face_label = -1; a vertex used by no valid face gets vertex_label = -1.  The components are
+ *   numbered by their lowest vertex index; face_label[f] is the label of its vertices; face_size[f] (NULL: not wanted) the number
+ *   of valid faces of the face's component, 0 for a face that is not valid.
+ * STATISTICS.  pnr_cc_stats, once the caller knows count: from labels and size as above, sizes (n_components) int32 and boxes
+ *   (n_components, 6) int32 (NULL: not wanted) = (ix_min, iy_min, iz_min, ix_max, iy_max, iz_max) in lattice indices.  Rows >=
+ *   n_components are never written; an element whose label is outside 0 .. n_components - 1 is skipped.
+ * HOW.  Union-find on a parent array P with P[i] <= i, in the labels buffer: (1) P[i] = i on foreground, -1 on background;
+ *   (2) every element unites with its backward neighbours (smaller flat index: 3 or 13 in a volume, 2 or 4 in an image), a face
+ *   unites (v0, v1) and (v1, v2): find both roots and, where they differ, an int32 atomic minimum of the smaller into the larger
+ *   root's entry, repeated from the returned value where that was no longer a root; (3) P[i] = its root, a flag per root, one
+ *   integer atomic add per element (per valid face) into the root's counter; (4) the shared exclusive scan of the flags: the
+ *   rank, and the 64-bit total = count; (5) labels[i] = rank[P[i]], size[i] = counter[P[i]].  The root of a finished component is
+ *   its lowest index whatever the interleaving.  A lattice takes steps (1) and (2) in two levels: a workgroup labels a tile of
+ *   PNR_CC_TILE_X x _Y elements of an image (res_z = 1), PNR_CC_TILE3_X x _Y x _Z of a volume, in LDS by the same union-find on
+ *   tile-local indices, whose order is the flat order, and writes P[i] = the global index of the tile-local root; only the links
+ *   across tile borders then go to global memory.  A build with -DPNR_CC_FLAT takes them in one level, every link a global
+ *   atomic: the baseline the tiled form was measured against, the same bits.  No kernel waits on another workgroup; every pointer chase steps only to a
+ *   strictly smaller non-negative index and stops otherwise, so a kernel terminates on any memory content.  No float atomics,
+ *   no 64-bit atomics.  A call is a plain chain of kernel nodes (no memset): capture-safe, and it never synchronises.
+ * LIMITS.  At most 2^31 - 2 elements (n + 1 int32 entries are scanned).  labels and size may not overlap the data or each other.
+ * workspace: pnr_cc_workspace_bytes(n_elements) bytes, 8-byte aligned (-1 for n outside 0 .. 2^31 - 2); n_elements = n_vertices
+ *   for a mesh.  PNR_EINVAL before any launch: an unknown mode; full outside {0, 1}; tol negative or NaN (values mode); a res < 0,
+ *   or a lattice over the limit; V outside 0 .. 2^31 - 2 or F outside 0 .. 2^31 - 1; n_components outside 0 .. 2^31 - 2; a null or
+ *   misaligned pointer (4 bytes; count and workspace 8); overlapping data and outputs.  A lattice with a res of 0 and a mesh
+ *   without vertices have no elements: count = 0, every face_label = -1, nothing else is written. */
+#define PNR_CC_KEYS 0
+#define PNR_CC_VALUES 1
+#define PNR_CC_TILE_X 32                /* the tile a workgroup labels in LDS first: TILE_X x TILE_Y elements of an image, */
+#define PNR_CC_TILE_Y 8                 /* one thread each; */
+#define PNR_CC_TILE3_X 8                /* TILE3_X x TILE3_Y x TILE3_Z of a volume */
+#define PNR_CC_TILE3_Y 8
+#define PNR_CC_TILE3_Z 4
+int64_t pnr_cc_workspace_bytes(int64_t n_elements);
+int pnr_cc_label(const void* data, int mode, float tol, int res_x, int res_y, int res_z, int full, int32_t* labels, int32_t* size,
+                 int64_t* count, void* workspace, void* stream);
+int pnr_cc_mesh(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* vertex_label, int32_t* face_label,
+                int32_t* face_size, int64_t* count, void* workspace, void* stream);
+int pnr_cc_stats(const int32_t* labels, const int32_t* size, int res_x, int res_y, int res_z, int64_t n_components, int32_t* sizes,
+                 int32_t* boxes, void* stream);
+
 /* ---- diagnostics.  Measurement helpers (hipEvent timing, MFMA / HBM ceilings of the device) live in libpnr_bench.so
  * (include/pnr_bench.h), not here: every export of this library is stream-ordered, never synchronises and keeps no mutable
  * state -- the one diagnostic hook of the MLP kernels is a descriptor field (pnr_mlp_desc.clk_probe). */

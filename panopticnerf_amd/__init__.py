@@ -16,8 +16,9 @@ from . import stereo  # noqa: F401
 from . import mesh  # noqa: F401
 from . import fusion  # noqa: F401
 from . import depth  # noqa: F401
+from . import components  # noqa: F401
 
 from .losses import NetworkWrapper  # noqa: F401,E402
 
 __all__ = ["NeRF", "Network", "make_network", "Renderer", "make_renderer", "NetworkWrapper", "Pinhole", "Fisheye", "Equirect", "FrameSet", "ConvexSet",
-           "extrude_polygon", "consistency", "pointcloud", "stereo", "mesh", "fusion", "depth"]
+           "extrude_polygon", "consistency", "pointcloud", "stereo", "mesh", "fusion", "depth", "components"]

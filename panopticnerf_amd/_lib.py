@@ -19,6 +19,8 @@ SAMPLE_POOLED, SAMPLE_FRAME = 0, 1        # pnr_sample_batch's mode (include/pnr
 NORMAL_OK, NORMAL_NO_DEPTH, NORMAL_NO_NEIGHBOUR, NORMAL_DEGENERATE, NORMAL_GRAZING = 0, 1, 2, 3, 4    # pnr_depth_normals' codes (PNR_NORMAL_*)
 MESHCAST_MAX_RES, MESHCAST_MAX_REACH, MESHCAST_PAD = 1024, 4096.0, 0.0625    # include/pnr.h "mesh ray casting" (PNR_MESHCAST_*)
 DEPTH_MAX_RADIUS = 8                      # pnr_depth_filter's largest radius (PNR_DEPTH_MAX_RADIUS)
+CC_KEYS, CC_VALUES = 0, 1                 # pnr_cc_label's mode (include/pnr.h PNR_CC_*)
+CC_TILE_2D, CC_TILE_3D = (32, 8), (8, 8, 4)      # the tiles pnr_cc_label labels in LDS first (PNR_CC_TILE_X / _Y, PNR_CC_TILE3_X / _Y / _Z)
 NN_MAX_TABLE, CLOUD_MAX_TAU, SAMPLE_MAX_PER_FACE = 1 << 28, 8, 65535      # include/pnr.h "nearest neighbours" (PNR_NN_MAX_TABLE, PNR_CLOUD_MAX_TAU, PNR_SAMPLE_MAX_PER_FACE)
 
 
@@ -137,6 +139,10 @@ SIGNATURES = {
     "pnr_nn_query": (c_int, [c_f, c_i64, ctypes.c_float, c_i64, c_f, c_f, c_f, c_i64, c_f, c_f, c_f, c_f]),
     "pnr_cloud_metrics_workspace_bytes": (c_i64, [c_i64]),
     "pnr_cloud_metrics": (c_int, [c_f, c_f, c_f, c_i64, ctypes.c_float, ctypes.POINTER(ctypes.c_float), c_int, c_f, c_f, c_f, c_f]),
+    "pnr_cc_workspace_bytes": (c_i64, [c_i64]),
+    "pnr_cc_label": (c_int, [c_f, c_int, ctypes.c_float, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_cc_mesh": (c_int, [c_f, c_i64, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "pnr_cc_stats": (c_int, [c_f, c_f, c_int, c_int, c_int, c_i64, c_f, c_f, c_f]),
     "pnr_mesh_sample_workspace_bytes": (c_i64, [c_i64]),
     "pnr_mesh_sample_count": (c_int, [c_f, c_i64, c_f, c_i64, ctypes.c_float, c_i64, c_f, c_f, c_f, c_f]),
     "pnr_mesh_sample_emit": (c_int, [c_f, c_i64, c_f, c_i64, c_i64, c_f, c_i64, c_f, c_f, c_f]),

@@ -13,7 +13,8 @@ frame before any volume exists (fusion.odometry).
 Conventions (this build's, unpinned): a depth is valid iff it is positive and finite; depth as render_view writes it (z-depth in a
 pinhole frame, range in a fisheye / equirect frame); the filter never fills a hole; normals are world-space unit vectors that face
 the camera (fusion.raycast's convention), from central differences of the camera-relative points where both neighbours pass the
-jump gate and one-sided ones otherwise.  Out of scope: image pyramids, hole filling, a median, normals from a larger stencil or a
+jump gate and one-sided ones otherwise.  `despeckle` removes whole blobs of wrong depth, which the filter's min_support cannot: the
+segments of similar depth (ops.cc_label, the values mode of include/pnr.h "connected components") below a size.  Out of scope: image pyramids, hole filling, a median, normals from a larger stencil or a
 plane fit, per-pixel confidence."""
 import torch
 
@@ -56,6 +57,22 @@ def filter(depth, radius=3, sigma_space=1.5, sigma_range=(0.0, 0.03), min_suppor
     sup = torch.empty(depth.shape, dtype=torch.int16, device=depth.device) if support else None
     ops.depth_filter(depth, out, radius, sigma_space, (sigma_a, sigma_b), min_support, support=sup)
     return (out, sup) if support else out
+
+
+def despeckle(depth, max_diff, min_size, connectivity=4):
+    """The depth image with every segment of fewer than min_size pixels set to 0 (the speckle stage of stereo matchers).  A
+    segment is a connected set of valid pixels, 4- or 8-linked, neighbours linked where |difference of depth| <= max_diff; its
+    closure, so a slope stays one segment.  Every other pixel is unchanged bit for bit (an invalid one stays what it was).  One
+    ops.cc_label and one torch.where; nothing is synchronised, the call can be captured in a graph."""
+    what = "depth.despeckle"
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be 4 or 8 (got %r)" % (what, connectivity))
+    tol = ops.cc_tol(what, max_diff)
+    if isinstance(min_size, bool) or not isinstance(min_size, int) or min_size < 0:
+        raise ValueError("%s: min_size must be an integer >= 0 (got %r)" % (what, min_size))
+    _image(what, depth)
+    _, size, _ = ops.cc_label(depth, connectivity == 8, tol)
+    return torch.where((size > 0) & (size < min_size), torch.zeros((), dtype=depth.dtype, device=depth.device), depth)
 
 
 def _pose(what, c2w):

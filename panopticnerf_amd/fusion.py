@@ -6,6 +6,7 @@ and `mesh.extract`: images -> depth -> volume -> mesh.
     vol = fusion.Volume(lo, hi, res, "cuda", color=True, labels=True)
     fusion.integrate(vol, frames, trunc=0.2)                 # every frame of the FrameSet that has a depth image
     m = fusion.extract(vol)                                   # mesh.Mesh with attributes sem_label, inst_label, rgb
+    m = fusion.extract(vol, min_faces=500)                    # ... without the connected pieces of fewer than 500 faces
     m.save_ply("scene.ply", colors=m.attributes["rgb"], labels=m.attributes["sem_label"])
 
 The volume lives on the lattice of `Network.query_grid` and `mesh.extract` (cell centres lo + (i + 0.5) step of the box
@@ -185,12 +186,13 @@ def filter_mesh(vertices, faces, src, observed):
     return vertices[index], new[f].to(torch.int32), src[index], index
 
 
-def extract(volume, min_weight=1.0):
+def extract(volume, min_weight=1.0, min_faces=0):
     """The mesh of the fused surface (mesh.Mesh), restricted to observed space.  field = where(weight >= min_weight, tsdf, -1)
     goes through mesh.extract at level 0; then `filter_mesh` removes the shell between observed and never-observed space --
     the back face at depth + trunc included.  attributes: sem_label, inst_label (volumes with labels) and rgb uint8 (volumes
     with colour) per vertex, read at src, so save_ply(colors=m.attributes["rgb"], labels=m.attributes["sem_label"]) works
-    directly.  Torch plumbing on the device around mesh.extract; no kernel of its own.
+    directly.  Torch plumbing on the device around mesh.extract; no kernel of its own.  min_faces > 0: the connected pieces of
+    fewer faces are removed last (Mesh.remove_small); 0 returns every piece.
 
     A `trunc` below 4 x the largest lattice step ERODES REAL SURFACE: a vertex needs all 27 points round its inside point
     observed, a neighbour of the first inside point can lie up to about 3.5 steps behind the surface (the inside end of a
@@ -198,6 +200,7 @@ def extract(volume, min_weight=1.0):
     observed."""
     if not isinstance(volume, Volume):
         raise TypeError("fusion.extract: volume must be a fusion.Volume")
+    min_faces = _mesh._min_faces("fusion.extract", min_faces)
     min_weight = float(min_weight)
     if not (min_weight > 0.0):
         raise ValueError("fusion.extract: min_weight must be positive (got %r)" % min_weight)
@@ -212,7 +215,7 @@ def extract(volume, min_weight=1.0):
         m.attributes["sem_label"], m.attributes["inst_label"] = m.labels(sem), m.labels(inst)
     if volume.rgb is not None:
         m.attributes["rgb"] = volume.colors().reshape(-1, 3)[m.src]
-    return m
+    return m.remove_small(min_faces) if min_faces else m
 
 
 HIT, NO_RAY, MISSED, NO_SURFACE = ops.RAYCAST_HIT, ops.RAYCAST_NO_RAY, ops.RAYCAST_MISSED, ops.RAYCAST_NO_SURFACE

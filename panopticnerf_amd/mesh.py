@@ -7,7 +7,9 @@ Every vertex lies on a lattice edge and knows the lattice point on the inside en
 reads any per-point array there.  `from_network` does query_grid + extract + labels.  The numbering of vertices and triangles
 is part of the rule, so the result is the CPU restatement's bit for bit, and the same on every call.  `Mesh.sample` puts points
 on the surface at a given density (ops.mesh_sample_count / mesh_sample_emit; include/pnr.h "nearest neighbours", MESH SAMPLING):
-what `Evaluator.evaluate_geometry` compares with a ground-truth scan.  `raycast` and `cast_rays` look at a mesh: the first hit of
+what `Evaluator.evaluate_geometry` compares with a ground-truth scan.  `Mesh.components` numbers the connected pieces of a
+mesh (ops.cc_mesh; include/pnr.h "connected components"), and `Mesh.remove_small`, `Mesh.largest` and `from_network(min_faces=)`
+drop the floaters a density field leaves.  `raycast` and `cast_rays` look at a mesh: the first hit of
 every pixel's ray of any camera, or of a list of rays, with depth, face, nearest vertex, flat normal and the per-vertex
 attributes carried into the image (ops.mesh_raycast / mesh_cast_rays through a `RayIndex`; include/pnr.h "mesh ray casting").
 
@@ -100,6 +102,44 @@ class Mesh:
         if grid.device != self.src.device:
             raise ValueError("Mesh.labels: grid is on %s, the mesh on %s" % (grid.device, self.src.device))
         return grid.reshape(-1)[self.src]
+
+    def components(self):
+        """The connected pieces of the mesh by its indices (components.MeshComponents: vertex_label, face_label, face_size, count
+        on the device).  Never synchronises."""
+        from . import components
+        return components.label_mesh(self)
+
+    def select(self, face_mask):
+        """A new Mesh of the faces where face_mask (F,) bool is set: vertices no kept face uses are dropped, what remains keeps
+        its order (a kept face with an index out of range is dropped); src and every attribute are carried over, the lattice fields
+        kept.  Torch indexing on the mesh's device
+        (fusion.filter_mesh's way); the sizes of the result are read back."""
+        F, V = self.faces.shape[0], self.vertices.shape[0]
+        if not isinstance(face_mask, torch.Tensor) or face_mask.dtype != torch.bool or tuple(face_mask.shape) != (F,):
+            raise ValueError("Mesh.select: face_mask must be a (%d,) bool tensor, got %s" % (
+                F, "%s %s" % (face_mask.dtype, tuple(face_mask.shape)) if isinstance(face_mask, torch.Tensor) else type(face_mask).__name__))
+        if face_mask.device != self.faces.device:
+            raise ValueError("Mesh.select: face_mask is on %s, the mesh on %s" % (face_mask.device, self.faces.device))
+        f = self.faces.long()[face_mask]
+        f = f[((f >= 0) & (f < V)).all(dim=1)]               # a face with an index out of range is dropped
+        used = torch.zeros(V, dtype=torch.bool, device=self.vertices.device)
+        used[f.reshape(-1)] = True
+        new = torch.cumsum(used, 0) - 1
+        index = torch.nonzero(used).reshape(-1)
+        faces = new[f].to(torch.int32)
+        m = Mesh(self.vertices[index], faces.contiguous(), None if self.src is None else self.src[index], self.res, self.lo, self.step, self.level)
+        for name, a in self.attributes.items():
+            m.attributes[name] = a[index]
+        m.grid = self.grid
+        return m
+
+    def remove_small(self, min_faces):
+        """select() of the pieces with at least min_faces faces; min_faces <= 1 keeps every valid face's piece"""
+        return self.select(self.components().keep(min_faces))
+
+    def largest(self, k=1):
+        """select() of the k pieces with the most faces (a tie goes to the piece with the lower first vertex)"""
+        return self.select(self.components().largest(k))
 
     def _corners(self):
         v = self.vertices.to(torch.float64)
@@ -201,14 +241,22 @@ def extract(field, lo, hi, level):
     return Mesh(vertices, faces, src, (rx, ry, rz), lo32, step, level)
 
 
-def from_network(net, lo, hi, res, level, want=("labels",), **query_kw):
+def _min_faces(what, min_faces):
+    if isinstance(min_faces, bool) or not isinstance(min_faces, int) or min_faces < 0:
+        raise ValueError("%s: min_faces must be an integer >= 0 (got %r)" % (what, min_faces))
+    return min_faces
+
+
+def from_network(net, lo, hi, res, level, want=("labels",), min_faces=0, **query_kw):
     """query_grid + extract on the raw density + per-vertex labels: the mesh of sigma = level of `net` over the box [lo, hi] at
     res cells per axis.  want: what query_grid computes beside sigma; "labels" also asks for "panoptic", so a network with
     both heads gives sem_label, inst_label and panoptic (query_grid leaves out the keys of a head the network lacks, "panoptic"
     with the semantic head: that is no refusal).  Every (res_z, res_y, res_x) output of the query is attached per
     vertex, through src, as mesh.attributes[name].  query_kw: query_grid's other keywords (is_thing, chunk, device, fast);
     nerf_level= is query()'s level (0 = coarse, 1 = fine), since `level` is the iso-value here.  mesh.grid holds the query's
-    own outputs."""
+    own outputs.  min_faces > 0: the pieces of fewer faces -- the floaters of a density field -- are removed last
+    (Mesh.remove_small); 0 returns every piece."""
+    min_faces = _min_faces("mesh.from_network", min_faces)
     want = (want,) if isinstance(want, str) else tuple(want)
     level = float(level)
     if not (abs(level) < float("inf")):
@@ -223,7 +271,7 @@ def from_network(net, lo, hi, res, level, want=("labels",), **query_kw):
         if g.dim() == 3:
             mesh.attributes[name] = mesh.labels(g)
     mesh.grid = grid
-    return mesh
+    return mesh.remove_small(min_faces) if min_faces else mesh
 
 
 HIT, NO_RAY, MISSED = ops.RAYCAST_HIT, ops.RAYCAST_NO_RAY, ops.RAYCAST_MISSED

@@ -782,6 +782,150 @@ def mesh_sample_emit(vertices, faces, seed, start, points, face):
     return points, face
 
 
+CC_MAX_ELEMENTS = 2 ** 31 - 2                   # include/pnr.h "connected components": n + 1 int32 entries are scanned
+CC_KEYS, CC_VALUES = _lib.CC_KEYS, _lib.CC_VALUES
+CC_TILE_2D, CC_TILE_3D = _lib.CC_TILE_2D, _lib.CC_TILE_3D      # (tx, ty) of an image, (tx, ty, tz) of a volume
+_CC_MODES = {torch.int32: CC_KEYS, torch.float32: CC_VALUES}
+
+
+def cc_tol(what, tol):
+    """tol of the values mode as a float32: >= 0, +inf allowed, NaN refused"""
+    try:
+        t = _f32(float(tol))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: tol must be a number >= 0 (got %r)" % (what, tol)) from None
+    if not (t >= 0.0):
+        raise ValueError("%s: tol must be >= 0 and not NaN (got %r)" % (what, tol))
+    return t
+
+
+def _cc_lattice(what, name, t):
+    """(res_x, res_y, res_z) of a components lattice: (res_z, res_y, res_x), or an image (height, width) as res_z = 1"""
+    if t.dim() not in (2, 3):
+        raise ValueError("%s: %s must be an image (height, width) or a lattice (res_z, res_y, res_x), got %s" % (what, name, tuple(t.shape)))
+    return _lattice_shape(what, name, t.unsqueeze(0) if t.dim() == 2 else t, 1, CC_MAX_ELEMENTS, "2^31 - 2")
+
+
+def _cc_workspace(what, n, workspace, dev):
+    """the int64 workspace of a components call over n elements: the caller's, checked, or a new one"""
+    words = cc_workspace_bytes(n) // 8
+    if workspace is None:
+        return torch.empty((words,), device=dev, dtype=torch.int64)
+    if not _is_tensor(workspace, torch.int64) or workspace.dim() != 1 or workspace.numel() < words:
+        raise ValueError("%s: workspace must be an int64 tensor of at least %d words" % (what, words))
+    return workspace
+
+
+def cc_workspace_bytes(n_elements):
+    """pnr_cc_workspace_bytes: host arithmetic only; more than 2^31 - 2 elements raises"""
+    return _size_or_raise(_lib.load().pnr_cc_workspace_bytes(int(n_elements)), "pnr_cc_workspace_bytes")
+
+
+@_on_device
+def cc_label(data, full=False, tol=None, labels=None, size=True, count=None, workspace=None):
+    """Connected components of the lattice `data` (res_z, res_y, res_x), or of an image (height, width) (pnr_cc_label; the rule
+    is in include/pnr.h "connected components").  int32 data are keys: foreground iff key >= 0, neighbours linked iff their
+    keys are equal.  float32 data are values and need tol: foreground iff finite and > 0, linked iff |a - b| <= tol.  full:
+    False links the 4 / 6 axis neighbours, True the 8 / 26.  Returns (labels, size, count): labels int32 of the data's shape,
+    -1 on background, else the component's number in 0 .. count - 1, by lowest flat index; size int32 of that shape, the
+    number of elements of each element's component (size=False: None; a tensor: caller-owned); count (1,) int64 ON THE
+    DEVICE.  Never synchronises: the call can be captured."""
+    what = "cc_label"
+    _tensor(what, "data", data)
+    if data.dtype not in _CC_MODES:
+        raise TypeError("%s: data must be torch.int32 (keys) or torch.float32 (values), got %s" % (what, data.dtype))
+    rx, ry, rz = _cc_lattice(what, "data", data)
+    mode = _CC_MODES[data.dtype]
+    if mode == CC_VALUES:
+        if tol is None:
+            raise ValueError("%s: float32 data are values and need tol" % what)
+        tol = cc_tol(what, tol)
+    elif tol is not None:
+        raise ValueError("%s: tol goes with float32 data; int32 keys are linked where they are equal" % what)
+    if full not in (False, True, 0, 1):
+        raise ValueError("%s: full must be False or True (got %r)" % (what, full))
+    shape = tuple(data.shape)
+    own_size = size if isinstance(size, torch.Tensor) else None
+    if own_size is None and size not in (False, True, None):
+        raise ValueError("%s: size must be True, False or an int32 tensor of the data's shape (got %s)" % (what, type(size).__name__))
+    _tensor_table(what, (), [("labels", labels, torch.int32, shape), ("size", own_size, torch.int32, shape), ("count", count, torch.int64, (1,))])
+    _same_device(what, data=data, labels=labels, size=own_size, count=count, workspace=workspace)
+    for name, t in (("labels", labels), ("size", own_size)):
+        if t is not None and t.data_ptr() == data.data_ptr():
+            raise ValueError("%s: %s may not alias data" % (what, name))
+    dev = data.device
+    workspace = _cc_workspace(what, data.numel(), workspace, dev)
+    labels = torch.empty(shape, device=dev, dtype=torch.int32) if labels is None else labels
+    if own_size is None and size:
+        own_size = torch.empty(shape, device=dev, dtype=torch.int32)
+    count = torch.empty((1,), device=dev, dtype=torch.int64) if count is None else count
+    _lib.check(_lib.load().pnr_cc_label(_p(data), mode, tol if mode == CC_VALUES else 0.0, rx, ry, rz, int(bool(full)), _p(labels), _p(own_size),
+                                        _p(count), _p(workspace), _stream()), "pnr_cc_label")
+    return labels, own_size, count
+
+
+@_on_device
+def cc_mesh(faces, n_vertices, vertex_label=None, face_label=None, face_size=True, count=None, workspace=None):
+    """Connected components of a mesh by its indices (pnr_cc_mesh): faces (F, 3) int32 over the vertices 0 .. n_vertices - 1; a
+    face links its three vertices, a face with an index out of range links nothing.  Returns (vertex_label (V,), face_label
+    (F,), face_size (F,), count (1,) int64 ON THE DEVICE): labels by lowest vertex index, -1 for a vertex no valid face uses and
+    for a face that is not valid; face_size the number of valid faces of the face's component (False: None).  Every output may
+    be caller-owned.  Never synchronises."""
+    what = "cc_mesh"
+    F = _cloud(what, "faces", faces, torch.int32)
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, int) or not (0 <= n_vertices <= CC_MAX_ELEMENTS):
+        raise ValueError("%s: n_vertices must be an integer in 0 .. 2^31 - 2 (got %r)" % (what, n_vertices))
+    V = n_vertices
+    own_size = face_size if isinstance(face_size, torch.Tensor) else None
+    if own_size is None and face_size not in (False, True, None):
+        raise ValueError("%s: face_size must be True, False or an (F,) int32 tensor (got %s)" % (what, type(face_size).__name__))
+    _tensor_table(what, (), [("vertex_label", vertex_label, torch.int32, (V,)), ("face_label", face_label, torch.int32, (F,)),
+                             ("face_size", own_size, torch.int32, (F,)), ("count", count, torch.int64, (1,))])
+    _same_device(what, faces=faces, vertex_label=vertex_label, face_label=face_label, face_size=own_size, count=count, workspace=workspace)
+    dev = faces.device
+    workspace = _cc_workspace(what, V, workspace, dev)
+    vertex_label = torch.empty((V,), device=dev, dtype=torch.int32) if vertex_label is None else vertex_label
+    face_label = torch.empty((F,), device=dev, dtype=torch.int32) if face_label is None else face_label
+    if own_size is None and face_size:
+        own_size = torch.empty((F,), device=dev, dtype=torch.int32)
+    count = torch.empty((1,), device=dev, dtype=torch.int64) if count is None else count
+    _lib.check(_lib.load().pnr_cc_mesh(_p(faces if F else None), F, V, _p(vertex_label if V else None), _p(face_label if F else None),
+                                       _p(own_size if own_size is not None and F else None), _p(count), _p(workspace), _stream()), "pnr_cc_mesh")
+    return vertex_label, face_label, own_size, count
+
+
+@_on_device
+def cc_stats(labels, size, n_components, sizes=None, boxes=True):
+    """Per-component statistics of a labelling (pnr_cc_stats): labels and size as cc_label wrote them (or cc_mesh's face_label
+    and face_size, (F,) viewed as a 1 x 1 x F lattice), n_components the count the caller read.  Returns (sizes (n,) int32,
+    boxes (n, 6) int32 = (ix_min, iy_min, iz_min, ix_max, iy_max, iz_max); boxes=False: None).  Both may be caller-owned.
+    Never synchronises."""
+    what = "cc_stats"
+    _tensor(what, "labels", labels)
+    if labels.dtype != torch.int32:
+        raise TypeError("%s: labels must be %s, got %s" % (what, torch.int32, labels.dtype))
+    if isinstance(n_components, bool) or not isinstance(n_components, int) or not (0 <= n_components <= CC_MAX_ELEMENTS):
+        raise ValueError("%s: n_components must be an integer in 0 .. 2^31 - 2 (got %r)" % (what, n_components))
+    n = n_components
+    own_boxes = boxes if isinstance(boxes, torch.Tensor) else None
+    if own_boxes is None and boxes not in (False, True, None):
+        raise ValueError("%s: boxes must be True, False or an (n, 6) int32 tensor (got %s)" % (what, type(boxes).__name__))
+    dev = labels.device
+    if labels.dim() == 1 and not labels.numel():            # no elements (a mesh without faces): nothing to launch
+        rx = ry = rz = 0
+    else:                                                   # (F,): a mesh's faces as a 1 x 1 x F lattice
+        rx, ry, rz = _cc_lattice(what, "labels", labels.reshape(1, 1, -1) if labels.dim() == 1 else labels)
+    _tensor_table(what, [("labels", labels, torch.int32, tuple(labels.shape)), ("size", size, torch.int32, tuple(labels.shape))],
+                  [("sizes", sizes, torch.int32, (n,)), ("boxes", own_boxes, torch.int32, (n, 6))])
+    _same_device(what, labels=labels, size=size, sizes=sizes, boxes=own_boxes)
+    sizes = torch.zeros((n,), device=dev, dtype=torch.int32) if sizes is None else sizes
+    if own_boxes is None and boxes:
+        own_boxes = torch.zeros((n, 6), device=dev, dtype=torch.int32)
+    if rx and n:
+        _lib.check(_lib.load().pnr_cc_stats(_p(labels), _p(size), rx, ry, rz, n, _p(sizes), _p(own_boxes), _stream()), "pnr_cc_stats")
+    return sizes, own_boxes
+
+
 TSDF_MAX_POINTS = 2 ** 31 - 1                   # include/pnr.h "depth fusion"
 TSDF_BLOCK, TSDF_BLOCKS_PER_CU = 256, 8         # PNR_TSDF_BLOCK, PNR_TSDF_BLOCKS_PER_CU
 

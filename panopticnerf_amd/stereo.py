@@ -8,8 +8,8 @@ that into z-depth of a pinhole camera, `depth_from_pair` does both.  All integer
 so the result is the CPU restatement's bit for bit.
 
 Conventions (this build's, unpinned: the reference's matcher is not available): the 9 x 7 census with a replicated border,
-constant penalties P1 / P2, the codes -1 (no right pixel) / -2 (not unique) / -3 (left-right check), 0 = no depth.  Out of scope:
-P2 adapted to image gradients, speckle or median filtering, fisheye or panoramic pairs, rectification, gradients through the
+constant penalties P1 / P2, the codes -1 (no right pixel) / -2 (not unique) / -3 (left-right check) / -4 (speckle, written by
+`despeckle` alone), 0 = no depth.  Out of scope: P2 adapted to image gradients, median filtering, fisheye or panoramic pairs, rectification, gradients through the
 matcher, more than 256 disparities."""
 import numpy as np
 import torch
@@ -17,7 +17,8 @@ import torch
 from . import ops
 from .camera import Pinhole
 
-CODES = {-1: "no right pixel", -2: "not unique", -3: "left-right check"}
+CODES = {-1: "no right pixel", -2: "not unique", -3: "left-right check", -4: "speckle"}
+SPECKLE = -4
 
 
 def to_gray(rgb):
@@ -65,6 +66,43 @@ def sgm(left, right, max_disp=128, p1=10, p2=120, paths=8, uniqueness=5, lr_tol=
     return out
 
 
+def _speckle_params(what, max_diff, min_size):
+    try:
+        max_diff = float(max_diff)
+    except (TypeError, ValueError):
+        raise ValueError("%s: max_diff must be a number >= 0 (got %r)" % (what, max_diff)) from None
+    if not (0.0 <= max_diff < float("inf")):
+        raise ValueError("%s: max_diff must be finite and >= 0 pixels (got %r)" % (what, max_diff))
+    if isinstance(min_size, bool) or not isinstance(min_size, int) or min_size < 0:
+        raise ValueError("%s: min_size must be an integer >= 0 (got %r)" % (what, min_size))
+    return max_diff, min_size
+
+
+def despeckle(result, max_diff=1.0, min_size=100):
+    """The speckle stage: a result of `sgm` with every segment of fewer than min_size pixels invalidated.  A segment is a
+    4-connected set of valid pixels, neighbours linked where their disparities differ by at most max_diff pixels (ops.cc_label
+    in the values mode on d16 + 1 as float32 with tol = 16 max_diff: exact integers, the + 1 keeps a valid disparity of 0 in
+    the foreground and cancels in the difference).  Returns a new dict of the same keys: removed pixels get the code -4 in d16
+    and code, disparity 0 and valid False; everything else is the result's.  Never synchronises."""
+    what = "stereo.despeckle"
+    if not hasattr(result, "keys") or "d16" not in result:
+        raise TypeError("%s: result must be the dict stereo.sgm returns" % what)
+    max_diff, min_size = _speckle_params(what, max_diff, min_size)
+    d16 = result["d16"]
+    if not isinstance(d16, torch.Tensor) or d16.dtype != torch.int16 or d16.dim() != 2:
+        raise ValueError("%s: result['d16'] must be an (H, W) int16 tensor" % what)
+    values = (d16.to(torch.int32) + 1).to(torch.float32)
+    _, size, _ = ops.cc_label(values, False, 16.0 * max_diff)
+    gone = (size > 0) & (size < min_size)
+    out = dict(result)
+    out["d16"] = torch.where(gone, torch.full((), SPECKLE, dtype=d16.dtype, device=d16.device), d16)
+    valid = out["d16"] >= 0
+    out["disparity"] = torch.where(valid, out["d16"].to(torch.float32) * 0.0625, torch.zeros((), device=d16.device))
+    out["valid"] = valid
+    out["code"] = torch.where(valid, torch.zeros_like(d16), out["d16"])
+    return out
+
+
 def focal_baseline(camera, baseline):
     """fb = fx * baseline as the rule makes it: one float32 multiply on the host"""
     if not isinstance(camera, Pinhole):
@@ -89,8 +127,18 @@ def depth(result_or_d16, camera, baseline, d_range=(1e-3, float("inf"))):
     return ops.disparity_depth(d16, fb, d_range)
 
 
-def depth_from_pair(left, right, camera, baseline, d_range=(1e-3, float("inf")), **sgm_args):
+def depth_from_pair(left, right, camera, baseline, d_range=(1e-3, float("inf")), speckle=None, **sgm_args):
     """`depth(sgm(left, right, **sgm_args), camera, baseline)`: the depth image of the left frame, ready for
-    `FrameSet.add(depth=...)` and `Evaluator.evaluate_depth(..., depth_gt)`."""
+    `FrameSet.add(depth=...)` and `Evaluator.evaluate_depth(..., depth_gt)`.  speckle: None, or (max_diff, min_size) of
+    `despeckle`, applied to the match before the division."""
     focal_baseline(camera, baseline)            # refuse before matching
-    return depth(sgm(left, right, **sgm_args), camera, baseline, d_range)
+    if speckle is not None:
+        try:
+            max_diff, min_size = speckle
+        except (TypeError, ValueError):
+            raise ValueError("stereo.depth_from_pair: speckle must be None or (max_diff, min_size)") from None
+        _speckle_params("stereo.depth_from_pair", max_diff, min_size)
+    result = sgm(left, right, **sgm_args)
+    if speckle is not None:
+        result = despeckle(result, max_diff, min_size)
+    return depth(result, camera, baseline, d_range)

@@ -202,6 +202,42 @@ def stereo_pair(height, width, layers=STEREO_LAYERS, seed=0, device=None):
     return out if device is None else tuple(t.to(device) for t in out)
 
 
+def blobs(shape, seed=0, n=6, radius=(1, 4), gap=2):
+    """Non-touching balls (discs in 2-D) in a lattice, for tests and timings of `components`: a bool mask with a known answer.
+    shape: (height, width) or (res_z, res_y, res_x).  Up to n balls of integer radius within `radius` (inclusive) are placed
+    at seeded random integer centres, whole inside the lattice; a ball that would come within `gap` cells (Chebyshev, between
+    bounding boxes) of an earlier one is dropped, so no two touch at any connectivity.  A ball is the cells with squared
+    distance <= r^2 from its centre: connected at the 4 / 6 connectivity.  Returns (mask bool tensor, count, sizes): count the
+    number of balls placed and sizes (count,) int64 numpy, in the order components numbers them (raster order of the first
+    cell).  CPU tensor; numpy, seeded."""
+    import numpy as np
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError("blobs: shape must be (height, width) or (res_z, res_y, res_x), every size >= 1")
+    r_lo, r_hi = int(radius[0]), int(radius[1])
+    if not 0 <= r_lo <= r_hi or int(gap) < 1:
+        raise ValueError("blobs: radius must be (lo, hi) with 0 <= lo <= hi, gap >= 1")
+    rng = np.random.default_rng(int(seed))
+    mask = np.zeros(shape, dtype=bool)
+    placed = []
+    grids = np.meshgrid(*[np.arange(s) for s in shape], indexing="ij")
+    for _ in range(int(n)):
+        r = int(rng.integers(r_lo, r_hi + 1))
+        if any(s < 2 * r + 1 for s in shape):
+            continue
+        c = [int(rng.integers(r, s - r)) for s in shape]
+        if any(all(abs(c[k] - q[k]) <= r + rq + int(gap) for k in range(len(shape))) for q, rq in placed):
+            continue
+        placed.append((c, r))
+        mask |= sum((g - ck) ** 2 for g, ck in zip(grids, c)) <= r * r
+    firsts = []
+    for c, r in placed:
+        ball = sum((g - ck) ** 2 for g, ck in zip(grids, c)) <= r * r
+        firsts.append((int(np.flatnonzero(ball.reshape(-1))[0]), int(ball.sum())))
+    firsts.sort()
+    return torch.from_numpy(mask), len(placed), np.asarray([s for _, s in firsts], dtype=np.int64)
+
+
 SDF_KINDS = ("sphere", "torus", "box", "plane")
 
 
