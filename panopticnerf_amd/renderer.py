@@ -121,6 +121,8 @@ class Renderer:
         self.lindisp = _get(cfg, "lindisp", False)
         self.max_hits = _get(cfg, "max_hits", 8)
         self.sem_mode = {"none": 0, "logits": 0, "softmax": 1}[_get(cfg, "semantic_activation", "none")]
+        # False: an inference render returns no weights_<lv> it does not need itself (weights_0 stays where a fine level samples it).
+        # Under autograd the switch has no effect: train.level_train returns the weights of both levels (the losses may read them)
         self.keep_weights = _get(cfg, "keep_weights", True)
         # inference levels run the fused MLP + compositing pass where it applies (bf16, logits compositing, N % 32 == 0);
         # cfg.fuse_composite = False (or PNR_FUSE=0) keeps the two-kernel path with the raw image in HBM
@@ -276,14 +278,16 @@ class Renderer:
         """THE maps of a render of R rays -- keys, shapes and dtypes as render_rays returns them, both levels, allocated and not
         written: what a frame of several chunks is rendered into (every chunk gets its row slices as out=) and, at R = 0, what
         a render of no rays returns.  fix_* only with a prior; no level 1 without a fine level; cfg.coarse_outputs = "weights"
-        (inference: not grad) drops the coarse maps that mode does not make."""
+        (inference: not grad) drops the coarse maps that mode does not make.  Under autograd (grad: only the render of no rays
+        asks) the per-ray keys are train.level_train's: the weights of both levels whatever cfg.keep_weights says.  The training
+        path's per-level scalars (ce3d_*: means over labelled samples, and their counts) are not maps and are not here."""
         n0 = self.net.nerf(0)
         lab = True if has_box else None
         Nc, Nf = self.N_samples, self.N_importance
         ret = {}
         for lv, N in ((0, Nc), (1, Nc + Nf)) if Nf > 0 else ((0, Nc),):
             drop = ops.WEIGHTS_ONLY_DROPS if (lv == 0 and not grad and self.coarse_outputs == "weights") else ()
-            m = ops._maps(None, R, N, n0.n_sem, n0.n_inst, lab, lab, self._need_weights(lv), dev, drop=drop)
+            m = ops._maps(None, R, N, n0.n_sem, n0.n_inst, lab, lab, grad or self._need_weights(lv), dev, drop=drop)
             ret.update(_keyed(m, torch.empty((R, N), device=dev, dtype=torch.float32), lv))
         return ret
 
@@ -299,7 +303,10 @@ class Renderer:
         split into two multiples of 8 (one per XCD: the dispatcher deals workgroups round-robin over the 8 XCDs, and a ninth
         workgroup on a 32-CU XCD waits for a whole launch -- 196 + 60 took 25 ms where 192 + 64 takes 14.2, tools/overlap_probe.py) in
         the ratio of the levels' samples within 5 %.  Not with cfg.coarse_outputs = "weights": the sigma-only coarse kernel takes no
-        workgroup cap, and the split above assumes the same cost per sample at both levels -- such frames run serially."""
+        workgroup cap, and the split above assumes the same cost per sample at both levels -- such frames run serially.  Nor with
+        explicit t_rand / u in the batch (the overlapped chunks take none), with cfg.strict_hits (its overflow count is gathered chunk
+        by chunk on one stream), with cfg.fuse_composite = False, or while the caller's stream is being captured (events across
+        streams).  The preamble is no condition: frames behind max_hits > 8 or convex primitives overlap too."""
         if (not self.overlap_levels or grad or train or len(plan) < 2 or not self.fuse or not self.frame_outputs or self.N_importance <= 0
                 or self.strict_hits or t_rand is not None or u is not None or self.raw_noise_std > 0 and train
                 or self.coarse_outputs == "weights" or torch.cuda.is_current_stream_capturing()):
@@ -392,15 +399,15 @@ class Renderer:
         elif box is not None:
             box = box.reshape(-1, 15).float().contiguous()
             box_ids = box_ids.reshape(-1, 2).int().contiguous()
+        self._overflow = None
+        if R == 0:          # (before t_rand / u: uniforms for no rays have no second dimension to infer)
+            return self._empty_outputs(lead, box is not None, rays.device, grad)
         t_rand, u = batch.get("t_rand"), batch.get("u")
         if t_rand is not None:
             t_rand = t_rand.reshape(R, -1).float().contiguous()
         if u is not None:
             u = u.reshape(R, -1).float().contiguous()
         train = self.net.training
-        self._overflow = None
-        if R == 0:
-            return self._empty_outputs(lead, box is not None, rays.device, grad)
         plan = chunk_plan(R, self.chunk_size)
         caps = self._overlap_caps(rays.device, plan, grad, train, box is not None, t_rand, u)
         if caps is not None:
