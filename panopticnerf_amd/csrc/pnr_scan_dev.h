@@ -8,6 +8,8 @@
 //                        thread that holds item n - 1 also writes out[n], the int32 total.
 // out has n + 1 entries and MAY BE `in` itself: a workgroup reads its own tile before it writes it, and launch 1 is over.
 // The int32 prefix wraps when the total passes 2^31 - 1; a caller for whom that can happen reads total64 and refuses.
+// tests/test_gpu_geometry_scale.py covers k_scan_top's carry -- three to five steps of its loop at every call site, every entry
+// of out compared, out[n] included -- and the 64-bit total: 2 149 548 000 from mesh sampling, which Mesh.sample refuses.
 // The block primitive is pnr_block_scan_excl (pnr_reduce_dev.h), the one pnr_mesh.hip scans its packed 64-bit counts with; that
 // file's multi-launch scan around it (chunk sums out of the classify kernel, 64-bit words) is a different one.
 #pragma once
